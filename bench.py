@@ -14,9 +14,11 @@ frame on the render stream, mgs_render_gathered; torch.distributed all_gather as
 up with the whole frame: strong scaling of a sub-millisecond frame ("scaling": "strong").  Strip boundaries are
 cost-balanced from the per-row list lengths of untimed calibration frames (--equal-strips turns that
 off).  The throughput partition (alternate frames: rank r renders poses r, r+N, ... with no collective) is measured in
-the same run and reported in the secondary `alternate_frames` object.
+the same run and reported in the secondary `alternate_frames` object when --full is given.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K frames and prints the headline (`value`, `ms_per_step`, ...).  --dump-outputs DIR
+also writes the frame of the last timed step (what mgs_frame_download hands a caller) to DIR.  Everything else is measured with
+--full only; the JSON line then also carries
   roofline      — the LONGEST stage of the frame by measured single-stream time: SURVEY.md 8d's algorithmic bytes / its HIP-event
                   duration, its PMC HBM bytes (`traffic`), and — when that stage is the compositor, which is not HBM-bound — its VALU
                   issue fraction with the calibration caveat (`valu`); roofline_project, roofline_sort, roofline_bin, roofline_frame
@@ -50,6 +52,23 @@ PMC_SQ_FILE = _first_profile("r6_z_pmc_sq_composite.json", "r5_z_pmc_sq_composit
 PMC_FILE = _first_profile("r6_z_pmc_hbm_traffic.json", "r5_z_pmc_hbm_traffic.json")  # written by tools/pmc_traffic.py
 HBM_PEAK = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 STAGES = ["project", "sort", "bin", "pairsort", "composite", "total"]
+DUMP_BYTES_MAX = 64 << 20    # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20  # pixels kept of a frame whose float32 copy would exceed DUMP_BYTES_MAX (3840x2160: 133 MB)
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the frame of the last timed step [H, W, 4] as float32 (its RGBA16F values exactly) in out_dir/frame.npy, or, when
+    that would exceed DUMP_BYTES_MAX, a fixed seeded sample of its pixels (frame_pixel_sample.npy [n, 4]) and their row-major pixel
+    indices (frame_pixel_sample_index.npy, float64)"""
+    os.makedirs(out_dir, exist_ok=True)
+    px = np.asarray(img, np.float32)
+    if px.nbytes <= DUMP_BYTES_MAX:
+        np.save(os.path.join(out_dir, "frame.npy"), px)
+        return
+    flat = px.reshape(-1, px.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], min(DUMP_SAMPLE_PIXELS, flat.shape[0]), replace=False))
+    np.save(os.path.join(out_dir, "frame_pixel_sample.npy"), flat[idx])
+    np.save(os.path.join(out_dir, "frame_pixel_sample_index.npy"), idx.astype(np.float64))
 
 
 def composite_roofline(ms, alg_bytes, world, N, args):
@@ -111,9 +130,14 @@ def main():
     ap.add_argument("--stochastic", action="store_true", help="MGS_SORT_STOCHASTIC (stochastic splats, a new frame_sample_id per frame) "
                     "instead of the sorted alpha blend; a secondary number, never the headline")
     ap.add_argument("--dof", type=float, default=0.0, help="3DGUT only: depth of field with this aperture (focus distance 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras of the default run (value_reference_alpha, "
-                    "value_uint8_storage): profiling passes want the headline frames only")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: calibration frames "
+                    "(per-stage times, rooflines), serial frames (value_single_frame), per-pose counters, the alternate-frame partition "
+                    "(N>1), parity against the committed fixture, the extras below and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed frames, write the frame of the last one to "
+                    "DIR/frame.npy (float32, H x W x 4; a seeded pixel sample above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without its untimed extras (value_reference_alpha, "
+                    "value_uint8_storage, key_plus_sort): profiling passes want the headline frames only")
     ap.add_argument("--inflight", type=int, default=3, help="frames in flight per GPU (each on its own HIP stream with "
                     "its own working buffers); >1 overlaps one frame's tails/launch gaps/all-gather with the next frame")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) | gloo (functional check of the N>1 path "
@@ -306,6 +330,15 @@ def main():
             src = strips[c].cpu() if args.backend != "nccl" else strips[c]
             gathered[c] = multigpu.gather_strips(src, world)  # padded to the tallest strip
 
+    def finish(out):
+        """rank 0 prints the JSON line; every rank releases its scene and leaves the process group"""
+        if rank == 0:
+            print(json.dumps(out, allow_nan=False))
+        for sc_k in reversed(scenes):
+            sc_k.close()
+        if world > 1:
+            dist.destroy_process_group()
+
     def assembled(c):
         """the whole frame on this rank after strip_frame (host tensor, int16 view of the fp16 pixels)"""
         if gather_mode.startswith("libmgs"):
@@ -317,38 +350,39 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
-    # calibration (untimed, single stream): which stage dominates a frame when nothing else shares the GPU
-    calib = []
-    for i in range(8):
-        pc = poses[i % 64]
-        pc.collect_timings = 2
-        pc.strip_row_begin, pc.strip_row_end = own_rows
-        with torch.cuda.stream(streams[0]):
-            scenes[0].render(pc)
-        torch.cuda.synchronize()
-        calib.append(scenes[0].timings_all(0))
-        pc.collect_timings = 2 if args.stage_events else 0
-        pc.strip_row_begin, pc.strip_row_end = 0, 0
-    calib_ms = np.array(calib[2:], np.float64).mean(axis=0)
-    fence()
-    # ... and the serial frame as a consumer gets it: graph-replayed frames one behind the other on ONE stream, HIP events around 24
-    # of them (untimed region; the calibration frames above carry six stage events and plain launches each: ~8 us more per frame)
-    serial_ms = None
-    if world == 1 and not args.stage_events:
-        try:
+    if args.full:
+        # calibration (untimed, single stream): which stage dominates a frame when nothing else shares the GPU
+        calib = []
+        for i in range(8):
+            pc = poses[i % 64]
+            pc.collect_timings = 2
+            pc.strip_row_begin, pc.strip_row_end = own_rows
             with torch.cuda.stream(streams[0]):
-                for i in range(4):
-                    scenes[0].render(poses[i % 64])
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record(streams[0])
-                for i in range(24):
-                    scenes[0].render(poses[(8 + i) % 64])
-                ev1.record(streams[0])
+                scenes[0].render(pc)
             torch.cuda.synchronize()
-            serial_ms = ev0.elapsed_time(ev1) / 24.0
-        except Exception:  # noqa: BLE001
-            serial_ms = None
+            calib.append(scenes[0].timings_all(0))
+            pc.collect_timings = 2 if args.stage_events else 0
+            pc.strip_row_begin, pc.strip_row_end = 0, 0
+        calib_ms = np.array(calib[2:], np.float64).mean(axis=0)
         fence()
+        # ... and the serial frame as a consumer gets it: graph-replayed frames one behind the other on ONE stream, HIP events around 24
+        # of them (untimed region; the calibration frames above carry six stage events and plain launches each: ~8 us more per frame)
+        serial_ms = None
+        if world == 1 and not args.stage_events:
+            try:
+                with torch.cuda.stream(streams[0]):
+                    for i in range(4):
+                        scenes[0].render(poses[i % 64])
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record(streams[0])
+                    for i in range(24):
+                        scenes[0].render(poses[(8 + i) % 64])
+                    ev1.record(streams[0])
+                torch.cuda.synchronize()
+                serial_ms = ev0.elapsed_time(ev1) / 24.0
+            except Exception:  # noqa: BLE001
+                serial_ms = None
+            fence()
     if world > 1 and args.check_gather:
         strip_frame(0)
         torch.cuda.synchronize()
@@ -371,7 +405,7 @@ def main():
         if K == 1:
             ref_scene.close()
         fence()
-    # Pre-roll (untimed, like the warm-up): the calibration frames above are synchronous — the GPU idles between them and falls
+    # Pre-roll (untimed, like the warm-up): the calibration frames above (--full) are synchronous — the GPU idles between them and falls
     # out of its sustained clocks, and a timed region of 20 frames (5 ms) that starts there reads 6-9 % low (round 6:
     # 3 430-3 560 frames/s against 3 720-3 870 at 128 steps; profiles/r6_p_warmup.log).  MGS_BENCH_PREROLL (default 128) dense frames through the
     # same step() as the timed ones put the device where a running renderer has it; then the fence, then the K timed frames.
@@ -395,6 +429,49 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        # the last timed frame, before anything else renders into its context (N>1: the whole frame every rank holds)
+        c_last = (args.warmup + args.steps - 1) % K
+        img = assembled(c_last).numpy().view(np.float16) if world > 1 else scenes[c_last].download_frame(capi.default_params(W, H))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, img)
+
+    # whole-job aggregate: single GPU = frames of this GPU; N>1 = frames of the strip partition (every step produces ONE
+    # frame, complete on every rank)
+    fps = args.steps / elapsed
+    out = {
+        "metric": "frames/s @1920x1080 + sorted Gsplats/s, garden-sized scene",
+        "value": fps,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "preroll_frames": preroll,  # untimed frames right in front of the timed region (with --full: after the synchronous calibration frames)
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if world > 1 else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic" if not args.ply else f"file:{os.path.basename(args.ply)}",
+        "frames_in_flight": K,
+        "submission": "per-stage events + plain launches" if args.stage_events else "hipGraph replay (one upload + one graph launch per frame)",
+        "config": {"workload": f"{'syn_garden' if not args.ply else os.path.basename(args.ply)} N={N * args.instances} x {args.instances} instance(s) SH deg 3, storage sh/rgba format {args.sh_format}/{args.rgba_format}, "
+                               f"{W}x{H}, 64-pose orbit r=4 h=1.5 fov60, GPU radix sort, cull at dist (configs[2])"
+                               + ("" if args.scene == "garden" else f", scene variant `{args.scene}`") + (", additive alpha (no early termination)" if args.alpha_sum else "")
+                               + (", 3DGUT pipeline" if args.pipeline == 1 else "") + (", stochastic splats" if args.stochastic else "")
+                               + (f", depth of field aperture {args.dof}" if args.dof > 0.0 else ""),
+                   "partition": "single GPU" if world == 1 else
+                   f"{world} tile-row strips of every frame ({'equal' if args.equal_strips else 'cost-balanced'} rows {bounds}) + strip exchange: {gather_mode}"},
+        "this_rank_strip_rows": list(my_rows) if world > 1 else None,
+        "gather_mode": gather_mode,  # which exchange ran (N > 1): libmgs's own RCCL call, or the torch.distributed fallback — never silent
+        "frame_interval_ms_percentiles": {"p50": float(np.percentile(intervals, 50)), "p95": float(np.percentile(intervals, 95)),
+                                          "mean": float(intervals.mean()), "max": float(intervals.max()),
+                                          "note": "time between consecutive frame completions in the timed region (HIP events at each frame's end)"},
+        "setup_s": setup_s,
+    }
+    if not args.full:
+        finish(out)
+        return
 
     # ---- per-stage HIP-event times of the timed frames (ring of 128) + counters per pose --------
     # context c rendered frames c, c+K, ... of the timed region (and possibly more during warm-up/calibration)
@@ -428,9 +505,6 @@ def main():
     else:
         Vs_all = Vs
 
-    # whole-job aggregate: single GPU = frames of this GPU; N>1 = frames of the strip partition (every step produces ONE
-    # frame, complete on every rank)
-    fps = args.steps / elapsed
     Ppix = W * H
 
     alt_out = None
@@ -513,32 +587,8 @@ def main():
     except Exception:
         pass
 
-    out = {
-        "metric": "frames/s @1920x1080 + sorted Gsplats/s, garden-sized scene",
-        "value": fps,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "preroll_frames": preroll,  # untimed frames right in front of the timed region (after the synchronous calibration frames)
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong" if world > 1 else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic" if not args.ply else f"file:{os.path.basename(args.ply)}",
-        "frames_in_flight": K,
-        "submission": "per-stage events + plain launches" if args.stage_events else "hipGraph replay (one upload + one graph launch per frame)",
-        "config": {"workload": f"{'syn_garden' if not args.ply else os.path.basename(args.ply)} N={N} x {args.instances} instance(s) SH deg 3, storage sh/rgba format {args.sh_format}/{args.rgba_format}, "
-                               f"{W}x{H}, 64-pose orbit r=4 h=1.5 fov60, GPU radix sort, cull at dist (configs[2])"
-                               + ("" if args.scene == "garden" else f", scene variant `{args.scene}`") + (", additive alpha (no early termination)" if args.alpha_sum else "")
-                               + (", 3DGUT pipeline" if args.pipeline == 1 else "") + (", stochastic splats" if args.stochastic else "")
-                               + (f", depth of field aperture {args.dof}" if args.dof > 0.0 else ""),
-                   "partition": "single GPU" if world == 1 else
-                   f"{world} tile-row strips of every frame ({'equal' if args.equal_strips else 'cost-balanced'} rows {bounds}) + strip exchange: {gather_mode}"},
+    out.update({
         "alternate_frames": alt_out,
-        "this_rank_strip_rows": list(my_rows) if world > 1 else None,
-        "gather_mode": gather_mode,  # which exchange ran (N > 1): libmgs's own RCCL call, or the torch.distributed fallback — never silent
         "sorted_gsplats_per_s": (Vs / (sort_ms * 1e-3)) / 1e9 if sort_ms > 0 else None,
         "sorted_gsplats_per_s_note": ("sorted pairs / time of the frame's sort stage (k_os_prepare + the two sort kernels + the launch that exits). "
                                       "EXCLUDED: the depth keys and the sort's first LSD pass, which the project kernel does while the keys are on chip "
@@ -548,9 +598,6 @@ def main():
         "visible_splats": {"frustum": Vf, "sorted": Vs, "tile_pairs": D, "shaded": shaded, "list_entries_scanned": scanned, "rect_escapes": escapes},
         "stage_ms": {STAGES[j]: float(stage_ms[j]) for j in range(6)},
         "stage_ms_single_stream": {STAGES[j]: float(calib_ms[j]) for j in range(6)},
-        "frame_interval_ms_percentiles": {"p50": float(np.percentile(intervals, 50)), "p95": float(np.percentile(intervals, 95)),
-                                          "mean": float(intervals.mean()), "max": float(intervals.max()),
-                                          "note": "time between consecutive frame completions in the timed region (HIP events at each frame's end)"},
         "frame_span_ms_percentiles": {"p50": float(np.percentile(st[:, 5], 50)), "p95": float(np.percentile(st[:, 5], 95)),
                                       "min": float(st[:, 5].min()), "max": float(st[:, 5].max())},
         # frames/s with ONE frame in flight: graph-replayed serial frames (round 6); the sum of the calibration frames' stage events
@@ -591,8 +638,7 @@ def main():
                            "survey_budget_ratio": b_frame * fps / HBM_PEAK if world == 1 else None,
                            "survey_budget_ratio_single_frame": (b_frame / (frame_gpu_ms * 1e-3)) / HBM_PEAK if frame_gpu_ms > 0 else None},
         "error_flags": err,
-        "setup_s": setup_s,
-    }
+    })
 
     if (rank == 0 and world == 1 and not args.ply and args.scene == "garden" and args.pipeline == 0 and args.instances == 1
             and not args.stochastic and args.splats == 5_830_000 and (W, H) == (1920, 1080) and args.sh_format == 0 and args.rgba_format == 0):
@@ -713,12 +759,7 @@ def main():
                                "sample": f"all {nb} splats of the workload's splat set, pose 0, best of {reps}; distance loop on all "
                                          f"cores, std::sort(par_unseq) serial unless libstdc++ finds TBB",
                                "ms": best}
-    if rank == 0:
-        print(json.dumps(out, allow_nan=False))
-    for sc_k in reversed(scenes):
-        sc_k.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

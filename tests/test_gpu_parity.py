@@ -1215,7 +1215,7 @@ def test_bench_prints_one_strict_json_line_with_the_contract_keys():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
-                          "--splats", "300000"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "--splats", "300000", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -1249,6 +1249,47 @@ def test_bench_prints_one_strict_json_line_with_the_contract_keys():
     assert d["error_flags"] == 0
 
 
+def test_bench_plain_run_dumps_the_last_timed_frame(tmp_path):
+    """bench.py without --full: the headline line only (none of the --full figures), and --dump-outputs writes the frame of the last
+    timed step as float32 — the same pixels in two runs with the same arguments, and the frame this library renders for that pose"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H, N, steps, warmup = 640, 360, 300_000, 7, 2
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                              "--splats", str(N), "--width", str(W), "--height", str(H), "--dump-outputs", str(out_dir)],
+                             capture_output=True, text=True, timeout=900, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0], parse_constant=lambda c: pytest.fail(f"non-strict JSON constant {c}"))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == steps and d["warmup"] == warmup and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["ms_per_step"] == pytest.approx(1e3 / d["value"], rel=1e-9)
+        for k in ("roofline", "cpu_baseline", "value_single_frame", "parity", "stage_ms", "error_flags"):
+            assert k not in d, k
+        assert sorted(os.listdir(out_dir)) == ["frame.npy"]
+        img = np.load(out_dir / "frame.npy")
+        assert img.dtype == np.float32 and img.shape == (H, W, 4)
+        dumps.append(img)
+    assert np.array_equal(dumps[0], dumps[1])
+    # the bench's scene and camera for the last timed step, rendered here
+    ss = mgs.SplatSet.from_arrays(**synth.make_scene(N, seed=0xC0FFEE + 2))
+    scene = mgs.Scene(0)
+    scene.add_instance(ss)
+    scene.commit()
+    p, *_ = camera((warmup + steps - 1) % 64, W, H)
+    scene.render(p)
+    want = scene.download_frame(p).astype(np.float32)
+    scene.close()
+    assert want[..., 3].max() > 0 and np.array_equal(dumps[0], want)
+
+
 @pytest.mark.parametrize("world,extra", [(2, []), (4, ["--equal-strips"]), (8, []), (3, ["--strip-bounds", "0,0,50,68"])])
 def test_bench_multi_rank_strip_partition_reassembles_the_frame(world, extra):
     """the N>1 path of bench.py end to end with several ranks sharing this one GPU (gloo: the strips are staged through
@@ -1261,7 +1302,7 @@ def test_bench_multi_rank_strip_partition_reassembles_the_frame(world, extra):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(29700 + world), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2",
-           "--splats", "400000", "--backend", "gloo", "--check-gather", "--inflight", "2", "--no-cpu-baseline"] + extra
+           "--splats", "400000", "--backend", "gloo", "--check-gather", "--inflight", "2", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     assert out.stderr.count("gathered frame == full frame: True") == world, out.stderr[-3000:]
@@ -1295,7 +1336,7 @@ def test_bench_multi_rank_rccl_call_path_through_the_test_double(world, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(29740 + world + len(extra)), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2",
            "--width", "1280", "--height", "720", "--splats", "400000", "--backend", "gloo", "--libmgs-gather", "--check-gather",
-           "--inflight", "2", "--no-cpu-baseline"] + extra
+           "--inflight", "2", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root,
                          env=dict(os.environ, MASTER_ADDR="127.0.0.1", MGS_RCCL_LIB=so, MGS_FAKE_RCCL_TIMEOUT="60"))
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]

@@ -350,13 +350,15 @@ def test_async_loader_queue_follows_the_reference_protocol(tmp_path):
     L.close()
 
 
-def test_file_readers_survive_mutated_files_under_sanitizers():
+def test_file_readers_survive_mutated_files_under_sanitizers(tmp_path):
     """tools/fuzz_loaders.sh, short run: csrc/host_model.cpp under ASan + UBSan over mutated .ply / .spz / .splat files —
     a reader returns an error or a consistent set, it never crashes, over-reads or allocates from an untrusted count"""
     import subprocess, shutil
     if shutil.which("g++") is None:
         pytest.skip("no g++")
-    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "fuzz_loaders.sh"), "120"], capture_output=True, text=True, timeout=900)
+    # the fuzzer's build and mutated files go under this test's own directory (the script uses $TMPDIR/mgs_fuzz)
+    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "fuzz_loaders.sh"), "120"], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     lines = [l for l in r.stdout.splitlines() if "mutated files" in l]
     assert len(lines) >= 9 and all("no crash / sanitizer report" in l for l in lines)
@@ -454,3 +456,26 @@ def test_compare_vkrepro_tool_reads_radiance_hdr(tmp_path):
     assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "compare_vkrepro.py"), "u8_storage", rle, "--flip-y"], capture_output=True, text=True)
     assert r.returncode == 1 and "FAIL" in r.stdout  # another case, upside down: far below the bar
+
+
+def test_bench_dump_outputs_keeps_a_frame_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: a 1080p frame is written whole as float32; a 3840x2160 one (133 MB as float32) becomes the same fixed
+    pixel sample every time, with its indices, under 64 MB in all"""
+    import bench
+    rng = np.random.default_rng(5)
+    small = rng.random((1080, 1920, 4)).astype(np.float16)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert os.listdir(tmp_path / "s") == ["frame.npy"]
+    got = np.load(tmp_path / "s" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    big = rng.random((2160, 3840, 4)).astype(np.float16)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+        names = sorted(os.listdir(tmp_path / run))
+        assert names == ["frame_pixel_sample.npy", "frame_pixel_sample_index.npy"]
+        assert sum(os.path.getsize(tmp_path / run / n) for n in names) <= 64 << 20
+    px, idx = (np.load(tmp_path / "a" / n) for n in ("frame_pixel_sample.npy", "frame_pixel_sample_index.npy"))
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(np.unique(idx)) == len(idx) == px.shape[0]
+    assert np.array_equal(px, big.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+    for n in ("frame_pixel_sample.npy", "frame_pixel_sample_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))

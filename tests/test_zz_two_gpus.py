@@ -23,7 +23,7 @@ def test_bench_two_gpus_rccl_exchange_inside_libmgs(bounds):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29731", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--width", "1280",
-           "--height", "720", "--splats", "400000", "--backend", "nccl", "--check-gather", "--inflight", "2", "--no-cpu-baseline"]
+           "--height", "720", "--splats", "400000", "--backend", "nccl", "--check-gather", "--inflight", "2", "--full", "--no-cpu-baseline"]
     if bounds:
         cmd += ["--strip-bounds", bounds]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))

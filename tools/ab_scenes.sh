@@ -2,7 +2,7 @@
 # noise-aware A/B over the scenes that stress the compositor: alternating repetitions of bench.py for csrc/libmgs.so ("base")
 # and csrc/libmgs_<tag>.so (MGS_LIB): garden at 1 and 3 frames in flight, fog, train-sized, 4K.  REPS=2 by default.
 C=vk_gaussian_splatting_amd/csrc
-one() { lib=$1; name=$2; shift 2; MGS_LIB=$lib python bench.py --no-cpu-baseline --no-extras "$@" 2>&1 | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],1), {k: round(v, 4) for k, v in d['stage_ms_single_stream'].items()})"; }
+one() { lib=$1; name=$2; shift 2; MGS_LIB=$lib python bench.py --full --no-cpu-baseline --no-extras "$@" 2>&1 | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],1), {k: round(v, 4) for k, v in d['stage_ms_single_stream'].items()})"; }
 for rep in $(seq 1 ${REPS:-2}); do for tag in base "$@"; do
   if [ "$tag" = base ]; then L=$C/libmgs.so; else L=$C/libmgs_$tag.so; fi
   one $L "$tag garden_if1" --inflight 1

@@ -1,7 +1,7 @@
 #!/bin/bash
-# bench.py over the configurations DESIGN.md quotes; one JSON line each into gpurun_out/matrix_*.json
-mkdir -p gpurun_out
-run() { name=$1; shift; python bench.py --no-cpu-baseline "$@" 2>&1 | grep -v amdgpu | tail -1 > gpurun_out/matrix_$name.json; }
+# bench.py over the configurations DESIGN.md quotes; one JSON line each into results/matrix_*.json
+mkdir -p results
+run() { name=$1; shift; python bench.py --full --no-cpu-baseline "$@" 2>&1 | grep -v amdgpu | tail -1 > results/matrix_$name.json; }
 run garden
 run garden_if1 --inflight 1
 run train --splats 1030000
@@ -20,7 +20,7 @@ run garden_3dgut_stoch --pipeline 1 --stochastic --steps 32 --warmup 4 --infligh
 run garden_3dgut_dof --pipeline 1 --dof 0.02 --steps 32 --warmup 4 --inflight 1
 python - <<'PY'
 import json, glob
-for f in sorted(glob.glob("gpurun_out/matrix_*.json")):
+for f in sorted(glob.glob("results/matrix_*.json")):
     try:
         d = json.loads(open(f).read())
         print(f.split("matrix_")[1][:-5].ljust(12), "fps %8.1f" % d["value"], "single-stream ms", {k: round(v, 3) for k, v in d["stage_ms_single_stream"].items()},

@@ -3,7 +3,7 @@
 # usage (on the GPU box): tools/frame_kernels.sh <out.csv> [extra bench.py args]
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$1; shift
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ps1
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps1 -- python $R/bench.py --steps 24 --warmup 4 --no-cpu-baseline --inflight 1 "$@" > /tmp/l3 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ps1 -- python $R/bench.py --full --steps 24 --warmup 4 --no-cpu-baseline --inflight 1 "$@" > /tmp/l3 2>&1
 cp $(find /tmp/ps1 -name "*kernel_stats.csv" | head -1) $R/$OUT
 python - <<PY
 import csv

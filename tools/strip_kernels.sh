@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-kernel rocprofv3 stats of ONE strip (tile rows B..E of a WxH frame), one frame in flight:
-#   tools/strip_kernels.sh 1920 1080 34 38  -> gpurun_out/strip_kernels_<W>x<H>_<B>_<E>.csv
+#   tools/strip_kernels.sh 1920 1080 34 38  -> results/strip_kernels_<W>x<H>_<B>_<E>.csv
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/psk
 cat > /tmp/strip_one.py <<PY
 import sys, os
@@ -20,7 +20,7 @@ torch.cuda.synchronize()
 print(s.last_stats() if hasattr(s, "last_stats") else "")
 PY
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/psk -- python /tmp/strip_one.py > /tmp/lsk 2>&1
-OUT=$R/gpurun_out/strip_kernels_$1x$2_$3_$4.csv
+OUT=$R/results/strip_kernels_$1x$2_$3_$4.csv
 cp $(find /tmp/psk -name "*kernel_stats.csv" | head -1) $OUT || tail -20 /tmp/lsk
 python - <<PY
 import csv
