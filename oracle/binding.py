@@ -233,6 +233,47 @@ def sort_stable(keys, ids):
     return k, v
 
 
+def caller_ids(storage_ids, counts, perms):
+    """global STORAGE ids -> the caller's global ids.  Instances are concatenated in creation order in both id spaces;
+    inside instance k only the index is permuted, by perms[k] (storage index -> caller's index, mgs_scene_storage_order)."""
+    ids = np.asarray(storage_ids, np.int64).reshape(-1)
+    offs = np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))])
+    if ids.size and (ids.min() < 0 or ids.max() >= offs[-1]):
+        raise ValueError("storage id out of range")
+    k = np.searchsorted(offs, ids, side="right") - 1
+    out = np.empty(ids.size, np.int64)
+    for q in np.unique(k):
+        m = k == q
+        out[m] = offs[q] + np.asarray(perms[q], np.int64)[ids[m] - offs[q]]
+    return out.astype(np.uint32)
+
+
+def storage_sorted_stream(frame, instances, sh_format=0, rgba_format=0):
+    """the oracle's stably sorted (key, id) stream of a scene whose instances may hold DIFFERENT splat sets, with ties
+    resolved in a library's storage order.  instances: [(arrays, perm, transform or None)] per scene instance in creation
+    order, perm = storage index -> caller's index of that instance's set.  Each instance is fed to the oracle as its own
+    set in storage order; the sorted ids are mapped back through per-instance offsets and permutations.
+    Returns (keys, caller_ids, storage_ids, inst): inst is the oracle instance array in storage order, which the
+    storage ids index (render / project with it and them)."""
+    prepared, lst, counts, perms = {}, [], [], []
+    for arrays, perm, m in instances:
+        perm = np.asarray(perm, np.int64)
+        n = int(np.asarray(arrays["positions"]).size // 3)
+        if perm.shape != (n,) or not np.array_equal(np.sort(perm), np.arange(n)):
+            raise ValueError("perm is not a permutation of the set's indices")
+        key = (id(arrays), perm.tobytes())
+        if key not in prepared:
+            prepared[key] = PreparedSet({k: (None if v is None else np.asarray(v)[perm]) for k, v in arrays.items()},
+                                        sh_format, rgba_format)
+        lst.append((prepared[key], m))
+        counts.append(n)
+        perms.append(perm)
+    inst = make_instances(lst)
+    ok, oi = key_cull(frame, inst)
+    oks, ois = sort_stable(ok, oi)
+    return oks, caller_ids(ois, counts, perms), ois, inst
+
+
 def project(frame, inst, k, local_idx):
     P = OrcProjected()
     lib().orc_project(C.byref(frame), C.byref(inst[k]), local_idx, C.byref(P))

@@ -6,7 +6,8 @@
     (>= 55 dB and the absolute tolerance below);
   * a whole 3840x2160 frame against the oracle at a size the oracle renders in ~20 s;
   * the 8-strip partition of configs[3] == the full frame, bit for bit, at full size;
-  * a12/a13: the projected per-splat records (centre, eigen basis, opacity) against orc_project.
+  * a12/a13 (SURVEY.md §8a): the projected per-splat records (centre, eigen basis, opacity) against orc_project;
+  * a small set of its own above 2^23 global splat ids (24 id bits) behind a large different set.
 """
 import hashlib
 import os
@@ -235,3 +236,49 @@ def test_projected_records_match_oracle_per_splat(ob, case):
     assert np.all((x0b >= gx0 // bw)[vis]) and np.all((x1b <= gx1 // bw)[vis])
     assert np.all((y0b >= gy0 // bh)[vis]) and np.all((y1b <= gy1 // bh)[vis])
     scene.close()
+
+
+def test_small_different_set_above_2_23_global_ids(ob):
+    """a large set of 2^23 splats followed by a small DIFFERENT set (SH degree 1): the small set's global ids are 2^23 and up,
+    idBits becomes 24 and the 1080p grid's ride codes go from riding whole to exactly filling the spare bits.  The sorted
+    stream bit-exact against the oracle (each instance's own set in its own storage order), the small instance's bin
+    rectangles contain its footprints, and a crop of the 1080p frame around it against the oracle."""
+    from mixed_scene import MixedScene, check_projected_records, make_set
+    n_big, n_small = 1 << 23, 3000
+    sets = dict(L=make_set(n_big, 201, 0), S=make_set(n_small, 202, 1))
+    Ms, _ = mgs.compute_transform([0.25, 0.25, 0.25], [0.0, 30.0, 10.0], [0.0, 0.3, 3.0])
+    m = MixedScene(sets, [("L", None), ("S", Ms)])
+    assert m.scene.splat_count == n_big + n_small
+    W, H = 1920, 1080
+    eye = np.array([0.0, 0.5, 6.0], np.float32)
+    V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, W, H)
+    p = capi.default_params(W, H)
+    capi.set_camera(p, V, P, eye)
+    fr = ob.make_frame(V, P, eye, W, H)
+    oks, ois, sids, inst_s = m.oracle_stream(ob, fr)
+    so = m.scene.sort_keys(p)
+    gk, gi = m.scene.sort_download(so.count)
+    small = ois >= n_big
+    print(f"2^23 + {n_small}: {so.count} sorted, {int(small.sum())} of the small set")
+    assert so.count == oks.size and np.array_equal(gk, oks) and np.array_equal(gi, ois)
+    assert small.sum() > 1000
+    out = m.scene.render(p, want_stats=True)
+    assert out.error_flags == 0 and out.frustum_count == oks.size
+    img = m.scene.download_frame(p).astype(np.float32)
+    _, fi = m.scene.sort_download(out.sorted_count)
+    fs = fi[fi >= n_big]
+    where = {int(c): j for j, c in enumerate(ois[small])}
+    j = np.array([where[int(g)] for g in fs])
+    rec, rect = m.scene.download_projected(fs)
+    want, _ = check_projected_records(ob, fr, inst_s, sids[small][j], np.ones(fs.size, np.int64), rec, rect, W, H,
+                                      "set above 2^23", records=False)
+    # a 256 x 256 crop around the small instance's splats
+    cx, cy = np.median(want[:, 0]), np.median(want[:, 1])
+    x0, y0 = int(np.clip(cx - 128, 0, W - 256)), int(np.clip(cy - 128, 0, H - 256))
+    win = (x0, y0, x0 + 255, y0 + 255)
+    oimg, _ = ob.render_window(ob.make_frame(V, P, eye, W, H, target_fp16=1), inst_s, sids, win)
+    got = img[y0:y0 + 256, x0:x0 + 256]
+    psnr, err = ob.psnr_rgb(got, oimg), np.abs(got[..., :3] - oimg[..., :3]).max()
+    print(f"  crop {win}: PSNR {psnr:.2f} dB, max abs {err:.4f}")
+    assert psnr >= PSNR_MIN and err <= ABS_TOL
+    m.close()

@@ -35,17 +35,13 @@ def scene_small():
 def oracle_sorted_stream(ob, scene, sc, frame_kw, transforms=(None,)):
     """oracle (key, id) stream with ties resolved in the library's documented order: STORAGE order
     (mgs_scene_storage_order).  The oracle is fed the arrays in storage order and its ids are mapped
-    back to the caller's ids — keys and ids can then be compared bit for bit."""
+    back to the caller's ids — keys and ids can then be compared bit for bit.  Every instance holds the set sc; scenes of
+    different sets go through ob.storage_sorted_stream with each instance's own set and order (test_gpu_mixed_sets.py)."""
     n = sc["positions"].shape[0]
-    perm = scene.storage_order(0, n)                       # storage index -> caller's index
-    sc_p = {k: (v[perm] if v is not None else None) for k, v in sc.items()}
-    ps = ob.PreparedSet(sc_p)
-    inst = ob.make_instances([(ps, m) for m in transforms])
-    fr = ob.make_frame(**frame_kw)
-    ok, oi = ob.key_cull(fr, inst)
-    oks, ois = ob.sort_stable(ok, oi)
-    k = ois // n
-    return oks, (k * n + perm[ois % n]).astype(np.uint32)
+    assert scene.splat_count == n * len(transforms), "oracle_sorted_stream: one set sc in every instance"
+    insts = [(sc, scene.storage_order(i, n), m) for i, m in enumerate(transforms)]   # storage index -> caller's index
+    oks, ois, _, _ = ob.storage_sorted_stream(ob.make_frame(**frame_kw), insts)
+    return oks, ois
 
 
 def camera(i, W, H, flip=False):

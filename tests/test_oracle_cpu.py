@@ -874,3 +874,41 @@ def test_fisheye_dist_cull_against_independent_numpy_fp64(ob, fov, gut, inside):
     pin_ok, _ = npr.dist_cull(sc["positions"], M, V, P, W, H, 0.2)
     print(f"fisheye cull fov {fov} gut {gut}: {ids.size} survive, pinhole box keeps {int(pin_ok.sum())}, differ on {int((pin_ok != got).sum())}")
     assert (pin_ok != got).sum() > 50
+
+
+def test_storage_sorted_stream_maps_ids_of_different_sets(ob):
+    """ob.storage_sorted_stream on a scene of two DIFFERENT sets (one of them used twice), each with its own storage
+    permutation: the keys equal the oracle's on the caller-ordered sets, every (key, caller id) pair is the caller-ordered
+    oracle's, ties follow the global storage order, and caller_ids inverts a brute-force per-instance mapping"""
+    import vk_gaussian_splatting_amd as mgs
+    a = synth.make_scene(700, seed=3)
+    b = synth.make_scene(301, seed=4, sh_coeffs_per_channel=3)
+    rng = np.random.default_rng(5)
+    pa, pb = rng.permutation(700).astype(np.uint32), rng.permutation(301).astype(np.uint32)
+    M, _ = mgs.compute_transform([0.8, 1.1, 1.0], [10.0, -25.0, 5.0], [0.4, 0.0, -0.3])
+    W, H = 160, 120
+    eye = np.array([2.5, 1.0, 3.0], np.float32)
+    fr = ob.make_frame(lookat(eye, [0, 0, 0], [0, 1, 0]), persp(60.0, W / H, 0.1, 100.0), eye, W, H)
+    insts = [(a, pa, None), (b, pb, M), (a, pa, M)]
+    keys, ids, sids, inst = ob.storage_sorted_stream(fr, insts)
+    # the same frame on the caller-ordered sets: same keys, same (key, id) pairs, ids ascending inside a tie run
+    ck, ci = ob.sort_stable(*ob.key_cull(fr, ob.make_instances([(ob.PreparedSet(a), None), (ob.PreparedSet(b), M),
+                                                                 (ob.PreparedSet(a), M)])))
+    assert keys.size > 300 and np.array_equal(keys, ck)
+    assert np.array_equal(ids[np.lexsort((ids, keys))], ci)
+    same = keys[1:] == keys[:-1]
+    assert same.any() and np.all(sids[1:][same] > sids[:-1][same])    # ties in global storage order
+    offs, perms = [0, 700, 1001, 1701], [pa, pb, pa]
+    for s, c in zip(sids, ids):
+        k = int(np.searchsorted(offs, s, side="right") - 1)
+        assert c == offs[k] + perms[k][s - offs[k]]
+    assert ((ids >= 700) & (ids < 1001)).any() and (ids >= 1001).any()
+    # the storage-order instance array is what the storage ids index: same frame as caller order + caller ids
+    img_s, _ = ob.render(fr, inst, order=sids)
+    img_c, _ = ob.render(fr, ob.make_instances([(ob.PreparedSet(a), None), (ob.PreparedSet(b), M), (ob.PreparedSet(a), M)]),
+                         order=ids)
+    assert np.array_equal(img_s, img_c) and img_s[..., 3].max() > 0
+    with pytest.raises(ValueError):
+        ob.caller_ids([1701], [700, 301, 700], perms)
+    with pytest.raises(ValueError):
+        ob.storage_sorted_stream(fr, [(a, pa[:-1], None)])
