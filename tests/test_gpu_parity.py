@@ -140,8 +140,7 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
     frame's key sort with the pass elision (default), with four plain passes (MGS_SORT_REMAP=0), the stand-alone sorts on
     the generic reduce-then-scan kernels instead of the key sort's (MGS_RAW_SORT=generic), without the bin rectangles'
     ride through the sort (MGS_RECT_RIDE=0), with the codes split between the key's low byte and the id's spare bits as scenes
-    beyond 8 M splats have them (MGS_RIDE_SPLIT=2), and with the project kernel's partitions in storage order instead of
-    fullest-slot-first (MGS_PRJ_ORDER=0), the binning's masks by ballots instead of the transpose (MGS_DB_TRANSPOSE=0), the sort passes'
+    beyond 8 M splats have them (MGS_RIDE_SPLIT=2), the binning's masks by ballots instead of the transpose (MGS_DB_TRANSPOSE=0), the sort passes'
     level-2 look-back as the chain of group prefixes instead of the counted sums (MGS_OS_FLAT=0).  Sizes around the partition and
     look-back group boundaries, distributions with giant runs / few values / many exponents, and whole frames — every sorted
     stream must equal the stable sort bit for bit, every frame must be the same frame"""
@@ -150,8 +149,7 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_child_sort.py")
     out = {}
     for mode, env_extra in (("default", {}), ("plain", {"MGS_SORT_REMAP": "0"}), ("generic", {"MGS_RAW_SORT": "generic"}),
-                            ("gather", {"MGS_RECT_RIDE": "0"}), ("nohistory", {"MGS_BIN_HISTORY": "0"}),
-                            ("split", {"MGS_RIDE_SPLIT": "2"}), ("storageorder", {"MGS_PRJ_ORDER": "0"}),
+                            ("gather", {"MGS_RECT_RIDE": "0"}), ("split", {"MGS_RIDE_SPLIT": "2"}),
                             ("fullproducts", {"MGS_EXACT_SHORTCUTS": "0"}), ("ballotmasks", {"MGS_DB_TRANSPOSE": "0"}),
                             ("chain", {"MGS_OS_FLAT": "0"}), ("fixedpart", {"MGS_OS_PART_MIN": "4096"}), ("part1024", {"MGS_OS_PART_MIN": "1024"})):
         r = subprocess.run([sys.executable, child], env=dict(os.environ, **env_extra), capture_output=True, text=True, timeout=900)
@@ -160,9 +158,8 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
         out[mode] = [l for l in r.stdout.splitlines() if l.startswith("FRAMES_SHA1")]
         print(mode, [l for l in r.stdout.splitlines() if l.startswith("STATS")])
     # (gather: the bin rectangles looked up by id instead of riding through the sort above the ids, k_osort.hip)
-    # nohistory: the compositor's bin order from the list lengths instead of the previous frame's region times (scheduling only)
-    assert out["default"] and out["default"] == out["plain"] == out["generic"] == out["gather"] == out["nohistory"]
-    assert out["default"] == out["split"] == out["storageorder"]
+    assert out["default"] and out["default"] == out["plain"] == out["generic"] == out["gather"]
+    assert out["default"] == out["split"]
     # fullproducts: P*V*M without the exact shortcuts of round 5 (products with exact zeros dropped): the same frames to the bit
     assert out["default"] == out["fullproducts"]
     # ballotmasks: the binning's column / row masks by ballots instead of the bit-matrix transpose (k_dbin_count): the same lists
@@ -1103,8 +1100,6 @@ def test_binning_paths_bit_identical():
 
     ref = run({})
     assert run({"MGS_DIRECT_BIN": "0"}) == ref
-    # optional fusions / culling refinements must not change a bit either
-    assert run({"MGS_LOOSE_MASK": "1"}) == ref     # compositor quarter masks from the footprint box only
     for shift in ("1,1", "2,3", "4,4"):
         a = run({"MGS_BIN_SHIFT": shift})
         b = run({"MGS_BIN_SHIFT": shift, "MGS_DIRECT_BIN": "0"})

@@ -27,6 +27,23 @@ def test_library_exports_every_symbol_declared_in_header():
     assert b"gfx950" in lib.mgs_version()
 
 
+def test_readme_knob_table_lists_exactly_the_switches_the_library_reads():
+    """every MGS_* switch of libmgs.so is read once, in csrc/tuning.hip; the README's knob table must list exactly those (plus
+    MGS_LIB, which is the Python binding's).  Outside tuning.hip only the trace builds' file paths are read from the environment."""
+    csrc = os.path.join(ROOT, "vk_gaussian_splatting_amd", "csrc")
+    src = open(os.path.join(csrc, "tuning.hip")).read()
+    read = set(re.findall(r'getenv\("(MGS_[A-Z0-9_]+)"\)', src)) | set(re.findall(r'flag\("(MGS_[A-Z0-9_]+)"', src))
+    assert read, "no switches parsed from tuning.hip"
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    rows = dict(re.findall(r"^\| `(MGS_[A-Z0-9_]+)[^|]*\|[^|]*\|([^\n]*)$", readme, flags=re.M))
+    assert "Python binding only" in rows.pop("MGS_LIB")
+    assert set(rows) == read
+    for name in os.listdir(csrc):
+        if name.endswith((".hip", ".h", ".cpp")) and name != "tuning.hip":
+            for var in re.findall(r"getenv\(\s*([^)]*)\)", open(os.path.join(csrc, name)).read()):
+                assert re.fullmatch(r'"MGS_[A-Z]+_TRACE_FILE"', var), (name, var)
+
+
 def test_struct_layouts_match_header_sizes():
     # MgsFrameParams: 16+16+3 floats, 2 ints, 3 floats, 12 ints + 6 reserved
 

@@ -5,7 +5,7 @@ set -e
 NAME=$1; FLAGS=$2; shift 2
 C=$(cd "$(dirname "$0")/../vk_gaussian_splatting_amd/csrc" && pwd)
 O=/tmp/mgs_var_$NAME; mkdir -p $O
-for f in mgs_api k_project k_sort k_osort k_raster k_gut; do
+for f in mgs_api k_project k_sort k_osort k_raster k_gut tuning; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $FLAGS -c $C/$f.hip -o $O/$f.o &
 done
 wait

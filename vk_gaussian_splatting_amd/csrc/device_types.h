@@ -122,7 +122,6 @@ struct CompositeArgs
   int32_t stripRow0, stripRow1;
   int32_t nInstances;
   int32_t shDegree;
-  int32_t looseMask;          // A/B knob (MGS_LOOSE_MASK)
 #ifdef MGS_CMP_TRACE
   uint64_t* trace;            // debug build only (tools/cmp_trace.py): per-workgroup time stamps and counts
 #endif

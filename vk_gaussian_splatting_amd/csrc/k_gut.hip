@@ -17,7 +17,6 @@
 // Depth of field and stochastic splats are the XT variant of the compositor (random numbers: kernels_common.h).
 // Kernel degrees other than 2 and the surface side outputs run in the XT variant too.  Not built (stated in DESIGN.md):
 // rolling shutter (untested in the reference).
-#include <cstdlib>
 #include "kernels_common.h"
 #include "sh_eval.h"
 #include "surface_normal.h"
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(kGutThreads) void k_project_gut(const FrameArgs* __
   __shared__ uint32_t s_cnt[32];
   __shared__ uint32_t s_base[33];
   const int      t = threadIdx.x, lane = laneId(), w = t >> 6;
-  const uint32_t part = order != nullptr ? order[blockIdx.x] : blockIdx.x;  // fullest slot of the previous frame first (k_project.hip)
+  const uint32_t part = order[blockIdx.x];  // fullest slot of the previous frame first (k_project.hip)
   int            k    = 0;
   for(int i = 1; i < A.f.nInstances; ++i)
     if(part >= A.inst[i].blockBegin)
@@ -1033,9 +1032,8 @@ void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs*
   if(tiles <= 0)
     return;
   const bool extras = A.f.dofMode != 0 || A.f.stochastic != 0 || A.f.kernelDegree != 2 || A.f.surfaceOutputs != 0;
-  static const bool kPacked = [] { const char* e = std::getenv("MGS_GUT_PACKED"); return e ? std::atoi(e) != 0 : true; }();
   const bool packedOk = A.f.kernelDegree == 2 && A.f.surfaceOutputs == 0 && (A.f.alphaMode == 0 || A.f.stochastic != 0);
-  if(kPacked && packedOk)
+  if(packedOk)
   {  // the quadratic-kernel modes without side outputs run on the packed two-pixels-per-lane compositor
     // all bins of the frame are enumerated (the bin order of the binning stage is over the whole frame; regions outside a
     // strip exit at once)

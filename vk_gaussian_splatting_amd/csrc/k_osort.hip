@@ -532,9 +532,6 @@ __device__ __forceinline__ uint32_t osPartOf(uint32_t n, uint32_t grid, uint32_t
   return (n + part - 1u) / part <= cap ? part : kOsPart;
 }
 
-#ifndef MGS_OS_WAVES
-#define MGS_OS_WAVES 4
-#endif
 template <int IN, bool REMAP>
 __global__ __launch_bounds__(kThreads, MGS_OS_WAVES) void k_os_pass(const OsPassArgs a)
 {
@@ -1094,21 +1091,12 @@ __global__ void k_os_plan_clear(OsPlan* plan)
 // as many workgroups as 1024-pair partitions of that count, up to kOsSmallGrid, so that a sort of few keys can spread over the chip
 // (osPartOf).  Workgroups beyond the partitions exit after the set-up.
 constexpr uint32_t kOsSmallGrid = 1024;
-// MGS_OS_PART_MIN = the smallest partition size the passes may choose on the device (osPartOf above; a multiple of 256 in
-// [1024, 4096]; default 1 536; 4096 = the fixed size of rounds 3-5).
-static uint32_t osPartMinEnv()
-{
-  static const uint32_t v = [] {
-    const char* e = std::getenv("MGS_OS_PART_MIN");
-    const int   x = e ? std::atoi(e) : 0;
-    return (x >= 1024 && x <= (int)kOsPart && x % 256 == 0) ? (uint32_t)x : 1536u;
-  }();
-  return v;
-}
-uint32_t osSortMaxParts(uint32_t maxElems)
+// partMin = the smallest partition size the passes may choose on the device (osPartOf above; Tuning::osPartMin): kOsPart = fixed
+// partitions, and a grid of kOsPart-pair partitions is enough.
+uint32_t osSortMaxParts(uint32_t maxElems, uint32_t partMin)
 {
   const uint32_t big = (uint32_t)(((uint64_t)maxElems + kOsPart - 1u) / kOsPart);
-  if(osPartMinEnv() >= kOsPart)
+  if(partMin >= kOsPart)
     return big;
   const uint32_t small = (uint32_t)std::min<uint64_t>(((uint64_t)maxElems + 1023u) / 1024u, kOsSmallGrid);
   return std::max(big, small);
@@ -1129,19 +1117,7 @@ void launchOsSort(hipStream_t stream, const OsLaunch& L)
   if(L.maxElems == 0 || (uint64_t)L.maxElems >= kOsMaxPairs)
     return;  // (the callers reject / re-route 2^30 pairs and more: a prefix would wrap inside its status word)
   const bool     frame    = L.pairs0 != nullptr;  // the project kernels' slots of pairs + their histograms / records
-  const uint32_t maxParts = osSortMaxParts(L.maxElems);
-  // the device-side choice of the partition size (osPartOf): off unless MGS_OS_PART_MIN asks for it (osPartMinEnv above)
-  static uint32_t       devSlots[64] = {};
-  int                   dev = 0;
-  (void)hipGetDevice(&dev);
-  if(dev >= 0 && dev < 64 && devSlots[dev] == 0u)
-  {
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    devSlots[dev] = (uint32_t)std::max(cus, 1) * (uint32_t)MGS_OS_WAVES;
-  }
-  const uint32_t partMin  = L.partMin ? L.partMin : osPartMinEnv();
-  const uint32_t resSlots = L.resSlots ? L.resSlots : ((dev >= 0 && dev < 64) ? devSlots[dev] : 1024u);
+  const uint32_t maxParts = osSortMaxParts(L.maxElems, L.partMin);
   const uint32_t sWords   = (uint32_t)osSortStatusWords(maxParts);
   // Three sets of look-back words: pass 0 uses set 0, pass 1 set 1, pass 2 set 2, pass 3 set 1 again.  Every set is zero when its
   // pass starts: pass 0 clears sets 1 and 2 (whatever the previous sort left there, whether its pass 3 ran or not), pass 1
@@ -1198,10 +1174,9 @@ void launchOsSort(hipStream_t stream, const OsLaunch& L)
     a.nPtr    = L.nPtr;
     a.ctr     = L.ctr;
     a.pass    = pass;
-    a.partMin  = partMin;
-    a.resSlots = resSlots;
-    static const uint32_t kFlat = [] { const char* e = std::getenv("MGS_OS_FLAT"); return e ? (uint32_t)std::atoi(e) : 1u; }();
-    a.flatLookback = kFlat;
+    a.partMin  = L.partMin;
+    a.resSlots = L.resSlots;
+    a.flatLookback = L.flatLookback;
     a.dstKeys = L.outKeys;
     a.dstVals = L.outVals;
     // stand-alone: pass 0 -> A, 1 -> B, 2 -> A, 3 -> the result.  Frame: pass 1 reads the project kernels' slots, which live in B,

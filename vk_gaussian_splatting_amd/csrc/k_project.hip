@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kPrjThreads, 6) void k_project(const FrameArgs* __r
 
   const int      t = threadIdx.x, lane = laneId(), w = t >> 6;
   // partitions are dispatched fullest slot of the PREVIOUS frame first (k_os_prepare leaves the order; scheduling only)
-  const uint32_t part = order != nullptr ? order[blockIdx.x] : blockIdx.x;
+  const uint32_t part = order[blockIdx.x];
   int            k    = 0;
   for(int i = 1; i < A.f.nInstances; ++i)  // instances own consecutive partition ranges
     if(part >= A.inst[i].blockBegin)

@@ -16,6 +16,7 @@
 #include "sh_eval.h"
 #include "surface_normal.h"
 #include "sort_plan.h"
+#include "tuning.h"
 
 namespace mgs {
 
@@ -686,7 +687,7 @@ __global__ __launch_bounds__(256) void k_dbin_emit(const uint32_t* __restrict__ 
     uint32_t*      s_tot = reinterpret_cast<uint32_t*>(s_spos);  // [256] (the stage is filled only after this block)
     const uint32_t btot = (t < nb) ? binTotal[t] : 0u;
     uint32_t       cost = 0u;
-    if(binCost != nullptr && t < nb)
+    if(t < nb)
     {
       cost       = binCost[t];
       binCost[t] = 0u;
@@ -1261,7 +1262,7 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
           const float mx = bcx + ((qd & 1) ? 8.0f : -8.0f) - ak.x, my = bcy + ((qd & 2) ? 4.0f : -4.0f) - ak.y;
           const float ds = fmaxf(fabsf(mx * sb.x + my * sb.y) - rs, 0.0f), du = fmaxf(fabsf(mx * sb.z + my * sb.w) - ru, 0.0f);
           const bool  box = ((qd & 1) ? xr : xl) && ((qd & 2) ? yb : yt);
-          qm |= (box && (ds * ds + du * du <= qLim || F.looseMask)) ? (1u << qd) : 0u;
+          qm |= (box && ds * ds + du * du <= qLim) ? (1u << qd) : 0u;
         }
         //  a record with a non-finite axis or centre takes no part: the folded fragment rule is clamp(fma) * exp2(nq), and a
         // NaN nq would pass the clamp as 0 and then poison colour and T through 0 * NaN — the select it replaced mapped NaN to 0.
@@ -1601,8 +1602,7 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
     atomicAdd(&stat[1], statScanned);
     // the bin's longest region, for the next frame of this context: regions that never saturate take twice as long as the
     // others, and starting them late is the kernel's tail; which ones they are is the same from one frame to the next
-    if(F.binCost != nullptr)
-      atomicMax(&F.binCost[bin], (uint32_t)(wall_clock64() - costT0) + 1u);
+    atomicMax(&F.binCost[bin], (uint32_t)(wall_clock64() - costT0) + 1u);
   }
   const v2f aout = early ? (v2f){1.0f - T.x, 1.0f - T.y} : asum;
 #pragma unroll
@@ -1674,10 +1674,9 @@ void launchDirectBinning(hipStream_t stream, const uint32_t* idsX, const uint32_
   const uint32_t maxChunks = (maxSplats + kDbChunk - 1) / kDbChunk;
   if(maxChunks == 0)
     return;
-  // MGS_DB_TRANSPOSE=0: the rounds' masks by ballots everywhere (A/B switch of the transpose path; the masks are the same)
-  static const int kTranspose = [] { const char* e = std::getenv("MGS_DB_TRANSPOSE"); return e ? std::atoi(e) : 1; }();
+  // MGS_DB_TRANSPOSE=0: the rounds' masks by ballots everywhere (the masks are the same; the transpose path is the default)
   hipLaunchKernelGGL(k_dbin_count, dim3((maxChunks + kDbCntMul - 1) / kDbCntMul), dim3(256), 0, stream, idsX, idsY, planKeys, rect, sortedCode16, maskBuf,
-                     binHist, pStride, binsX, binsY, kTranspose);
+                     binHist, pStride, binsX, binsY, tuning().dbTranspose);
   hipLaunchKernelGGL(k_dbin_scan, dim3(binsX * binsY), dim3(256), 0, stream, planKeys, binHist, pStride, binTotal);
 #ifdef MGS_DB_TRACE
   static uint64_t* traceBuf = nullptr;
@@ -1737,7 +1736,7 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
   C.width = F.width; C.height = F.height; C.tilesX = F.tilesX;
   C.binShiftX = F.binShiftX; C.binShiftY = F.binShiftY; C.binsX = F.binsX; C.binsY = F.binsY;
   C.stripRow0 = F.stripRow0; C.stripRow1 = F.stripRow1;
-  C.nInstances = F.nInstances; C.shDegree = F.shDegree; C.looseMask = (F.debugFlags & 256) ? 1 : 0;
+  C.nInstances = F.nInstances; C.shDegree = F.shDegree;
   C.depthIsoThreshold = F.depthIsoThreshold;
   C.shOnly     = (F.debugFlags & 2) ? 1 : 0;
   C.binCost    = binCost;

@@ -13,7 +13,6 @@
 //     scatter workgroups turn the 256 totals into digit bases themselves.
 //   * a pass whose digit is identical for every key (the high byte of a bin id) is detected by its scan kernel and
 //     its scatter exits; the ping-pong selection is derived from the skip flags on the device.
-#include <cstdlib>
 
 #include "kernels_common.h"
 #include "sort_plan.h"
@@ -334,8 +333,7 @@ void launchRadixSort(hipStream_t stream, const SortLaunch& s)
     return;
   // big sorts use 4096-key partitions (digit runs of ~16 keys = 64-byte scatter segments), small ones keep 2048 so
   // that 256 CUs still see enough workgroups
-  static const uint32_t kPartOverride = [] { const char* e = std::getenv("MGS_SORT_PART"); return e ? (uint32_t)std::atoi(e) : 0u; }();
-  const uint32_t part  = kPartOverride ? kPartOverride : ((s.maxElems >= (2u << 20)) ? 4096u : 2048u);
+  const uint32_t part  = (s.maxElems >= (2u << 20)) ? 4096u : 2048u;
   const uint32_t parts = (uint32_t)(((uint64_t)s.maxElems + part - 1) / part);
   for(int pass = 0; pass < nPasses; ++pass)
   {

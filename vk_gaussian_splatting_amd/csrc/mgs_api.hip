@@ -29,6 +29,7 @@
 #include "device_types.h"
 #include "host_model.h"
 #include "sort_plan.h"
+#include "tuning.h"
 
 namespace mgs {
 // kernels_*.hip
@@ -276,6 +277,7 @@ struct SceneData
 struct MgsScene_t
 {
   int         device = 0;
+  uint32_t    osResSlots = 0;  // workgroups of a key-sort pass the device holds at once: CUs x MGS_OS_WAVES (OsLaunch::resSlots)
   hipStream_t stream = nullptr, ownStream = nullptr;
 
   std::shared_ptr<SceneData> d;   // shared with the frame contexts (mgs_frame_context_create)
@@ -679,6 +681,11 @@ static int mgs_scene_create_impl(int device, MgsScene* out)
   HIPCHK(hipSetDevice(device));
   auto* s   = new MgsScene_t();
   s->device = device;
+  {
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    s->osResSlots = (uint32_t)std::max(cus, 1) * (uint32_t)MGS_OS_WAVES;
+  }
   s->d      = std::make_shared<SceneData>();
   s->d->device = device;
   s->d->handles.push_back(s);
@@ -825,8 +832,9 @@ static int mgs_frame_context_create_impl(MgsScene parent, MgsScene* out)
     return rc;
   {
     std::lock_guard<std::mutex> lk(parent->d->mtx);
-    c->d         = parent->d;  // drops the context's own (empty) SceneData
-    c->isContext = true;
+    c->d          = parent->d;  // drops the context's own (empty) SceneData
+    c->isContext  = true;
+    c->osResSlots = parent->osResSlots;
     c->d->handles.push_back(c);
   }
   *out = c;
@@ -1102,24 +1110,16 @@ static int mgs_scene_commit_impl(MgsScene s, int shFormat, int rgbaFormat)
     d.count               = (uint32_t)n;
     d.shDegree            = std::max(0, h.maxShDegree());
     d.shStride            = shStride(h.fRestPerSplat());
-    // storage order: Morton order of the centres (MGS_REORDER=0 keeps the caller's order).  Global ids
-    // used inside the pipeline are STORAGE ids; the API maps them back (mgs_sort_download,
-    // mgs_scene_download_set, mgs_scene_storage_order).  Ties between equal depth keys resolve in
-    // storage order — the reference's tie order is nondeterministic (dist.comp.slang:137-139).
-    static const bool kReorder = [] { const char* e = std::getenv("MGS_REORDER"); return e ? std::atoi(e) != 0 : true; }();
+    // storage order: Morton order of the centres.  Global ids used inside the pipeline are STORAGE ids; the
+    // API maps them back (mgs_sort_download, mgs_scene_download_set, mgs_scene_storage_order).  Ties between
+    // equal depth keys resolve in storage order — the reference's tie order is nondeterministic
+    // (dist.comp.slang:137-139).
     std::vector<float> cov;
     buildCov6(h, cov);
-    if(kReorder)
     {
       std::vector<float> radius(n);
       parallelBatches(n, [&](size_t i) { radius[i] = std::sqrt(8.0f * (cov[6 * i] + cov[6 * i + 3] + cov[6 * i + 5])); });
       mortonOrder(h, &radius, d.newToOld);
-    }
-    else
-    {
-      d.newToOld.resize(n);
-      for(size_t i = 0; i < n; ++i)
-        d.newToOld[i] = (uint32_t)i;
     }
     d.oldToNew.resize(n);
     parallelBatches(n, [&](size_t i) { d.oldToNew[d.newToOld[i]] = (uint32_t)i; });
@@ -1292,7 +1292,7 @@ static int sizeWorkingSet(MgsScene s)
   HIPCHK(hipMemset(s->top16Count.p, 0, 65536u * 4u));
   {  // look-back words of the key sort's passes: zero once, the passes clear them for their successors (k_osort.hip)
     // (the three sets' offsets depend on the element bound: a re-sized working set starts from zeroed words)
-    const size_t words = 3u * osSortStatusWords(osSortMaxParts((uint32_t)total));
+    const size_t words = 3u * osSortStatusWords(osSortMaxParts((uint32_t)total, tuning().osPartMin));
     if((rc = s->osStatus.ensure(words))) return rc;
     HIPCHK(hipMemset(s->osStatus.p, 0, words * 4u));
   }
@@ -1319,8 +1319,8 @@ static int sizeWorkingSet(MgsScene s)
   if((rc = ensureFrameState(s))) return rc;
 
   uint64_t cap = std::max<uint64_t>(32ull * total, 64ull << 20);  // 16 B per pair: 3 GB for a garden-sized scene
-  if(const char* e = std::getenv("MGS_PAIR_CAPACITY"))
-    cap = std::strtoull(e, nullptr, 10);
+  if(tuning().pairCapacity)
+    cap = *tuning().pairCapacity;
   if(s->listCapacityOverride)
     cap = s->listCapacityOverride;
   cap = std::min<uint64_t>(std::max<uint64_t>(cap, kPart), 0xFFFFF000ull);
@@ -1546,17 +1546,16 @@ static void mapIdsToStorage(MgsScene s, uint32_t* ids, size_t n)
 // ------------------------------------------------------------------------------------------------
 // coarse bins (the default): stable multi-split straight into the per-bin lists, no records, no pair sort; MGS_DIRECT_BIN=0
 // forces the record + pair-sort path of frames with more than 256 bins
-static const bool kDirectBin = [] { const char* e = std::getenv("MGS_DIRECT_BIN"); return e ? std::atoi(e) != 0 : true; }();
+static bool directBinning(const FrameConst& F) { return tuning().directBin && directBinningSupported(F.binsX, F.binsY); }
 
 // The bin rectangles ride through the key sort as codes in the id word's spare bits (kernels_common.h: rideEncode) when the
 // frame bins directly and the GPU sorts: as many of the shapes 1x1, 2x1, 1x2, 2x2 as fit the spare bits (at most 16).
-// MGS_RECT_RIDE=0: k_dbin_count gathers every rectangle by id instead (A/B).
-static const bool kRectRide = [] { const char* e = std::getenv("MGS_RECT_RIDE"); return e ? std::atoi(e) != 0 : true; }();
+// MGS_RECT_RIDE=0: k_dbin_count gathers every rectangle by id instead (as frames without spare bits do).
 static void chooseRide(MgsScene s, FrameConst& F, bool cpuMode)
 {
   F.rideShift = F.rideShapes = F.rideSplit = 0;
   F.rideEscape = 0;
-  if(!kRectRide || cpuMode || !kDirectBin || !directBinningSupported(F.binsX, F.binsY) || s->d->totalSplats == 0)
+  if(!tuning().rectRide || cpuMode || !directBinning(F) || s->d->totalSplats == 0)
     return;
   int idBits = 1;
   while(idBits < 32 && (1ull << idBits) < (uint64_t)s->d->totalSplats)
@@ -1565,16 +1564,14 @@ static void chooseRide(MgsScene s, FrameConst& F, bool cpuMode)
   const int codes[4] = {nb, nb + (bx - 1) * by, nb + (bx - 1) * by + bx * (by - 1), nb + (bx - 1) * by + bx * (by - 1) + (bx - 1) * (by - 1)};
   // Where the id word's spare bits hold all four shapes the code rides there whole.  Otherwise (round 5; 8 garden instances
   // need 26 id bits) it is split: its low 8 bits replace the KEY's low byte in the slot — the slot is grouped by that byte, so
-  // the sort never looks at it again (slot_emit.h) — and only the rest rides above the id: 8 + spare bits.  MGS_RIDE_SPLIT=0:
-  // as before (fewer shapes, or the gather by id); =2: always split (tests: small scenes take the split path too).
-  static const int kSplitMode = [] { const char* e = std::getenv("MGS_RIDE_SPLIT"); return e ? std::atoi(e) : 1; }();
-  const bool kSplit = kSplitMode != 0;
-  const int  spare  = 32 - idBits;
-  for(int pass = kSplitMode == 2 ? 1 : 0; pass < 2; ++pass)
+  // the sort never looks at it again (slot_emit.h) — and only the rest rides above the id: 8 + spare bits.  MGS_RIDE_SPLIT=2:
+  // always split (tests: small scenes take the split path too).
+  const int spare = 32 - idBits;
+  for(int pass = tuning().rideSplitAlways ? 1 : 0; pass < 2; ++pass)
   {
     const bool split    = pass == 1;
     const int  codeBits = std::min(split ? spare + 8 : spare, 16);
-    if(split && (!kSplit || spare < 1))
+    if(split && spare < 1)
       break;
     for(int shapes = 4; shapes >= (split ? 1 : 4); --shapes)
       if(codeBits >= 1 && codes[shapes - 1] + 1 <= (1 << codeBits))
@@ -1586,25 +1583,13 @@ static void chooseRide(MgsScene s, FrameConst& F, bool cpuMode)
         return;
       }
   }
-  if(kSplit)
-    return;
-  const int codeBits = std::min(spare, 16);
-  for(int shapes = 3; shapes >= 1; --shapes)
-    if(codeBits >= 1 && codes[shapes - 1] + 1 <= (1 << codeBits))
-    {
-      F.rideShift  = idBits;
-      F.rideShapes = shapes;
-      F.rideEscape = (1u << codeBits) - 1u;
-      return;
-    }
 }
 
 
 // the frames the adaptive bin size applies to: the default compositing mode of the 3DGS pipeline with the GPU sort
-static const bool kBinAdapt = [] { const char* e = std::getenv("MGS_BIN_ADAPT"); return (e ? std::atoi(e) != 0 : true) && std::getenv("MGS_BIN_SHIFT") == nullptr; }();
 static bool binPolicyEligible(const MgsFrameParams* p)
 {
-  return kBinAdapt && p->alpha_mode != MGS_ALPHA_SUM && p->pipeline == MGS_PIPELINE_3DGS && p->sort_mode == MGS_SORT_GPU_RADIX && p->surface_outputs == 0;
+  return tuning().binAdapt && p->alpha_mode != MGS_ALPHA_SUM && p->pipeline == MGS_PIPELINE_3DGS && p->sort_mode == MGS_SORT_GPU_RADIX && p->surface_outputs == 0;
 }
 
 static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
@@ -1620,9 +1605,8 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   std::memcpy(F.proj, p->proj, sizeof(F.proj));
   {  // affine view + perspective projection, bit patterns and magnitudes checked: the project kernels may drop the products with
      // the exact zeros (kernels_common.h: mulMat4ExactAffineW1 / mulPerspExactW1*).  MGS_EXACT_SHORTCUTS=0: never (A/B).
-    static const bool kShort = [] { const char* e = std::getenv("MGS_EXACT_SHORTCUTS"); return e ? std::atoi(e) != 0 : true; }();
     const float vrow[4] = {p->view[3], p->view[7], p->view[11], p->view[15]}, want[4] = {0.0f, 0.0f, 0.0f, 1.0f};
-    bool        ok      = kShort && std::memcmp(vrow, want, sizeof(want)) == 0;
+    bool        ok      = tuning().exactShortcuts && std::memcmp(vrow, want, sizeof(want)) == 0;
     static const int kZero[9] = {1, 2, 3, 4, 6, 7, 12, 13, 15};
     const float      zero     = 0.0f;
     for(int q = 0; q < 9 && ok; ++q)
@@ -1661,8 +1645,11 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   }
   else if(binPolicyEligible(p) && s->binPolicy.fine)
     bsx = bsy = 3;  // 128x128 px: this context's regions scan most of their lists (BinPolicy)
-  if(const char* e = std::getenv("MGS_BIN_SHIFT"))
-    std::sscanf(e, "%d,%d", &bsx, &bsy);
+  if(tuning().binShiftSet)
+  {
+    bsx = tuning().binShiftX.value_or(bsx);
+    bsy = tuning().binShiftY.value_or(bsy);
+  }
   else
   {  // keep the frame at <= 256 bins so that the direct (record-free) binning applies: 4K -> 256x128 px bins
     // (8K UHD: 512x512 px bins)
@@ -1698,7 +1685,6 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   F.msAA            = p->ms_antialiasing;
   F.alphaMode       = p->alpha_mode;
   F.debugFlags      = p->debug_flags;
-  if(std::getenv("MGS_LOOSE_MASK")) F.debugFlags |= 256;
   F.sizeCulling     = p->size_culling;
   F.sizeCullingMinPixels = p->size_culling_min_pixels;
   F.surfaceOutputs  = p->surface_outputs ? 1 : 0;
@@ -1746,8 +1732,7 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   F.nInstances      = (int)s->d->instances.size();
   F.totalSplats     = s->d->totalSplats;
   F.totalPartitions = s->d->totalParts;
-  static const bool kPartCull = [] { const char* e = std::getenv("MGS_PARTITION_CULL"); return e ? std::atoi(e) != 0 : true; }();
-  F.partitionCull   = (kPartCull && F.cullMode == MGS_CULL_AT_DIST) ? 1 : 0;
+  F.partitionCull   = F.cullMode == MGS_CULL_AT_DIST ? 1 : 0;
   uint32_t offset = 0, block = 0;
   for(int k = 0; k < F.nInstances; ++k)
   {
@@ -1830,18 +1815,10 @@ static int pairSortBits(int nTiles)
 }
 
 
-// the compositor's bin order from the previous frame's region times (k_dbin_emit); MGS_BIN_HISTORY=0: longest list first (A/B)
-static const bool kBinHistory = [] { const char* e = std::getenv("MGS_BIN_HISTORY"); return e ? std::atoi(e) != 0 : true; }();
-
-// pass elision of the key sort (sort_plan.h): on by default, MGS_SORT_REMAP=0 keeps the four plain passes
-static const bool kRemap = [] { const char* e = std::getenv("MGS_SORT_REMAP"); return e ? std::atoi(e) != 0 : true; }();
-
-// the project kernels' partitions are dispatched fullest slot of the previous frame first (k_os_prepare writes the order,
-// k_project reads it; scheduling only); MGS_PRJ_ORDER=0: storage order (A/B)
-static const bool kPrjOrder = [] { const char* e = std::getenv("MGS_PRJ_ORDER"); return e ? std::atoi(e) != 0 : true; }();
-
-// the frame's key sort (k_osort.hip): slots of the project kernel -> sorted ids in idsA (keys in keysA when wanted)
-static void keySort(MgsScene s, hipStream_t st, bool wantKeys, bool allowRemap, const FrameConst* ride = nullptr)
+// the frame's key sort (k_osort.hip): slots of the project kernel -> sorted ids in idsA (keys in keysA when wanted).  Its pass
+// elision (sort_plan.h) is on unless MGS_SORT_REMAP=0.  It leaves the project kernels' next dispatch order in prjOrder: fullest
+// slot of this frame first (scheduling only).
+static void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr)
 {
   OsLaunch L{};
   L.pairs0       = s->pairB.p;
@@ -1850,7 +1827,7 @@ static void keySort(MgsScene s, hipStream_t st, bool wantKeys, bool allowRemap, 
   L.chunkSum     = s->chunkSum.p;
   L.runTab       = s->runTab.p;
   L.nOut         = &s->ctr.p->sortedCount;
-  L.prjOrderOut  = kPrjOrder ? s->prjOrder.p : nullptr;
+  L.prjOrderOut  = s->prjOrder.p;
   L.slotHist     = s->slotHist2.p;
   L.top16Rec     = s->top16Rec.p;
   L.top16Count   = s->top16Count.p;
@@ -1864,7 +1841,10 @@ static void keySort(MgsScene s, hipStream_t st, bool wantKeys, bool allowRemap, 
   L.planOut      = &s->plans.p->keys;
   L.status       = s->osStatus.p;
   L.ctr          = s->ctr.p;
-  L.allowRemap   = allowRemap;
+  L.allowRemap   = tuning().sortRemap;
+  L.partMin      = tuning().osPartMin;
+  L.resSlots     = s->osResSlots;
+  L.flatLookback = tuning().osFlat;
   if(ride != nullptr && ride->rideShift != 0 && !wantKeys)
   {
     int codeBits = 0;
@@ -2150,7 +2130,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   if(F.temporalSampling)
     if((rc = s->accum.ensure((size_t)F.width * F.height))) return rc;
   {
-    if(!(kDirectBin && directBinningSupported(F.binsX, F.binsY)) && s->pairKey0.n < s->pairCapacity)
+    if(!directBinning(F) && s->pairKey0.n < s->pairCapacity)
     {  // first frame on the record + pair-sort path (> 256 bins, or forced): its buffers
       const uint64_t cap = s->pairCapacity;
       if((rc = s->pairKey0.ensure(cap))) return rc;
@@ -2184,7 +2164,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   auto issue = [&](bool withEvents) -> int {
     if(withEvents) HIPCHK(hipEventRecord(fev[0], st));
     // (counters and sort plans arrive zeroed with the upload)
-    if(!(kDirectBin && directBinningSupported(F.binsX, F.binsY)))
+    if(!directBinning(F))
       launchFrameInit(st, s->ranges.p, nTiles);  // record path: tiles without entries keep an empty range
     if(withEvents) HIPCHK(hipEventRecord(fev[6], st));  // MGS_STAGE_CULL ends here; it is part of MGS_STAGE_PROJECT too
     const bool cpuMode = (p->sort_mode == MGS_SORT_CPU_ASYNC);
@@ -2192,13 +2172,13 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
       hipLaunchKernelGGL(k_fill_u32, dim3(1024), dim3(256), 0, st, s->rect.p, 1u, s->d->totalSplats);
     if(gut)
       launchProjectGut(st, A, s->dArgs.p, s->d->shFormat, ctr, s->pairB.p, s->slotCount.p, s->recGut.p, s->rect.p,
-                       s->slotHist2.p, s->top16Rec.p, cpuMode ? nullptr : s->top16Count.p, &s->plans.p->os, kPrjOrder ? s->prjOrder.p : nullptr);
+                       s->slotHist2.p, s->top16Rec.p, cpuMode ? nullptr : s->top16Count.p, &s->plans.p->os, s->prjOrder.p);
     else
       launchProject(st, A, s->dArgs.p, true, ctr, s->pairB.p, s->slotCount.p, s->rec.p, s->rect.p,
-                    s->slotHist2.p, s->top16Rec.p, cpuMode ? nullptr : s->top16Count.p, &s->plans.p->os, kPrjOrder ? s->prjOrder.p : nullptr);
+                    s->slotHist2.p, s->top16Rec.p, cpuMode ? nullptr : s->top16Count.p, &s->plans.p->os, s->prjOrder.p);
     if(withEvents) HIPCHK(hipEventRecord(fev[1], st));
     if(!cpuMode)
-      keySort(s, st, false, kRemap, &F);
+      keySort(s, st, false, &F);
     else
     {
       rc = cpuSortStep(s, p, p->cpu_sort_blocking != 0);
@@ -2216,12 +2196,12 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     }
     if(withEvents) HIPCHK(hipEventRecord(fev[2], st));
     // coarse bins (the default): stable multi-split straight into the per-bin lists, no records, no pair sort
-    const bool direct = kDirectBin && directBinningSupported(F.binsX, F.binsY);
+    const bool direct = directBinning(F);
     if(direct)
     {
       launchDirectBinning(st, s->idsA.p, s->idsA.p, planK, s->rect.p, s->sortedCode16.p, s->dbinMasks.p, s->d->totalSplats,
                           s->partHist.p, s->pStride, &planP->ghist[0][0], s->pairVal1.p, s->ranges.p, ctr, s->pairCapacity,
-                          F.binsX, F.binsY, kBinHistory ? s->binCost.p : nullptr);
+                          F.binsX, F.binsY, s->binCost.p);
       if(withEvents) HIPCHK(hipEventRecord(fev[3], st));
     }
     else
@@ -2259,7 +2239,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     else
       launchComposite(st, A, s->ranges.p, s->pairVal1.p, s->pairVal0.p, planP, s->rec.p, s->image.p, half, s->d->shFormat, ctr,
                       F.surfaceOutputs ? s->surfDepth.p : nullptr, F.surfaceOutputs ? s->surfId.p : nullptr, s->d->compInst.p,
-                      s->dArgs.p, F.surfaceOutputs ? s->surfNormal.p : nullptr, kBinHistory ? s->binCost.p : nullptr);
+                      s->dArgs.p, F.surfaceOutputs ? s->surfNormal.p : nullptr, s->binCost.p);
     if(F.temporalSampling)
       hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, st, s->dArgs.p, s->accum.p, s->image.p, half);
     if(withEvents) HIPCHK(hipEventRecord(fev[5], st));
@@ -2269,9 +2249,8 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   // launch sequence does not depend on host-side data (GPU sort, no per-stage events) is captured ONCE per
   // (resolution, strip, mode) into a hipGraph and replayed: the kernels read everything that changes from frame to
   // frame through dArgs.  MGS_GRAPH=0 forces plain launches.
-  static const bool kUseGraph = [] { const char* e = std::getenv("MGS_GRAPH"); return e ? std::atoi(e) != 0 : true; }();
   bool launched = false;
-  if(kUseGraph && s->graphOk && !timed && !cpuModeOuter)
+  if(tuning().useGraph && s->graphOk && !timed && !cpuModeOuter)
   {
     MgsScene_t::GraphKey key;
     std::memset(&key, 0, sizeof(key));
@@ -2279,7 +2258,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     std::memcpy(&isoBits, &F.depthIsoThreshold, 4);
     // everything the compositor receives by value (CompositeArgs) must be part of the key
     const int32_t kv[16] = {F.width, F.height, F.stripRow0, F.stripRow1, F.binShiftX, F.binShiftY, F.partitionCull, F.alphaMode,
-                            F.debugFlags & (2 | 4 | 256), F.surfaceOutputs, half, F.nInstances, F.shDegree, isoBits,
+                            F.debugFlags & (2 | 4), F.surfaceOutputs, half, F.nInstances, F.shDegree, isoBits,
                             F.pipeline, F.stochastic | (F.dofMode << 1) | (F.temporalSampling << 2) | ((F.pipeline == 1 && F.kernelDegree != 2) ? 8 : 0) |
                                 ((F.pipeline == 1 && F.normalMethod == 1) ? 16 : 0) |
                                 (F.rideShift << 8) | (F.rideShapes << 16) | (F.rideSplit << 24)};  // ... and everything that selects a kernel variant or a launch argument
@@ -2321,7 +2300,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     if(rc != MGS_OK)
       return rc;
   }
-  if(policyFrame && kDirectBin && directBinningSupported(F.binsX, F.binsY))
+  if(policyFrame && directBinning(F))
   {  // adaptive bin size: every 32nd eligible frame leaves a copy of its statistics lines (4 KB) for the frame eight later
     MgsScene_t::BinPolicy& B = s->binPolicy;
     if((B.frames & 31u) == 16u && !B.pending)
@@ -2580,8 +2559,8 @@ Rccl& rccl()
     Rccl r;
     // MGS_RCCL_LIB=path: load THIS library instead (and nothing else if it fails) — the seam of the test double that lets several
     // ranks share one GPU (tests/helpers/fake_rccl.cpp); never set in production, never a fallback
-    if(const char* forced = std::getenv("MGS_RCCL_LIB"))
-      r.lib = dlopen(forced, RTLD_NOW | RTLD_LOCAL);
+    if(tuning().rcclLib)
+      r.lib = dlopen(tuning().rcclLib->c_str(), RTLD_NOW | RTLD_LOCAL);
     else
       for(const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
         if((r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL)))
@@ -3030,10 +3009,10 @@ int mgs_sort_keys(MgsScene s, const MgsFrameParams* p, MgsSortOut* out)
   if((rc = uploadFrameState(s, A, st))) return rc;
   HIPCHK(hipEventRecord(s->ev[0], st));
   launchProject(st, A, s->dArgs.p, false, s->ctr.p, s->pairB.p, s->slotCount.p, s->rec.p, s->rect.p,
-                s->slotHist2.p, s->top16Rec.p, s->top16Count.p, &s->plans.p->os, kPrjOrder ? s->prjOrder.p : nullptr);
+                s->slotHist2.p, s->top16Rec.p, s->top16Count.p, &s->plans.p->os, s->prjOrder.p);
   HIPCHK(hipEventRecord(s->ev[1], st));
   if((rc = s->keysA.ensure(s->d->totalSplats))) return rc;  // the hook returns the sorted keys too
-  keySort(s, st, true, kRemap);
+  keySort(s, st, true);
   HIPCHK(hipEventRecord(s->ev[2], st));
   HIPCHK(hipMemcpyAsync(s->hCtr, s->ctr.p, sizeof(FrameCounters), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(s->hPlans, s->plans.p, sizeof(FramePlans), hipMemcpyDeviceToHost, st));
@@ -3142,10 +3121,9 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
   if((rc = plan.ensure(1))) return rc;
   // a full-width sort runs on the frame key sort's kernels (k_osort.hip, uniform input, four plain passes): the battery of
   // the stand-alone sort tests exercises exactly what the frame uses; partial bit ranges take the generic sort (k_sort.hip).
-  // MGS_RAW_SORT=generic forces the generic one for every range (A/B).
-  static const bool kRawGeneric = [] { const char* e = std::getenv("MGS_RAW_SORT"); return e && std::strcmp(e, "generic") == 0; }();
+  // MGS_RAW_SORT=generic forces the generic one for every range.
   // (2^30 pairs or more: the look-back words of k_os_pass hold 30-bit prefixes — the generic sort has no such limit)
-  const bool os = !kRawGeneric && beginBit == 0 && endBit == 32 && (uint64_t)count < kOsMaxPairs;
+  const bool os = !tuning().rawSortGeneric && beginBit == 0 && endBit == 32 && (uint64_t)count < kOsMaxPairs;
   if(os)
   {
     if((rc = s->rsPairA.ensure(count))) return rc;
@@ -3153,13 +3131,14 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
     if((rc = s->rsOsPlan.ensure(1))) return rc;
     // the passes keep the three sets of look-back words zeroed for each other (k_osort.hip); the sets' offsets depend on
     // the count, so a sort of another size starts from freshly zeroed words
-    const size_t words = 3u * osSortStatusWords(osSortMaxParts(count));
-    if(s->rsStatus.n < words || s->rsStatusParts != osSortMaxParts(count))
+    const uint32_t maxParts = osSortMaxParts(count, tuning().osPartMin);
+    const size_t   words    = 3u * osSortStatusWords(maxParts);
+    if(s->rsStatus.n < words || s->rsStatusParts != maxParts)
     {
       if((rc = s->rsStatus.ensure(words))) return rc;
       HIPCHK(hipMemset(s->rsStatus.p, 0, s->rsStatus.n * 4u));
       HIPCHK(hipDeviceSynchronize());
-      s->rsStatusParts = osSortMaxParts(count);
+      s->rsStatusParts = maxParts;
     }
   }
   hipStream_t st = s->stream;
@@ -3185,6 +3164,9 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
     O.ctr      = s->ctr.p;
     O.status   = s->rsStatus.p;
     O.allowRemap = false;
+    O.partMin    = tuning().osPartMin;
+    O.resSlots   = s->osResSlots;
+    O.flatLookback = tuning().osFlat;
     HIPCHK(hipMemsetAsync(&s->ctr.p->errorFlags, 0, sizeof(uint32_t), st));  // whatever an earlier frame left there is not this sort's
     launchOsSort(st, O);
   }

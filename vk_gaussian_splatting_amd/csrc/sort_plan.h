@@ -48,6 +48,9 @@ void launchRadixSort(hipStream_t stream, const SortLaunch& s);
 #define MGS_OS_PART 4096
 #endif
 constexpr uint32_t kOsPart    = MGS_OS_PART;  // pairs per partition (256 threads x 16)
+#ifndef MGS_OS_WAVES
+#define MGS_OS_WAVES 4  // resident workgroups per CU the sort passes are built for (__launch_bounds__ of k_os_pass)
+#endif
 constexpr uint32_t kOsSlot    = 2048;  // pairs a project workgroup's slot can hold (== its partition of splats): 11-bit starts
 constexpr uint32_t kSlotHistWords = 384;  // what a slot leaves per partition (slot_emit.h): counts of key bits 0-7 and 8-15,
                                           // starts of the digit-0 groups — 16-bit values, two per word
@@ -107,8 +110,11 @@ struct OsLaunch
   uint32_t*       status   = nullptr;  // 3 x osSortStatusWords(osSortMaxParts(...)) words, zero on first use
   FrameCounters*  ctr      = nullptr;  // errorFlags |= kErrSpinTimeout if a look-back wait ever gives up
   bool            allowRemap = true;
-  uint32_t        partMin    = 0;      // smallest partition size the passes may choose on the device (k_osort.hip: osPartOf); 0 = MGS_OS_PART_MIN or, by default, kOsPart = fixed
-  uint32_t        resSlots   = 0;      // workgroups of a pass the device holds at once; 0 = 4 per CU of the current device (126 VGPRs, 36-40 KB of LDS)
+  // required: every caller fills these from its scene and tuning() (no defaults here)
+  uint32_t        partMin      = 0;    // smallest partition size the passes may choose on the device (k_osort.hip: osPartOf; Tuning::osPartMin,
+                                       // default 1 536; kOsPart = fixed partitions); the status words were sized by osSortMaxParts with it
+  uint32_t        resSlots     = 0;    // workgroups of a pass the scene's device holds at once: CUs x MGS_OS_WAVES (126 VGPRs, 36-40 KB of LDS)
+  uint32_t        flatLookback = 0;    // != 0: the flat level 2 of the look-back where it applies (k_osort.hip; Tuning::osFlat)
 };
 
 // the per-frame sort state of one context, contiguous so that the frame's first kernel zeroes it in one sweep
@@ -140,7 +146,7 @@ __device__ __forceinline__ uint32_t* frameStatSlotFromOs(const OsPlan* osPlan /*
 }
 #endif
 
-uint32_t osSortMaxParts(uint32_t maxElems);
+uint32_t osSortMaxParts(uint32_t maxElems, uint32_t partMin);
 inline uint32_t osSortChunks(uint32_t prjParts) { return (prjParts + kOsChunk - 1u) / kOsChunk; }
 size_t   osSortStatusWords(uint32_t maxParts);
 void     launchOsSortClearPlan(hipStream_t stream, OsPlan* plan);
