@@ -25,9 +25,10 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 4 /* 2: MgsFrameParams grew the 3DGUT fields; loader, strip-exchange and debug entry points added;
+#define MGS_ABI_VERSION 5 /* 2: MgsFrameParams grew the 3DGUT fields; loader, strip-exchange and debug entry points added;
                             3: stochastic splats, depth of field, temporal accumulation (MgsFrameParams 256 -> 288 bytes);
-                            4: MgsFrameOut 80 -> 88 bytes (escape_count) */
+                            4: MgsFrameOut 80 -> 88 bytes (escape_count);
+                            5: occluder entry points (mgs_frame_set_occluder, mgs_frame_upload_occluder); no struct changed */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -153,6 +154,41 @@ void mgs_frame_context_destroy(MgsScene context);
  * sets bit 0 of error_flags (the analogue of the reference's fixed-size sorting buffers, splat_set_manager_vk.cpp:2304-2360,
  * which are sized for the splat count and cannot overflow because a quad is not a list entry). */
 int  mgs_scene_set_list_capacity(MgsScene scene_or_context, uint64_t entries);
+/* ---- occluder: splats composited with the caller's opaque geometry.  Replaces the mesh passes of renderHybridPipeline
+ * (src/gaussian_splatting.cpp:697-805): the depth pre-pass the splats are tested against (test on, write off, :1377-1395) and the
+ * composition final = meshColor * (1 - dstAlpha) + splatColor (:2343-2356); in back-to-front mode the meshes are drawn first and the
+ * splats blend over them (:836-843, :2066-2087).  The caller rasterises its own geometry (mesh loading and shading are out of
+ * scope) and binds the two images that yields.
+ *
+ * Bind the images for the following frames of this handle (scene or frame context; per handle, like
+ * mgs_scene_set_list_capacity).  depth_device: [height][width] float32, row 0 = NDC y -1 (the frame's own layout), window depth
+ * in [0,1] made with the SAME proj as the frame (clip z in [0,1]); 1.0 = no geometry (the reference's depth clear).
+ * color_device: [height][width][4] float32 linear, or NULL (= transparent black).  Caller-owned device memory, read on the handle's
+ * stream by every later frame until re-bound; the caller may rewrite the contents between frames, ordered on that stream, without
+ * re-binding.  NULL depth unbinds both.  A frame whose params width/height differ from the bound size: MGS_ERR_INVALID_ARG.
+ *
+ * Per pixel, with D the bound depth and z_i the ndc depth of splat i's centre (every quad of the reference is emitted at that one
+ * depth, threedgs_raster.mesh.slang:286):
+ *   - a fragment of splat i exists only if z_i <= D.  LESS_OR_EQUAL is what the reference states wherever it names the operator
+ *     for blended geometry over a depth pre-pass (:1489-1493); the splat pipelines inherit the default of a pipeline-state class
+ *     that is not part of the reference tree, so PARITY OF THE OPERATOR IS UNPINNED (LESS would differ only where z_i == D
+ *     bit for bit).  A NaN depth passes nothing.
+ *   - z_i is computed by the operations of the depth key (dist.comp.slang:55-62), not by those of the quad's vertex
+ *     (mesh.slang:175-178): the same quantity with another product order, a last-bit difference of the kind documented for the
+ *     front end.  It makes the per-bin lists exactly monotone in the tested value, so that a region whose remaining list lies
+ *     behind the geometry stops early without ever changing a pixel (MGS_SORT_GPU_RADIX; MGS_SORT_CPU_ASYNC orders by plane
+ *     distance and only tests per fragment).
+ *   - MGS_ALPHA_COVERAGE: rgb = C + T * color.rgb, a = 1 - T (the geometry's alpha is ignored);
+ *     MGS_ALPHA_SUM:      rgb = C + T * color.rgb, a = sum(alpha of the fragments that passed) + color.a.
+ *     C, T are the fp32 accumulators; the target conversion happens after the background term.
+ *   - surface_outputs: fragments that fail the test take no part in picked depth, picked id or integrated normal.
+ * Works with mgs_render, strips (the images are full-frame; a strip indexes its own rows), mgs_render_gathered, frame contexts,
+ * both sort modes, graph replay on and off.  MGS_SORT_STOCHASTIC with an occluder bound: MGS_ERR_UNSUPPORTED.  Temporal
+ * accumulation needs nothing special.  With nothing bound a frame is what it was before ABI 5. */
+int  mgs_frame_set_occluder(MgsScene scene_or_context, const float* depth_device, const float* color_device, int width, int height);
+/* host convenience: copies into device buffers the handle owns (waits for the handle's frames in flight first), then binds them;
+ * NULL depth_host unbinds */
+int  mgs_frame_upload_occluder(MgsScene scene_or_context, const float* depth_host, const float* color_host, int width, int height);
 /* device bytes held by the committed scene data (shared by all its contexts) and by this handle's working set */
 int  mgs_scene_memory_usage(MgsScene scene_or_context, uint64_t* scene_bytes, uint64_t* working_bytes);
 /* The device keeps every splat set in a spatially coherent STORAGE ORDER (Morton order of the centres;

@@ -3,6 +3,10 @@
 
   python tools/mgs_render.py scene.ply|scene.spz|scene.splat|syn:<n> out.png [--size W H] [--eye x y z]
                              [--center x y z] [--fov deg] [--flip-y] [--sh-format 0|1|2] [--rgba-format 0|1|2]
+                             [--occluder-depth FILE.npy [--background FILE.npy]]
+
+--occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
+depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear colour of that geometry, shown through the splats.
 
 PNG = linear RGB clamped to [0,1] over a black background, 8 bit, no tonemap — like the reference's
 screenshot path (gaussian_splatting_ui.cpp:508-540).  Needs an MI355X.
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--flip-y", action="store_true")
     ap.add_argument("--sh-format", type=int, default=0)
     ap.add_argument("--rgba-format", type=int, default=0)
+    ap.add_argument("--occluder-depth", default=None, metavar="FILE.npy")
+    ap.add_argument("--background", default=None, metavar="FILE.npy")
     a = ap.parse_args()
     if a.scene.startswith("syn:"):
         ss = mgs.SplatSet.from_arrays(**synth.make_scene(int(a.scene[4:])))
@@ -42,6 +48,14 @@ def main():
     p = capi.default_params(W, H)
     capi.set_camera(p, V, P, a.eye)
     p.collect_timings = 1
+    if a.background and not a.occluder_depth:
+        ap.error("--background needs --occluder-depth")
+    if a.occluder_depth:
+        depth = np.load(a.occluder_depth)
+        back = np.load(a.background) if a.background else None
+        if depth.shape != (H, W) or (back is not None and back.shape != (H, W, 4)):
+            ap.error(f"--occluder-depth must be [{H}, {W}] and --background [{H}, {W}, 4]")
+        scene.upload_occluder(depth, back)
     o = scene.render(p)
     img = scene.download_frame(p).astype(np.float32)
     print(f"{scene.splat_count} splats, {o.frustum_count} in frustum, {o.sorted_count} sorted, {o.tile_pairs} bin records, "

@@ -113,6 +113,8 @@ def load_library():
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
         "mgs_scene_set_list_capacity": (C.c_int, [vp, C.c_uint64]),
+        "mgs_frame_set_occluder": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+        "mgs_frame_upload_occluder": (C.c_int, [vp, P(F), P(F), C.c_int, C.c_int]),
         "mgs_scene_download_set": (C.c_int, [vp, C.c_int, C.c_int, P(F), C.c_size_t]),
         "mgs_scene_storage_order": (C.c_int, [vp, C.c_int, P(C.c_uint32), C.c_size_t]),
         "mgs_frame_params_default": (None, [P(FrameParams)]),
@@ -155,6 +157,7 @@ EXPORTED_SYMBOLS = [
     "mgs_splatset_destroy", "mgs_scene_create", "mgs_scene_destroy", "mgs_scene_set_stream", "mgs_instance_add",
     "mgs_instance_set_transform", "mgs_scene_commit", "mgs_scene_splat_count", "mgs_scene_storage_order", "mgs_scene_download_set",
     "mgs_frame_context_create", "mgs_frame_context_destroy", "mgs_scene_memory_usage", "mgs_scene_set_list_capacity",
+    "mgs_frame_set_occluder", "mgs_frame_upload_occluder",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -337,6 +340,31 @@ class Scene:
 
     def set_list_capacity(self, entries):
         _check(self._lib.mgs_scene_set_list_capacity(self._h, int(entries)))
+
+    # ---- the caller's opaque geometry: splats are depth-tested against it, its colour shows through them ----
+    def set_occluder(self, depth_ptr, color_ptr, width, height):
+        """bind device images for the following frames of this handle (mgs_frame_set_occluder): depth_ptr float32[H,W] window
+        depth in [0,1] made with the frame's proj (1.0 = no geometry), color_ptr float32[H,W,4] linear or 0/None.  The memory stays
+        the caller's; its contents are read by every frame until re-bound.  The test is z_splat <= depth (LESS_OR_EQUAL; the
+        reference does not pin the operator for the splat pipelines)."""
+        _check(self._lib.mgs_frame_set_occluder(self._h, C.c_void_p(depth_ptr or None), C.c_void_p(color_ptr or None),
+                                                int(width), int(height)))
+
+    def upload_occluder(self, depth, color=None):
+        """host convenience (mgs_frame_upload_occluder): depth float32[H,W], color float32[H,W,4] or None, copied into buffers
+        the handle owns"""
+        d = _f32(depth)
+        if d.ndim != 2:
+            raise ValueError("upload_occluder: depth must be [height, width]")
+        c = None
+        if color is not None:
+            c = _f32(color)
+            if c.shape != d.shape + (4,):
+                raise ValueError("upload_occluder: color must be [height, width, 4]")
+        _check(self._lib.mgs_frame_upload_occluder(self._h, _fp(d), None if c is None else _fp(c), d.shape[1], d.shape[0]))
+
+    def clear_occluder(self):
+        _check(self._lib.mgs_frame_set_occluder(self._h, None, None, 0, 0))
 
     def memory_usage(self):
         """(scene_bytes, working_bytes): the committed data shared by all contexts, and this handle's working set"""

@@ -140,6 +140,25 @@ struct CompositeArgs
   const Inst* instTable;      // all instances (device memory, rebuilt at commit); used when nInstances > kMaxInlineInstances
 };
 
+// ... and what the occluder instantiations (MODE bit 4, mgs_frame_set_occluder) receive: the same, plus the caller's images.  A type
+// of its own so that the other instantiations keep their argument block — and with it their code — byte for byte.  By value like
+// the rest: the pointers are part of the captured graph's key (binding other images takes another graph), the images' CONTENTS
+// are read every frame.
+struct CompositeArgsOcc : CompositeArgs
+{
+  const float*  occDepth;     // [height][width] window depth of the caller's geometry
+  const float4* occColor;     // [height][width] linear RGBA of that geometry, nullptr = transparent black
+  int32_t       occStop;      // 1: the lists are sorted by the depth key (GPU sort): a record behind every pixel ends the walk
+};
+
+// the caller's geometry as the compositors' launchers receive it
+struct Occluder
+{
+  const float* depth = nullptr;
+  const float* color = nullptr;
+  bool         sortedByKey = false;
+};
+
 // projected splat record consumed by the compositor: 32 B = half a 64-byte sector, 16-B aligned.  It holds only what
 // the per-fragment arithmetic and the region cull need; base colour, view direction and fragCoord.z are rebuilt by the
 // compositor for the records it stages (a quarter of them), from the splat's own buffers.

@@ -441,14 +441,37 @@ constexpr int kGutBatch = 256;  // list entries scanned per round == staging cap
 
 // XT 1 (2: + the non-quadratic particle kernels, the surface side outputs and their LDS; 3: + NORMAL_METHOD_ISO_SURFACE): the variant with depth of field (frag.slang:104-109, cameras.h.slang:85-108), stochastic splats (:150-172) and/or
 // a particle kernel other than the quadratic one, and/or the surface side outputs (picked depth, splat id, integrated normal)
-template <int SHF, int XT>
+// OCC: occluder (mgs_frame_set_occluder): fragments depth-tested against occDepth with the record's key depth (kernels_common.h:
+// keyDepthNdcZ, staged in the free lane of the record's second quad), the caller's colour added behind them; occStop (lists sorted by
+// the depth key): a pixel whose last record failed the test is finished, every later record fails too
+struct GutOccArgs
+{
+  const float*  depth;  // [height][width] window depth of the caller's geometry
+  const float4* color;  // [height][width] linear RGBA of that geometry, nullptr = transparent black
+  int32_t       stop;   // 1: the lists are sorted by the depth key
+};
+template <class T>
+__device__ __forceinline__ const T& firstArg(const T& a) { return a; }
+// (OCC's extra argument is a parameter pack so that the instantiations without an occluder keep their argument block as it was)
+template <int SHF, int XT, bool OCC = false, class... OccArg>
 __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restrict__ Ap, const uint2* __restrict__ ranges,
                                                        const uint32_t* __restrict__ valX, const uint32_t* __restrict__ valY,
                                                        const SortPlan* __restrict__ plan, const GutRec* __restrict__ rec,
                                                        void* __restrict__ outImage, int halfOut, FrameCounters* __restrict__ ctr,
                                                        float* __restrict__ outDepth, uint32_t* __restrict__ outSplatId,
-                                                       float4* __restrict__ outNormal)
+                                                       float4* __restrict__ outNormal, const OccArg... occArg)
 {
+  static_assert(sizeof...(OccArg) == (OCC ? 1 : 0), "the occluder variant takes one GutOccArgs");
+  const float*  occDepth = nullptr;
+  const float4* occColor = nullptr;
+  int           occStop  = 0;
+  if constexpr(OCC)
+  {
+    const GutOccArgs& O = firstArg(occArg...);
+    occDepth = O.depth;
+    occColor = O.color;
+    occStop  = O.stop;
+  }
   __shared__ float4   s_r[kGutBatch][6];
   __shared__ uint32_t s_gid[XT ? kGutBatch : 1];
   __shared__ float4   s_n[XT >= 2 ? kGutBatch : 1];  // surface outputs (XT 2): world normal of the record (.w = 1: minus the pixel's ray)
@@ -497,6 +520,10 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
   const int      bin   = (ty >> F.binShiftY) * F.binsX + (tx >> F.binShiftX);
   const uint2    range = ranges[bin];
   float T = (inside && rayOk) ? 1.0f : 0.0f, cr = 0.f, cg = 0.f, cb = 0.f, asum = 0.f;
+  float occD = 0.0f;          // this pixel's bound depth (-inf outside the image; NaN passes nothing)
+  bool  occBehind = !inside;  // the last record seen lies behind it
+  if constexpr(OCC)
+    occD = inside ? occDepth[(size_t)py * F.width + px] : -__builtin_huge_valf();
   const bool surf = XT >= 2 && F.surfaceOutputs != 0;
   float      nx = 0.f, ny = 0.f, nz = 0.f, pickZ = 0.f;
   uint32_t   pickId = 0xFFFFFFFFu;
@@ -554,8 +581,11 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
       // response * density) > 1/255 and response > kMin  <=>  response > max(kMin, 1 / (255 density)) — a per-record cutoff
       // that takes the slot of the box extents (needed above only)
       const float rcut = (c5.w > F.alphaCull) ? fmaxf(F.kernelMinResponse, 1.0f / (255.0f * fmaxf(c5.w, 1e-30f))) : 3.0e38f;
+      float zo = 0.0f;
+      if constexpr(OCC)
+        zo = keyDepthNdcZ(I.model, F.view, F.proj, I.centers[3 * (size_t)li], I.centers[3 * (size_t)li + 1], I.centers[3 * (size_t)li + 2]);
       s_r[pos][0] = r0;
-      s_r[pos][1] = make_float4(r1.x, r1.y, rcut, 0.0f);
+      s_r[pos][1] = make_float4(r1.x, r1.y, rcut, zo);
       s_r[pos][2] = r2;
       s_r[pos][3] = r3;
       s_r[pos][4] = r4;
@@ -635,7 +665,9 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
         }
       }
       const float al    = fminf(F.alphaClamp, resp * c4.w);          // :263
-      const bool  hit   = inQuad && resp > a1.z && T >= tMin;
+      bool        hit   = inQuad && resp > a1.z && T >= tMin;
+      if constexpr(OCC)
+        hit = hit && a1.w <= occD;  // the depth test: LESS_OR_EQUAL, one z per record
       float       op    = hit ? (noGauss ? 1.0f : al) : 0.0f;
       if constexpr(XT != 0)
       {
@@ -698,9 +730,14 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
         }
       }
     }
-    if(early)
+    if constexpr(OCC)
     {
-      if(T >= tMin)
+      if(fill > 0u)
+        occBehind = !inside || s_r[fill - 1u][1].w > occD;  // (the batch's last record has its largest z)
+    }
+    if(early || (OCC && occStop != 0))
+    {
+      if((T >= tMin) && !(OCC && occStop != 0 && occBehind))
         s_live = 1u;  // benign race: every writer stores 1
       __syncthreads();
       if(s_live == 0u)
@@ -717,8 +754,21 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
   }
   if(!inside)
     return;
-  const float alphaOut = F.alphaMode == 1 ? asum : 1.0f - ((inside && rayOk) ? T : 1.0f);
+  float alphaOut = F.alphaMode == 1 ? asum : 1.0f - ((inside && rayOk) ? T : 1.0f);
   const size_t pix = (size_t)py * F.width + px;
+  if constexpr(OCC)
+  {  // the caller's geometry behind the splats (k_raster.hip has the rule); a pixel without a valid ray has T = 1 here
+    if(occColor)
+    {
+      const float4 bg = occColor[pix];
+      const float  Tb = rayOk ? T : 1.0f;
+      cr += Tb * bg.x;
+      cg += Tb * bg.y;
+      cb += Tb * bg.z;
+      if(F.alphaMode == 1)
+        alphaOut += bg.w;
+    }
+  }
   if constexpr(XT >= 2)
   {
     if(surf)
@@ -1026,13 +1076,16 @@ void launchProjectGut(hipStream_t stream, const FrameArgs& args, const FrameArgs
 
 void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs* dArgs, const uint2* ranges, const uint32_t* valX,
                         const uint32_t* valY, const SortPlan* planPairs, const GutRec* rec, void* image, int halfOut,
-                        FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal)
+                        FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal,
+                        const Occluder& occ)
 {
   const int tiles = A.f.tilesX * (A.f.stripRow1 - A.f.stripRow0);
   if(tiles <= 0)
     return;
   const bool extras = A.f.dofMode != 0 || A.f.stochastic != 0 || A.f.kernelDegree != 2 || A.f.surfaceOutputs != 0;
-  const bool packedOk = A.f.kernelDegree == 2 && A.f.surfaceOutputs == 0 && (A.f.alphaMode == 0 || A.f.stochastic != 0);
+  // (a frame with an occluder runs on the one-pixel-per-lane compositor, whatever its mode)
+  const bool packedOk = A.f.kernelDegree == 2 && A.f.surfaceOutputs == 0 && (A.f.alphaMode == 0 || A.f.stochastic != 0) && !occ.depth;
+  const GutOccArgs occArgs{occ.depth, reinterpret_cast<const float4*>(occ.color), occ.sortedByKey ? 1 : 0};
   if(packedOk)
   {  // the quadratic-kernel modes without side outputs run on the packed two-pixels-per-lane compositor
     // all bins of the frame are enumerated (the bin order of the binning stage is over the whole frame; regions outside a
@@ -1064,10 +1117,22 @@ void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs*
 #define MGS_LAUNCH(SHF, XT)                                                                                                          \
   hipLaunchKernelGGL((k_composite_gut<SHF, XT>), dim3(tiles), dim3(256), 0, stream, dArgs, ranges, valX, valY, planPairs, rec, image, \
                      halfOut, ctr, outDepth, outSplatId, outNormal)
+#define MGS_LAUNCH_OCC(SHF, XT)                                                                                                      \
+  hipLaunchKernelGGL((k_composite_gut<SHF, XT, true, GutOccArgs>), dim3(tiles), dim3(256), 0, stream, dArgs, ranges, valX, valY,     \
+                     planPairs, rec, image, halfOut, ctr, outDepth, outSplatId, outNormal, occArgs)
 #define MGS_LAUNCH_X(SHF)            \
   do                                 \
   {                                  \
-    if(A.f.surfaceOutputs != 0 && A.f.normalMethod == 1) \
+    if(occ.depth)                    \
+    {                                \
+      if(A.f.surfaceOutputs != 0 && A.f.normalMethod == 1) \
+        MGS_LAUNCH_OCC(SHF, 3);      \
+      else if(A.f.surfaceOutputs != 0 || A.f.kernelDegree != 2) \
+        MGS_LAUNCH_OCC(SHF, 2);      \
+      else                           \
+        MGS_LAUNCH_OCC(SHF, 1);      \
+    }                                \
+    else if(A.f.surfaceOutputs != 0 && A.f.normalMethod == 1) \
       MGS_LAUNCH(SHF, 3);            \
     else if(A.f.surfaceOutputs != 0 || A.f.kernelDegree != 2) \
       MGS_LAUNCH(SHF, 2);            \
@@ -1083,6 +1148,7 @@ void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs*
   else
     MGS_LAUNCH_X(2);
 #undef MGS_LAUNCH_X
+#undef MGS_LAUNCH_OCC
 #undef MGS_LAUNCH
 }
 

@@ -9,6 +9,7 @@
 // accumulate front-to-back with transmittance, which is the same sum in exact arithmetic:
 //   C = sum_i c_i a_i prod_{j nearer than i} (1 - a_j).
 #include <cstring>
+#include <type_traits>
 #include <cstdio>
 #include <vector>
 
@@ -944,9 +945,13 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 // MODE bit 0: additive alpha (no early-out), bit 1: DISABLE_OPACITY_GAUSSIAN, bit 2: surface side outputs,
 // bit 3: stochastic splats (frag.slang:265-290: a fragment is accepted with probability alpha and written opaque; the
-// depth test keeps the nearest accepted one == the first accepted one of the nearest-first list); SHF: SH storage format
+// depth test keeps the nearest accepted one == the first accepted one of the nearest-first list); bit 4: occluder
+// (mgs_frame_set_occluder: fragments depth-tested against the caller's depth image, the caller's colour behind them); SHF: SH storage format
 constexpr bool surf_lds(int mode) { return (mode & 4) != 0; }
-constexpr bool sum_walk(int mode) { return (mode & 1) != 0 && (mode & 4) == 0; }  // MGS_ALPHA_SUM without surface outputs
+constexpr bool occ_lds(int mode) { return (mode & 16) != 0; }
+// MGS_ALPHA_SUM without surface outputs and without an occluder (the saturated-tail walks sum fragments without looking at them one
+// by one; with an occluder every fragment is tested, so that mode takes the general walk, as the surface outputs do)
+constexpr bool sum_walk(int mode) { return (mode & 1) != 0 && (mode & 4) == 0 && (mode & 16) == 0; }
 #ifndef MGS_SUM_ENTRIES
 #define MGS_SUM_ENTRIES MGS_CMP_ENTRIES
 #endif
@@ -975,7 +980,7 @@ constexpr bool sum_walk(int mode) { return (mode & 1) != 0 && (mode & 4) == 0; }
 #define MGS_CMP_WAVES 6
 #endif
 template <int MODE, int SHF>
-__global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const CompositeArgs F, const uint2* __restrict__ ranges,
+__global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const std::conditional_t<occ_lds(MODE), CompositeArgsOcc, CompositeArgs> F, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ valX, const uint32_t* __restrict__ valY,
                                                    const SortPlan* __restrict__ plan, const SplatRec* __restrict__ rec,
                                                    void* __restrict__ outImage, int halfOut, FrameCounters* __restrict__ ctr,
@@ -1004,6 +1009,8 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
   __shared__ uint32_t s_g[cCap];  // global id: what the deferred shading needs
   __shared__ float    s_z[surf_lds(MODE) ? cCap : 1];  // fragCoord.z of the record (surface outputs only)
   __shared__ float4   s_n[surf_lds(MODE) ? cCap : 1];  // world normal of the record (surface outputs only)
+  __shared__ float    s_zo[occ_lds(MODE) ? cCap : 1];  // the record's tested depth: ndc z as the depth key has it (occluder only)
+  __shared__ float    s_dmax[occ_lds(MODE) ? 4 : 1];   // per wave: the largest bound depth of its pixels (occluder only)
   __shared__ uint32_t s_wc[2][cEnt][4];
   __shared__ uint8_t  s_m[cCap];  // which of the 4 quarters (waves) the record's footprint touches
   // MGS_ALPHA_SUM without surface outputs: s_a = (k1, k2, log2 opacity, cutoff term) feeds the saturated waves' two-quad walk
@@ -1055,6 +1062,7 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
   constexpr bool noGauss = (MODE & 2) != 0;
   constexpr bool surf    = (MODE & 4) != 0;  // FTB side outputs: picked depth + the splat that set it (frag.slang:320-349)
   constexpr bool stoch   = (MODE & 8) != 0;
+  constexpr bool occ     = (MODE & 16) != 0;
   constexpr bool sumWalk = sum_walk(MODE);
   constexpr bool fold    = MGS_CMP_FOLD != 0;  // s_a = (k1, k2, log2 a, cutoff term), s_b = (p1x, p2x, p1y, p2y)  // saturated waves only sum alpha (s_a layout: see s_t)
   constexpr float kSumBig = 1073741824.0f;   // 2^30: (log2 alpha - cutoff) * 2^30, clamped to [0, 1], is the fragment's 0 / 1 weight
@@ -1087,6 +1095,27 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
   // retires at this point) — they are only SUMMED: no colour, no transmittance, and once all four waves are there the batch is
   // not shaded either (the SH sum is most of a staged record's cost).  The switch is checked per record, like the retirement.
   bool waveSat = waveDone, allSat = false;  // (a wave without pixels inside the image has nothing to saturate)
+  // Occluder: D = the bound depth of this lane's two pixels (-inf outside the image; a NaN stays a NaN and passes nothing).  A fragment
+  // of a record exists iff z <= D, z = the record's key depth (kernels_common.h: keyDepthNdcZ).  With a GPU-sorted list (F.occStop)
+  // the records arrive in ascending z, so a record with z > max D of a wave ends that wave exactly as saturation does, and a
+  // record with z > max D of the region is not even shaded.
+  v2f   occD = {0.f, 0.f};
+  float waveMaxD = 0.0f, regMaxD = 0.0f;
+  if constexpr(occ)
+  {
+    constexpr float kNegInf = -__builtin_huge_valf();
+    occD.x  = in0 ? F.occDepth[(size_t)py * (size_t)F.width + (size_t)px] : kNegInf;
+    occD.y  = in1 ? F.occDepth[(size_t)py * (size_t)F.width + (size_t)(px + 8)] : kNegInf;
+    float m = fmaxf(fmaxf(occD.x, kNegInf), fmaxf(occD.y, kNegInf));  // (fmaxf drops a NaN)
+#pragma unroll
+    for(int o = 32; o > 0; o >>= 1)
+      m = fmaxf(m, __shfl_xor(m, o, 64));
+    waveMaxD = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m)));
+    if(lane == 0)
+      s_dmax[w] = waveMaxD;
+    __syncthreads();
+    regMaxD = fmaxf(fmaxf(s_dmax[0], s_dmax[1]), fmaxf(s_dmax[2], s_dmax[3]));
+  }
 
   uint32_t hi   = range.y;
   uint32_t fill = 0;  // records currently in the LDS batch
@@ -1309,6 +1338,16 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
       // was measured: the extra live registers spill, 0.140 -> 0.179 ms.)
       const float4 col = I.rgba[li];  // fetchColor, dequantised at commit
       const float  cpx = I.centers[3 * (size_t)li], cpy = I.centers[3 * (size_t)li + 1], cpz = I.centers[3 * (size_t)li + 2];
+      if constexpr(occ)
+      {
+        const float zo = keyDepthNdcZ(Ap->inst[instIdx].model, Ap->f.view, Ap->f.proj, cpx, cpy, cpz);
+        s_zo[j]        = zo;
+        if(F.occStop && zo > regMaxD)
+        {  // behind the occluder at every pixel of the region: no wave walks it, nothing to shade
+          s_m[j] = 0;
+          continue;
+        }
+      }
       const float* cam = Ap->inst[instIdx].camModel;
       float        dx = cpx - cam[0], dy = cpy - cam[1], dz = cpz - cam[2];
       const float  dl = rsqrtf(dx * dx + dy * dy + dz * dz);
@@ -1411,6 +1450,16 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
         {
           const uint32_t j = j0 + (uint32_t)__builtin_ctzll(hits);
           hits &= hits - 1ull;
+          float zo = 0.0f;
+          if constexpr(occ)
+          {
+            zo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s_zo[j])));
+            if(F.occStop && zo > waveMaxD)
+            {  // this record and every later one of the list lie behind the occluder at every pixel of the wave
+              waveDone = true;
+              break;
+            }
+          }
 #if MGS_CMP_FOLD
           // alpha = a 2^-q as 2^(log2 a - q); the fragment rule of frag.slang:242-262 (discard A > 8, discard alpha <= 1/255: one
           // cutoff per record, stage A) as clamp((log2 a - q) * 2^30 + cutoff term) in {0, 1} — a packed fma instead of two
@@ -1461,6 +1510,11 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
           ah.y = (q.y <= qc) ? al.y : 0.0f;
 #endif
 #endif
+          if constexpr(occ)
+          {  // the depth test: LESS_OR_EQUAL against the pixel's bound depth, one z per record
+            ah.x = (zo <= occD.x) ? ah.x : 0.0f;
+            ah.y = (zo <= occD.y) ? ah.y : 0.0f;
+          }
           if constexpr(stoch)
           {  // frag.slang:272-276: seed = xxhash32(uint3(seed, splatId, primitiveID)); accept iff rand(seed) < opacity.
             // primitiveID = 2 * (index of the splat in its mesh workgroup of 32) + triangle; the quad (-1,-1),(1,-1),(1,1),(-1,1)
@@ -1578,11 +1632,16 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
     }
     ++traceIters;
 #endif
+    if constexpr(occ)
+    {  // records the wave's quarter mask skipped count too: the batch's last record has the batch's largest z
+      if(F.occStop && fill > 0u && s_zo[fill - 1u] > waveMaxD)
+        waveDone = true;
+    }
     fill = 0;
-    const int allFlag = __syncthreads_and((early ? waveDone : waveSat) ? 1 : 0);
+    const int allFlag = __syncthreads_and(((early || occ) ? waveDone : waveSat) ? 1 : 0);
     MGS_TRACE_PHASE(traceB)
-    const bool allDone = early && allFlag != 0;
-    allSat             = !early && !surf && allFlag != 0;  // (surface outputs: the records' depth and normal stay needed)
+    const bool allDone = (early || occ) && allFlag != 0;
+    allSat             = !early && !surf && !occ && allFlag != 0;  // (surface outputs: the records' depth and normal stay needed)
     if(allDone || hi <= range.x)
       break;
   }
@@ -1610,8 +1669,22 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const Composit
   {
     if(h ? in1 : in0)
     {
-      const float  r = h ? cr.y : cr.x, g = h ? cg.y : cg.x, b = h ? cb.y : cb.x, ao = h ? aout.y : aout.x;
+      float        r = h ? cr.y : cr.x, g = h ? cg.y : cg.x, b = h ? cb.y : cb.x, ao = h ? aout.y : aout.x;
       const size_t o = (size_t)py * (size_t)F.width + (size_t)(px + 8 * h);
+      if constexpr(occ)
+      {  // the caller's geometry behind the splats: final = splats + T * geometry (gaussian_splatting.cpp:2343-2356); MGS_ALPHA_SUM
+         // adds the geometry's alpha (the blend equations started from a destination that holds it)
+        if(F.occColor)
+        {
+          const float4 bg = F.occColor[o];
+          const float  Th = h ? T.y : T.x;
+          r += Th * bg.x;
+          g += Th * bg.y;
+          b += Th * bg.z;
+          if(!early)
+            ao += bg.w;
+        }
+      }
       if(halfOut == 2)
       {  // RGBA8 UNORM: clamp, scale, round to nearest
         auto q8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
@@ -1717,7 +1790,7 @@ void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* 
 void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges, const uint32_t* valX,
                      const uint32_t* valY, const SortPlan* planPairs, const SplatRec* rec, void* image, int halfOut,
                      int shFormat, FrameCounters* ctr, float* outDepth, uint32_t* outSplatId,
-                     const void* instTable, const FrameArgs* dArgs, float4* outNormal, uint32_t* binCost)
+                     const void* instTable, const FrameArgs* dArgs, float4* outNormal, uint32_t* binCost, const Occluder& occ)
 {
   const FrameConst& F = A.f;
   if(F.stripRow1 <= F.stripRow0)
@@ -1726,12 +1799,12 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
   // a strip have empty regions that exit at once)
   const int nBins   = F.binsX * F.binsY;
   const int per     = ((nBins + 7) / 8) * (1 << (F.binShiftX - 1 + F.binShiftY));  // workgroups per XCD
-  int mode = (F.alphaMode != 0 ? 1 : 0) | ((F.debugFlags & 4) ? 2 : 0) | (F.surfaceOutputs ? 4 : 0);
+  int mode = (F.alphaMode != 0 ? 1 : 0) | ((F.debugFlags & 4) ? 2 : 0) | (F.surfaceOutputs ? 4 : 0) | (occ.depth ? 16 : 0);
   // stochastic splats: opaque writes, so the alpha mode is irrelevant; with the opacity gaussian disabled every fragment is
   // accepted (alpha 1) and the plain path already yields the nearest fragment
   if(F.stochastic && !(F.debugFlags & 4))
     mode = 8 | (F.surfaceOutputs ? 4 : 0);
-  CompositeArgs C;
+  CompositeArgsOcc C;  // (the instantiations without an occluder take its CompositeArgs part)
   std::memset(&C, 0, sizeof(C));
   C.width = F.width; C.height = F.height; C.tilesX = F.tilesX;
   C.binShiftX = F.binShiftX; C.binShiftY = F.binShiftY; C.binsX = F.binsX; C.binsY = F.binsY;
@@ -1749,6 +1822,9 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
     C.inst[i].shDegree     = A.inst[i].shDegree;
   }
   C.instTable = static_cast<const CompositeArgs::Inst*>(instTable);
+  C.occDepth  = occ.depth;
+  C.occColor  = reinterpret_cast<const float4*>(occ.color);
+  C.occStop   = occ.sortedByKey ? 1 : 0;
 #ifdef MGS_CMP_TRACE
   static uint64_t* traceBuf = nullptr;
   const char*      tracePath = std::getenv("MGS_CMP_TRACE_FILE");
@@ -1782,7 +1858,15 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
     case 6: MGS_CMP_FMT(6); break;
     case 7: MGS_CMP_FMT(7); break;
     case 8: MGS_CMP_FMT(8); break;
-    default: MGS_CMP_FMT(12); break;
+    case 12: MGS_CMP_FMT(12); break;
+    case 16: MGS_CMP_FMT(16); break;
+    case 17: MGS_CMP_FMT(17); break;
+    case 18: MGS_CMP_FMT(18); break;
+    case 19: MGS_CMP_FMT(19); break;
+    case 20: MGS_CMP_FMT(20); break;
+    case 21: MGS_CMP_FMT(21); break;
+    case 22: MGS_CMP_FMT(22); break;
+    default: MGS_CMP_FMT(23); break;  // (a stochastic frame with an occluder never gets here: mgs_render refuses it)
   }
 #undef MGS_CMP_FMT
 #undef MGS_CMP

@@ -262,6 +262,20 @@ __device__ __forceinline__ float divExact(float a, float b)
   return a / b;
 }
 
+// ndc z of a splat centre by the very operations the project kernels use for the depth key (dist.comp.slang:55-62: model, view,
+// proj, each product and sum rounded separately, then an IEEE division; their shortcuts are bit-identical to this form).  The
+// occluder test (mgs_frame_set_occluder) compares THIS value with the caller's depth image: it is bit-equal to the depth the
+// bin lists are sorted by, so a nearest-first list is exactly monotone in it and "the current record is behind every pixel of
+// the wave" ends the wave's walk without a margin.
+__device__ __forceinline__ float keyDepthNdcZ(const float* model, const float* view, const float* proj, float x, float y, float z)
+{
+  float wp[4], vp[4], cz, cw;
+  mulMat4Exact(model, x, y, z, 1.0f, wp);
+  mulMat4Exact(view, wp[0], wp[1], wp[2], wp[3], vp);
+  mulMat4ExactZW(proj, vp[0], vp[1], vp[2], vp[3], cz, cw);
+  return divExact(cz, cw);
+}
+
 // ---- fisheye dist-stage cull (CAMERA_TYPE == CAMERA_FISHEYE) -------------------------------------------------------
 // shaders/dist.comp.slang:75-90 culls with projectPointFisheye (threedgut_camera_projections.h.slang:149-171) of the perfect
 // fisheye model (initPerfectFisheyeCamera, threedgut_camera_models.h.slang:120-136: zero radial coefficients, principal point

@@ -51,13 +51,14 @@ void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* 
 void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges, const uint32_t* valX,
                      const uint32_t* valY, const SortPlan* planPairs, const SplatRec* rec, void* image, int halfOut,
                      int shFormat, FrameCounters* ctr, float* outDepth, uint32_t* outSplatId, const void* instTable, const FrameArgs* dArgs,
-                     float4* outNormal, uint32_t* binCost);
+                     float4* outNormal, uint32_t* binCost, const Occluder& occ);
 void launchProjectGut(hipStream_t stream, const FrameArgs& args, const FrameArgs* dArgs, int shFormat, FrameCounters* ctr,
                       uint2* slotPairs, uint32_t* slotCount, GutRec* rec, uint32_t* rect,
                       uint32_t* slotHist2, uint32_t* top16Rec, uint32_t* top16Count, OsPlan* osPlan, const uint32_t* order);
 void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs* dArgs, const uint2* ranges, const uint32_t* valX,
                         const uint32_t* valY, const SortPlan* planPairs, const GutRec* rec, void* image, int halfOut,
-                        FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal);
+                        FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal,
+                        const Occluder& occ);
 constexpr uint32_t kPart = 2048;  // == kPrjPart == kSortPart == kBinPart
 }  // namespace mgs
 
@@ -282,6 +283,11 @@ struct MgsScene_t
 
   std::shared_ptr<SceneData> d;   // shared with the frame contexts (mgs_frame_context_create)
   uint64_t    listCapacityOverride = 0;  // mgs_scene_set_list_capacity: entries of the per-bin lists (0 = 32 per splat)
+  // the caller's opaque geometry (mgs_frame_set_occluder), per handle: caller-owned images, or the library-owned copies below
+  const float* occDepth = nullptr;
+  const float* occColor = nullptr;
+  int          occW = 0, occH = 0;
+  DevBuf<float> occOwnDepth, occOwnColor;  // mgs_frame_upload_occluder
   bool        isContext = false;  // a frame context: own stream, working buffers and graphs; the scene data is the parent's
   uint64_t    wsEpoch   = ~0ull;  // d->epoch the working set below was sized for
 
@@ -310,7 +316,7 @@ struct MgsScene_t
   struct GraphKey
   {
     int32_t v[16];
-    const void* p[2];
+    const void* p[4];  // image, picked depth, occluder depth, occluder colour
     bool operator<(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(*this)) < 0; }
   };
   std::map<GraphKey, hipGraphExec_t> graphs;  // captured frames, one per (resolution, strip, mode); cleared at commit
@@ -422,7 +428,7 @@ static int guarded(const char* what, Fn&& fn) noexcept
 extern "C" {
 
 const char* mgs_last_error(void) { return lastError(); }
-const char* mgs_version(void) { return "mgs 0.4 (gfx950, ABI 4)"; }
+const char* mgs_version(void) { return "mgs 0.4 (gfx950, ABI 5)"; }
 
 static int mgs_splatset_load_impl(const char* path, MgsSplatSet* out);
 int mgs_splatset_load(const char* path, MgsSplatSet* out)
@@ -778,7 +784,7 @@ void mgs_scene_destroy(MgsScene s)
   s->surfDepth.release(); s->surfId.release(); s->surfNormal.release(); s->accum.release(); s->fstate.release(); s->dbinMasks.release();
   for(auto& g : s->graphs) (void)hipGraphExecDestroy(g.second);
   s->graphs.clear();
-  s->ranges.release(); s->image.release(); s->cpuDistDev.release();
+  s->ranges.release(); s->image.release(); s->cpuDistDev.release(); s->occOwnDepth.release(); s->occOwnColor.release();
   s->rsKeys.release(); s->rsVals.release(); s->rsHist.release(); s->rsCount.release(); s->rsPlan.release();
   s->rsPairA.release(); s->rsPairB.release(); s->rsStatus.release(); s->rsOsPlan.release();
   if(s->hCtr) (void)hipHostFree(s->hCtr);
@@ -856,6 +862,66 @@ int mgs_scene_set_list_capacity(MgsScene s, uint64_t entries)
   s->listCapacityOverride = entries;
   s->wsEpoch              = ~0ull;  // the working set is re-sized before the next frame (or by the next commit)
   return MGS_OK;
+}
+
+// ---- occluder: the caller's opaque geometry -----------------------------------------------------------------------------
+// The reference's hybrid pipeline draws the meshes' depth first, tests the splats against it and adds the meshes' colour behind
+// them (src/gaussian_splatting.cpp:697-805, 2343-2356).  The library consumes the two images such a rasterisation yields.
+int mgs_frame_set_occluder(MgsScene s, const float* depthDevice, const float* colorDevice, int width, int height)
+{
+  if(!s)
+  {
+    setError("mgs_frame_set_occluder: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(!depthDevice)
+  {  // unbind both
+    s->occDepth = s->occColor = nullptr;
+    s->occW = s->occH = 0;
+    return MGS_OK;
+  }
+  if(width <= 0 || height <= 0)
+  {
+    setError("mgs_frame_set_occluder: width and height must be positive");
+    return MGS_ERR_INVALID_ARG;
+  }
+  s->occDepth = depthDevice;
+  s->occColor = colorDevice;
+  s->occW     = width;
+  s->occH     = height;
+  return MGS_OK;
+}
+
+static int mgs_frame_upload_occluder_impl(MgsScene s, const float* depthHost, const float* colorHost, int width, int height)
+{
+  if(!s)
+  {
+    setError("mgs_frame_upload_occluder: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(!depthHost)
+    return mgs_frame_set_occluder(s, nullptr, nullptr, 0, 0);
+  if(width <= 0 || height <= 0)
+  {
+    setError("mgs_frame_upload_occluder: width and height must be positive");
+    return MGS_ERR_INVALID_ARG;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  const size_t n = (size_t)width * (size_t)height;
+  // frames in flight may still read the previous copy (and captured graphs point at it): wait before it is rewritten or moved
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if(int rc = s->occOwnDepth.ensure(n)) return rc;
+  HIPCHK(hipMemcpy(s->occOwnDepth.p, depthHost, n * sizeof(float), hipMemcpyHostToDevice));
+  if(colorHost)
+  {
+    if(int rc = s->occOwnColor.ensure(n * 4)) return rc;
+    HIPCHK(hipMemcpy(s->occOwnColor.p, colorHost, n * 4 * sizeof(float), hipMemcpyHostToDevice));
+  }
+  return mgs_frame_set_occluder(s, s->occOwnDepth.p, colorHost ? s->occOwnColor.p : nullptr, width, height);
+}
+int mgs_frame_upload_occluder(MgsScene s, const float* depthHost, const float* colorHost, int width, int height)
+{
+  return guarded("mgs_frame_upload_occluder", [&] { return mgs_frame_upload_occluder_impl(s, depthHost, colorHost, width, height); });
 }
 
 static uint64_t setBytes(const DeviceSet& d)
@@ -2114,6 +2180,25 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     setError("frame: dof_mode / frame_sample_id out of range");
     return MGS_ERR_INVALID_ARG;
   }
+  Occluder occ;
+  if(s->occDepth)
+  {
+    if(s->occW != F.width || s->occH != F.height)
+    {
+      setError("frame: the bound occluder images are " + std::to_string(s->occW) + "x" + std::to_string(s->occH) + ", the frame is " +
+               std::to_string(F.width) + "x" + std::to_string(F.height) + " (mgs_frame_set_occluder)");
+      return MGS_ERR_INVALID_ARG;
+    }
+    if(p->sort_mode == MGS_SORT_STOCHASTIC)
+    {
+      setError("frame: MGS_SORT_STOCHASTIC with an occluder bound is not supported (the reference resolves it through the depth buffer "
+               "itself, a different mechanism); unbind it with mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
+      return MGS_ERR_UNSUPPORTED;
+    }
+    occ.depth       = s->occDepth;
+    occ.color       = s->occColor;
+    occ.sortedByKey = p->sort_mode == MGS_SORT_GPU_RADIX;  // the CPU sorter orders by plane distance, not by the key's depth
+  }
   const void* before[6] = {s->ranges.p, s->image.p, s->surfDepth.p, s->surfId.p, s->surfNormal.p, s->accum.p};
   if((rc = s->ranges.ensure(std::max<uint32_t>(nTiles, 256u)))) return rc;
   if(s->image.n < s->imageBytes)
@@ -2235,11 +2320,11 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     if(gut)
       launchCompositeGut(st, A, s->dArgs.p, s->ranges.p, s->pairVal1.p, s->pairVal0.p, planP, s->recGut.p, s->image.p, half, ctr, s->d->shFormat,
                          F.surfaceOutputs ? s->surfDepth.p : nullptr, F.surfaceOutputs ? s->surfId.p : nullptr,
-                         F.surfaceOutputs ? s->surfNormal.p : nullptr);
+                         F.surfaceOutputs ? s->surfNormal.p : nullptr, occ);
     else
       launchComposite(st, A, s->ranges.p, s->pairVal1.p, s->pairVal0.p, planP, s->rec.p, s->image.p, half, s->d->shFormat, ctr,
                       F.surfaceOutputs ? s->surfDepth.p : nullptr, F.surfaceOutputs ? s->surfId.p : nullptr, s->d->compInst.p,
-                      s->dArgs.p, F.surfaceOutputs ? s->surfNormal.p : nullptr, s->binCost.p);
+                      s->dArgs.p, F.surfaceOutputs ? s->surfNormal.p : nullptr, s->binCost.p, occ);
     if(F.temporalSampling)
       hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, st, s->dArgs.p, s->accum.p, s->image.p, half);
     if(withEvents) HIPCHK(hipEventRecord(fev[5], st));
@@ -2265,6 +2350,8 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     std::memcpy(key.v, kv, sizeof(kv));
     key.p[0] = s->image.p;
     key.p[1] = s->surfDepth.p;
+    key.p[2] = occ.depth;  // the compositors receive the occluder's pointers by value: another binding is another graph
+    key.p[3] = occ.color;
     auto it = s->graphs.find(key);
     if(it == s->graphs.end())
     {
