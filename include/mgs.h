@@ -29,6 +29,10 @@ extern "C" {
                             3: stochastic splats, depth of field, temporal accumulation (MgsFrameParams 256 -> 288 bytes);
                             4: MgsFrameOut 80 -> 88 bytes (escape_count);
                             5: occluder entry points (mgs_frame_set_occluder, mgs_frame_upload_occluder); no struct changed */
+#define MGS_ABI_MINOR 1   /* backward-compatible additions within MGS_ABI_VERSION (same struct sizes, same defaults):
+                            5.1: deferred lighting — MgsFrameParams::reserved_[0] is named lighting_mode (0 = what it was), MgsLight / MgsMaterial,
+                                 mgs_light_default, mgs_material_default, mgs_scene_set_lights, mgs_instance_set_material,
+                                 mgs_frame_download_surface(which = 3), MGS_STAGE_LIGHT */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -68,6 +72,12 @@ enum { MGS_ALPHA_COVERAGE = 0 /* 1-T */, MGS_ALPHA_SUM = 1 /* sum(alpha); disabl
 enum { MGS_NORMAL_MAX_DENSITY_PLANE = 0, MGS_NORMAL_ISO_SURFACE = 1 };
 /* raster pipelines (parameters.h PIPELINE_MESH / PIPELINE_MESH_3DGUT), 3DGUT camera models and quad extents */
 enum { MGS_PIPELINE_3DGS = 0, MGS_PIPELINE_3DGUT = 1 };
+/* lighting of the splat surface — shaderio.h:131-133 (LIGHTING_*), parameters.h:128-132.  The raster-only pipelines only test
+ * "!= disabled" (deferred_shading.comp.slang has no branch on direct / indirect): DIRECT and INDIRECT render the same frame. */
+enum { MGS_LIGHTING_DISABLED = 0, MGS_LIGHTING_DIRECT = 1, MGS_LIGHTING_INDIRECT = 2 };
+/* LightType, shaders/wavefront.h:73-78 */
+enum { MGS_LIGHT_DIRECTIONAL = 0, MGS_LIGHT_POINT = 1, MGS_LIGHT_SPOT = 2 };
+#define MGS_MAX_LIGHTS 64 /* build-defined cap of mgs_scene_set_lights (the reference's light table is a device buffer without one) */
 enum { MGS_CAMERA_PINHOLE = 0, MGS_CAMERA_FISHEYE = 1 };
 enum { MGS_EXTENT_EIGEN = 0, MGS_EXTENT_CONIC = 1 };
 
@@ -135,6 +145,39 @@ int  mgs_instance_set_transform(MgsScene scene, int instance_id, const float tra
  * device buffers (centres, 3D covariances, RGBA, interleaved SH) in the requested formats.
  * Idempotent; call again after changing formats (the reference's --updateData). */
 int  mgs_scene_commit(MgsScene scene, int sh_format, int rgba_format);
+/* ---- lights and materials of the deferred lighting pass (MgsFrameParams::lighting_mode).
+ * MgsLight: the fields of shaderio::LightSource (shaders/wavefront.h:81-93) minus `radius` (soft shadows are ray traced: out of
+ * scope).  direction is the direction the light shines in (the reference derives it from the light instance's rotation applied
+ * to (0,0,-1), light_manager_vk.cpp:470-471); cone angles in degrees; attenuation_mode 0 none, 1 linear, 2 quadratic, 3 physical. */
+typedef struct MgsLight {
+  int32_t type;             /* MGS_LIGHT_*, default MGS_LIGHT_POINT */
+  float   color[3];         /* default 1 1 1 */
+  float   intensity;        /* default 1 */
+  float   position[3];      /* default 0 0 0 */
+  float   range;            /* default 10: point / spot lights shade nothing farther away */
+  float   direction[3];     /* default 0 0 -1 */
+  float   inner_cone_deg, outer_cone_deg; /* default 30, 45 */
+  int32_t attenuation_mode; /* default 2 */
+} MgsLight;
+void mgs_light_default(MgsLight* light); /* fills the defaults above (wavefront.h:81-93) */
+/* The scene's light table, shared by all its frame contexts like the instance transforms (MGS_ERR_STATE on a context handle).
+ * Copies `count` lights; count = 0 restores "no lights", which the lighting pass renders with a headlight at the camera
+ * (createHeadlight, wavefront.h.slang:104-119).  More than MGS_MAX_LIGHTS lights, a type or an attenuation mode out of range:
+ * MGS_ERR_INVALID_ARG.  Takes effect on every context's next frame without a re-commit: the call waits for the frames in
+ * flight on all contexts, then rewrites the device table the lighting pass reads (captured frames are not re-captured). */
+int  mgs_scene_set_lights(MgsScene scene, const MgsLight* lights, int count);
+/* An instance's material: splatMaterial of the splat set instance (shaderio::ObjMaterial, wavefront.h:37-50, reduced to what the
+ * deferred pass reads).  needShading is derived inside as updateMaterialNeedsShading does (wavefront.h:55-59: the length of
+ * diffuse, ambient or specular above 0.001). */
+typedef struct MgsMaterial {
+  float ambient[3], diffuse[3], specular[3], emission[3];
+  float shininess;
+} MgsMaterial;
+/* the splat sets' default (src/splat_set_vk.cpp:128-135): all zero except emission = 1 — fully emissive, the lit frame shows the
+ * splats' own colours */
+void mgs_material_default(MgsMaterial* material);
+/* same ordering rule as mgs_scene_set_lights; valid before and after mgs_scene_commit */
+int  mgs_instance_set_material(MgsScene scene, int instance_id, const MgsMaterial* material);
 uint64_t mgs_scene_splat_count(MgsScene scene); /* getTotalGlobalSplatCount, gaussian_splatting.cpp:369 */
 /* ---- frame contexts: frames in flight over ONE resident scene.
  * The reference keeps a single copy of the splat buffers however many frames its application loop has in flight; that is why
@@ -265,7 +308,30 @@ typedef struct MgsFrameParams {
                                    (default) | MGS_NORMAL_ISO_SURFACE: the fragment's normal is the normal of the kernel ellipsoid
                                    (3 sigma) where the pixel's ray enters it (threedgrt.h.slang:423-497).  The 3DGS pipeline's
                                    mesh shader always uses the max-density plane (threedgs_raster.mesh.slang:219). */
-  int32_t reserved_[1];
+  /* ---- deferred lighting of the splat surface (ABI 5.1; the struct's last word, reserved until then): MGS_LIGHTING_*.  deferred_shading.comp.slang, dispatched
+   * by the raster-only pipelines whenever lightingMode != eLightingDisabled (src/gaussian_splatting.cpp:888-908).  A frame with
+   * lighting on
+   *  - is rendered as if surface_outputs = 1 (needSurfaceInfo, gaussian_splatting.h:169-179) with the caller's depth_iso_threshold,
+   *    thin_particle_threshold, quantize_normals and normal_method; the side outputs are downloadable afterwards;
+   *  - after the compositor (hence after the occluder's background term) and BEFORE temporal accumulation (the reference shades the
+   *    fresh sample and post.comp averages shaded samples) has every pixel of the handle's strip rewritten in place
+   *    (deferred_shading.comp.slang:52-167): integrated normal .w < 0.001 -> pixel untouched; else n = normalize(normal.xyz), world
+   *    position from (pixel + 0.5) / viewport * 2 - 1, the picked depth (0 where none: followed as written), projInverse and
+   *    viewInverse; base colour = the frame's pixel AS STORED in the target format; material = the material of the instance that owns
+   *    the picked splat, each colour times the base colour (id 0xFFFFFFFF: diffuse = base colour, ambient 0.1, specular 0, shininess
+   *    32, no emission); colour = emission + for each light of the scene's table (the headlight when it is empty)
+   *    wavefrontComputeShadingDirectOnly (wavefront.h.slang:104-280,388-403: ambient once PER LIGHT, diffuse by type with range cull,
+   *    attenuation mode and spot cone, specular with max(shininess, 4)) if the material needs shading; the pixel becomes
+   *    (colour, 1.0) in the target format.
+   *  - projInverse / viewInverse: glm::inverse is not part of the reference tree, so the rounding of the inverses is PARITY UNPINNED.
+   *    Here both are computed on the host in double and rounded once to fp32.
+   *  - the normal attachment is RGBA16F in the reference and fp32 here (see mgs_frame_download_surface, which = 2); the lighting
+   *    reads the fp32 one.
+   * MGS_SORT_STOCHASTIC with lighting on: MGS_ERR_UNSUPPORTED.  MGS_ALPHA_SUM with lighting: lit pixels get alpha 1.0 as written.
+   * Works with strips (a strip lights its own rows; the pass is per pixel), mgs_render_gathered, frame contexts, both pipelines, all
+   * targets, both sort modes, graph replay.  Values other than MGS_LIGHTING_*: MGS_ERR_INVALID_ARG.  0 (the default): the frame is
+   * what it was before ABI 5.1. */
+  int32_t lighting_mode;
 } MgsFrameParams;
 
 void mgs_frame_params_default(MgsFrameParams* p); /* fills the defaults cited above */
@@ -274,6 +340,8 @@ enum { MGS_STAGE_PROJECT = 0, MGS_STAGE_SORT = 1, MGS_STAGE_BIN = 2, MGS_STAGE_P
        MGS_STAGE_COMPOSITE = 4, MGS_STAGE_TOTAL = 5,
        MGS_STAGE_CULL = 6, /* the head of MGS_STAGE_PROJECT (included in it): from the frame's upload to the first kernel; the partition
                               cull ran here as a kernel of its own until round 3, it is part of the project kernels now */
+       MGS_STAGE_LIGHT = 7, /* the deferred lighting pass (lighting_mode != 0), 0 otherwise; not part of MGS_STAGE_COMPOSITE, part of
+                               MGS_STAGE_TOTAL */
        MGS_STAGE_COUNT = 8 };
 
 typedef struct MgsFrameOut {
@@ -309,7 +377,12 @@ int mgs_timings_query(MgsScene scene, uint32_t frames_back, float stage_ms[MGS_S
  * which 1: global id (caller's order) of the splat that set it, uint32 (0xFFFFFFFF where none);
  * which 2: integrated normal, float32 x 4 per pixel = sum over the fragments (front to back) of
  *          (world normal * opacity, opacity) * transmittance — the RASTER_NORMAL attachment
- *          (gaussian_splatting.cpp:2090-2107, RGBA16F in the reference, fp32 here) */
+ *          (gaussian_splatting.cpp:2090-2107, RGBA16F in the reference, fp32 here);
+ * which 3: consolidated depth, float32 (depth_consolidate.frag.slang, gaussian_splatting.cpp:807-834,2374-2404): one depth image
+ *          for whatever follows the splats — picked > 0.0001 && picked < D ? picked : D, with D the occluder depth bound when the
+ *          frame was rendered (1.0, the depth clear, where nothing was bound; compare op LESS, :2383).  Computed when asked for,
+ *          from that image's contents at the time of the call (caller-owned images must still be alive).
+ * Available after a frame with surface_outputs = 1 or lighting_mode != 0; MGS_ERR_STATE after any other frame. */
 int mgs_frame_download_surface(MgsScene scene, int which, void* host_dst, size_t bytes);
 /* copy the last frame to the host (screenshot path, gaussian_splatting_ui.cpp:508-540, no tonemap) */
 int mgs_frame_download(MgsScene scene, void* host_dst, size_t bytes);

@@ -4,9 +4,15 @@
   python tools/mgs_render.py scene.ply|scene.spz|scene.splat|syn:<n> out.png [--size W H] [--eye x y z]
                              [--center x y z] [--fov deg] [--flip-y] [--sh-format 0|1|2] [--rgba-format 0|1|2]
                              [--occluder-depth FILE.npy [--background FILE.npy]]
+                             [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
 
 --occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
 depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear colour of that geometry, shown through the splats.
+
+--lighting 1: deferred direct lighting of the splat surface (MgsFrameParams.lighting_mode).  --lights: a JSON list of light dicts
+with the field names of MgsLight (type, color, intensity, position, range, direction, inner_cone_deg, outer_cone_deg,
+attenuation_mode; absent fields keep the reference's defaults); without it the headlight at the camera lights the scene.
+--material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
 
 PNG = linear RGB clamped to [0,1] over a black background, 8 bit, no tonemap — like the reference's
 screenshot path (gaussian_splatting_ui.cpp:508-540).  Needs an MI355X.
@@ -35,6 +41,9 @@ def main():
     ap.add_argument("--rgba-format", type=int, default=0)
     ap.add_argument("--occluder-depth", default=None, metavar="FILE.npy")
     ap.add_argument("--background", default=None, metavar="FILE.npy")
+    ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
+    ap.add_argument("--lights", default=None, metavar="FILE.json")
+    ap.add_argument("--material", type=float, nargs=13, default=None)
     a = ap.parse_args()
     if a.scene.startswith("syn:"):
         ss = mgs.SplatSet.from_arrays(**synth.make_scene(int(a.scene[4:])))
@@ -56,10 +65,21 @@ def main():
         if depth.shape != (H, W) or (back is not None and back.shape != (H, W, 4)):
             ap.error(f"--occluder-depth must be [{H}, {W}] and --background [{H}, {W}, 4]")
         scene.upload_occluder(depth, back)
+    if (a.lights or a.material) and not a.lighting:
+        ap.error("--lights / --material need --lighting 1")
+    if a.lighting:
+        p.lighting_mode = capi.LIGHTING_DIRECT
+        if a.lights:
+            import json
+            with open(a.lights) as f:
+                scene.set_lights([capi.make_light(**l) for l in json.load(f)])
+        if a.material:
+            m = a.material
+            scene.set_material(0, capi.make_material(ambient=m[0:3], diffuse=m[3:6], specular=m[6:9], emission=m[9:12], shininess=m[12]))
     o = scene.render(p)
     img = scene.download_frame(p).astype(np.float32)
     print(f"{scene.splat_count} splats, {o.frustum_count} in frustum, {o.sorted_count} sorted, {o.tile_pairs} bin records, "
-          f"{o.stage_ms[5]:.3f} ms on the GPU")
+          f"{o.stage_ms[5]:.3f} ms on the GPU" + (f" ({o.stage_ms[capi.STAGE_LIGHT]:.3f} ms lighting)" if a.lighting else ""))
     if a.out.endswith(".npy"):
         np.save(a.out, img)
     else:

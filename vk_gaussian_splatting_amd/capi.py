@@ -18,6 +18,10 @@ PIPELINE_3DGS, PIPELINE_3DGUT = 0, 1
 NORMAL_MAX_DENSITY_PLANE, NORMAL_ISO_SURFACE = 0, 1
 CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1
 EXTENT_EIGEN, EXTENT_CONIC = 0, 1
+LIGHTING_DISABLED, LIGHTING_DIRECT, LIGHTING_INDIRECT = 0, 1, 2
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
+MAX_LIGHTS = 64
+STAGE_LIGHT = 7  # index into timings_all(): the deferred lighting pass
 STAGE_NAMES = ["project", "sort", "bin", "pairsort", "composite", "total"]
 
 
@@ -53,7 +57,48 @@ class FrameParams(C.Structure):
                 ("alpha_clamp", C.c_float), ("kernel_min_response", C.c_float),
                 ("dof_mode", C.c_int32), ("focus_dist", C.c_float), ("aperture", C.c_float),
                 ("frame_sample_id", C.c_int32), ("temporal_sampling", C.c_int32), ("kernel_degree", C.c_int32),
-                ("normal_method", C.c_int32), ("reserved_", C.c_int32 * 1)]
+                ("normal_method", C.c_int32), ("lighting_mode", C.c_int32)]
+
+
+class Light(C.Structure):
+    """MgsLight: shaderio::LightSource minus the soft-shadow radius; angles in degrees"""
+    _fields_ = [("type", C.c_int32), ("color", C.c_float * 3), ("intensity", C.c_float), ("position", C.c_float * 3),
+                ("range", C.c_float), ("direction", C.c_float * 3), ("inner_cone_deg", C.c_float), ("outer_cone_deg", C.c_float),
+                ("attenuation_mode", C.c_int32)]
+
+
+class Material(C.Structure):
+    """MgsMaterial: an instance's splatMaterial as the deferred pass reads it"""
+    _fields_ = [("ambient", C.c_float * 3), ("diffuse", C.c_float * 3), ("specular", C.c_float * 3), ("emission", C.c_float * 3),
+                ("shininess", C.c_float)]
+
+
+def make_light(**kw):
+    """an MgsLight with the reference's defaults (mgs_light_default), fields overridden by keyword"""
+    l = Light()
+    load_library().mgs_light_default(C.byref(l))
+    for k, v in kw.items():
+        if k not in dict(Light._fields_):
+            raise TypeError(f"make_light: unknown field {k}")
+        if k in ("color", "position", "direction"):
+            setattr(l, k, (C.c_float * 3)(*[float(x) for x in v]))
+        else:
+            setattr(l, k, v)
+    return l
+
+
+def make_material(**kw):
+    """an MgsMaterial with the splat sets' default (mgs_material_default: emission 1, everything else 0), fields overridden"""
+    m = Material()
+    load_library().mgs_material_default(C.byref(m))
+    for k, v in kw.items():
+        if k not in dict(Material._fields_):
+            raise TypeError(f"make_material: unknown field {k}")
+        if k == "shininess":
+            m.shininess = float(v)
+        else:
+            setattr(m, k, (C.c_float * 3)(*[float(x) for x in v]))
+    return m
 
 
 class FrameOut(C.Structure):
@@ -108,6 +153,10 @@ def load_library():
         "mgs_instance_add": (C.c_int, [vp, vp, P(F), P(C.c_int)]),
         "mgs_instance_set_transform": (C.c_int, [vp, C.c_int, P(F)]),
         "mgs_scene_commit": (C.c_int, [vp, C.c_int, C.c_int]),
+        "mgs_light_default": (None, [P(Light)]),
+        "mgs_material_default": (None, [P(Material)]),
+        "mgs_scene_set_lights": (C.c_int, [vp, P(Light), C.c_int]),
+        "mgs_instance_set_material": (C.c_int, [vp, C.c_int, P(Material)]),
         "mgs_scene_splat_count": (C.c_uint64, [vp]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
@@ -158,6 +207,7 @@ EXPORTED_SYMBOLS = [
     "mgs_instance_set_transform", "mgs_scene_commit", "mgs_scene_splat_count", "mgs_scene_storage_order", "mgs_scene_download_set",
     "mgs_frame_context_create", "mgs_frame_context_destroy", "mgs_scene_memory_usage", "mgs_scene_set_list_capacity",
     "mgs_frame_set_occluder", "mgs_frame_upload_occluder",
+    "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_instance_set_material",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -386,6 +436,16 @@ class Scene:
         m = _f32(transform).T.reshape(-1).copy()
         _check(self._lib.mgs_instance_set_transform(self._h, instance, _fp(m)))
 
+    # ---- deferred lighting (FrameParams.lighting_mode): the scene's light table and the instances' materials ----
+    def set_lights(self, lights):
+        """replace the scene's lights (mgs_scene_set_lights): a sequence of Light (make_light); empty = the headlight"""
+        lights = list(lights)
+        arr = (Light * max(len(lights), 1))(*lights)
+        _check(self._lib.mgs_scene_set_lights(self._h, arr if lights else None, len(lights)))
+
+    def set_material(self, instance, material):
+        _check(self._lib.mgs_instance_set_material(self._h, int(instance), C.byref(material)))
+
     def commit(self, sh_format=FORMAT_FLOAT32, rgba_format=FORMAT_FLOAT32):
         _check(self._lib.mgs_scene_commit(self._h, sh_format, rgba_format))
 
@@ -450,6 +510,13 @@ class Scene:
         nrm = np.zeros((params.height, params.width, 4), np.float32)
         _check(self._lib.mgs_frame_download_surface(self._h, 2, nrm.ctypes.data_as(C.c_void_p), nrm.nbytes))
         return depth, ids, nrm
+
+    def download_consolidated_depth(self, params):
+        """mgs_frame_download_surface(which = 3): float32[H,W], the picked depth where it is valid and in front of the occluder
+        the frame was rendered against, that occluder's depth (1.0 where none was bound) elsewhere"""
+        depth = np.zeros((params.height, params.width), np.float32)
+        _check(self._lib.mgs_frame_download_surface(self._h, 3, depth.ctypes.data_as(C.c_void_p), depth.nbytes))
+        return depth
 
     def copy_strip(self, device_ptr, nbytes):
         _check(self._lib.mgs_frame_copy_strip(self._h, C.c_void_p(device_ptr), nbytes))

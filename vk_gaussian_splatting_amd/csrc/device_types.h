@@ -6,6 +6,7 @@ namespace mgs {
 
 constexpr int kMaxInstances       = 256;  // instances per scene: FrameArgs lives in device memory, only the used part is uploaded
 constexpr int kMaxInlineInstances = 16;   // SH-table entries the compositor carries by value; larger scenes read a device table
+constexpr int kMaxLights          = 64;   // == MGS_MAX_LIGHTS: entries of the scene's light table (LightTable)
 constexpr int kTilePx             = 16;  // compositing tile edge in pixels (one workgroup; 8x8 pixels per wave)
 
 // error bits reported through MgsFrameOut.error_flags
@@ -101,6 +102,11 @@ struct FrameConst
                                    // entries < 2^24 in magnitude: the project kernels may take the exact shortcuts of kernels_common.h
   int32_t  rideSplit;              // 1: the id word's spare bits do not hold the whole code (> 8 M splats): its low 8 bits travel in the
                                    // key's low byte — dead weight once the slot is grouped by it (slot_emit.h) —, the rest above the id
+  // deferred lighting (k_light.hip; read by no other kernel)
+  int32_t  lightingMode;           // MGS_LIGHTING_*: != 0 runs the pass
+  float    cameraPos[3];           // frameInfo.cameraPosition
+  float    lightViewInv[16], lightProjInv[16];  // viewInverse / projInverse computed in double and rounded once (viewInv / projInv
+                                                // above are the fp32 closed form the 3DGUT rays are pinned to)
 };
 
 struct FrameArgs
@@ -149,6 +155,50 @@ struct CompositeArgsOcc : CompositeArgs
   const float*  occDepth;     // [height][width] window depth of the caller's geometry
   const float4* occColor;     // [height][width] linear RGBA of that geometry, nullptr = transparent black
   int32_t       occStop;      // 1: the lists are sorted by the depth key (GPU sort): a record behind every pixel ends the walk
+};
+
+// ---- deferred lighting (k_light.hip) ----
+// One light as the pass reads it: MgsLight with what is the same for every pixel done once on the host (the normalised direction,
+// the cosines of the cone angles).  64 B.
+struct LightDev
+{
+  int32_t type, attMode;
+  float   color[3], intensity;
+  float   pos[3], range;
+  float   dirN[3];             // normalize(direction)
+  float   innerCos, outerCos;  // cos(radians(angle))
+  float   pad;
+};
+// one instance's material (shaderio::ObjMaterial reduced) + needShading as updateMaterialNeedsShading derives it.  64 B.
+struct alignas(16) MaterialDev
+{
+  float   ambient[3], diffuse[3], specular[3], emission[3];
+  float   shininess;
+  int32_t needShading;
+  float   pad[2];
+};
+// The scene's lights and materials: ONE device block per scene, read by the lighting pass of every context through its pointer,
+// so that changing a light or a material re-captures nothing.
+struct LightTable
+{
+  int32_t     count;  // 0: the headlight
+  int32_t     pad[15];
+  LightDev    lights[kMaxLights];
+  MaterialDev mats[kMaxInstances];
+};
+static_assert(sizeof(LightDev) == 64 && sizeof(MaterialDev) == 64, "16 words each");
+// what the lighting pass receives by value (all of it constant for a captured frame graph: part of its key, or buffers whose
+// move drops the captured frames)
+struct LightArgs
+{
+  void*             image;    // the frame, in the target format
+  const float*      depth;    // picked depth
+  const uint32_t*   id;       // picked splat (storage id space: instances are concatenated in creation order as in the caller's)
+  const float4*     normal;   // integrated normal
+  const LightTable* table;
+  const FrameArgs*  frame;    // camera, inverses, instance prefix: this frame's upload
+  int32_t           width;
+  int32_t           row0, row1;  // pixel rows [row0, row1) of the handle's strip
 };
 
 // the caller's geometry as the compositors' launchers receive it

@@ -1,0 +1,275 @@
+// k_light.hip — deferred lighting of the splat surface and depth consolidation.
+//
+// k_light restates shaders/deferred_shading.comp.slang:52-167 with the shading functions of shaders/wavefront.h.slang:104-280,388-403
+// in their own order of operations: one launch per lit frame between the compositor and k_post_accumulate, one thread per pixel of
+// the handle's strip.  Per pixel it reads the integrated normal (16 B), the picked depth (4 B), the picked id (4 B) and the frame's
+// pixel (4 / 8 / 16 B) and rewrites the pixel: a streaming pass without reuse.  Consecutive lanes take consecutive pixels, the four
+// loads are issued before the first is used, lanes without a surface (normal.w < 0.001) write nothing.  Lights are read through
+// wave-uniform (scalar) loads inside the loop; a material is 64 B gathered by the pixel's instance (a table of at most 16 KB).
+//
+// k_depth_consolidate restates shaders/depth_consolidate.frag.slang (one depth image for what follows the splats).
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include "../../include/mgs.h"
+#include "device_types.h"
+
+namespace mgs {
+
+namespace {
+
+struct V3
+{
+  float x, y, z;
+};
+__device__ __forceinline__ V3    operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3    operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3    operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+__device__ __forceinline__ V3    operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ V3    operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3    normalize3(V3 a) { return a * (1.0f / sqrtf(dot3(a, a))); }
+__device__ __forceinline__ V3    load3(const float* p) { return {p[0], p[1], p[2]}; }
+
+// mul(v, M) of the shaders on a glm column-major matrix == M * v, each component summed in the order of v's components
+__device__ __forceinline__ float4 mulMat(const float* __restrict__ m, float4 v)
+{
+  float4 r;
+  r.x = ((v.x * m[0] + v.y * m[4]) + v.z * m[8]) + v.w * m[12];
+  r.y = ((v.x * m[1] + v.y * m[5]) + v.z * m[9]) + v.w * m[13];
+  r.z = ((v.x * m[2] + v.y * m[6]) + v.z * m[10]) + v.w * m[14];
+  r.w = ((v.x * m[3] + v.y * m[7]) + v.z * m[11]) + v.w * m[15];
+  return r;
+}
+
+struct Mat
+{
+  V3    ambient, diffuse, specular, emission;
+  float shininess;
+  int   needShading;
+};
+
+// distance attenuation of computePointLight / computeSpotLight (wavefront.h.slang:160-174, 193-206)
+__device__ __forceinline__ float attenuate(int mode, float distance, float range)
+{
+  float attenuation = 1.0f;
+  if(mode == 1)
+    attenuation = 1.0f - (distance / range);
+  else if(mode == 2)
+    attenuation = 1.0f / (1.0f + distance * distance);
+  else if(mode == 3)
+    attenuation = 1.0f / (distance * distance + 0.01f);
+  return attenuation;
+}
+
+// wavefrontComputeShadingDirectOnly (wavefront.h.slang:233-280) with inShadow = false, transmittance = 1
+__device__ __forceinline__ void shadeDirect(const LightDev& light, V3 worldPos, V3 n, const Mat& mat, V3 viewDir, V3& radiance)
+{
+  radiance = radiance + mat.ambient;  // ambient once per light, as written
+  const V3 lightColor = load3(light.color);
+  V3       L;
+  V3       lightDiffuse = {0.0f, 0.0f, 0.0f};
+  if(light.type == MGS_LIGHT_DIRECTIONAL)
+  {
+    L                 = -load3(light.dirN);
+    const float NdotL = fmaxf(dot3(n, L), 0.0f);
+    lightDiffuse      = lightColor * light.intensity * NdotL;
+  }
+  else
+  {
+    const V3    toLight  = load3(light.pos) - worldPos;
+    const float distance = sqrtf(dot3(toLight, toLight));
+    L                    = toLight * (1.0f / distance);
+    if(!(distance > light.range))
+    {
+      const float attenuation = attenuate(light.attMode, distance, light.range);
+      const float NdotL       = fmaxf(dot3(n, L), 0.0f);
+      if(light.type == MGS_LIGHT_POINT)
+        lightDiffuse = lightColor * light.intensity * attenuation * NdotL;
+      else if(light.type == MGS_LIGHT_SPOT)
+      {
+        const float theta = dot3(L, -load3(light.dirN));
+        if(!(theta < light.outerCos))
+        {  // smoothstep(outerCos, innerCos, theta)
+          const float t          = fminf(fmaxf((theta - light.outerCos) / (light.innerCos - light.outerCos), 0.0f), 1.0f);
+          const float spotEffect = t * t * (3.0f - 2.0f * t);
+          lightDiffuse           = lightColor * light.intensity * attenuation * spotEffect * NdotL;
+        }
+      }
+    }
+  }
+  const V3 fragDiffuse = mat.diffuse * lightDiffuse;
+  // wavefrontComputeSpecular (:388-403)
+  const float kPi                 = 3.14159265f;
+  const float kShininess          = fmaxf(mat.shininess, 4.0f);
+  const float kEnergyConservation = (2.0f + kShininess) / (2.0f * kPi);
+  const V3    V                   = normalize3(-viewDir);
+  const V3    I                   = -L;
+  const V3    R                   = I - n * (2.0f * dot3(n, I));  // reflect(-L, n)
+  // powf, not the fast intrinsic: with shininess up to 2000 the exponent multiplies the base's relative error, and __powf's own
+  // exp2(y * log2(x)) would add ~2000 x 2^-22 on top of it
+  const float specular             = kEnergyConservation * powf(fmaxf(dot3(V, R), 0.0f), kShininess);
+  const V3    specularContribution = mat.specular * specular * lightColor * light.intensity;
+  radiance                         = radiance + (fragDiffuse + specularContribution);
+}
+
+template <int HALF>
+__device__ __forceinline__ float4 loadPixel(const void* image, size_t o)
+{
+  if(HALF == 1)
+  {
+    const uint2  pk = reinterpret_cast<const uint2*>(image)[o];
+    const float2 lo = __half22float2(*reinterpret_cast<const __half2*>(&pk.x)), hi = __half22float2(*reinterpret_cast<const __half2*>(&pk.y));
+    return make_float4(lo.x, lo.y, hi.x, hi.y);
+  }
+  if(HALF == 2)
+  {
+    const uint32_t pk = reinterpret_cast<const uint32_t*>(image)[o];
+    return make_float4((float)(pk & 255u) / 255.0f, (float)((pk >> 8) & 255u) / 255.0f, (float)((pk >> 16) & 255u) / 255.0f, (float)(pk >> 24) / 255.0f);
+  }
+  return reinterpret_cast<const float4*>(image)[o];
+}
+template <int HALF>
+__device__ __forceinline__ void storePixel(void* image, size_t o, float4 c)
+{
+  if(HALF == 1)
+  {
+    const __half2 lo = __floats2half2_rn(c.x, c.y), hi = __floats2half2_rn(c.z, c.w);
+    uint2         pk;
+    pk.x = *reinterpret_cast<const uint32_t*>(&lo);
+    pk.y = *reinterpret_cast<const uint32_t*>(&hi);
+    reinterpret_cast<uint2*>(image)[o] = pk;
+  }
+  else if(HALF == 2)
+  {  // the compositors' UNORM conversion
+    auto q8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
+    reinterpret_cast<uint32_t*>(image)[o] = q8(c.x) | (q8(c.y) << 8) | (q8(c.z) << 16) | (q8(c.w) << 24);
+  }
+  else
+    reinterpret_cast<float4*>(image)[o] = c;
+}
+
+}  // namespace
+
+// HALF: the target format as the compositors name it (0 RGBA32F, 1 RGBA16F, 2 RGBA8)
+template <int HALF>
+__global__ void __launch_bounds__(256) k_light(const LightArgs a)
+{
+  const uint32_t W = (uint32_t)a.width;
+  const uint32_t n = (uint32_t)(a.row1 - a.row0) * W;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if(i >= n)
+    return;
+  const size_t o = (size_t)a.row0 * W + i;
+  // all four inputs in flight before the first is used
+  const float4   normalData    = a.normal[o];
+  const float    ndcDepth      = a.depth[o];
+  const uint32_t globalSplatId = a.id[o];
+  const float4   baseColor     = loadPixel<HALF>(a.image, o);
+  if(normalData.w < 0.001f)
+    return;  // no surface: colour and alpha pass through
+
+  const FrameConst& F      = a.frame->f;
+  const V3          normal = normalize3({normalData.x, normalData.y, normalData.z});
+  // reconstructWorldPos (deferred_shading.comp.slang:39-50)
+  const uint32_t py = i / W, px = i - py * W;
+  const float    fx = (float)px + 0.5f, fy = (float)(py + (uint32_t)a.row0) + 0.5f;
+  const float4   clipPos = make_float4(fx / (float)F.width * 2.0f - 1.0f, fy / (float)F.height * 2.0f - 1.0f, ndcDepth, 1.0f);
+  float4         viewPos = mulMat(F.lightProjInv, clipPos);
+  viewPos = make_float4(viewPos.x / viewPos.w, viewPos.y / viewPos.w, viewPos.z / viewPos.w, viewPos.w / viewPos.w);
+  const float4 wp4      = mulMat(F.lightViewInv, viewPos);
+  const V3     worldPos = {wp4.x, wp4.y, wp4.z};
+  const V3     cameraPos = load3(F.cameraPos);
+
+  const V3 baseRadiance = {baseColor.x, baseColor.y, baseColor.z};
+  Mat      mat;
+  if(globalSplatId != 0xFFFFFFFFu)
+  {  // the instance that owns the id: the last one whose first global id is not above it (instances are concatenated in creation
+     // order); log2(instances) steps, the same count for every lane
+    int lo = 0, hi = F.nInstances;
+    while(hi - lo > 1)
+    {
+      const int mid = (lo + hi) >> 1;
+      if(a.frame->inst[mid].globalOffset <= globalSplatId)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    const float4* mp = reinterpret_cast<const float4*>(&a.table->mats[lo]);
+    const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
+    mat.ambient      = baseRadiance * V3{m0.x, m0.y, m0.z};
+    mat.diffuse      = baseRadiance * V3{m0.w, m1.x, m1.y};
+    mat.specular     = baseRadiance * V3{m1.z, m1.w, m2.x};
+    mat.emission     = baseRadiance * V3{m2.y, m2.z, m2.w};
+    mat.shininess    = m3.x;
+    mat.needShading  = __float_as_int(m3.y);
+  }
+  else
+  {  // the shader's default material with the base colour as diffuse
+    mat.ambient     = {0.1f, 0.1f, 0.1f};
+    mat.diffuse     = baseRadiance;
+    mat.specular    = {0.0f, 0.0f, 0.0f};
+    mat.emission    = {0.0f, 0.0f, 0.0f};
+    mat.shininess   = 32.0f;
+    mat.needShading = 1;
+  }
+  const V3 viewDir = normalize3(worldPos - cameraPos);
+  V3       color   = mat.emission;
+  if(mat.needShading != 0)
+  {
+    const int count = a.table->count;
+    for(int l = 0; l < count; ++l)
+      shadeDirect(a.table->lights[l], worldPos, normal, mat, viewDir, color);
+    if(count == 0)
+    {  // createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation
+      LightDev h;
+      h.type      = MGS_LIGHT_POINT;
+      h.attMode   = 0;
+      h.color[0] = h.color[1] = h.color[2] = 1.0f;
+      h.intensity = 1.0f;
+      h.pos[0]    = cameraPos.x;
+      h.pos[1]    = cameraPos.y;
+      h.pos[2]    = cameraPos.z;
+      h.range     = 1e10f;
+      h.dirN[0] = h.dirN[1] = 0.0f;
+      h.dirN[2]  = -1.0f;
+      h.innerCos = h.outerCos = 1.0f;
+      shadeDirect(h, worldPos, normal, mat, viewDir, color);
+    }
+  }
+  storePixel<HALF>(a.image, o, make_float4(color.x, color.y, color.z, 1.0f));
+}
+
+// depth_consolidate.frag.slang: the picked splat depth where it is valid and in front of the geometry (depth test LESS against the
+// geometry's depth, gaussian_splatting.cpp:2383), the geometry's depth (1.0 = the clear value when none is bound) elsewhere
+__global__ void __launch_bounds__(256) k_depth_consolidate(const float* __restrict__ picked, const float* __restrict__ occDepth, float* __restrict__ out, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if(i >= n)
+    return;
+  const float p = picked[i];
+  const float D = occDepth ? occDepth[i] : 1.0f;
+  out[i]        = (p > 0.0001f && p < D) ? p : D;
+}
+
+void launchLight(hipStream_t stream, const LightArgs& a, int halfOut)
+{
+  const uint32_t n = (uint32_t)(a.row1 - a.row0) * (uint32_t)a.width;
+  if(n == 0)
+    return;
+  const dim3 grid((n + 255u) / 256u), block(256);
+  if(halfOut == 1)
+    hipLaunchKernelGGL(k_light<1>, grid, block, 0, stream, a);
+  else if(halfOut == 2)
+    hipLaunchKernelGGL(k_light<2>, grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL(k_light<0>, grid, block, 0, stream, a);
+}
+
+void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n)
+{
+  if(n)
+    hipLaunchKernelGGL(k_depth_consolidate, dim3((n + 255u) / 256u), dim3(256), 0, stream, picked, occDepth, out, n);
+}
+
+}  // namespace mgs

@@ -59,6 +59,8 @@ void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs*
                         const uint32_t* valY, const SortPlan* planPairs, const GutRec* rec, void* image, int halfOut,
                         FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal,
                         const Occluder& occ);
+void launchLight(hipStream_t stream, const LightArgs& a, int halfOut);
+void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 constexpr uint32_t kPart = 2048;  // == kPrjPart == kSortPart == kBinPart
 }  // namespace mgs
 
@@ -107,6 +109,24 @@ struct Instance
   int   set;  // index into sets
   float M[16];
 };
+
+static void materialDefault(MgsMaterial& m)
+{  // the splat sets' default, src/splat_set_vk.cpp:128-135: fully emissive
+  std::memset(&m, 0, sizeof(m));
+  m.emission[0] = m.emission[1] = m.emission[2] = 1.0f;
+}
+static MaterialDev materialToDevice(const MgsMaterial& m)
+{
+  MaterialDev d{};
+  std::memcpy(d.ambient, m.ambient, 12);
+  std::memcpy(d.diffuse, m.diffuse, 12);
+  std::memcpy(d.specular, m.specular, 12);
+  std::memcpy(d.emission, m.emission, 12);
+  d.shininess = m.shininess;
+  auto len = [](const float* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+  d.needShading = (len(m.diffuse) > 0.001f || len(m.ambient) > 0.001f || len(m.specular) > 0.001f) ? 1 : 0;  // wavefront.h:55-59
+  return d;
+}
 
 template <typename T>
 struct DevBuf
@@ -269,6 +289,10 @@ struct SceneData
   int                    shFormat = 0, rgbaFormat = 0;
   uint32_t               totalSplats = 0, totalParts = 0;
   DevBuf<CompositeArgs::Inst> compInst;  // SH table of all instances for the compositor (scenes with > 16 instances)
+  // lights and per-instance materials of the lighting pass (mgs_scene_set_lights, mgs_instance_set_material): the host copy, and
+  // the device block every context's pass reads (allocated once: its address is baked into captured frames)
+  std::unique_ptr<LightTable> lightHost;
+  DevBuf<LightTable>     lightTab;
   uint64_t               epoch = 0;      // bumped by every commit: a context re-sizes its working set when it lags
   std::mutex             mtx;            // guards `handles`
   std::vector<MgsScene_t*> handles;      // the owning scene and its live frame contexts
@@ -324,6 +348,9 @@ struct MgsScene_t
   DevBuf<float>         surfDepth;   // FTB side outputs of the last frame rendered with surface_outputs
   DevBuf<uint32_t>      surfId;
   DevBuf<float4>        surfNormal;
+  DevBuf<float>         consDepth;   // consolidated depth, computed when mgs_frame_download_surface(3) asks for it
+  const float*          lastOccDepth = nullptr;  // the occluder depth the last frame was rendered against
+  bool                  lastOccGone  = false;    // ... was a library-owned copy that has been freed since
   DevBuf<float4>        accum;       // temporal accumulation (post.comp.slang): running mean of the frame samples, fp32
   bool                  haveSurface = false;
   DevBuf<SplatRec>      rec;
@@ -341,7 +368,8 @@ struct MgsScene_t
 
   static constexpr int kRing = 128;
   hipEvent_t ev[8] = {};              // [0..2] sort-only hook, [6..7] raw radix sort
-  hipEvent_t evRing[kRing][7] = {};   // per-frame stage brackets ([6]: end of the partition cull), so timed frames need no host sync
+  hipEvent_t evRing[kRing][9] = {};   // per-frame stage brackets ([6]: end of the partition cull, [7] [8]: around the lighting pass), so timed frames need no host sync
+  bool       litRing[kRing] = {};     // the timed frame of that slot ran the lighting pass
   uint64_t   frameIndex = 0;          // frames rendered with collect_timings
   bool       evReady = false;
 
@@ -428,7 +456,7 @@ static int guarded(const char* what, Fn&& fn) noexcept
 extern "C" {
 
 const char* mgs_last_error(void) { return lastError(); }
-const char* mgs_version(void) { return "mgs 0.4 (gfx950, ABI 5)"; }
+const char* mgs_version(void) { return "mgs 0.4 (gfx950, ABI 5.1)"; }
 
 static int mgs_splatset_load_impl(const char* path, MgsSplatSet* out);
 int mgs_splatset_load(const char* path, MgsSplatSet* out)
@@ -760,6 +788,7 @@ SceneData::~SceneData()
   for(auto& d : sets)
     freeSet(d);
   compInst.release();
+  lightTab.release();
 }
 
 void mgs_scene_destroy(MgsScene s)
@@ -781,7 +810,7 @@ void mgs_scene_destroy(MgsScene s)
   s->osStatus.release(); s->keysA.release(); s->idsA.release(); s->rect.release(); s->partHist.release(); s->blockCount.release();
   s->rec.release(); s->recGut.release(); s->pairKey0.release(); s->pairVal0.release(); s->pairKey1.release(); s->pairVal1.release();
   s->sortedRect.release(); s->splatOffset.release(); s->chunkStart.release();
-  s->surfDepth.release(); s->surfId.release(); s->surfNormal.release(); s->accum.release(); s->fstate.release(); s->dbinMasks.release();
+  s->surfDepth.release(); s->surfId.release(); s->surfNormal.release(); s->consDepth.release(); s->accum.release(); s->fstate.release(); s->dbinMasks.release();
   for(auto& g : s->graphs) (void)hipGraphExecDestroy(g.second);
   s->graphs.clear();
   s->ranges.release(); s->image.release(); s->cpuDistDev.release(); s->occOwnDepth.release(); s->occOwnColor.release();
@@ -910,6 +939,8 @@ static int mgs_frame_upload_occluder_impl(MgsScene s, const float* depthHost, co
   const size_t n = (size_t)width * (size_t)height;
   // frames in flight may still read the previous copy (and captured graphs point at it): wait before it is rewritten or moved
   HIPCHK(hipStreamSynchronize(s->stream));
+  if(n > s->occOwnDepth.n && s->lastOccDepth == s->occOwnDepth.p && s->lastOccDepth)
+    s->lastOccGone = true;  // the copy the last frame was tested against is about to be freed (mgs_frame_download_surface, which = 3)
   if(int rc = s->occOwnDepth.ensure(n)) return rc;
   HIPCHK(hipMemcpy(s->occOwnDepth.p, depthHost, n * sizeof(float), hipMemcpyHostToDevice));
   if(colorHost)
@@ -944,7 +975,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   }
   if(sceneBytes)
   {
-    uint64_t b = s->d->compInst.n * sizeof(CompositeArgs::Inst);
+    uint64_t b = s->d->compInst.n * sizeof(CompositeArgs::Inst) + s->d->lightTab.n * sizeof(LightTable);
     for(const auto& d : s->d->sets)
       b += setBytes(d);
     *sceneBytes = b;
@@ -955,7 +986,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
     auto add = [&](auto& buf) { b += (uint64_t)buf.n * sizeof(*buf.p); };
     add(s->pairA); add(s->pairB); add(s->prjOrder); add(s->slotCount); add(s->chunkSum); add(s->runTab); add(s->sortedCode16); add(s->binCost); add(s->slotHist2); add(s->top16Rec); add(s->top16Count); add(s->osStatus); add(s->keysA); add(s->idsA); add(s->rect);
     add(s->partHist); add(s->blockCount); add(s->sortedRect); add(s->splatOffset); add(s->chunkStart);
-    add(s->dbinMasks); add(s->fstate); add(s->surfDepth); add(s->surfId); add(s->surfNormal); add(s->accum); add(s->rec); add(s->recGut);
+    add(s->dbinMasks); add(s->fstate); add(s->surfDepth); add(s->surfId); add(s->surfNormal); add(s->consDepth); add(s->accum); add(s->rec); add(s->recGut);
     add(s->pairKey0); add(s->pairVal0); add(s->pairKey1); add(s->pairVal1); add(s->ranges); add(s->image);
     add(s->rsKeys); add(s->rsVals); add(s->rsHist); add(s->rsCount); add(s->rsPairA); add(s->rsPairB); add(s->rsStatus); add(s->rsOsPlan); add(s->rsPlan); add(s->cpuDistDev);
     *workingBytes = b;
@@ -1032,6 +1063,132 @@ int mgs_instance_set_transform(MgsScene s, int id, const float m[16])
   }
   std::memcpy(s->d->instances[id].M, m, sizeof(float) * 16);
   return MGS_OK;  // transforms travel with every frame (of every context); no re-commit needed
+}
+
+// ---- lights and materials of the lighting pass ------------------------------------------------------------------------------
+void mgs_light_default(MgsLight* l)
+{  // shaderio::LightSource, wavefront.h:81-93
+  if(!l)
+    return;
+  std::memset(l, 0, sizeof(*l));
+  l->type = MGS_LIGHT_POINT;
+  l->color[0] = l->color[1] = l->color[2] = 1.0f;
+  l->intensity        = 1.0f;
+  l->range            = 10.0f;
+  l->direction[2]     = -1.0f;
+  l->inner_cone_deg   = 30.0f;
+  l->outer_cone_deg   = 45.0f;
+  l->attenuation_mode = 2;
+}
+void mgs_material_default(MgsMaterial* m)
+{
+  if(m)
+    materialDefault(*m);
+}
+// The device table exists from the first call that needs it (a setter, or the first lit frame) and never moves.  Its contents are
+// shared by every context's frames: a rewrite waits for the frames in flight on all of them first, the rule of mgs_scene_commit.
+static int ensureLightTable(SceneData& d)
+{
+  if(d.lightTab.p)
+    return MGS_OK;
+  if(!d.lightHost)
+  {
+    d.lightHost.reset(new LightTable());
+    std::memset(d.lightHost.get(), 0, sizeof(LightTable));
+    MgsMaterial def;
+    materialDefault(def);
+    for(auto& m : d.lightHost->mats)
+      m = materialToDevice(def);
+  }
+  HIPCHK(hipSetDevice(d.device));
+  if(int rc = d.lightTab.ensure(1))
+    return rc;
+  HIPCHK(hipMemcpy(d.lightTab.p, d.lightHost.get(), sizeof(LightTable), hipMemcpyHostToDevice));
+  return MGS_OK;
+}
+static int rewriteLightTable(SceneData& d, const void* hostPart, size_t bytes)
+{
+  {
+    std::lock_guard<std::mutex> lk(d.mtx);
+    for(MgsScene_t* h : d.handles)
+      HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  const size_t off = (const uint8_t*)hostPart - (const uint8_t*)d.lightHost.get();
+  HIPCHK(hipMemcpy((uint8_t*)d.lightTab.p + off, hostPart, bytes, hipMemcpyHostToDevice));
+  return MGS_OK;
+}
+static int mgs_scene_set_lights_impl(MgsScene s, const MgsLight* lights, int count)
+{
+  if(!s || count < 0 || (count > 0 && !lights))
+  {
+    setError(!s ? "mgs_scene_set_lights: null handle" : "mgs_scene_set_lights: bad argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(s->isContext)
+  {
+    setError("mgs_scene_set_lights: a frame context is read-only; the lights belong to the scene it was created from");
+    return MGS_ERR_STATE;
+  }
+  if(count > kMaxLights)
+  {
+    setError("mgs_scene_set_lights: at most " + std::to_string(kMaxLights) + " lights in this build (MGS_MAX_LIGHTS)");
+    return MGS_ERR_INVALID_ARG;
+  }
+  for(int i = 0; i < count; ++i)
+    if(lights[i].type < MGS_LIGHT_DIRECTIONAL || lights[i].type > MGS_LIGHT_SPOT || lights[i].attenuation_mode < 0 || lights[i].attenuation_mode > 3)
+    {
+      setError("mgs_scene_set_lights: light " + std::to_string(i) + ": type must be MGS_LIGHT_DIRECTIONAL / POINT / SPOT and attenuation_mode 0..3");
+      return MGS_ERR_INVALID_ARG;
+    }
+  if(int rc = ensureLightTable(*s->d))
+    return rc;
+  LightTable& T = *s->d->lightHost;
+  T.count       = count;
+  for(int i = 0; i < count; ++i)
+  {
+    const MgsLight& L = lights[i];
+    LightDev&       D = T.lights[i];
+    std::memset(&D, 0, sizeof(D));
+    D.type    = L.type;
+    D.attMode = L.attenuation_mode;
+    std::memcpy(D.color, L.color, 12);
+    D.intensity = L.intensity;
+    std::memcpy(D.pos, L.position, 12);
+    D.range = L.range;
+    // the same for every pixel, so done once here: normalize(direction), cos(radians(angle)) (wavefront.h.slang:141,209-214)
+    const float inv = 1.0f / std::sqrt(L.direction[0] * L.direction[0] + L.direction[1] * L.direction[1] + L.direction[2] * L.direction[2]);
+    for(int c = 0; c < 3; ++c)
+      D.dirN[c] = L.direction[c] * inv;
+    D.innerCos = std::cos(L.inner_cone_deg * (3.14159265358979323846f / 180.0f));
+    D.outerCos = std::cos(L.outer_cone_deg * (3.14159265358979323846f / 180.0f));
+  }
+  return rewriteLightTable(*s->d, &T, offsetof(LightTable, lights) + (size_t)count * sizeof(LightDev));
+}
+int mgs_scene_set_lights(MgsScene s, const MgsLight* lights, int count)
+{
+  return guarded("mgs_scene_set_lights", [&] { return mgs_scene_set_lights_impl(s, lights, count); });
+}
+static int mgs_instance_set_material_impl(MgsScene s, int id, const MgsMaterial* m)
+{
+  if(!s || !m || id < 0 || id >= (int)s->d->instances.size())
+  {
+    setError(!s ? "mgs_instance_set_material: null handle" : "mgs_instance_set_material: bad argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(s->isContext)
+  {
+    setError("mgs_instance_set_material: a frame context is read-only; edit the scene it was created from");
+    return MGS_ERR_STATE;
+  }
+  if(int rc = ensureLightTable(*s->d))
+    return rc;
+  MaterialDev& D = s->d->lightHost->mats[id];
+  D              = materialToDevice(*m);
+  return rewriteLightTable(*s->d, &D, sizeof(D));
+}
+int mgs_instance_set_material(MgsScene s, int id, const MgsMaterial* m)
+{
+  return guarded("mgs_instance_set_material", [&] { return mgs_instance_set_material_impl(s, id, m); });
 }
 
 uint64_t mgs_scene_splat_count(MgsScene s)
@@ -1568,6 +1725,45 @@ void mgs_frame_params_default(MgsFrameParams* p)
   p->temporal_sampling       = 0;
   p->kernel_degree           = 2;       // parameters.h:215
   p->normal_method           = MGS_NORMAL_MAX_DENSITY_PLANE;  // parameters.h:162
+  p->lighting_mode           = MGS_LIGHTING_DISABLED;
+}
+
+// a lit frame needs the side outputs the pass reads (needSurfaceInfo, gaussian_splatting.h:169-179)
+static bool wantsSurface(const MgsFrameParams* p) { return p->surface_outputs != 0 || p->lighting_mode != MGS_LIGHTING_DISABLED; }
+
+// inverse of a glm column-major 4x4 in double (Gauss-Jordan with partial pivoting), rounded once to fp32
+static void mat4InverseDouble(const float m[16], float out[16])
+{
+  double a[4][8];
+  for(int r = 0; r < 4; ++r)
+    for(int c = 0; c < 4; ++c)
+    {
+      a[r][c]     = (double)m[c * 4 + r];
+      a[r][4 + c] = r == c ? 1.0 : 0.0;
+    }
+  for(int k = 0; k < 4; ++k)
+  {
+    int piv = k;
+    for(int r = k + 1; r < 4; ++r)
+      if(std::fabs(a[r][k]) > std::fabs(a[piv][k]))
+        piv = r;
+    if(piv != k)
+      for(int c = 0; c < 8; ++c)
+        std::swap(a[k][c], a[piv][c]);
+    const double d = 1.0 / a[k][k];
+    for(int c = 0; c < 8; ++c)
+      a[k][c] *= d;
+    for(int r = 0; r < 4; ++r)
+      if(r != k)
+      {
+        const double f = a[r][k];
+        for(int c = 0; c < 8; ++c)
+          a[r][c] -= f * a[k][c];
+      }
+  }
+  for(int r = 0; r < 4; ++r)
+    for(int c = 0; c < 4; ++c)
+      out[c * 4 + r] = (float)a[r][4 + c];
 }
 
 // storage global id <-> caller global id.  Instances are concatenated in creation order in both spaces;
@@ -1655,7 +1851,7 @@ static void chooseRide(MgsScene s, FrameConst& F, bool cpuMode)
 // the frames the adaptive bin size applies to: the default compositing mode of the 3DGS pipeline with the GPU sort
 static bool binPolicyEligible(const MgsFrameParams* p)
 {
-  return tuning().binAdapt && p->alpha_mode != MGS_ALPHA_SUM && p->pipeline == MGS_PIPELINE_3DGS && p->sort_mode == MGS_SORT_GPU_RADIX && p->surface_outputs == 0;
+  return tuning().binAdapt && p->alpha_mode != MGS_ALPHA_SUM && p->pipeline == MGS_PIPELINE_3DGS && p->sort_mode == MGS_SORT_GPU_RADIX && !wantsSurface(p);
 }
 
 static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
@@ -1753,7 +1949,7 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   F.debugFlags      = p->debug_flags;
   F.sizeCulling     = p->size_culling;
   F.sizeCullingMinPixels = p->size_culling_min_pixels;
-  F.surfaceOutputs  = p->surface_outputs ? 1 : 0;
+  F.surfaceOutputs  = wantsSurface(p) ? 1 : 0;
   F.depthIsoThreshold = p->depth_iso_threshold;
   F.thinParticleThreshold = p->thin_particle_threshold;
   F.quantizeNormals       = p->quantize_normals ? 1 : 0;
@@ -1793,6 +1989,13 @@ static int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   }
   mat4Inverse(p->view, F.viewInv);
   mat4Inverse(p->proj, F.projInv);
+  F.lightingMode = p->lighting_mode;
+  if(F.lightingMode != MGS_LIGHTING_DISABLED)
+  {  // (unlit frames keep these zero)
+    std::memcpy(F.cameraPos, p->camera_pos, sizeof(F.cameraPos));
+    mat4InverseDouble(p->view, F.lightViewInv);
+    mat4InverseDouble(p->proj, F.lightProjInv);
+  }
   F.maxFocal        = std::max(std::fabs(F.gutFocal[0]), std::fabs(F.gutFocal[1]));  // frameInfo.focal (dist.comp.slang:125)
   F.targetFormat    = p->target_format;
   F.nInstances      = (int)s->d->instances.size();
@@ -2180,6 +2383,20 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     setError("frame: dof_mode / frame_sample_id out of range");
     return MGS_ERR_INVALID_ARG;
   }
+  const bool lit = p->lighting_mode != MGS_LIGHTING_DISABLED;
+  if(p->lighting_mode < MGS_LIGHTING_DISABLED || p->lighting_mode > MGS_LIGHTING_INDIRECT)
+  {
+    setError("frame: lighting_mode must be MGS_LIGHTING_DISABLED, MGS_LIGHTING_DIRECT or MGS_LIGHTING_INDIRECT");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(lit && p->sort_mode == MGS_SORT_STOCHASTIC)
+  {
+    setError("frame: lighting of MGS_SORT_STOCHASTIC frames is not supported (the reference's stochastic pipeline is not front to back: "
+             "it yields no surface to light)");
+    return MGS_ERR_UNSUPPORTED;
+  }
+  if(lit)
+    if((rc = ensureLightTable(*s->d))) return rc;
   Occluder occ;
   if(s->occDepth)
   {
@@ -2226,6 +2443,8 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     }
   }
   s->haveSurface    = F.surfaceOutputs != 0;
+  s->lastOccDepth   = occ.depth;
+  s->lastOccGone    = false;
   {
     const void* after[6] = {s->ranges.p, s->image.p, s->surfDepth.p, s->surfId.p, s->surfNormal.p, s->accum.p};
     if(std::memcmp(before, after, sizeof(before)) != 0 && !s->graphs.empty())
@@ -2325,6 +2544,22 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
       launchComposite(st, A, s->ranges.p, s->pairVal1.p, s->pairVal0.p, planP, s->rec.p, s->image.p, half, s->d->shFormat, ctr,
                       F.surfaceOutputs ? s->surfDepth.p : nullptr, F.surfaceOutputs ? s->surfId.p : nullptr, s->d->compInst.p,
                       s->dArgs.p, F.surfaceOutputs ? s->surfNormal.p : nullptr, s->binCost.p, occ);
+    if(lit)
+    {  // deferred lighting: shades the fresh sample in place, before it is folded into the running mean
+      if(withEvents) HIPCHK(hipEventRecord(fev[7], st));
+      LightArgs L{};
+      L.image  = s->image.p;
+      L.depth  = s->surfDepth.p;
+      L.id     = s->surfId.p;
+      L.normal = s->surfNormal.p;
+      L.table  = s->d->lightTab.p;
+      L.frame  = s->dArgs.p;
+      L.width  = F.width;
+      L.row0   = F.stripRow0 * kTilePx;
+      L.row1   = std::min(F.stripRow1 * kTilePx, F.height);
+      launchLight(st, L, half);
+      if(withEvents) HIPCHK(hipEventRecord(fev[8], st));
+    }
     if(F.temporalSampling)
       hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, st, s->dArgs.p, s->accum.p, s->image.p, half);
     if(withEvents) HIPCHK(hipEventRecord(fev[5], st));
@@ -2346,6 +2581,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
                             F.debugFlags & (2 | 4), F.surfaceOutputs, half, F.nInstances, F.shDegree, isoBits,
                             F.pipeline, F.stochastic | (F.dofMode << 1) | (F.temporalSampling << 2) | ((F.pipeline == 1 && F.kernelDegree != 2) ? 8 : 0) |
                                 ((F.pipeline == 1 && F.normalMethod == 1) ? 16 : 0) |
+                                (F.lightingMode << 5) |  // 0..2: the lighting pass is a launch of its own; what it gets by value is in this key or moves with the buffers
                                 (F.rideShift << 8) | (F.rideShapes << 16) | (F.rideSplit << 24)};  // ... and everything that selects a kernel variant or a launch argument
     std::memcpy(key.v, kv, sizeof(kv));
     key.p[0] = s->image.p;
@@ -2433,7 +2669,10 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
     s->lastBinShift[1] = F.binShiftY;
   }
   if(timed)
+  {
+    s->litRing[s->frameIndex % MgsScene_t::kRing] = lit;
     ++s->frameIndex;
+  }
   if(out)
   {
     std::memset(out, 0, sizeof(*out));
@@ -2471,6 +2710,12 @@ int mgs_timings_query(MgsScene s, uint32_t framesBack, float* stageMs)
   stageMs[MGS_STAGE_TOTAL] = ms;
   HIPCHK(hipEventElapsedTime(&ms, fev[0], fev[6]));
   stageMs[MGS_STAGE_CULL] = ms;
+  if(s->litRing[(s->frameIndex - 1 - framesBack) % MgsScene_t::kRing])
+  {
+    HIPCHK(hipEventElapsedTime(&ms, fev[7], fev[8]));
+    stageMs[MGS_STAGE_LIGHT] = ms;
+    stageMs[MGS_STAGE_COMPOSITE] -= ms;  // (the composite bracket ends behind the pass)
+  }
   return MGS_OK;
 }
 
@@ -2534,14 +2779,14 @@ int mgs_frame_stats(MgsScene s, MgsFrameOut* out)
 
 int mgs_frame_download_surface(MgsScene s, int which, void* dst, size_t bytes)
 {
-  if(!s || !dst || which < 0 || which > 2)
+  if(!s || !dst || which < 0 || which > 3)
   {
     setError("mgs_frame_download_surface: bad argument");
     return MGS_ERR_INVALID_ARG;
   }
   if(!s->haveFrame || !s->haveSurface || s->lastWasSortOnly)
   {
-    setError("mgs_frame_download_surface: the last frame was not rendered with surface_outputs = 1");
+    setError("mgs_frame_download_surface: the last frame was not rendered with surface_outputs = 1 or lighting on");
     return MGS_ERR_STATE;
   }
   const size_t n = (size_t)s->lastParams.width * (size_t)s->lastParams.height;
@@ -2551,6 +2796,21 @@ int mgs_frame_download_surface(MgsScene s, int which, void* dst, size_t bytes)
     return MGS_ERR_INVALID_ARG;
   }
   HIPCHK(hipSetDevice(s->device));
+  if(which == 3)
+  {  // depth consolidation, on demand: frames pay nothing for it
+    if(s->lastOccGone)
+    {
+      setError("mgs_frame_download_surface: the occluder depth the last frame was rendered against has been replaced since");
+      return MGS_ERR_STATE;
+    }
+    if(int rc = s->consDepth.ensure(n))
+      return rc;
+    launchDepthConsolidate(s->stream, s->surfDepth.p, s->lastOccDepth, s->consDepth.p, (uint32_t)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst, s->consDepth.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return MGS_OK;
+  }
   HIPCHK(hipStreamSynchronize(s->stream));
   if(which == 2)
   {

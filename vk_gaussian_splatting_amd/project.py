@@ -4,8 +4,11 @@ Format = the JSON written by VkgsProjectWriter (src/vkgs_project_writer.cpp:75-3
 read by VkgsProjectReader (src/vkgs_project_reader.cpp:55-345).  Only the sections the VK3DGSR path consumes are
 interpreted: "renderer" (raster knobs), "camera" / "cameras", "splatsGlobals" (storage formats), "splatSets"
 (assets: id + path relative to the project file) and "splats" (instances: splatSetId + position / rotation in
-degrees / scale, composed as T*R*S like computeTransform, src/utilities.h:170-199).  Lights, meshes, RTX and
-DLSS settings are carried through untouched on save but otherwise ignored (out of scope).
+degrees / scale, composed as T*R*S like computeTransform, src/utilities.h:170-199; "material" = the instance's splatMaterial,
+:252-260), "renderer.lightingMode" (and the legacy "lightingEnabled", :143-153) and "lights" in the three layouts the reader accepts
+(:616-770: assets / instances of version 3+, with the version 3 names "radius" / "position"; the flat list of versions 0-2).  The raw
+"lights" section is also kept in `extra` and written back unchanged.  Meshes, RTX and DLSS settings are carried through untouched on
+save but otherwise ignored (out of scope).
 """
 import json
 import os
@@ -25,6 +28,7 @@ class SplatInstance:
     position: tuple = (0.0, 0.0, 0.0)
     rotation: tuple = (0.0, 0.0, 0.0)   # Euler degrees
     scale: tuple = (1.0, 1.0, 1.0)
+    material: dict = None               # {"ambient", "diffuse", "specular", "emission": [3], "shininess"}; None = the splat sets' default
 
 
 @dataclass
@@ -37,7 +41,16 @@ class Project:
     rgba_format: int = 0
     splat_sets: dict = field(default_factory=dict)      # id -> absolute path
     instances: list = field(default_factory=list)       # [SplatInstance]
-    extra: dict = field(default_factory=dict)           # sections we do not interpret (lights, meshes, ...)
+    extra: dict = field(default_factory=dict)           # sections written back as read (meshes, ..., and the raw "lights")
+    lights: list = field(default_factory=list)          # "lights" interpreted: dicts with the field names of MgsLight
+
+    @property
+    def lighting_mode(self):
+        """renderer.lightingMode; files from before it have "lightingEnabled", which maps to indirect (vkgs_project_reader.cpp:143-153)"""
+        r = self.renderer
+        if "lightingMode" in r:
+            return int(r["lightingMode"])
+        return 2 if r.get("lightingEnabled", False) else 0
 
     # ---- mapping onto the C ABI ------------------------------------------------------------------
     def frame_params(self, width, height, flip_y=False):
@@ -68,6 +81,7 @@ class Project:
         p.debug_flags = ((capi.DEBUG_POINT_CLOUD if r.get("pointCloudModeEnabled", False) else 0)
                          | (capi.DEBUG_SH_ONLY if r.get("showShOnly", False) else 0)
                          | (capi.DEBUG_OPACITY_GAUSSIAN_DISABLED if r.get("opacityGaussianDisabled", False) else 0))
+        p.lighting_mode = self.lighting_mode
         return p
 
     def build_scene(self, device=0):
@@ -79,8 +93,12 @@ class Project:
             if inst.splat_set_id not in sets:
                 continue  # "Invalid splatSetId reference" is skipped by the reader (vkgs_project_reader.cpp:268-270)
             M, _ = capi.compute_transform(inst.scale, inst.rotation, inst.position)
-            scene.add_instance(sets[inst.splat_set_id], M)
+            idx = scene.add_instance(sets[inst.splat_set_id], M)
+            if inst.material is not None:
+                scene.set_material(idx, capi.make_material(**inst.material))
         scene.commit(self.sh_format, self.rgba_format)
+        if self.lights:
+            scene.set_lights([capi.make_light(**l) for l in self.lights])
         return scene
 
 
@@ -106,6 +124,63 @@ def _cam_to(c):
             "focusDist": float(c.focus_dist), "aperture": float(c.aperture)}
 
 
+def _material_from(item):
+    """LOAD3 / LOAD1 keep the default where a key is absent; the default is the splat sets' (emission 1, splat_set_vk.cpp:128-135)"""
+    m = {"ambient": [0.0, 0.0, 0.0], "diffuse": [0.0, 0.0, 0.0], "specular": [0.0, 0.0, 0.0], "emission": [1.0, 1.0, 1.0], "shininess": 0.0}
+    for k in ("ambient", "diffuse", "specular", "emission"):
+        if k in item:
+            m[k] = [float(x) for x in item[k]]
+    if "shininess" in item:
+        m["shininess"] = float(item["shininess"])
+    return m
+
+
+def _light_direction(rotation_deg):
+    """the instance rotation applied to (0, 0, -1) (light_manager_vk.cpp:470-471, rotateDirection in utilities.h: the rotation of
+    computeTransform)"""
+    if not any(float(x) != 0.0 for x in rotation_deg):
+        return [0.0, 0.0, -1.0]
+    from . import capi
+    M, _ = capi.compute_transform((1.0, 1.0, 1.0), rotation_deg, (0.0, 0.0, 0.0))
+    return [float(x) for x in (np.asarray(M, np.float64)[:3, :3] @ np.array([0.0, 0.0, -1.0]))]
+
+
+def _lights_from(section, version):
+    """loadLights (vkgs_project_reader.cpp:616-770) -> dicts with the field names of MgsLight"""
+    def asset_fields(a, v4):
+        L = {"type": int(a.get("type", 1)), "color": [float(x) for x in a.get("color", (1.0, 1.0, 1.0))], "intensity": float(a.get("intensity", 1.0)),
+             "range": 10.0, "inner_cone_deg": 30.0, "outer_cone_deg": 45.0, "attenuation_mode": 2}
+        if v4:
+            for src, dst, conv in (("range", "range", float), ("innerConeAngle", "inner_cone_deg", float), ("outerConeAngle", "outer_cone_deg", float),
+                                   ("attenuationMode", "attenuation_mode", int)):
+                if src in a:
+                    L[dst] = conv(a[src])
+        elif "radius" in a:  # the old "radius" is the new "range"
+            L["range"] = float(a["radius"])
+        return L
+
+    out = []
+    if version >= 3 and isinstance(section, dict) and "assets" in section and "instances" in section:
+        assets = {int(a["id"]): a for a in section["assets"]}
+        for inst in section["instances"]:
+            L = asset_fields(assets[int(inst["assetId"])], version >= 4)
+            if version >= 4:
+                L["position"] = [float(x) for x in inst.get("translation", (0.0, 2.0, 0.0))]
+                L["direction"] = _light_direction(inst.get("rotation", (0.0, 0.0, 0.0)))
+            else:
+                L["position"] = [float(x) for x in inst.get("position", (0.0, 2.0, 0.0))]
+                L["direction"] = [0.0, 0.0, -1.0]
+            out.append(L)
+        return out
+    items = section["items"] if isinstance(section, dict) and "items" in section else section
+    for item in (items if isinstance(items, list) else []):
+        L = asset_fields(item, False)
+        L["position"] = [float(x) for x in item.get("position", (0.0, 2.0, 0.0))]
+        L["direction"] = [0.0, 0.0, -1.0]
+        out.append(L)
+    return out
+
+
 def load_project(path):
     with open(path) as f:
         data = json.load(f)
@@ -126,6 +201,8 @@ def load_project(path):
             inst = SplatInstance(int(item["splatSetId"]), item.get("name", ""))
             if all(k in item for k in ("position", "rotation", "scale")):
                 inst.position, inst.rotation, inst.scale = tuple(item["position"]), tuple(item["rotation"]), tuple(item["scale"])
+            if "material" in item:
+                inst.material = _material_from(item["material"])
             pr.instances.append(inst)
     else:  # legacy (version 0): every splat entry carries its own path
         for i, item in enumerate(data.get("splats", [])):
@@ -133,9 +210,13 @@ def load_project(path):
             inst = SplatInstance(i, item.get("name", ""))
             if all(k in item for k in ("position", "rotation", "scale")):
                 inst.position, inst.rotation, inst.scale = tuple(item["position"]), tuple(item["rotation"]), tuple(item["scale"])
+            if "material" in item:
+                inst.material = _material_from(item["material"])
             pr.instances.append(inst)
     pr.extra = {k: v for k, v in data.items()
                 if k not in ("version", "renderer", "camera", "cameras", "splatsGlobals", "splatSets", "splats")}
+    if "lights" in data:
+        pr.lights = _lights_from(data["lights"], pr.version)
     return pr
 
 
@@ -146,8 +227,9 @@ def save_project(pr, path):
             "splatsGlobals": {"shFormat": pr.sh_format, "rgbaFormat": pr.rgba_format},
             "splatSets": [{"id": sid, "path": os.path.relpath(p, base), "storage": 0, "shFormat": pr.sh_format,
                            "rgbaFormat": pr.rgba_format} for sid, p in sorted(pr.splat_sets.items())],
-            "splats": [{"splatSetId": i.splat_set_id, "name": i.name, "position": list(i.position),
-                        "rotation": list(i.rotation), "scale": list(i.scale)} for i in pr.instances]}
-    data.update(pr.extra)
+            "splats": [dict({"splatSetId": i.splat_set_id, "name": i.name, "position": list(i.position),
+                             "rotation": list(i.rotation), "scale": list(i.scale)},
+                            **({"material": dict(i.material)} if i.material is not None else {})) for i in pr.instances]}
+    data.update(pr.extra)  # the raw "lights" section among them, unchanged
     with open(path, "w") as f:
         json.dump(data, f, indent=4)
