@@ -32,7 +32,11 @@ extern "C" {
 #define MGS_ABI_MINOR 1   /* backward-compatible additions within MGS_ABI_VERSION (same struct sizes, same defaults):
                             5.1: deferred lighting — MgsFrameParams::reserved_[0] is named lighting_mode (0 = what it was), MgsLight / MgsMaterial,
                                  mgs_light_default, mgs_material_default, mgs_scene_set_lights, mgs_instance_set_material,
-                                 mgs_frame_download_surface(which = 3), MGS_STAGE_LIGHT */
+                                 mgs_frame_download_surface(which = 3), MGS_STAGE_LIGHT;
+                            image compare (MGS_HAS_IMAGE_COMPARE below): entry points only, both numbers stay — mgs_compare_capture,
+                                 mgs_compare_capture_upload, mgs_compare_release, mgs_compare_params_default, mgs_compare_metrics,
+                                 mgs_compare_view_default, mgs_compare_composite, mgs_compare_download_composite */
+#define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -413,6 +417,83 @@ int mgs_render_gathered(MgsScene scene, const MgsFrameParams* params, MgsFrameOu
  * mgs_render calls: after mgs_render_gathered the lists cover this rank's rows only, every rank would derive a different
  * table and the exchange sizes would disagree — MGS_ERR_STATE. */
 int mgs_frame_row_costs(MgsScene scene, uint32_t* cost_per_tile_row, size_t rows);
+
+/* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
+ * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).
+ * Capture a frame, then compute MSE / PSNR / FLIP of every later frame against it on the device and build the split view.  Valid
+ * per handle (scene or frame context, like mgs_frame_set_occluder): a capture belongs to the handle it was made on.  With no
+ * capture held, and as long as these entry points are not called, the library does what it did before they existed.
+ *
+ * The "current image" is the handle's last complete frame as mgs_frame_download would return it (after lighting and temporal
+ * accumulation), read AS STORED in its target format (fp16 / fp32 / UNORM8 -> float).  A frame is complete after mgs_render of the
+ * whole frame or after mgs_render_gathered; after a strip-only mgs_render the buffer holds only some rows: MGS_ERR_STATE. */
+enum { MGS_FLIP_DISABLED = 0, MGS_FLIP_APPROX = 1, MGS_FLIP_REFERENCE = 2 };   /* FLIPMode, image_compare_shaderio.h:52-57 */
+enum { MGS_COMPARE_SHOW_CAPTURE = 0, MGS_COMPARE_SHOW_CURRENT = 1, MGS_COMPARE_SHOW_DIFF_RAW = 2, MGS_COMPARE_SHOW_DIFF_RED_GRAY = 3,
+       MGS_COMPARE_SHOW_DIFF_RED_ONLY = 4, MGS_COMPARE_SHOW_FLIP = 5 };          /* DisplayMode, image_compare_shaderio.h:37-45 */
+/* ImageCompare::capture (image_compare.cpp:145-223): device-to-device copy of the last complete frame into an image the handle
+ * owns, ordered on the handle's stream; the copy keeps the frame's size and target format.  MGS_ERR_STATE before any frame and
+ * after a strip-only frame. */
+int  mgs_compare_capture(MgsScene scene_or_context);
+/* a capture made elsewhere (a reference screenshot, another build's frame): [height][width][4] float32, kept as RGBA32F */
+int  mgs_compare_capture_upload(MgsScene scene_or_context, const float* rgba_host, int width, int height);
+int  mgs_compare_release(MgsScene scene_or_context); /* releaseCaptureImage; valid without a capture */
+typedef struct MgsCompareParams {
+  int32_t flip_mode;          /* MGS_FLIP_*, default MGS_FLIP_REFERENCE (PushConstantMetrics, image_compare_shaderio.h:105-112) */
+  float   pixels_per_degree;  /* default 67: the reference's hard-coded value with its TODO (image_compare.cpp:785-788) */
+} MgsCompareParams;
+void mgs_compare_params_default(MgsCompareParams* p);
+typedef struct MgsCompareMetrics {
+  /* as written: the shader's two uint32 sums (each pixel adds uint(contribution / N * 1e9), truncated), and what
+   * collectMetricsResult derives from them (image_compare.cpp:869-906): float(sum) / 1e9f; PSNR 99.99 below 1e-10, else
+   * min(10 log10(1 / mse), 99.99) in float; FLIP = float(pow(double(sum) / 1e9, 1/3)).  The truncation drops most of the signal at
+   * real sizes (at 1920 x 1080 a pixel's contribution is below 1 for errors below about 0.05): compare with the exact fields.
+   * Defined for images in [0,1]; outside that range the reference's sum can wrap and its float-to-uint conversion is undefined,
+   * here a pixel's contribution saturates (negative or NaN: 0; too large: 0xFFFFFFFF) and the sum wraps. */
+  uint32_t mse_fixed, flip_fixed;
+  float    mse, psnr, flip;
+  /* exact: the same per-pixel fp32 values without the truncation, summed in double — per-workgroup partials combined in a fixed
+   * order, no floating-point atomics: two calls on the same images return the same bits.  mse_exact = sum / (W H 3), psnr_exact =
+   * 10 log10(1 / mse_exact) (+inf for identical images), flip_exact = (sum of powered errors / (W H))^(1/3).  Defined for all
+   * finite inputs. */
+  double   mse_exact, psnr_exact, flip_exact;
+  float    elapsed_ms;        /* HIP events around the metric launches */
+  uint32_t reserved0;
+} MgsCompareMetrics;
+/* computeMetrics + readBackMetricsResult + collectMetricsResult (image_compare.cpp:735-924).  Runs on the handle's stream after its
+ * last frame and waits.  Semantics, as written (image_compare_metric.comp.slang):
+ *  - one value per pixel of the CAPTURE.  The current image is read by Load when the sizes are equal and sampled bilinearly at
+ *    (p + 0.5) / captureSize otherwise (:96-110).  The sampler is nvvk's pool default and nvpro_core2 is not part of the reference
+ *    tree: clamp-to-edge with fp32 weights is chosen here, PARITY UNPINNED.  Loads outside an image (approx mode on a smaller
+ *    current image) return 0, the robust-access rule; likewise unpinned.
+ *  - MSE over RGB only, divider float(W * H * 3) (:117-130, image_compare.cpp:783).
+ *  - MGS_FLIP_APPROX (:371-477): YCxCz colour error with the CSF at 1 cycle per degree (both images loaded at the capture's
+ *    coordinate), 3 x 3 Sobel on Rec.709 luminance with zero feature on the one-pixel border of each image's own size, CSF at 4 cpd,
+ *    weight 3.83, pow(saturate(e), 3).
+ *  - MGS_FLIP_REFERENCE (:198-304, :486-541): sigma = max(ppd / (f * 6.28), 0.5) for f = 0.5, 1, 2, 4, 8; r = ceil(3 sigma); a pixel
+ *    within r of any border takes its centre luminance as the blurred value (feature 0), otherwise the normalised Gaussian mean of
+ *    the luminance; feature = |centre - blurred| * csfLuminance(f); on a current image of another size the feature is taken at
+ *    int(uv * currentSize); error = colour error + sum |feature difference|, saturated and cubed.  The shader's (2r+1)^2 loop is
+ *    evaluated as a row pass and a column pass (the weights are a product of two 1-D Gaussians and interior pixels never clamp),
+ *    normalised by the square of the 1-D weight sum: the same value up to fp32 rounding.  Radii above 96 (pixels_per_degree above
+ *    100) are not held by this build: MGS_ERR_UNSUPPORTED.
+ * MGS_ERR_STATE without a capture, before a frame, after a strip-only frame. */
+int  mgs_compare_metrics(MgsScene scene_or_context, const MgsCompareParams* params, MgsCompareMetrics* out);
+typedef struct MgsCompareView {
+  float   split_position;     /* default 0.5 (PushConstantComparison, image_compare_shaderio.h:93-102) */
+  int32_t left, right;        /* MGS_COMPARE_SHOW_*, default capture | current */
+  float   difference_amplify; /* default 5.0 */
+  int32_t width, height;      /* output size; 0 = the current frame's */
+} MgsCompareView;
+void mgs_compare_view_default(MgsCompareView* v);
+/* ImageCompare::render's composite dispatch (image_compare.cpp:690-733, image_compare_composite.comp.slang:44-267): splitPos =
+ * int(split * width), a 5-pixel divider with a 1-pixel white centre, the side's display mode elsewhere; sampleImage loads when that
+ * image's size equals the output's and samples bilinearly (the sampler above) otherwise; the heat map is the composite shader's own
+ * computeFLIP (:186-254: sRGB -> opponent colour, three-scale contrast at the output pixel's coordinate, pow(., 0.75), Turbo colour
+ * map) — a different formula from the metric's.  The output is [height][width][4] float32 in a buffer the handle owns, valid until
+ * the next call; *device_out / *bytes (either may be NULL) receive it.  Ordered on the handle's stream, does not wait. */
+int  mgs_compare_composite(MgsScene scene_or_context, const MgsCompareView* view, void** device_out, uint64_t* bytes);
+/* copies the last composite to the host and waits */
+int  mgs_compare_download_composite(MgsScene scene_or_context, void* host_dst, size_t bytes);
 
 /* test/debug hook (no reference counterpart: these are the mesh shader's per-quad outputs,
  * threedgs_raster.mesh.slang:243-289, which the reference never stores): the projected records the last full frame

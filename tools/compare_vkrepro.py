@@ -1,6 +1,6 @@
 """Closes the loop of tests/golden/vkrepro on a Vulkan box: PSNR of a screenshot of the REFERENCE against the expected frame of a case.
 
-    python tools/compare_vkrepro.py <case | path/to/expected.npy> <reference screenshot: .hdr | .npy | .png> [--flip-y]
+    python tools/compare_vkrepro.py <case | path/to/expected.npy> <reference screenshot: .hdr | .npy | .png> [--flip-y] [--device]
 
   <case>       base | base_3dgut | u8_storage | fisheye150_3dgut | msaa_3dgs | two_instances_trs  (tests/golden/vkrepro/...;
                camera.json["reference_command"] of the case says how the reference produces the screenshot)
@@ -107,6 +107,32 @@ def psnr_rgb(ref, cur):
     return 99.99 if mse <= 0.0 else min(99.99, 10.0 * np.log10(1.0 / mse)), mse
 
 
+def device_psnr(want, got):
+    """PSNR of two host images of one size through mgs_compare_metrics (needs an MI355X): `want` is uploaded as the capture; `got`
+    becomes the handle's current image by being drawn as the background of a frame in which an occluder at window depth 0 hides
+    every splat (RGBA32F target: rgb = 0 + 1 * background, bit for bit).  tests/test_gpu_compare.py holds this to the host value."""
+    sys.path.insert(0, ROOT)
+    import vk_gaussian_splatting_amd as mgs
+    from vk_gaussian_splatting_amd import capi, synth
+    H, W = want.shape[:2]
+    one = np.ones((H, W, 1), np.float32)
+    scene = mgs.Scene(0)
+    try:
+        scene.add_instance(mgs.SplatSet.from_arrays(**synth.make_scene(1000)))
+        scene.commit()
+        scene.compare_capture_upload(np.concatenate([want[..., :3].astype(np.float32), one], axis=2))
+        scene.upload_occluder(np.zeros((H, W), np.float32), np.concatenate([got[..., :3].astype(np.float32), one], axis=2))
+        eye = synth.orbit_pose(0)
+        V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, W, H)
+        p = capi.default_params(W, H)
+        capi.set_camera(p, V, P, eye)
+        p.target_format = capi.TARGET_RGBA32F
+        scene.render(p)
+        return scene.compare_metrics(capi.FLIP_DISABLED).psnr_exact
+    finally:
+        scene.close()
+
+
 def main(argv):
     if len(argv) < 3:
         print(__doc__)
@@ -132,6 +158,8 @@ def main(argv):
     flipped, _ = psnr_rgb(want, got[::-1])
     print(f"{os.path.relpath(exp_path, ROOT)} vs {shot}: PSNR {psnr:.2f} dB (MSE {mse:.3e}), max abs {err.max():.4f}, "
           f"99.9th pct {np.percentile(err, 99.9):.4f}; north_star bar 40 dB -> {'PASS' if psnr >= 40.0 else 'FAIL'}")
+    if "--device" in argv:  # the same comparison through the library; the host value above stays the verdict
+        print(f"device (mgs_compare_metrics): PSNR {device_psnr(want, got):.2f} dB against the host's {psnr:.2f} dB")
     if flipped > psnr + 3.0:
         print(f"(the vertically flipped screenshot scores {flipped:.2f} dB: rerun with --flip-y)")
     return 0 if psnr >= 40.0 else 1

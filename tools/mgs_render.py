@@ -5,6 +5,7 @@
                              [--center x y z] [--fov deg] [--flip-y] [--sh-format 0|1|2] [--rgba-format 0|1|2]
                              [--occluder-depth FILE.npy [--background FILE.npy]]
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
+                             [--compare-with FRAME.npy [--flip-mode 0|1|2] [--compare-view OUT.png --split 0.5 --left capture --right diff-red-gray]]
 
 --occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
 depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear colour of that geometry, shown through the splats.
@@ -13,6 +14,10 @@ depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear co
 with the field names of MgsLight (type, color, intensity, position, range, direction, inner_cone_deg, outer_cone_deg,
 attenuation_mode; absent fields keep the reference's defaults); without it the headlight at the camera lights the scene.
 --material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
+
+--compare-with: float32 [H, W, 3|4] frame made elsewhere (a reference screenshot, another build's frame), uploaded as the capture;
+prints MSE / PSNR / FLIP of the rendered frame against it, computed on the device (mgs_compare_metrics).  --compare-view writes
+the split view (left | right of --split; modes capture, current, diff-raw, diff-red-gray, diff-red-only, flip).
 
 PNG = linear RGB clamped to [0,1] over a black background, 8 bit, no tonemap — like the reference's
 screenshot path (gaussian_splatting_ui.cpp:508-540).  Needs an MI355X.
@@ -44,7 +49,15 @@ def main():
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
+    ap.add_argument("--compare-with", default=None, metavar="FRAME.npy")
+    ap.add_argument("--flip-mode", type=int, choices=[0, 1, 2], default=capi.FLIP_REFERENCE)
+    ap.add_argument("--compare-view", default=None, metavar="OUT.png")
+    ap.add_argument("--split", type=float, default=0.5)
+    ap.add_argument("--left", choices=sorted(capi.SHOW_NAMES), default="capture")
+    ap.add_argument("--right", choices=sorted(capi.SHOW_NAMES), default="current")
     a = ap.parse_args()
+    if a.compare_view and not a.compare_with:
+        ap.error("--compare-view needs --compare-with")
     if a.scene.startswith("syn:"):
         ss = mgs.SplatSet.from_arrays(**synth.make_scene(int(a.scene[4:])))
     else:
@@ -86,6 +99,18 @@ def main():
         from PIL import Image
         rgb = np.clip(img[..., :3], 0, 1)
         Image.fromarray((rgb * 255 + 0.5).astype(np.uint8)).save(a.out)
+    if a.compare_with:
+        scene.compare_capture_upload(np.load(a.compare_with))
+        m = scene.compare_metrics(a.flip_mode)
+        print(f"against {a.compare_with}: as the reference computes it MSE {m.mse:.6g} PSNR {m.psnr:.2f} dB FLIP {m.flip:.5f}; "
+              f"exact MSE {m.mse_exact:.6g} PSNR {m.psnr_exact:.2f} dB FLIP {m.flip_exact:.5f}; {m.elapsed_ms:.3f} ms on the GPU")
+        if a.compare_view:
+            view = scene.compare_composite(split=a.split, left=a.left, right=a.right)
+            if a.compare_view.endswith(".npy"):
+                np.save(a.compare_view, view)
+            else:
+                from PIL import Image
+                Image.fromarray((np.clip(view[..., :3], 0, 1) * 255 + 0.5).astype(np.uint8)).save(a.compare_view)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,9 @@ from .capi import (MgsError, SplatSet, Scene, Loader, FrameParams, FrameOut, Sor
                    camera_lookat_perspective, compute_transform,
                    FORMAT_FLOAT32, FORMAT_FLOAT16, FORMAT_UINT8, SORT_GPU_RADIX, SORT_CPU_ASYNC, SORT_STOCHASTIC, DOF_DISABLED, DOF_FIXED_FOCUS,
                    CULL_NONE, CULL_AT_DIST, CULL_AT_RASTER, TARGET_RGBA16F, TARGET_RGBA32F,
-                   ALPHA_COVERAGE, ALPHA_SUM)
+                   ALPHA_COVERAGE, ALPHA_SUM,
+                   CompareParams, CompareMetrics, CompareView, FLIP_DISABLED, FLIP_APPROX, FLIP_REFERENCE,
+                   SHOW_CAPTURE, SHOW_CURRENT, SHOW_DIFF_RAW, SHOW_DIFF_RED_GRAY, SHOW_DIFF_RED_ONLY, SHOW_FLIP)
 from . import synth
 
 __all__ = ["MgsError", "SplatSet", "Scene", "Loader", "FrameParams", "FrameOut", "SortOut", "lib_path", "load_library",

@@ -22,6 +22,10 @@ LIGHTING_DISABLED, LIGHTING_DIRECT, LIGHTING_INDIRECT = 0, 1, 2
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
 MAX_LIGHTS = 64
 STAGE_LIGHT = 7  # index into timings_all(): the deferred lighting pass
+FLIP_DISABLED, FLIP_APPROX, FLIP_REFERENCE = 0, 1, 2  # FLIPMode
+# DisplayMode of the split view, by value and by the names tools/mgs_render.py accepts
+SHOW_CAPTURE, SHOW_CURRENT, SHOW_DIFF_RAW, SHOW_DIFF_RED_GRAY, SHOW_DIFF_RED_ONLY, SHOW_FLIP = 0, 1, 2, 3, 4, 5
+SHOW_NAMES = {"capture": 0, "current": 1, "diff-raw": 2, "diff-red-gray": 3, "diff-red-only": 4, "flip": 5}
 STAGE_NAMES = ["project", "sort", "bin", "pairsort", "composite", "total"]
 
 
@@ -101,6 +105,28 @@ def make_material(**kw):
     return m
 
 
+class CompareParams(C.Structure):
+    """MgsCompareParams"""
+    _fields_ = [("flip_mode", C.c_int32), ("pixels_per_degree", C.c_float)]
+
+
+class CompareMetrics(C.Structure):
+    """MgsCompareMetrics: the reference's fixed-point sums and what it derives from them, the exact values, the device time"""
+    _fields_ = [("mse_fixed", C.c_uint32), ("flip_fixed", C.c_uint32), ("mse", C.c_float), ("psnr", C.c_float), ("flip", C.c_float),
+                ("mse_exact", C.c_double), ("psnr_exact", C.c_double), ("flip_exact", C.c_double),
+                ("elapsed_ms", C.c_float), ("reserved0", C.c_uint32)]
+
+    def __repr__(self):
+        return (f"CompareMetrics(mse={self.mse:.6g}, psnr={self.psnr:.2f}, flip={self.flip:.5f}, mse_exact={self.mse_exact:.6g}, "
+                f"psnr_exact={self.psnr_exact:.2f}, flip_exact={self.flip_exact:.5f}, elapsed_ms={self.elapsed_ms:.3f})")
+
+
+class CompareView(C.Structure):
+    """MgsCompareView"""
+    _fields_ = [("split_position", C.c_float), ("left", C.c_int32), ("right", C.c_int32), ("difference_amplify", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class FrameOut(C.Structure):
     _fields_ = [("rgba_device", C.c_void_p), ("rgba_bytes", C.c_uint64),
                 ("frustum_count", C.c_uint32), ("sorted_count", C.c_uint32), ("tile_pairs", C.c_uint64),
@@ -158,6 +184,14 @@ def load_library():
         "mgs_scene_set_lights": (C.c_int, [vp, P(Light), C.c_int]),
         "mgs_instance_set_material": (C.c_int, [vp, C.c_int, P(Material)]),
         "mgs_scene_splat_count": (C.c_uint64, [vp]),
+        "mgs_compare_capture": (C.c_int, [vp]),
+        "mgs_compare_capture_upload": (C.c_int, [vp, P(F), C.c_int, C.c_int]),
+        "mgs_compare_release": (C.c_int, [vp]),
+        "mgs_compare_params_default": (None, [P(CompareParams)]),
+        "mgs_compare_metrics": (C.c_int, [vp, P(CompareParams), P(CompareMetrics)]),
+        "mgs_compare_view_default": (None, [P(CompareView)]),
+        "mgs_compare_composite": (C.c_int, [vp, P(CompareView), P(vp), P(C.c_uint64)]),
+        "mgs_compare_download_composite": (C.c_int, [vp, vp, C.c_size_t]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -208,6 +242,8 @@ EXPORTED_SYMBOLS = [
     "mgs_frame_context_create", "mgs_frame_context_destroy", "mgs_scene_memory_usage", "mgs_scene_set_list_capacity",
     "mgs_frame_set_occluder", "mgs_frame_upload_occluder",
     "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_instance_set_material",
+    "mgs_compare_capture", "mgs_compare_capture_upload", "mgs_compare_release", "mgs_compare_params_default", "mgs_compare_metrics",
+    "mgs_compare_view_default", "mgs_compare_composite", "mgs_compare_download_composite",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -383,6 +419,7 @@ class Scene:
             _check(lib.mgs_frame_context_create(_context_of._h, C.byref(h)))
         self._h = h
         self._sets = [] if _context_of is None else _context_of._sets
+        self._frame_wh = None  # size of the last frame rendered through this object (compare_composite's default output size)
 
     def frame_context(self):
         """a frame in flight over this scene's committed data: own stream, working buffers and graphs (mgs_frame_context_create)"""
@@ -467,6 +504,7 @@ class Scene:
     def render(self, params, want_stats=False):
         out = FrameOut()
         self._sort_only = False
+        self._frame_wh = (params.width, params.height)
         _check(self._lib.mgs_render(self._h, C.byref(params), C.byref(out)))
         if want_stats and not params.collect_timings:
             _check(self._lib.mgs_frame_stats(self._h, C.byref(out)))
@@ -518,6 +556,43 @@ class Scene:
         _check(self._lib.mgs_frame_download_surface(self._h, 3, depth.ctypes.data_as(C.c_void_p), depth.nbytes))
         return depth
 
+    # ---- image comparison (mgs_compare_*): a capture per handle, metrics and the split view against the last complete frame ----
+    def compare_capture(self):
+        """keep a device copy of the last complete frame as this handle's capture"""
+        _check(self._lib.mgs_compare_capture(self._h))
+
+    def compare_capture_upload(self, img):
+        """take float32[H,W,4] (RGBA; a 3-channel image gets alpha 1) made elsewhere as the capture"""
+        img = np.asarray(img)
+        if img.ndim != 3 or img.shape[2] not in (3, 4):
+            raise ValueError("compare_capture_upload: expected an [H,W,3|4] image")
+        if img.shape[2] == 3:
+            img = np.concatenate([img, np.ones(img.shape[:2] + (1,), img.dtype)], axis=2)
+        a = _f32(img)
+        _check(self._lib.mgs_compare_capture_upload(self._h, _fp(a), a.shape[1], a.shape[0]))
+
+    def compare_release(self):
+        _check(self._lib.mgs_compare_release(self._h))
+
+    def compare_metrics(self, flip_mode=FLIP_REFERENCE, ppd=67.0):
+        """MSE / PSNR / FLIP of the last complete frame against the capture: a CompareMetrics"""
+        p = CompareParams(int(flip_mode), float(ppd))
+        m = CompareMetrics()
+        _check(self._lib.mgs_compare_metrics(self._h, C.byref(p), C.byref(m)))
+        return m
+
+    def compare_composite(self, split=0.5, left=SHOW_CAPTURE, right=SHOW_CURRENT, amplify=5.0, width=0, height=0):
+        """the split view as float32[H,W,4]; left / right: SHOW_* values or their names (SHOW_NAMES)"""
+        v = CompareView(float(split), int(SHOW_NAMES.get(left, left)), int(SHOW_NAMES.get(right, right)), float(amplify), int(width), int(height))
+        nbytes = C.c_uint64(0)
+        _check(self._lib.mgs_compare_composite(self._h, C.byref(v), None, C.byref(nbytes)))
+        out = np.zeros(nbytes.value // 4, np.float32)
+        _check(self._lib.mgs_compare_download_composite(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        if not width and self._frame_wh is None:
+            raise MgsError(-1, "compare_composite: pass width and height (this object has rendered no frame itself)")
+        w = int(width) if width else self._frame_wh[0]  # 0 = the current frame's size
+        return out.reshape(-1, w, 4)
+
     def copy_strip(self, device_ptr, nbytes):
         _check(self._lib.mgs_frame_copy_strip(self._h, C.c_void_p(device_ptr), nbytes))
 
@@ -543,6 +618,7 @@ class Scene:
     def render_gathered(self, params):
         out = FrameOut()
         self._sort_only = False
+        self._frame_wh = (params.width, params.height)
         _check(self._lib.mgs_render_gathered(self._h, C.byref(params), C.byref(out)))
         return out
 

@@ -27,6 +27,7 @@
 
 #include "../../include/mgs.h"
 #include "device_types.h"
+#include "compare_types.h"
 #include "host_model.h"
 #include "sort_plan.h"
 #include "tuning.h"
@@ -351,6 +352,16 @@ struct MgsScene_t
   DevBuf<float>         consDepth;   // consolidated depth, computed when mgs_frame_download_surface(3) asks for it
   const float*          lastOccDepth = nullptr;  // the occluder depth the last frame was rendered against
   bool                  lastOccGone  = false;    // ... was a library-owned copy that has been freed since
+  // image comparison (mgs_compare_*): the captured image as stored, the planes of the FLIP reference passes, the sums, the split view
+  DevBuf<uint8_t>       cmpCapture;
+  CmpImage              cmpCap{};
+  bool                  cmpHaveCapture = false;
+  DevBuf<float>         cmpPlanes;
+  DevBuf<uint32_t>      cmpFixed;
+  DevBuf<double>        cmpPartials;
+  DevBuf<float4>        cmpOut;
+  int                   cmpOutW = 0, cmpOutH = 0;
+  hipEvent_t            cmpEv[2] = {};
   DevBuf<float4>        accum;       // temporal accumulation (post.comp.slang): running mean of the frame samples, fp32
   bool                  haveSurface = false;
   DevBuf<SplatRec>      rec;
@@ -816,6 +827,9 @@ void mgs_scene_destroy(MgsScene s)
   s->ranges.release(); s->image.release(); s->cpuDistDev.release(); s->occOwnDepth.release(); s->occOwnColor.release();
   s->rsKeys.release(); s->rsVals.release(); s->rsHist.release(); s->rsCount.release(); s->rsPlan.release();
   s->rsPairA.release(); s->rsPairB.release(); s->rsStatus.release(); s->rsOsPlan.release();
+  s->cmpCapture.release(); s->cmpPlanes.release(); s->cmpFixed.release(); s->cmpPartials.release(); s->cmpOut.release();
+  for(auto& e : s->cmpEv)
+    if(e) (void)hipEventDestroy(e);
   if(s->hCtr) (void)hipHostFree(s->hCtr);
   if(s->hPlans) (void)hipHostFree(s->hPlans);
   if(s->binPolicy.host) (void)hipHostFree(s->binPolicy.host);
@@ -989,6 +1003,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
     add(s->dbinMasks); add(s->fstate); add(s->surfDepth); add(s->surfId); add(s->surfNormal); add(s->consDepth); add(s->accum); add(s->rec); add(s->recGut);
     add(s->pairKey0); add(s->pairVal0); add(s->pairKey1); add(s->pairVal1); add(s->ranges); add(s->image);
     add(s->rsKeys); add(s->rsVals); add(s->rsHist); add(s->rsCount); add(s->rsPairA); add(s->rsPairB); add(s->rsStatus); add(s->rsOsPlan); add(s->rsPlan); add(s->cpuDistDev);
+    add(s->cmpCapture); add(s->cmpPlanes); add(s->cmpFixed); add(s->cmpPartials); add(s->cmpOut);
     *workingBytes = b;
   }
   return MGS_OK;
@@ -3644,5 +3659,349 @@ void mgs_compute_transform(const float scale[3], const float rotDeg[3], const fl
   if(Minv)
     mat4Inverse(M, Minv);
 }
+
+// ---- runtime image comparison (ImageCompare, src/image_compare.cpp) ----------------------------------------------------------
+// The capture, the planes of the FLIP reference passes and the composite output belong to the handle; nothing here is touched by
+// a frame, and a frame touches nothing here.
+static int cmpFormatOf(int targetFormat) { return targetFormat == MGS_TARGET_RGBA16F ? 1 : (targetFormat == MGS_TARGET_RGBA8 ? 2 : 0); }
+static size_t cmpPixelBytes(int fmt) { return fmt == 1 ? 8 : (fmt == 2 ? 4 : 16); }
+
+// the handle's last complete frame as a compare image, or the reason there is none
+static int cmpCurrentImage(MgsScene s, const char* who, CmpImage& img)
+{
+  if(!s->haveFrame || s->lastWasSortOnly)
+  {
+    setError(std::string(who) + ": no frame rendered yet");
+    return MGS_ERR_STATE;
+  }
+  const MgsFrameParams& q = s->lastParams;
+  if(q.strip_row_begin != 0 || q.strip_row_end * kTilePx < q.height)
+  {
+    setError(std::string(who) + ": the last frame was a strip-only mgs_render; the frame buffer holds only some rows");
+    return MGS_ERR_STATE;
+  }
+  img.p   = s->image.p;
+  img.w   = q.width;
+  img.h   = q.height;
+  img.fmt = cmpFormatOf(q.target_format);
+  return MGS_OK;
+}
+
+static int mgs_compare_capture_impl(MgsScene s)
+{
+  if(!s)
+  {
+    setError("mgs_compare_capture: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  CmpImage cur{};
+  if(int rc = cmpCurrentImage(s, "mgs_compare_capture", cur))
+    return rc;
+  HIPCHK(hipSetDevice(s->device));
+  const size_t bytes = (size_t)cur.w * (size_t)cur.h * cmpPixelBytes(cur.fmt);
+  if(bytes > s->cmpCapture.n)
+    HIPCHK(hipStreamSynchronize(s->stream));  // a composite in flight may still read the copy that is about to be freed
+  if(int rc = s->cmpCapture.ensure(bytes))
+    return rc;
+  HIPCHK(hipMemcpyAsync(s->cmpCapture.p, cur.p, bytes, hipMemcpyDeviceToDevice, s->stream));
+  s->cmpCap        = cur;
+  s->cmpCap.p      = s->cmpCapture.p;
+  s->cmpHaveCapture = true;
+  return MGS_OK;
+}
+int mgs_compare_capture(MgsScene s)
+{
+  return guarded("mgs_compare_capture", [&] { return mgs_compare_capture_impl(s); });
+}
+
+static int mgs_compare_capture_upload_impl(MgsScene s, const float* rgbaHost, int width, int height)
+{
+  if(!s || !rgbaHost || width <= 0 || height <= 0 || (uint64_t)width * (uint64_t)height > 0x7FFFFFFFull / 16)
+  {
+    setError(!s ? "mgs_compare_capture_upload: null handle" : "mgs_compare_capture_upload: bad argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  const size_t bytes = (size_t)width * (size_t)height * 16;
+  HIPCHK(hipStreamSynchronize(s->stream));  // whatever still reads the previous capture
+  if(int rc = s->cmpCapture.ensure(bytes))
+    return rc;
+  HIPCHK(hipMemcpy(s->cmpCapture.p, rgbaHost, bytes, hipMemcpyHostToDevice));
+  s->cmpCap         = CmpImage{s->cmpCapture.p, width, height, 0};
+  s->cmpHaveCapture = true;
+  return MGS_OK;
+}
+int mgs_compare_capture_upload(MgsScene s, const float* rgbaHost, int width, int height)
+{
+  return guarded("mgs_compare_capture_upload", [&] { return mgs_compare_capture_upload_impl(s, rgbaHost, width, height); });
+}
+
+static int mgs_compare_release_impl(MgsScene s)
+{
+  if(!s)
+  {
+    setError("mgs_compare_release: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  s->cmpCapture.release();
+  s->cmpPlanes.release();
+  s->cmpOut.release();
+  s->cmpFixed.release();
+  s->cmpPartials.release();
+  s->cmpHaveCapture = false;
+  s->cmpOutW = s->cmpOutH = 0;
+  return MGS_OK;
+}
+int mgs_compare_release(MgsScene s)
+{
+  return guarded("mgs_compare_release", [&] { return mgs_compare_release_impl(s); });
+}
+
+void mgs_compare_params_default(MgsCompareParams* p)
+{
+  if(!p)
+    return;
+  p->flip_mode         = MGS_FLIP_REFERENCE;  // PushConstantMetrics
+  p->pixels_per_degree = 67.0f;               // image_compare.cpp:788
+}
+
+void mgs_compare_view_default(MgsCompareView* v)
+{
+  if(!v)
+    return;
+  v->split_position     = 0.5f;
+  v->left               = MGS_COMPARE_SHOW_CAPTURE;
+  v->right              = MGS_COMPARE_SHOW_CURRENT;
+  v->difference_amplify = 5.0f;
+  v->width = v->height = 0;
+}
+
+// csfLuminance (image_compare_metric.comp.slang:198-208) in fp32
+static float cmpCsfLuminance(float freq)
+{
+  const float s = 1.0f / std::sqrt(1.0f + std::pow(freq / 4.0f, 2.0f));
+  return s * std::exp(-0.5f * freq);
+}
+
+static int mgs_compare_metrics_impl(MgsScene s, const MgsCompareParams* p, MgsCompareMetrics* out)
+{
+  if(!s || !out)
+  {
+    setError(!s ? "mgs_compare_metrics: null handle" : "mgs_compare_metrics: null argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  MgsCompareParams q;
+  mgs_compare_params_default(&q);
+  if(p)
+    q = *p;
+  if(q.flip_mode < MGS_FLIP_DISABLED || q.flip_mode > MGS_FLIP_REFERENCE || !(q.pixels_per_degree > 0.0f) || !std::isfinite(q.pixels_per_degree))
+  {
+    setError("mgs_compare_metrics: flip_mode must be MGS_FLIP_DISABLED / APPROX / REFERENCE and pixels_per_degree positive");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(!s->cmpHaveCapture)
+  {
+    setError("mgs_compare_metrics: no capture held (mgs_compare_capture / mgs_compare_capture_upload)");
+    return MGS_ERR_STATE;
+  }
+  CmpImage cur{};
+  if(int rc = cmpCurrentImage(s, "mgs_compare_metrics", cur))
+    return rc;
+  const CmpImage cap = s->cmpCap;
+  HIPCHK(hipSetDevice(s->device));
+
+  CmpMetricArgs a{};
+  a.cap     = cap;
+  a.cur     = cur;
+  a.divider = float(cap.w * cap.h * 3);  // image_compare.cpp:783
+  a.csfY    = cmpCsfLuminance(1.0f);
+  a.csfC    = a.csfY * 0.4f;  // csfChrominance
+  a.csfEdge = cmpCsfLuminance(4.0f);
+  {  // huntAdjustment at adaptation luminance 1 (color.h.slang:101-115)
+    const float k = 5.0f * 1.0f, kCbrt = std::pow(k, 1.0f / 3.0f);
+    a.huntFL = 0.2f * kCbrt * (1.0f - std::exp(-0.42f * kCbrt));
+  }
+  const size_t capN = (size_t)cap.w * (size_t)cap.h, curN = (size_t)cur.w * (size_t)cur.h;
+  std::unique_ptr<CmpFlipTab> tab;
+  if(q.flip_mode == MGS_FLIP_REFERENCE)
+  {
+    tab.reset(new CmpFlipTab());
+    std::memset(tab.get(), 0, sizeof(CmpFlipTab));
+    const float freq[kCmpChannels] = {0.5f, 1.0f, 2.0f, 4.0f, 8.0f};
+    for(int i = 0; i < kCmpChannels; ++i)
+    {
+      float sigma = q.pixels_per_degree / (freq[i] * 6.28f);
+      sigma       = std::max(sigma, 0.5f);
+      const float rf = std::ceil(3.0f * sigma);
+      if(!(rf <= (float)kCmpMaxRadius))
+      {
+        setError("mgs_compare_metrics: pixels_per_degree gives a filter radius above " + std::to_string(kCmpMaxRadius) + ", which this build does not hold");
+        return MGS_ERR_UNSUPPORTED;
+      }
+      tab->r[i]   = (int)rf;
+      tab->csf[i] = cmpCsfLuminance(freq[i]);
+      float wsum  = 0.0f;
+      for(int d = -tab->r[i]; d <= tab->r[i]; ++d)
+      {
+        const float x = (float)d;
+        const float w = std::exp(-(x * x) / (2.0f * sigma * sigma));  // gaussianWeight
+        tab->w[i][d < 0 ? -d : d] = w;
+        wsum += w;
+      }
+      tab->norm[i] = wsum * wsum;
+    }
+    // planes: luminance of both images, the row pass's five planes (shared by the two images), five feature planes each
+    const size_t need = capN + curN + kCmpChannels * std::max(capN, curN) + kCmpChannels * (capN + curN);
+    if(need > s->cmpPlanes.n)
+      HIPCHK(hipStreamSynchronize(s->stream));
+    if(int rc = s->cmpPlanes.ensure(need))
+      return rc;
+  }
+  const uint32_t bx = (uint32_t)(cap.w + 15) / 16, by = (uint32_t)(cap.h + 15) / 16;
+  if(int rc = s->cmpPartials.ensure(2 * (size_t)bx * by + 2))
+    return rc;
+  if(int rc = s->cmpFixed.ensure(4))
+    return rc;
+  if(!s->cmpEv[0])
+  {
+    HIPCHK(hipEventCreate(&s->cmpEv[0]));
+    HIPCHK(hipEventCreate(&s->cmpEv[1]));
+  }
+  a.fixed    = s->cmpFixed.p;
+  a.partials = s->cmpPartials.p + 2;  // [0..1]: the folded sums
+  hipStream_t st = s->stream;
+  HIPCHK(hipEventRecord(s->cmpEv[0], st));
+  HIPCHK(hipMemsetAsync(s->cmpFixed.p, 0, 4 * sizeof(uint32_t), st));  // vkCmdFillBuffer, image_compare.cpp:765
+  if(q.flip_mode == MGS_FLIP_REFERENCE)
+  {
+    float* lumCap  = s->cmpPlanes.p;
+    float* lumCur  = lumCap + capN;
+    float* rows    = lumCur + curN;
+    float* featCap = rows + kCmpChannels * std::max(capN, curN);
+    float* featCur = featCap + kCmpChannels * capN;
+    launchCmpLuminance(st, cap, lumCap);
+    launchCmpLuminance(st, cur, lumCur);
+    launchCmpBlurRows(st, lumCap, rows, cap.w, cap.h, *tab);
+    launchCmpBlurCols(st, rows, lumCap, featCap, cap.w, cap.h, *tab);
+    launchCmpBlurRows(st, lumCur, rows, cur.w, cur.h, *tab);
+    launchCmpBlurCols(st, rows, lumCur, featCur, cur.w, cur.h, *tab);
+    a.featCap = featCap;
+    a.featCur = featCur;
+  }
+  launchCmpMetric(st, a, q.flip_mode, bx, by);
+  launchCmpFold(st, a.partials, bx * by, s->cmpPartials.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(s->cmpEv[1], st));
+  uint32_t fixed[4] = {};
+  double   sums[2]  = {};
+  HIPCHK(hipMemcpyAsync(fixed, s->cmpFixed.p, sizeof(fixed), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(sums, s->cmpPartials.p, sizeof(sums), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+
+  std::memset(out, 0, sizeof(*out));
+  HIPCHK(hipEventElapsedTime(&out->elapsed_ms, s->cmpEv[0], s->cmpEv[1]));
+  // collectMetricsResult, image_compare.cpp:869-906
+  out->mse_fixed  = fixed[0];
+  out->flip_fixed = fixed[2];
+  out->mse        = (float)fixed[0] / 1000000000.0f;
+  out->psnr       = out->mse < 1e-10f ? 99.99f : std::min(10.0f * std::log10(1.0f / out->mse), 99.99f);
+  out->flip       = (float)std::pow((double)fixed[2] / 1000000000.0, 1.0 / 3.0);
+  out->mse_exact  = sums[0] / ((double)cap.w * (double)cap.h * 3.0);
+  out->psnr_exact = out->mse_exact > 0.0 ? 10.0 * std::log10(1.0 / out->mse_exact) : HUGE_VAL;
+  out->flip_exact = q.flip_mode == MGS_FLIP_DISABLED ? 0.0 : std::pow(sums[1] / ((double)cap.w * (double)cap.h), 1.0 / 3.0);
+  return MGS_OK;
+}
+int mgs_compare_metrics(MgsScene s, const MgsCompareParams* p, MgsCompareMetrics* out)
+{
+  return guarded("mgs_compare_metrics", [&] { return mgs_compare_metrics_impl(s, p, out); });
+}
+
+static int mgs_compare_composite_impl(MgsScene s, const MgsCompareView* view, void** deviceOut, uint64_t* bytes)
+{
+  if(!s)
+  {
+    setError("mgs_compare_composite: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  MgsCompareView v;
+  mgs_compare_view_default(&v);
+  if(view)
+    v = *view;
+  if(v.left < 0 || v.left > MGS_COMPARE_SHOW_FLIP || v.right < 0 || v.right > MGS_COMPARE_SHOW_FLIP || v.width < 0 || v.height < 0
+     || (v.width == 0) != (v.height == 0) || !std::isfinite(v.split_position) || !std::isfinite(v.difference_amplify)
+     || (uint64_t)v.width * (uint64_t)v.height > 0x7FFFFFFFull / 16)
+  {
+    setError("mgs_compare_composite: display modes must be MGS_COMPARE_SHOW_*, the output size non-negative (both 0 or both set)");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(!s->cmpHaveCapture)
+  {
+    setError("mgs_compare_composite: no capture held (mgs_compare_capture / mgs_compare_capture_upload)");
+    return MGS_ERR_STATE;
+  }
+  CmpImage cur{};
+  if(int rc = cmpCurrentImage(s, "mgs_compare_composite", cur))
+    return rc;
+  HIPCHK(hipSetDevice(s->device));
+  CmpCompositeArgs a{};
+  a.cap  = s->cmpCap;
+  a.cur  = cur;
+  a.outW = v.width ? v.width : cur.w;
+  a.outH = v.height ? v.height : cur.h;
+  const size_t n = (size_t)a.outW * (size_t)a.outH;
+  if(n > s->cmpOut.n)
+    HIPCHK(hipStreamSynchronize(s->stream));
+  if(int rc = s->cmpOut.ensure(n))
+    return rc;
+  a.out     = s->cmpOut.p;
+  a.split   = v.split_position;
+  a.amplify = v.difference_amplify;
+  a.left    = v.left;
+  a.right   = v.right;
+  launchCmpComposite(s->stream, a);
+  HIPCHK(hipGetLastError());
+  s->cmpOutW = a.outW;
+  s->cmpOutH = a.outH;
+  if(deviceOut)
+    *deviceOut = s->cmpOut.p;
+  if(bytes)
+    *bytes = (uint64_t)n * sizeof(float4);
+  return MGS_OK;
+}
+int mgs_compare_composite(MgsScene s, const MgsCompareView* view, void** deviceOut, uint64_t* bytes)
+{
+  return guarded("mgs_compare_composite", [&] { return mgs_compare_composite_impl(s, view, deviceOut, bytes); });
+}
+
+static int mgs_compare_download_composite_impl(MgsScene s, void* dst, size_t bytes)
+{
+  if(!s || !dst)
+  {
+    setError(!s ? "mgs_compare_download_composite: null handle" : "mgs_compare_download_composite: null argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(!s->cmpOutW)
+  {
+    setError("mgs_compare_download_composite: no composite built yet (mgs_compare_composite)");
+    return MGS_ERR_STATE;
+  }
+  const size_t n = (size_t)s->cmpOutW * (size_t)s->cmpOutH * sizeof(float4);
+  if(bytes < n)
+  {
+    setError("mgs_compare_download_composite: destination too small");
+    return MGS_ERR_INVALID_ARG;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipMemcpyAsync(dst, s->cmpOut.p, n, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return MGS_OK;
+}
+int mgs_compare_download_composite(MgsScene s, void* dst, size_t bytes)
+{
+  return guarded("mgs_compare_download_composite", [&] { return mgs_compare_download_composite_impl(s, dst, bytes); });
+}
+
 
 }  // extern "C"
