@@ -1,4 +1,4 @@
-// fake_rccl.cpp — TEST DOUBLE of the RCCL entry points libmgs resolves with dlopen (csrc/mgs_api.hip: rccl()), for the ranks of
+// fake_rccl.cpp — TEST DOUBLE of the RCCL entry points libmgs resolves with dlopen (csrc/api_comm.hip: rccl()), for the ranks of
 // a multi-process job that SHARE ONE GPU.  Not part of the product: libmgs loads it only when MGS_RCCL_LIB names it (the tests
 // do), and the driver's list of loaded native libraries shows it as tests/helpers/libfakerccl.so.
 //

@@ -175,7 +175,7 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
 @pytest.mark.parametrize("kind", ["thin", "opaque"])
 def test_adaptive_bin_size_is_scheduling_only_and_follows_the_scan_ratio(kind):
     """Round 6: a frame context picks 128x128-px bins instead of 256x128 when its regions scan most of their lists (sampled every
-    32nd frame: scanned entries / (list entries x regions per bin) > 0.025 AND more than 900 entries walked per region; mgs_api.hip: BinPolicy).  A 72-frame sequence with the
+    32nd frame: scanned entries / (list entries x regions per bin) > 0.025 AND more than 900 entries walked per region; api_frame.hip: BinPolicy).  A 72-frame sequence with the
     policy (default) and without (MGS_BIN_ADAPT=0): the SAME frames bit for bit; on the translucent scene the number of list entries
     changes at the frame the policy is applied (24 frames in) and stays changed, on the opaque one it never does."""
     import subprocess

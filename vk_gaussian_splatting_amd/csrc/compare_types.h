@@ -1,4 +1,4 @@
-// compare_types.h — launch arguments of the image-compare kernels (k_compare.hip), shared with mgs_api.hip.
+// compare_types.h — launch arguments of the image-compare kernels (k_compare.hip), shared with api_compare.hip.
 #pragma once
 #include <stdint.h>
 

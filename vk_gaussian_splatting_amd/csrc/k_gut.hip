@@ -20,7 +20,7 @@
 #include "kernels_common.h"
 #include "sh_eval.h"
 #include "surface_normal.h"
-#include "sort_plan.h"
+#include "launchers.h"
 #include "slot_emit.h"
 #include "partition_cull.h"
 
@@ -1063,22 +1063,29 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
-void launchProjectGut(hipStream_t stream, const FrameArgs& args, const FrameArgs* dArgs, int shFormat, FrameCounters* ctr,
-                      uint2* slotPairs, uint32_t* slotCount, GutRec* rec, uint32_t* rect,
-                      uint32_t* slotHist2, uint32_t* top16Rec, uint32_t* top16Count, OsPlan* osPlan, const uint32_t* order)
+void launchProjectGut(hipStream_t stream, const ProjectLaunch& L)
 {
-  (void)shFormat;
-  if(args.f.totalPartitions == 0)
+  if(L.totalPartitions == 0)
     return;
-  hipLaunchKernelGGL(k_project_gut, dim3(args.f.totalPartitions), dim3(kGutThreads), 0, stream, dArgs, ctr, slotPairs, slotCount, rec, rect,
-                     slotHist2, top16Rec, top16Count, osPlan, order);
+  hipLaunchKernelGGL(k_project_gut, dim3(L.totalPartitions), dim3(kGutThreads), 0, stream, L.dArgs, L.ctr, L.slotPairs, L.slotCount, L.recGut,
+                     L.rect, L.slotHist2, L.top16Rec, L.top16Count, L.osPlan, L.order);
 }
 
-void launchCompositeGut(hipStream_t stream, const FrameArgs& A, const FrameArgs* dArgs, const uint2* ranges, const uint32_t* valX,
-                        const uint32_t* valY, const SortPlan* planPairs, const GutRec* rec, void* image, int halfOut,
-                        FrameCounters* ctr, int shFormat, float* outDepth, uint32_t* outSplatId, float4* outNormal,
-                        const Occluder& occ)
+void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L)
 {
+  const FrameArgs& A         = *L.A;
+  const FrameArgs* dArgs     = L.dArgs;
+  const uint2*     ranges    = L.ranges;
+  const uint32_t * valX = L.valX, *valY = L.valY;
+  const SortPlan*  planPairs = L.planPairs;
+  const GutRec*    rec       = L.recGut;
+  void*            image     = L.image;
+  const int        halfOut = L.halfOut, shFormat = L.shFormat;
+  FrameCounters*   ctr        = L.ctr;
+  float*           outDepth   = L.outDepth;
+  uint32_t*        outSplatId = L.outSplatId;
+  float4*          outNormal  = L.outNormal;
+  const Occluder&  occ        = L.occ;
   const int tiles = A.f.tilesX * (A.f.stripRow1 - A.f.stripRow0);
   if(tiles <= 0)
     return;

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mgs.h"
-#include "device_types.h"
+#include "launchers.h"
 
 namespace mgs {
 

@@ -23,7 +23,7 @@
 #include <cstdlib>
 #include <vector>
 #include "kernels_common.h"
-#include "sort_plan.h"
+#include "launchers.h"
 #include "slot_emit.h"
 #include "partition_cull.h"
 
@@ -536,17 +536,17 @@ __global__ __launch_bounds__(kPrjThreads, 6) void k_project(const FrameArgs* __r
 
 // ---------------------------------------------------------------------------------------------
 // host-callable launcher
-void launchProject(hipStream_t stream, const FrameArgs& args, const FrameArgs* dArgs, bool full, FrameCounters* ctr, uint2* slotPairs,
-                   uint32_t* slotCount, SplatRec* rec, uint32_t* rect, uint32_t* slotHist2,
-                   uint32_t* top16Rec, uint32_t* top16Count, OsPlan* osPlan, const uint32_t* order)
+static_assert(kPrjPart == (int)kPart, "the host sizes partitions by kPart");
+void launchProject(hipStream_t stream, const ProjectLaunch& L)
 {
-  const dim3 grid(args.f.totalPartitions), block(kPrjThreads);
-  if(args.f.totalPartitions == 0)
+  const dim3 grid(L.totalPartitions), block(kPrjThreads);
+  if(L.totalPartitions == 0)
     return;
+  const bool full = L.full;
 #ifdef MGS_PRJ_TRACE
   static uint64_t* traceBuf = nullptr;
   const char*      tracePath = std::getenv("MGS_PRJ_TRACE_FILE");
-  const size_t     traceN = (size_t)args.f.totalPartitions * 8;
+  const size_t     traceN = (size_t)L.totalPartitions * 8;
   if(tracePath && full)
   {
     if(!traceBuf)
@@ -558,8 +558,8 @@ void launchProject(hipStream_t stream, const FrameArgs& args, const FrameArgs* d
   }
 #endif
 #define MGS_LAUNCH(FULLV)                                                                                                \
-  hipLaunchKernelGGL((k_project<FULLV>), grid, block, 0, stream, dArgs, ctr, slotPairs, slotCount, rec, rect, slotHist2, \
-                     top16Rec, top16Count, osPlan, order)
+  hipLaunchKernelGGL((k_project<FULLV>), grid, block, 0, stream, L.dArgs, L.ctr, L.slotPairs, L.slotCount, L.rec, L.rect, \
+                     L.slotHist2, L.top16Rec, L.top16Count, L.osPlan, L.order)
   if(full)
     MGS_LAUNCH(true);
   else

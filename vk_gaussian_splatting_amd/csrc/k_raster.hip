@@ -16,7 +16,7 @@
 #include "kernels_common.h"
 #include "sh_eval.h"
 #include "surface_normal.h"
-#include "sort_plan.h"
+#include "launchers.h"
 #include "tuning.h"
 
 namespace mgs {
@@ -713,7 +713,7 @@ __global__ __launch_bounds__(256) void k_dbin_emit(const uint32_t* __restrict__ 
     {
       ctr->pairCount = (uint32_t)min(D64, (uint64_t)capacity);
       // (round 6) ... and beside the compositor's statistics (sort_plan.h: frameStatSlot, slot 0 word 4), so that ONE small copy
-      // tells the host how much of their lists the regions scan: the adaptive bin size's input (mgs_api.hip: BinPolicy)
+      // tells the host how much of their lists the regions scan: the adaptive bin size's input (api_frame.hip: BinPolicy)
       const_cast<uint32_t*>(&plan->ghist[0][0])[4] = (uint32_t)min(D64, (uint64_t)capacity);
       if(D64 > capacity)
         atomicOr(&ctr->errorFlags, kErrPairOverflow);
@@ -1717,21 +1717,19 @@ void launchFrameInit(hipStream_t stream, uint2* ranges, uint32_t nTiles)
   hipLaunchKernelGGL(k_frame_init, dim3(blocks), dim3(256), 0, stream, ranges, nTiles);
 }
 
-void launchBinning(hipStream_t stream, const uint32_t* idsX, const uint32_t* idsY, const SortPlan* planKeys,
-                   const uint32_t* rect, uint32_t* blockCount, uint32_t maxBlocks, FrameCounters* ctr, uint32_t* sortedRect,
-                   uint32_t* splatOffset, uint32_t* chunkStart, uint32_t* pairKey, uint32_t* pairVal, uint32_t capacity,
-                   int binsX, bool gatherRects)
+static_assert(kBinPart == (int)kPart, "the host sizes the binning's grid by kPart");
+void launchBinning(hipStream_t stream, const BinLaunch& L)
 {
-  if(maxBlocks == 0)
+  if(L.maxBlocks == 0)
     return;
-  hipLaunchKernelGGL(k_bin_count, dim3(maxBlocks), dim3(kBinThreads), 0, stream, idsX, idsY, planKeys, rect, sortedRect,
-                     blockCount, gatherRects ? 1 : 0);
-  hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(256), 0, stream, planKeys, blockCount, ctr, capacity);
-  const uint32_t chunks = (capacity + kChunk - 1) / kChunk;
-  hipLaunchKernelGGL(k_bin_offsets, dim3(maxBlocks), dim3(kBinThreads), 0, stream, planKeys, sortedRect, blockCount,
-                     splatOffset, chunkStart, chunks + 1);
-  hipLaunchKernelGGL(k_bin_expand, dim3(chunks), dim3(kBinThreads), 0, stream, idsX, idsY, planKeys, ctr, sortedRect,
-                     splatOffset, chunkStart, pairKey, pairVal, binsX);
+  hipLaunchKernelGGL(k_bin_count, dim3(L.maxBlocks), dim3(kBinThreads), 0, stream, L.idsX, L.idsY, L.planKeys, L.rect, L.sortedRect,
+                     L.blockCount, L.gatherRects ? 1 : 0);
+  hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(256), 0, stream, L.planKeys, L.blockCount, L.ctr, L.capacity);
+  const uint32_t chunks = (L.capacity + kChunk - 1) / kChunk;
+  hipLaunchKernelGGL(k_bin_offsets, dim3(L.maxBlocks), dim3(kBinThreads), 0, stream, L.planKeys, L.sortedRect, L.blockCount,
+                     L.splatOffset, L.chunkStart, chunks + 1);
+  hipLaunchKernelGGL(k_bin_expand, dim3(chunks), dim3(kBinThreads), 0, stream, L.idsX, L.idsY, L.planKeys, L.ctr, L.sortedRect,
+                     L.splatOffset, L.chunkStart, L.pairKey, L.pairVal, L.binsX);
 }
 
 bool directBinningSupported(int binsX, int binsY)
@@ -1739,18 +1737,15 @@ bool directBinningSupported(int binsX, int binsY)
   return binsX <= kDbMaxDim && binsY <= kDbMaxDim && binsX * binsY <= 256 && binsX + binsY <= kDbMaxSum;
 }
 
-void launchDirectBinning(hipStream_t stream, const uint32_t* idsX, const uint32_t* idsY, const SortPlan* planKeys,
-                         const uint32_t* rect, const uint16_t* sortedCode16, uint64_t* maskBuf, uint32_t maxSplats, uint32_t* binHist, uint32_t pStride,
-                         uint32_t* binTotal, uint32_t* binList, uint2* ranges, FrameCounters* ctr, uint32_t capacity,
-                         int binsX, int binsY, uint32_t* binCost)
+void launchDirectBinning(hipStream_t stream, const DirectBinLaunch& L)
 {
-  const uint32_t maxChunks = (maxSplats + kDbChunk - 1) / kDbChunk;
+  const uint32_t maxChunks = (L.maxSplats + kDbChunk - 1) / kDbChunk;
   if(maxChunks == 0)
     return;
   // MGS_DB_TRANSPOSE=0: the rounds' masks by ballots everywhere (the masks are the same; the transpose path is the default)
-  hipLaunchKernelGGL(k_dbin_count, dim3((maxChunks + kDbCntMul - 1) / kDbCntMul), dim3(256), 0, stream, idsX, idsY, planKeys, rect, sortedCode16, maskBuf,
-                     binHist, pStride, binsX, binsY, tuning().dbTranspose);
-  hipLaunchKernelGGL(k_dbin_scan, dim3(binsX * binsY), dim3(256), 0, stream, planKeys, binHist, pStride, binTotal);
+  hipLaunchKernelGGL(k_dbin_count, dim3((maxChunks + kDbCntMul - 1) / kDbCntMul), dim3(256), 0, stream, L.idsX, L.idsY, L.planKeys, L.rect, L.sortedCode16,
+                     L.maskBuf, L.binHist, L.pStride, L.binsX, L.binsY, tuning().dbTranspose);
+  hipLaunchKernelGGL(k_dbin_scan, dim3(L.binsX * L.binsY), dim3(256), 0, stream, L.planKeys, L.binHist, L.pStride, L.binTotal);
 #ifdef MGS_DB_TRACE
   static uint64_t* traceBuf = nullptr;
   const char*      tracePath = std::getenv("MGS_DB_TRACE_FILE");
@@ -1764,8 +1759,8 @@ void launchDirectBinning(hipStream_t stream, const uint32_t* idsX, const uint32_
     (void)hipMemsetAsync(traceBuf, 0, (size_t)maxChunks * 64, stream);
   }
 #endif
-  hipLaunchKernelGGL(k_dbin_emit, dim3(maxChunks), dim3(256), 0, stream, idsX, idsY, planKeys, maskBuf, binHist, pStride,
-                     binTotal, binList, ranges, ctr, capacity, binsX, binsY, binTotal + 256, sortedCode16, binCost);
+  hipLaunchKernelGGL(k_dbin_emit, dim3(maxChunks), dim3(256), 0, stream, L.idsX, L.idsY, L.planKeys, L.maskBuf, L.binHist, L.pStride,
+                     L.binTotal, L.binList, L.ranges, L.ctr, L.capacity, L.binsX, L.binsY, L.binTotal + 256, L.sortedCode16, L.binCost);
 #ifdef MGS_DB_TRACE
   if(tracePath)
   {
@@ -1787,12 +1782,11 @@ void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* 
   hipLaunchKernelGGL(k_tile_ranges, dim3(4096), dim3(256), 0, stream, keyX, keyY, planPairs, ranges);
 }
 
-void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges, const uint32_t* valX,
-                     const uint32_t* valY, const SortPlan* planPairs, const SplatRec* rec, void* image, int halfOut,
-                     int shFormat, FrameCounters* ctr, float* outDepth, uint32_t* outSplatId,
-                     const void* instTable, const FrameArgs* dArgs, float4* outNormal, uint32_t* binCost, const Occluder& occ)
+void launchComposite(hipStream_t stream, const CompositeLaunch& L)
 {
-  const FrameConst& F = A.f;
+  const FrameArgs&  A   = *L.A;
+  const FrameConst& F   = A.f;
+  const Occluder&   occ = L.occ;
   if(F.stripRow1 <= F.stripRow0)
     return;
   // all bins of the frame are enumerated (the bin order of the binning stage is over the whole frame; bins outside
@@ -1812,7 +1806,7 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
   C.nInstances = F.nInstances; C.shDegree = F.shDegree;
   C.depthIsoThreshold = F.depthIsoThreshold;
   C.shOnly     = (F.debugFlags & 2) ? 1 : 0;
-  C.binCost    = binCost;
+  C.binCost    = L.binCost;
   for(int i = 0; i < F.nInstances && i < kMaxInlineInstances; ++i)
   {
     C.inst[i].sh           = A.inst[i].sh;
@@ -1821,7 +1815,7 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
     C.inst[i].globalOffset = A.inst[i].globalOffset;
     C.inst[i].shDegree     = A.inst[i].shDegree;
   }
-  C.instTable = static_cast<const CompositeArgs::Inst*>(instTable);
+  C.instTable = static_cast<const CompositeArgs::Inst*>(L.instTable);
   C.occDepth  = occ.depth;
   C.occColor  = reinterpret_cast<const float4*>(occ.color);
   C.occStop   = occ.sortedByKey ? 1 : 0;
@@ -1838,10 +1832,10 @@ void launchComposite(hipStream_t stream, const FrameArgs& A, const uint2* ranges
   }
 #endif
 #define MGS_CMP(M, S)                                                                                                  \
-  hipLaunchKernelGGL((k_composite<M, S>), dim3(per * 8), dim3(256), 0, stream, C, ranges, valX, valY, planPairs, rec, image, \
-                     halfOut, ctr, outDepth, outSplatId, dArgs, outNormal)
+  hipLaunchKernelGGL((k_composite<M, S>), dim3(per * 8), dim3(256), 0, stream, C, L.ranges, L.valX, L.valY, L.planPairs, L.rec, \
+                     L.image, L.halfOut, L.ctr, L.outDepth, L.outSplatId, L.dArgs, L.outNormal)
 #define MGS_CMP_FMT(M)                                                                                                 \
-  switch(shFormat)                                                                                                     \
+  switch(L.shFormat)                                                                                                   \
   {                                                                                                                    \
     case 0: MGS_CMP(M, 0); break;                                                                                      \
     case 1: MGS_CMP(M, 1); break;                                                                                      \

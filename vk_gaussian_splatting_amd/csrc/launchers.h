@@ -1,0 +1,114 @@
+// launchers.h — every host-callable kernel launcher, declared once: the k_*.hip file that defines one includes this header, and
+// so does every caller, so a mismatch between the two is a compile error.  The sorts' and the compare kernels' launchers are
+// declared next to their argument structs in the two headers included below.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "compare_types.h"
+#include "device_types.h"
+#include "sort_plan.h"
+
+namespace mgs {
+
+// splats per workgroup of the project kernels, sorted splats per workgroup of the binning: k_project.hip and k_raster.hip
+// assert that their own constants equal it
+constexpr uint32_t kPart = 2048;
+
+// the project kernels (k_project.hip, k_gut.hip): cull, project, hand (key, id) pairs to the key sort (slot_emit.h)
+struct ProjectLaunch
+{
+  const FrameArgs* dArgs;            // the frame's constants on the device
+  uint32_t         totalPartitions;  // the grid: FrameConst::totalPartitions
+  bool             full;             // false: keys only (mgs_sort_keys); the 3DGUT kernel always runs in full
+  FrameCounters*   ctr;
+  uint2*           slotPairs;
+  uint32_t*        slotCount;
+  SplatRec*        rec;     // launchProject
+  GutRec*          recGut;  // launchProjectGut
+  uint32_t*        rect;
+  uint32_t*        slotHist2;
+  uint32_t*        top16Rec;
+  uint32_t*        top16Count;  // null: nobody consumes the counts (CPU sort)
+  OsPlan*          osPlan;
+  const uint32_t*  order;
+};
+void launchProject(hipStream_t stream, const ProjectLaunch& L);
+void launchProjectGut(hipStream_t stream, const ProjectLaunch& L);
+
+// the record + pair-sort path's binning (k_raster.hip)
+struct BinLaunch
+{
+  const uint32_t* idsX;  // the sorted ids: planKeys->finalSel selects X or Y; the frame's key sort always ends in one buffer,
+  const uint32_t* idsY;  // so the frame passes it as both
+  const SortPlan* planKeys;
+  const uint32_t* rect;
+  uint32_t*       blockCount;
+  uint32_t        maxBlocks;
+  FrameCounters*  ctr;
+  uint32_t*       sortedRect;
+  uint32_t*       splatOffset;
+  uint32_t*       chunkStart;
+  uint32_t*       pairKey;
+  uint32_t*       pairVal;
+  uint32_t        capacity;
+  int             binsX;
+  bool            gatherRects;
+};
+void launchBinning(hipStream_t stream, const BinLaunch& L);
+
+// the direct binning of frames with at most 256 bins (k_raster.hip)
+struct DirectBinLaunch
+{
+  const uint32_t* idsX;  // as in BinLaunch
+  const uint32_t* idsY;
+  const SortPlan* planKeys;
+  const uint32_t* rect;
+  const uint16_t* sortedCode16;
+  uint64_t*       maskBuf;
+  uint32_t        maxSplats;
+  uint32_t*       binHist;
+  uint32_t        pStride;
+  uint32_t*       binTotal;
+  uint32_t*       binList;
+  uint2*          ranges;
+  FrameCounters*  ctr;
+  uint32_t        capacity;
+  int             binsX, binsY;
+  uint32_t*       binCost;
+};
+bool directBinningSupported(int binsX, int binsY);
+void launchDirectBinning(hipStream_t stream, const DirectBinLaunch& L);
+
+// the compositors (k_raster.hip, k_gut.hip)
+struct CompositeLaunch
+{
+  const FrameArgs* A;      // host copy of the frame's constants: selects the kernel variant and the grid
+  const FrameArgs* dArgs;  // the same on the device
+  const uint2*     ranges;
+  const uint32_t*  valX;  // the per-bin lists: planPairs->finalSel selects X or Y
+  const uint32_t*  valY;
+  const SortPlan*  planPairs;
+  const SplatRec*  rec;     // launchComposite
+  const GutRec*    recGut;  // launchCompositeGut
+  void*            image;
+  int              halfOut;
+  int              shFormat;
+  FrameCounters*   ctr;
+  float*           outDepth;  // the three side outputs: null unless the frame has surface outputs
+  uint32_t*        outSplatId;
+  float4*          outNormal;
+  const void*      instTable;  // launchComposite: the scene's SH table of all instances
+  uint32_t*        binCost;    // launchComposite
+  Occluder         occ;
+};
+void launchComposite(hipStream_t stream, const CompositeLaunch& L);
+void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L);
+
+void launchFrameInit(hipStream_t stream, uint2* ranges, uint32_t nTiles);
+void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* keyY, const SortPlan* planPairs, uint2* ranges);
+void launchLight(hipStream_t stream, const LightArgs& a, int halfOut);
+void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
+
+}  // namespace mgs
