@@ -35,8 +35,12 @@ extern "C" {
                                  mgs_frame_download_surface(which = 3), MGS_STAGE_LIGHT;
                             image compare (MGS_HAS_IMAGE_COMPARE below): entry points only, both numbers stay — mgs_compare_capture,
                                  mgs_compare_capture_upload, mgs_compare_release, mgs_compare_params_default, mgs_compare_metrics,
-                                 mgs_compare_view_default, mgs_compare_composite, mgs_compare_download_composite */
+                                 mgs_compare_view_default, mgs_compare_composite, mgs_compare_download_composite;
+                            meshes (MGS_HAS_MESHES below): entry points only, both numbers stay — mgs_mesh_from_arrays, mgs_mesh_load_obj, mgs_mesh_view,
+                                 mgs_mesh_destroy, mgs_mesh_instance_add, mgs_mesh_instance_set_transform, mgs_mesh_instance_set_visible,
+                                 mgs_meshes_render, mgs_meshes_download */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -204,8 +208,8 @@ int  mgs_scene_set_list_capacity(MgsScene scene_or_context, uint64_t entries);
 /* ---- occluder: splats composited with the caller's opaque geometry.  Replaces the mesh passes of renderHybridPipeline
  * (src/gaussian_splatting.cpp:697-805): the depth pre-pass the splats are tested against (test on, write off, :1377-1395) and the
  * composition final = meshColor * (1 - dstAlpha) + splatColor (:2343-2356); in back-to-front mode the meshes are drawn first and the
- * splats blend over them (:836-843, :2066-2087).  The caller rasterises its own geometry (mesh loading and shading are out of
- * scope) and binds the two images that yields.
+ * splats blend over them (:836-843, :2066-2087).  The caller rasterises its own geometry and binds the two images that yields, or
+ * lets mgs_meshes_render (below) make them from the scene's mesh instances.
  *
  * Bind the images for the following frames of this handle (scene or frame context; per handle, like
  * mgs_scene_set_list_capacity).  depth_device: [height][width] float32, row 0 = NDC y -1 (the frame's own layout), window depth
@@ -417,6 +421,106 @@ int mgs_render_gathered(MgsScene scene, const MgsFrameParams* params, MgsFrameOu
  * mgs_render calls: after mgs_render_gathered the lists cover this rank's rows only, every rank would derive a different
  * table and the exchange sizes would disagree — MGS_ERR_STATE. */
 int mgs_frame_row_costs(MgsScene scene, uint32_t* cost_per_tile_row, size_t rows);
+
+/* ---- triangle meshes and the mesh pass (MGS_HAS_MESHES): the producer of the occluder images.  Replaces ObjLoader
+ * (src/obj_loader.cpp:26-205), the instances of MeshManagerVk (src/mesh_manager_vk.cpp, transformRotScaleInverse at :187), the
+ * shaders threedmesh_raster.{vert,frag}.slang and GaussianSplatting::drawMeshPrimitives (src/gaussian_splatting.cpp:1467-1525).
+ * Out of scope: textures (the reference's fragment shader samples none), light proxies, wireframe, the hybrid / ray-traced variants
+ * (HYBRID_ENABLED), MSAA. */
+typedef struct MgsMesh_t* MgsMesh;
+typedef struct MgsMeshView {           /* indexed triangles, RUB frame like the splats */
+  const float*       positions;        /* [3 * vertex_count] */
+  const float*       normals;          /* [3 * vertex_count] or NULL: generated as obj_loader.cpp:95-152 does (faces in index order: the
+                                          first face at a vertex sets its normal, each later one replaces it by mix(old, face normal, 0.5)) */
+  const uint32_t*    indices;          /* [index_count], index_count % 3 == 0, each < vertex_count */
+  const uint32_t*    material_ids;     /* [index_count / 3] or NULL (= 0); ids >= material_count become 0 (obj_loader.cpp:190-196) */
+  const MgsMaterial* materials;        /* material_count == 0: the loader's default (ambient .1, diffuse .7, specular 1, shininess 32, :72-81) */
+  uint64_t vertex_count, index_count;
+  uint32_t material_count;
+} MgsMeshView;
+/* copies the arrays.  NULL positions / indices, no vertices, index_count % 3 != 0, an index >= vertex_count: MGS_ERR_INVALID_ARG
+ * (checked on the host; no device is touched).  2^29 or more triangles: MGS_ERR_UNSUPPORTED. */
+int  mgs_mesh_from_arrays(const MgsMeshView* view, MgsMesh* out);
+/* Host only.  Reads this SUBSET of Wavefront OBJ: "v x y z", "vn x y z", "f" with corners v, v/t, v//n or v/t/n (1-based; negative
+ * indices count back from the last element read so far), triangles and polygons (fan-triangulated from their first corner), "o" and
+ * "g" (a new shape, if the current one has faces), "usemtl name", "mtllib file..." (relative to the OBJ; statements newmtl, Ka, Kd,
+ * Ks, Ke, Ns; a material starts as all zero with shininess 1; a missing library is ignored and leaves the default material).
+ * Every other statement is skipped.  Output as ObjLoader::load emits it: vertices de-indexed, one per face corner, indices 0, 1,
+ * 2, ...; a corner without a normal takes the generated normal of its position (as written, :98-151: per shape, faces in order,
+ * running mix(., n, 0.5); the arrays persist across shapes); a triangle without usemtl, or with an unknown name, gets material 0.
+ * The reference parses with tinyobj, which is not restated here: the subset is build-defined and files outside it (other polygon
+ * triangulation, smoothing groups, vertex colours, ...) are PARITY UNPINNED.
+ * A file that cannot be opened: MGS_ERR_IO.  A malformed v / vn / f statement, an index out of range, a face with fewer than three
+ * corners, no face at all: MGS_ERR_FORMAT. */
+int  mgs_mesh_load_obj(const char* path, MgsMesh* out);
+int  mgs_mesh_view(MgsMesh mesh, MgsMeshView* out);   /* borrow the arrays (valid until mgs_mesh_destroy); normals and material ids are always set */
+void mgs_mesh_destroy(MgsMesh mesh);                  /* instances keep their own reference to the data */
+/* Mesh instances belong to the SCENE and are shared by its frame contexts, like the light table: the calls below return
+ * MGS_ERR_STATE on a context handle, wait for the frames in flight on all contexts and then rewrite the device table (the rule of
+ * mgs_scene_set_lights).  Device copies of vertices, indices and materials are made when a mesh's first instance is added;
+ * mgs_scene_commit is not involved and a scene without splats may hold meshes.  At most 256 instances and 2^29 - 1 triangles per
+ * scene (build-defined).  The bytes are part of scene_bytes of mgs_scene_memory_usage.
+ * transformRotScaleInverse = inverse(mat3(transform)) is computed on the host in double and rounded once to fp32; glm::inverse is
+ * not part of the reference tree: PARITY UNPINNED (as for projInverse of the lighting pass). */
+int  mgs_mesh_instance_add(MgsScene scene, MgsMesh mesh, const float transform[16], int* mesh_instance_id);
+int  mgs_mesh_instance_set_transform(MgsScene scene, int mesh_instance_id, const float transform[16]);
+int  mgs_mesh_instance_set_visible(MgsScene scene, int mesh_instance_id, int visible);
+typedef struct MgsMeshOut {
+  uint64_t triangles_in;          /* triangles of the visible instances */
+  uint64_t triangles_rasterised;  /* ... that reached coverage with a non-empty bounding box in the handle's rows and a non-zero area */
+  uint64_t fragments;             /* samples covered with depth in [0, 1), summed over all (sub-)triangles: covered pixels plus overdraw */
+  float    elapsed_ms;            /* HIP events around the four launches */
+  uint32_t flags;                 /* MGS_MESH_WORK_LIST_FULL: the images are exact, the pass was slow (see below) */
+} MgsMeshOut;
+#define MGS_MESH_WORK_LIST_FULL 1u
+/* The mesh pass.  Rasterises all visible mesh instances of the scene for `params` (read: view, proj, camera_pos, width, height,
+ * strip_row_begin, strip_row_end, lighting_mode; everything else is ignored) into a depth image [height][width] float32 and a colour
+ * image [height][width][4] float32 that the handle owns — the same buffers mgs_frame_upload_occluder fills — and binds them as the
+ * handle's occluder exactly as that call does.  Ordered on the handle's stream; does not wait unless `out` is given.  The next
+ * mgs_render / mgs_render_gathered on the handle composites the splats over the meshes through the occluder path; the frame graph
+ * is not changed.  No mesh instance, or none visible: the cleared images (depth 1.0, colour 0 0 0 0).  With strip rows only those
+ * pixel rows are written, bit-identical to the same rows of the full pass.
+ *
+ * Vertex stage (threedmesh_raster.vert.slang:53-62, fp32, products in the written order): worldPos = M p; clip = P (V worldPos);
+ * worldNrm = normalize(transpose(transformRotScaleInverse) n); viewDir = worldPos - origin, origin = the translation of
+ * viewInverse (host double, rounded once).
+ * Clipping: the depth range is the frame's, clip z in [0, w].  A triangle with a non-finite clip coordinate is dropped.  Triangles
+ * are clipped geometrically (Sutherland-Hodgman on the weights of the three vertices, planes in this order) at the near plane
+ * z >= 0 and at a guard band |x| <= 256 w, |y| <= 256 w, which keeps window coordinates below 2^21 pixels at the 8192-pixel limit
+ * (2^29 in fixed point); the resulting polygon is fan-triangulated from its first vertex and every sub-triangle is snapped and
+ * rasterised on its own.  A primitive with a clipped vertex whose w is not positive is dropped (a projection whose z >= 0 half
+ * space does not imply w > 0 is not supported).  Fragments with depth outside [0, 1] are dropped (depth clip).  At most two
+ * sub-triangles per triangle are held on average (every triangle may cross the near plane); beyond that geometry is dropped and a
+ * pass that was asked for `out` returns MGS_ERR_OVERFLOW.
+ * Triangles whose bounding box exceeds 8 x 8 pixels are cut into chunks of 16 tiles of 8 x 8 pixels on a device-side work list of
+ * 2^20 chunks (environment MGS_MESH_WORK_ITEMS, 1 .. 2^26).  A triangle whose chunks no longer fit is rasterised by a single lane
+ * instead: the images are the same bit for bit, the pass is slower, and MgsMeshOut.flags carries MGS_MESH_WORK_LIST_FULL.
+ * Coverage: window = (ndc * 0.5 + 0.5) * size in fp32, row 0 = NDC y -1; snapped to 1/256 pixel, round to nearest even; edge
+ * functions in 64-bit integers; sample = the pixel centre; top-left rule in the frame's row order: with the triangle oriented so
+ * that its interior has positive edge functions, a LEFT edge is one whose interior lies toward larger x, a TOP edge is a horizontal
+ * edge whose interior lies toward larger row index; samples exactly on such an edge are covered, on any other edge not.  Both
+ * windings are drawn (VK_CULL_MODE_NONE, gaussian_splatting.cpp:2057); zero-area triangles produce nothing.  A shared edge is
+ * covered exactly once whatever the order of execution.  Vulkan asks for at least 4 sub-pixel bits and the reference names no
+ * device: the sub-pixel precision is PARITY UNPINNED.
+ * Depth: fp32 z / w per vertex, interpolated linearly in window space as fma(b2, z2 - z0, fma(b1, z1 - z0, z0)) with b_i =
+ * float(edge function i) / float(2 area), each operation rounded once, so that a triangle of constant depth keeps exactly that depth;
+ * compare LESS against a clear of 1.0 (:1493) in primitive order (instances in creation order, triangles in index order,
+ * sub-triangles in fan order): equal depths keep the earlier primitive.  A fragment at exactly 1.0 fails.  Implemented as a 64-bit
+ * unsigned atomic minimum on (depth bits << 32 | primitive << 3 | sub-triangle): the frame is bit-reproducible.
+ * Fragment stage (threedmesh_raster.frag.slang:67-103, non-hybrid colour branch), evaluated for the winning fragment only:
+ * worldPos, worldNrm (not renormalised), viewDir interpolated with perspective correction from the snapped triangle; the
+ * primitive's material; lighting_mode 0: colour = emission + ambient + diffuse; otherwise emission, plus, if the material needs
+ * shading, wavefrontComputeShadingDirectOnly for each light of the scene's table (mgs_scene_set_lights), or for the headlight
+ * when it is empty — the function the lighting pass calls.  Colour alpha is 1 on mesh pixels, 0 elsewhere; fp32 (the occluder
+ * path converts after the background term).
+ * With the splats: the reference's back-to-front order (meshes first, splats blended over them, :836-843) and its front-to-back
+ * order (depth pre-pass, splats, mesh colour times the remaining transmittance, :697-805) both reduce to the composition
+ * documented at mgs_frame_set_occluder.  mgs_frame_download_surface(which = 3) then consolidates against the mesh depth. */
+int  mgs_meshes_render(MgsScene scene_or_context, const MgsFrameParams* params, MgsMeshOut* out /* may be NULL */);
+/* the last pass's images, [height][width] of that pass; waits.  which 0: depth float32; 1: colour float32 x 4; 2: primitive id
+ * uint32 (global: instances concatenated in creation order, visible or not; 0xFFFFFFFF = none).  MGS_ERR_STATE before any pass.
+ * (The depth and colour images are the handle's owned occluder buffers: a later mgs_frame_upload_occluder overwrites them.) */
+int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, size_t bytes);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

@@ -4,6 +4,7 @@
   python tools/mgs_render.py scene.ply|scene.spz|scene.splat|syn:<n> out.png [--size W H] [--eye x y z]
                              [--center x y z] [--fov deg] [--flip-y] [--sh-format 0|1|2] [--rgba-format 0|1|2]
                              [--occluder-depth FILE.npy [--background FILE.npy]]
+                             [--mesh FILE.obj [--mesh-transform 16 floats]]...
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
                              [--compare-with FRAME.npy [--flip-mode 0|1|2] [--compare-view OUT.png --split 0.5 --left capture --right diff-red-gray]]
 
@@ -46,6 +47,8 @@ def main():
     ap.add_argument("--rgba-format", type=int, default=0)
     ap.add_argument("--occluder-depth", default=None, metavar="FILE.npy")
     ap.add_argument("--background", default=None, metavar="FILE.npy")
+    ap.add_argument("--mesh", action="append", default=[], metavar="FILE.obj")
+    ap.add_argument("--mesh-transform", action="append", type=float, nargs=16, default=[], metavar="M")
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
@@ -89,6 +92,17 @@ def main():
         if a.material:
             m = a.material
             scene.set_material(0, capi.make_material(ambient=m[0:3], diffuse=m[3:6], specular=m[6:9], emission=m[9:12], shininess=m[12]))
+    if a.mesh:
+        # --mesh FILE.obj [--mesh-transform 16 floats, row by row]: rasterised on the device into this handle's occluder (mgs_meshes_render)
+        if a.occluder_depth:
+            ap.error("--mesh makes the occluder images itself: do not combine it with --occluder-depth")
+        if len(a.mesh_transform) > len(a.mesh):
+            ap.error("more --mesh-transform than --mesh")
+        for k, path in enumerate(a.mesh):
+            m = np.array(a.mesh_transform[k], np.float32).reshape(4, 4) if k < len(a.mesh_transform) else None
+            scene.add_mesh_instance(mgs.Mesh.load_obj(path), m)
+        mo = scene.render_meshes(p, want_stats=True)
+        print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
     o = scene.render(p)
     img = scene.download_frame(p).astype(np.float32)
     print(f"{scene.splat_count} splats, {o.frustum_count} in frustum, {o.sorted_count} sorted, {o.tile_pairs} bin records, "

@@ -105,6 +105,22 @@ def make_material(**kw):
     return m
 
 
+class MeshView(C.Structure):
+    """MgsMeshView: indexed triangles in the RUB frame"""
+    _fields_ = [("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("indices", C.POINTER(C.c_uint32)),
+                ("material_ids", C.POINTER(C.c_uint32)), ("materials", C.POINTER(Material)),
+                ("vertex_count", C.c_uint64), ("index_count", C.c_uint64), ("material_count", C.c_uint32)]
+
+
+MESH_WORK_LIST_FULL = 1
+
+
+class MeshOut(C.Structure):
+    """MgsMeshOut: counters and device time of one mesh pass; flags & MESH_WORK_LIST_FULL: exact images, slow pass"""
+    _fields_ = [("triangles_in", C.c_uint64), ("triangles_rasterised", C.c_uint64), ("fragments", C.c_uint64),
+                ("elapsed_ms", C.c_float), ("flags", C.c_uint32)]
+
+
 class CompareParams(C.Structure):
     """MgsCompareParams"""
     _fields_ = [("flip_mode", C.c_int32), ("pixels_per_degree", C.c_float)]
@@ -192,6 +208,15 @@ def load_library():
         "mgs_compare_view_default": (None, [P(CompareView)]),
         "mgs_compare_composite": (C.c_int, [vp, P(CompareView), P(vp), P(C.c_uint64)]),
         "mgs_compare_download_composite": (C.c_int, [vp, vp, C.c_size_t]),
+        "mgs_mesh_from_arrays": (C.c_int, [P(MeshView), P(vp)]),
+        "mgs_mesh_load_obj": (C.c_int, [C.c_char_p, P(vp)]),
+        "mgs_mesh_view": (C.c_int, [vp, P(MeshView)]),
+        "mgs_mesh_destroy": (None, [vp]),
+        "mgs_mesh_instance_add": (C.c_int, [vp, vp, P(F), P(C.c_int)]),
+        "mgs_mesh_instance_set_transform": (C.c_int, [vp, C.c_int, P(F)]),
+        "mgs_mesh_instance_set_visible": (C.c_int, [vp, C.c_int, C.c_int]),
+        "mgs_meshes_render": (C.c_int, [vp, P(FrameParams), P(MeshOut)]),
+        "mgs_meshes_download": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -244,6 +269,8 @@ EXPORTED_SYMBOLS = [
     "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_instance_set_material",
     "mgs_compare_capture", "mgs_compare_capture_upload", "mgs_compare_release", "mgs_compare_params_default", "mgs_compare_metrics",
     "mgs_compare_view_default", "mgs_compare_composite", "mgs_compare_download_composite",
+    "mgs_mesh_from_arrays", "mgs_mesh_load_obj", "mgs_mesh_view", "mgs_mesh_destroy", "mgs_mesh_instance_add",
+    "mgs_mesh_instance_set_transform", "mgs_mesh_instance_set_visible", "mgs_meshes_render", "mgs_meshes_download",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -314,6 +341,69 @@ class SplatSet:
     def close(self):
         if self._h:
             load_library().mgs_splatset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MESH_NONE = 0xFFFFFFFF  # primitive id of a pixel no mesh covers
+
+
+class Mesh:
+    """RAM triangle mesh (ObjLoader's output, src/obj_loader.h): mgs_mesh_*"""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_arrays(cls, positions, indices, normals=None, material_ids=None, materials=None):
+        """positions [V,3], indices [T,3] (or flat), normals [V,3] or None (generated), material_ids [T] or None, materials: a
+        sequence of Material (make_material) or None (the loader's default)"""
+        pos = _f32(positions).reshape(-1)
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        nrm = None if normals is None else _f32(normals).reshape(-1)
+        mid = None if material_ids is None else np.ascontiguousarray(material_ids, np.uint32).reshape(-1)
+        mats = list(materials or [])
+        if nrm is not None and nrm.size != pos.size:
+            raise ValueError("Mesh.from_arrays: normals must match positions")
+        if mid is not None and mid.size * 3 != idx.size:
+            raise ValueError("Mesh.from_arrays: one material id per triangle")
+        v = MeshView()
+        v.positions = _fp(pos) if pos.size else None
+        v.normals = None if nrm is None else _fp(nrm)
+        v.indices = idx.ctypes.data_as(C.POINTER(C.c_uint32)) if idx.size else None
+        v.material_ids = None if mid is None else mid.ctypes.data_as(C.POINTER(C.c_uint32))
+        arr = (Material * max(len(mats), 1))(*mats)
+        v.materials = arr if mats else None
+        v.vertex_count, v.index_count, v.material_count = pos.size // 3, idx.size, len(mats)
+        h = C.c_void_p()
+        _check(load_library().mgs_mesh_from_arrays(C.byref(v), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def load_obj(cls, path):
+        h = C.c_void_p()
+        _check(load_library().mgs_mesh_load_obj(os.fsencode(path), C.byref(h)))
+        return cls(h)
+
+    def view(self):
+        """dict of numpy copies: positions [V,3], normals [V,3], indices [T,3], material_ids [T], materials (list of dicts)"""
+        v = MeshView()
+        _check(load_library().mgs_mesh_view(self._h, C.byref(v)))
+        nv, ni = int(v.vertex_count), int(v.index_count)
+        cp = lambda ptr, cnt: np.ctypeslib.as_array(ptr, shape=(cnt,)).copy()
+        mats = [{k: (float(getattr(v.materials[i], k)) if k == "shininess" else tuple(getattr(v.materials[i], k))) for k, _ in Material._fields_}
+                for i in range(v.material_count)]
+        return dict(positions=cp(v.positions, 3 * nv).reshape(-1, 3), normals=cp(v.normals, 3 * nv).reshape(-1, 3),
+                    indices=cp(v.indices, ni).reshape(-1, 3), material_ids=cp(v.material_ids, ni // 3), materials=mats)
+
+    def close(self):
+        if self._h:
+            load_library().mgs_mesh_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -482,6 +572,36 @@ class Scene:
 
     def set_material(self, instance, material):
         _check(self._lib.mgs_instance_set_material(self._h, int(instance), C.byref(material)))
+
+    # ---- triangle meshes: instances of the scene, the mesh pass that makes this handle's occluder images ----
+    def add_mesh_instance(self, mesh, transform=None):
+        m = _f32(IDENTITY if transform is None else transform).T.reshape(-1).copy()
+        idx = C.c_int()
+        _check(self._lib.mgs_mesh_instance_add(self._h, mesh._h, _fp(m), C.byref(idx)))
+        return idx.value
+
+    def set_mesh_transform(self, mesh_instance, transform):
+        m = _f32(transform).T.reshape(-1).copy()
+        _check(self._lib.mgs_mesh_instance_set_transform(self._h, int(mesh_instance), _fp(m)))
+
+    def set_mesh_visible(self, mesh_instance, visible):
+        _check(self._lib.mgs_mesh_instance_set_visible(self._h, int(mesh_instance), int(bool(visible))))
+
+    def render_meshes(self, params, want_stats=False):
+        """mgs_meshes_render: rasterise the visible mesh instances for params and bind the result as this handle's occluder;
+        want_stats waits and returns a MeshOut"""
+        out = MeshOut()
+        self._mesh_wh = (params.width, params.height)
+        _check(self._lib.mgs_meshes_render(self._h, C.byref(params), C.byref(out) if want_stats else None))
+        return out if want_stats else None
+
+    def download_meshes(self):
+        """(depth float32[H,W], colour float32[H,W,4], primitive id uint32[H,W], MESH_NONE = none) of the last mesh pass"""
+        w, h = self._mesh_wh
+        depth, color, prim = np.zeros((h, w), np.float32), np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.uint32)
+        for which, a in enumerate((depth, color, prim)):
+            _check(self._lib.mgs_meshes_download(self._h, which, a.ctypes.data_as(C.c_void_p), a.nbytes))
+        return depth, color, prim
 
     def commit(self, sh_format=FORMAT_FLOAT32, rgba_format=FORMAT_FLOAT32):
         _check(self._lib.mgs_scene_commit(self._h, sh_format, rgba_format))

@@ -110,6 +110,9 @@ SceneData::~SceneData()
     freeSet(d);
   compInst.release();
   lightTab.release();
+  for(auto& m : meshes)
+    m.release();
+  meshTab.release();
 }
 
 void mgs_scene_destroy(MgsScene s)
@@ -133,6 +136,7 @@ void mgs_scene_destroy(MgsScene s)
   s->occ.release();
   s->surf.release();
   s->cmp.release();
+  s->mesh.release();
   s->rs.release();
   s->cpu.release();
   s->binPolicy.release();
@@ -216,7 +220,9 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   }
   if(sceneBytes)
   {
-    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes();
+    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes();
+    for(const auto& m : s->d->meshes)
+      b += m.bytes();
     for(const auto& d : s->d->sets)
       b += setBytes(d);
     *sceneBytes = b;
@@ -225,7 +231,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   {
     uint64_t b   = s->cpu.distDev.bytes();
     auto     add = [&](auto& buf) { b += buf.bytes(); };
-    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add);
+    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add);
     *workingBytes = b;
   }
   return MGS_OK;

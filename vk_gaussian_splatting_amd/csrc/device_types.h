@@ -201,6 +201,86 @@ struct LightArgs
   int32_t           row0, row1;  // pixel rows [row0, row1) of the handle's strip
 };
 
+// ---- mesh pass (k_mesh.hip, api_mesh.hip) ----
+constexpr int      kMaxMeshInstances = 256;          // build-defined cap of mesh instances per scene
+constexpr uint32_t kMeshMaxPrims     = 1u << 29;     // a visibility word holds (primitive << 3 | sub-triangle) in its low half
+constexpr uint32_t kMeshNone         = 0xFFFFFFFFu;  // primitive id of a pixel no mesh covers
+constexpr uint32_t kMeshWorkItems    = 1u << 20;     // default capacity of the large-triangle work list (MGS_MESH_WORK_ITEMS; a lane whose
+                                                     // chunks do not fit walks its triangle itself)
+constexpr int      kMeshSmallBox     = 8;            // bounding boxes up to this many pixels on each side are walked by their own lane
+constexpr int      kMeshChunkTiles   = 16;           // 8 x 8-pixel tiles per work item
+// one mesh instance as the kernels read it (MeshDesc, shaders/shaderio.h, reduced)
+struct alignas(16) MeshInstDev
+{
+  const float*       pos;      // [3 * vertices]
+  const float*       nrm;      // [3 * vertices]
+  const uint32_t*    idx;      // [3 * triangles]
+  const uint32_t*    matId;    // [triangles], already clamped to the material count
+  const MaterialDev* mats;
+  float              M[16];     // transform
+  float              rsInv[9];  // transformRotScaleInverse = inverse(mat3(transform)), glm column-major; the shader transposes it
+  uint32_t           triBegin;  // first global primitive index of this instance
+  uint32_t           triCount;
+  uint32_t           visible;
+  uint32_t           pad[2];
+};
+struct MeshTable
+{
+  uint32_t    count, totalTris;
+  uint32_t    pad[2];
+  MeshInstDev inst[kMaxMeshInstances];
+};
+// set-up record of one rasterised triangle: window coordinates snapped to 1/256 pixel, window depth and 1 / w per vertex.  64 B,
+// fetched by the resolve pass with four 16-byte loads.  A primitive that was clipped keeps its sub-triangles in MeshClipRec.
+struct alignas(16) MeshTriRec
+{
+  int32_t  x[3], y[3];
+  float    z[3], invw[3];
+  uint32_t clipBase;  // kMeshNone: the primitive's own three vertices; otherwise the first of nSub MeshClipRec
+  uint32_t nSub;
+  uint32_t pad[2];
+};
+// a sub-triangle of a clipped primitive: the same, plus each vertex as weights of the primitive's three vertices.  96 B.
+struct alignas(16) MeshClipRec
+{
+  int32_t x[3], y[3];
+  float   z[3], invw[3];
+  float   bary[9];  // [vertex][weight]
+  uint32_t pad[3];
+};
+static_assert(sizeof(MeshTriRec) == 64 && sizeof(MeshClipRec) == 96, "whole 16-byte vectors");
+struct MeshCounters
+{
+  unsigned long long workCount;  // work-list slots claimed (never decremented; may exceed the capacity)
+  unsigned long long fragments;
+  uint32_t clipCount;            // MeshClipRec allocated
+  uint32_t trisRasterised;
+  uint32_t flags;                // bit 0: the clip records overflowed (geometry was dropped); bit 1: the work list was full (slow, exact)
+  uint32_t pad;
+};
+// what the mesh kernels receive by value
+struct MeshPassArgs
+{
+  float              view[16], proj[16];
+  float              origin[3];   // translation of viewInverse (host double, rounded once)
+  float              cameraPos[3];
+  int32_t            width, height;
+  int32_t            row0, row1;  // pixel rows [row0, row1) of the handle's strip
+  int32_t            lightingMode;
+  const MeshTable*   table;
+  const LightTable*  lights;
+  unsigned long long* vis;        // [height][width] depth bits << 32 | primitive << 3 | sub-triangle
+  MeshTriRec*        recs;        // [totalTris]
+  MeshClipRec*       clips;
+  uint32_t           clipCapacity;
+  uint2*             work;        // (primitive << 3 | sub-triangle, chunk of tiles); x == kMeshNone: a void slot
+  uint32_t           workCapacity;
+  MeshCounters*      ctr;
+  float*             outDepth;
+  float4*            outColor;
+  uint32_t*          outPrim;
+};
+
 // the caller's geometry as the compositors' launchers receive it
 struct Occluder
 {

@@ -927,3 +927,277 @@ float halfToFloat(uint16_t h)
 }
 
 }  // namespace mgs
+
+// ---- triangle meshes: the OBJ subset of mgs_mesh_load_obj (include/mgs.h) ------------------------------------------------------
+// Written against the Wavefront OBJ / MTL statements themselves and the way src/obj_loader.cpp:26-205 consumes what its parser
+// returns; the parser (tinyobj) is not restated.
+namespace mgs {
+
+HostMeshMaterial defaultMeshMaterial()
+{
+  HostMeshMaterial m{};
+  for(int c = 0; c < 3; ++c)
+  {
+    m.ambient[c]  = 0.1f;
+    m.diffuse[c]  = 0.7f;
+    m.specular[c] = 1.0f;
+  }
+  m.shininess = 32.0f;
+  return m;
+}
+
+void accumulateFaceNormals(const float* pos, const uint32_t* idx, size_t indexCount, std::vector<float>& normals, std::vector<uint8_t>& visited)
+{
+  for(size_t i = 0; i + 2 < indexCount; i += 3)
+  {
+    const uint32_t id[3] = {idx[i], idx[i + 1], idx[i + 2]};
+    for(uint32_t v : id)
+      if((size_t)v >= visited.size())
+      {  // the reference sizes these arrays by the number of face corners seen so far; an index beyond that is out of its bounds
+        visited.resize((size_t)v + 1, 0);
+        normals.resize(3 * ((size_t)v + 1), 0.0f);
+      }
+    const float* p0 = pos + 3 * (size_t)id[0];
+    const float* p1 = pos + 3 * (size_t)id[1];
+    const float* p2 = pos + 3 * (size_t)id[2];
+    const float  a[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, b[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    float        n[3] = {a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]};  // glm::cross
+    const float  inv  = 1.0f / std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);                           // glm::normalize
+    for(float& c : n)
+      c *= inv;
+    for(uint32_t v : id)
+    {
+      float* dst = &normals[3 * (size_t)v];
+      if(visited[v])
+        for(int c = 0; c < 3; ++c)
+          dst[c] = dst[c] * 0.5f + n[c] * 0.5f;  // glm::mix(old, n, 0.5): both products are exact, one rounding either way
+      else
+      {
+        for(int c = 0; c < 3; ++c)
+          dst[c] = n[c];
+        visited[v] = 1;
+      }
+    }
+  }
+}
+
+namespace {
+
+struct ObjCorner
+{
+  int v, n;  // resolved, zero-based; n = -1: none
+};
+
+bool parseFloats(std::istringstream& ss, float* out, int count)
+{
+  for(int i = 0; i < count; ++i)
+    if(!(ss >> out[i]))
+      return false;
+  return true;
+}
+
+// one "v", "v/t", "v//n" or "v/t/n" corner; indices are 1-based, negative ones count back from the end
+bool parseCorner(const std::string& tok, size_t nPos, size_t nNrm, ObjCorner& out)
+{
+  long long field[3] = {0, 0, 0};
+  bool      have[3]  = {false, false, false};
+  size_t    at       = 0;
+  for(int f = 0; f < 3 && at <= tok.size(); ++f)
+  {
+    const size_t slash = tok.find('/', at);
+    const std::string part = tok.substr(at, slash == std::string::npos ? std::string::npos : slash - at);
+    if(!part.empty())
+    {
+      char*           end = nullptr;
+      const long long v   = std::strtoll(part.c_str(), &end, 10);
+      if(end == part.c_str() || *end != 0)
+        return false;
+      field[f] = v;
+      have[f]  = true;
+    }
+    if(slash == std::string::npos)
+      break;
+    at = slash + 1;
+  }
+  auto resolve = [](long long i, size_t count, int& o) {
+    const long long z = i > 0 ? i - 1 : (long long)count + i;
+    if(i == 0 || z < 0 || z >= (long long)count)
+      return false;
+    o = (int)z;
+    return true;
+  };
+  if(!have[0] || !resolve(field[0], nPos, out.v))
+    return false;
+  out.n = -1;
+  if(have[2] && !resolve(field[2], nNrm, out.n))
+    return false;
+  return true;
+}
+
+void loadMtl(const std::string& path, std::vector<HostMeshMaterial>& mats, std::vector<std::string>& names)
+{
+  std::ifstream f(path);
+  if(!f)
+    return;  // a missing material library is a warning to the reference's parser, not an error
+  std::string line;
+  while(std::getline(f, line))
+  {
+    std::istringstream ss(line);
+    std::string        key;
+    if(!(ss >> key))
+      continue;
+    if(key == "newmtl")
+    {
+      std::string name;
+      ss >> name;
+      HostMeshMaterial m{};  // the parser's initial material: colours 0, shininess 1
+      m.shininess = 1.0f;
+      mats.push_back(m);
+      names.push_back(name);
+    }
+    else if(!mats.empty())
+    {
+      float v[3];
+      if(key == "Ka" && parseFloats(ss, v, 3))
+        std::memcpy(mats.back().ambient, v, 12);
+      else if(key == "Kd" && parseFloats(ss, v, 3))
+        std::memcpy(mats.back().diffuse, v, 12);
+      else if(key == "Ks" && parseFloats(ss, v, 3))
+        std::memcpy(mats.back().specular, v, 12);
+      else if(key == "Ke" && parseFloats(ss, v, 3))
+        std::memcpy(mats.back().emission, v, 12);
+      else if(key == "Ns" && parseFloats(ss, v, 1))
+        mats.back().shininess = v[0];
+    }
+  }
+}
+
+}  // namespace
+
+int loadObj(const std::string& path, HostMesh& out)
+{
+  std::ifstream f(path);
+  if(!f)
+  {
+    setError("cannot open " + path);
+    return MGS_ERR_IO;
+  }
+  out = HostMesh();
+  out.path = path;
+  const size_t      slash = path.find_last_of("/\\");
+  const std::string dir   = slash == std::string::npos ? std::string() : path.substr(0, slash + 1);
+  std::vector<float>       pos, nrm;
+  std::vector<std::string> matNames;
+  struct Shape
+  {
+    std::vector<ObjCorner> corners;  // 3 per triangle
+    std::vector<int>       matIds;   // 1 per triangle
+  };
+  std::vector<Shape> shapes(1);
+  int                curMat = -1;
+  std::string        line;
+  size_t             lineNo = 0;
+  auto bad = [&](const std::string& why) {
+    setError(path + ":" + std::to_string(lineNo) + ": " + why);
+    return MGS_ERR_FORMAT;
+  };
+  while(std::getline(f, line))
+  {
+    ++lineNo;
+    if(!line.empty() && line.back() == '\r')
+      line.pop_back();
+    std::istringstream ss(line);
+    std::string        key;
+    if(!(ss >> key) || key[0] == '#')
+      continue;
+    float v[3];
+    if(key == "v")
+    {
+      if(!parseFloats(ss, v, 3))
+        return bad("malformed vertex");
+      pos.insert(pos.end(), v, v + 3);
+    }
+    else if(key == "vn")
+    {
+      if(!parseFloats(ss, v, 3))
+        return bad("malformed normal");
+      nrm.insert(nrm.end(), v, v + 3);
+    }
+    else if(key == "f")
+    {
+      std::vector<ObjCorner> face;
+      std::string            tok;
+      while(ss >> tok)
+      {
+        ObjCorner c;
+        if(!parseCorner(tok, pos.size() / 3, nrm.size() / 3, c))
+          return bad("malformed face corner '" + tok + "'");
+        face.push_back(c);
+      }
+      if(face.size() < 3)
+        return bad("a face needs at least three corners");
+      for(size_t k = 1; k + 1 < face.size(); ++k)
+      {  // fan from the first corner
+        shapes.back().corners.push_back(face[0]);
+        shapes.back().corners.push_back(face[k]);
+        shapes.back().corners.push_back(face[k + 1]);
+        shapes.back().matIds.push_back(curMat);
+      }
+    }
+    else if(key == "o" || key == "g")
+    {
+      if(!shapes.back().corners.empty())
+        shapes.emplace_back();
+    }
+    else if(key == "usemtl")
+    {
+      std::string name;
+      ss >> name;
+      curMat = -1;
+      for(size_t k = 0; k < matNames.size(); ++k)
+        if(matNames[k] == name)
+          curMat = (int)k;
+    }
+    else if(key == "mtllib")
+    {
+      std::string name;
+      while(ss >> name)
+        loadMtl(dir + name, out.materials, matNames);
+    }
+    // everything else is skipped
+  }
+  if(out.materials.empty())
+    out.materials.push_back(defaultMeshMaterial());
+  std::vector<float>   genNormals;
+  std::vector<uint8_t> visited;
+  std::vector<uint32_t> shapeIdx;
+  for(const Shape& sh : shapes)
+  {
+    if(sh.corners.empty())
+      continue;
+    // sized as the reference sizes them: by the face corners seen so far (src/obj_loader.cpp:101-102)
+    visited.resize(visited.size() + sh.corners.size(), 0);
+    genNormals.resize(3 * visited.size(), 0.0f);
+    shapeIdx.clear();
+    for(const ObjCorner& c : sh.corners)
+      shapeIdx.push_back((uint32_t)c.v);
+    accumulateFaceNormals(pos.data(), shapeIdx.data(), shapeIdx.size(), genNormals, visited);
+    for(const ObjCorner& c : sh.corners)
+    {  // de-indexed: one vertex per face corner (:156-187)
+      out.positions.insert(out.positions.end(), &pos[3 * (size_t)c.v], &pos[3 * (size_t)c.v] + 3);
+      const float* n = (!nrm.empty() && c.n >= 0) ? &nrm[3 * (size_t)c.n] : &genNormals[3 * (size_t)c.v];
+      out.normals.insert(out.normals.end(), n, n + 3);
+      out.indices.push_back((uint32_t)out.indices.size());
+    }
+    for(int m : sh.matIds)
+      out.materialIds.push_back(((uint32_t)m >= out.materials.size()) ? 0u : (uint32_t)m);  // :190-196
+  }
+  if(out.indices.empty())
+  {
+    setError(path + ": no faces");
+    return MGS_ERR_FORMAT;
+  }
+  return MGS_OK;
+}
+
+}  // namespace mgs

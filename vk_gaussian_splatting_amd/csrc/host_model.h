@@ -23,6 +23,26 @@ struct HostSplatSet
   void     convertRdfToRub();                   // src/splat_set.h:78-114 with (RDF -> RUB)
 };
 
+// RAM-side triangle mesh (ObjLoader's m_vertices / m_indices / m_matIndices / m_materials, src/obj_loader.h), RUB frame
+struct HostMeshMaterial
+{
+  float ambient[3], diffuse[3], specular[3], emission[3];
+  float shininess;
+};
+struct HostMesh
+{
+  std::vector<float>            positions, normals;  // 3 per vertex
+  std::vector<uint32_t>         indices;             // 3 per triangle
+  std::vector<uint32_t>         materialIds;         // 1 per triangle, < materials.size()
+  std::vector<HostMeshMaterial> materials;           // never empty
+  std::string                   path;
+};
+HostMeshMaterial defaultMeshMaterial();  // the loader's default, src/obj_loader.cpp:72-81
+// per-vertex normals the way src/obj_loader.cpp:98-151 generates them: faces in index order, the first face that touches a vertex sets
+// its normal, every later one replaces it by mix(old, face normal, 0.5).  normals / visited persist across the shapes of a file.
+void accumulateFaceNormals(const float* positions, const uint32_t* indices, size_t indexCount, std::vector<float>& normals, std::vector<uint8_t>& visited);
+int  loadObj(const std::string& path, HostMesh& out);  // the OBJ subset documented in include/mgs.h (mgs_mesh_load_obj)
+
 // thread-local error message used by the C ABI
 void        setError(const std::string& msg);
 const char* lastError();

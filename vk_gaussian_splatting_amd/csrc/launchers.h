@@ -109,6 +109,9 @@ void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L);
 void launchFrameInit(hipStream_t stream, uint2* ranges, uint32_t nTiles);
 void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* keyY, const SortPlan* planPairs, uint2* ranges);
 void launchLight(hipStream_t stream, const LightArgs& a, int halfOut);
+// the mesh pass (k_mesh.hip): clear, set-up + small triangles, large triangles, resolve + shade
+// (totalTris: the grid of the set-up stage; largeBlocks: the fixed grid that strides over the device-side work list)
+void launchMeshPass(hipStream_t stream, const MeshPassArgs& a, uint32_t totalTris, uint32_t largeBlocks);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 
 }  // namespace mgs

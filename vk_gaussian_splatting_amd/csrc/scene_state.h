@@ -134,6 +134,27 @@ struct DevView
   T* p = nullptr;
 };
 
+struct MgsMesh_t
+{
+  std::shared_ptr<HostMesh> data;
+};
+// device copy of a mesh (made when its first instance is added) and the scene's mesh instances (api_mesh.hip)
+struct DeviceMesh
+{
+  std::shared_ptr<HostMesh> host;
+  DevBuf<float>             pos, nrm;
+  DevBuf<uint32_t>          idx, matId;
+  DevBuf<MaterialDev>       mats;
+  uint64_t bytes() const { return pos.bytes() + nrm.bytes() + idx.bytes() + matId.bytes() + mats.bytes(); }
+  void     release() { pos.release(), nrm.release(), idx.release(), matId.release(), mats.release(); }
+};
+struct MeshInstance
+{
+  int   mesh;  // index into SceneData::meshes
+  float M[16];
+  bool  visible = true;
+};
+
 // One device block per handle: the per-frame device state that every frame starts from zero (counters, sort plans), followed by
 // the frame's constants.  A frame begins with ONE upload that carries the zeros along with the constants — no kernel has to
 // sweep them (the frame's first kernel used to).
@@ -219,6 +240,12 @@ struct SceneData
   // the device block every context's pass reads (allocated once: its address is baked into captured frames)
   std::unique_ptr<LightTable> lightHost;
   DevBuf<LightTable>     lightTab;
+  // triangle meshes of the mesh pass (mgs_mesh_instance_*): device copies, instances in creation order, and the device table every
+  // handle's pass reads (allocated once, rewritten by the editing calls after they waited for the frames in flight)
+  std::vector<DeviceMesh>   meshes;
+  std::vector<MeshInstance> meshInstances;
+  std::unique_ptr<MeshTable> meshHost;
+  DevBuf<MeshTable>      meshTab;
   uint64_t               epoch = 0;      // bumped by every commit: a context re-sizes its working set when it lags
   std::mutex             mtx;            // guards `handles`
   std::vector<MgsScene_t*> handles;      // the owning scene and its live frame contexts
@@ -398,6 +425,30 @@ struct CompareState
   }
 };
 
+// the mesh pass (mgs_meshes_render): visibility words, set-up records, work list, counters and the primitive-id image.  The depth
+// and colour images it produces are the handle's owned occluder buffers (OccluderBinding::ownDepth / ownColor)
+struct MeshPassState
+{
+  DevBuf<unsigned long long> vis;
+  DevBuf<MeshTriRec>         recs;
+  DevBuf<MeshClipRec>        clips;
+  DevBuf<uint2>              work;
+  DevBuf<MeshCounters>       ctr;
+  DevBuf<uint32_t>           prim;
+  int                        w = 0, h = 0;  // size of the last pass (mgs_meshes_download)
+  bool                       have = false;
+  hipEvent_t                 ev[2] = {};
+  template <class F>
+  void eachBuffer(F&& f) { f(vis); f(recs); f(clips); f(work); f(ctr); f(prim); }
+  void release()
+  {
+    eachBuffer([](auto& b) { b.release(); });
+    for(auto& e : ev)
+      if(e) (void)hipEventDestroy(e);
+    ev[0] = ev[1] = nullptr;
+  }
+};
+
 // scratch of the stand-alone sort (mgs_radix_sort_u32): owned by the handle (its device, its stream)
 struct SortScratch
 {
@@ -528,6 +579,7 @@ struct MgsScene_t
   OccluderBinding occ;
   SurfaceOutputs  surf;
   CompareState    cmp;
+  MeshPassState   mesh;
   SortScratch     rs;
   CommState       comm;
   CpuSortState    cpu;

@@ -1,0 +1,101 @@
+// shade_direct.h — the direct shading both the deferred lighting pass (k_light.hip) and the mesh pass (k_mesh.hip) evaluate:
+// wavefrontComputeShadingDirectOnly with wavefrontComputeSpecular (shaders/wavefront.h.slang:233-280,388-403) in their own order of
+// operations, the material and light types it reads, and the small vector helpers.  Device code only; every kernel file that
+// includes it gets its own inlined copy.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/mgs.h"
+#include "device_types.h"
+
+namespace mgs {
+
+namespace {
+
+struct V3
+{
+  float x, y, z;
+};
+__device__ __forceinline__ V3    operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3    operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3    operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+__device__ __forceinline__ V3    operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ V3    operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3    normalize3(V3 a) { return a * (1.0f / sqrtf(dot3(a, a))); }
+__device__ __forceinline__ V3    load3(const float* p) { return {p[0], p[1], p[2]}; }
+
+struct Mat
+{
+  V3    ambient, diffuse, specular, emission;
+  float shininess;
+  int   needShading;
+};
+
+// distance attenuation of computePointLight / computeSpotLight (wavefront.h.slang:160-174, 193-206)
+__device__ __forceinline__ float attenuate(int mode, float distance, float range)
+{
+  float attenuation = 1.0f;
+  if(mode == 1)
+    attenuation = 1.0f - (distance / range);
+  else if(mode == 2)
+    attenuation = 1.0f / (1.0f + distance * distance);
+  else if(mode == 3)
+    attenuation = 1.0f / (distance * distance + 0.01f);
+  return attenuation;
+}
+
+// wavefrontComputeShadingDirectOnly (wavefront.h.slang:233-280) with inShadow = false, transmittance = 1
+__device__ __forceinline__ void shadeDirect(const LightDev& light, V3 worldPos, V3 n, const Mat& mat, V3 viewDir, V3& radiance)
+{
+  radiance = radiance + mat.ambient;  // ambient once per light, as written
+  const V3 lightColor = load3(light.color);
+  V3       L;
+  V3       lightDiffuse = {0.0f, 0.0f, 0.0f};
+  if(light.type == MGS_LIGHT_DIRECTIONAL)
+  {
+    L                 = -load3(light.dirN);
+    const float NdotL = fmaxf(dot3(n, L), 0.0f);
+    lightDiffuse      = lightColor * light.intensity * NdotL;
+  }
+  else
+  {
+    const V3    toLight  = load3(light.pos) - worldPos;
+    const float distance = sqrtf(dot3(toLight, toLight));
+    L                    = toLight * (1.0f / distance);
+    if(!(distance > light.range))
+    {
+      const float attenuation = attenuate(light.attMode, distance, light.range);
+      const float NdotL       = fmaxf(dot3(n, L), 0.0f);
+      if(light.type == MGS_LIGHT_POINT)
+        lightDiffuse = lightColor * light.intensity * attenuation * NdotL;
+      else if(light.type == MGS_LIGHT_SPOT)
+      {
+        const float theta = dot3(L, -load3(light.dirN));
+        if(!(theta < light.outerCos))
+        {  // smoothstep(outerCos, innerCos, theta)
+          const float t          = fminf(fmaxf((theta - light.outerCos) / (light.innerCos - light.outerCos), 0.0f), 1.0f);
+          const float spotEffect = t * t * (3.0f - 2.0f * t);
+          lightDiffuse           = lightColor * light.intensity * attenuation * spotEffect * NdotL;
+        }
+      }
+    }
+  }
+  const V3 fragDiffuse = mat.diffuse * lightDiffuse;
+  // wavefrontComputeSpecular (:388-403)
+  const float kPi                 = 3.14159265f;
+  const float kShininess          = fmaxf(mat.shininess, 4.0f);
+  const float kEnergyConservation = (2.0f + kShininess) / (2.0f * kPi);
+  const V3    V                   = normalize3(-viewDir);
+  const V3    I                   = -L;
+  const V3    R                   = I - n * (2.0f * dot3(n, I));  // reflect(-L, n)
+  // powf, not the fast intrinsic: with shininess up to 2000 the exponent multiplies the base's relative error, and __powf's own
+  // exp2(y * log2(x)) would add ~2000 x 2^-22 on top of it
+  const float specular             = kEnergyConservation * powf(fmaxf(dot3(V, R), 0.0f), kShininess);
+  const V3    specularContribution = mat.specular * specular * lightColor * light.intensity;
+  radiance                         = radiance + (fragDiffuse + specularContribution);
+}
+
+}  // namespace
+
+}  // namespace mgs

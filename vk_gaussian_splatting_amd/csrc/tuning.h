@@ -26,6 +26,8 @@ struct Tuning
   uint32_t osFlat          = 1;      // MGS_OS_FLAT: the key sort's flat level-2 look-back where it applies (raw atoi; != 0 = on)
   uint32_t osPartMin       = 1536;   // MGS_OS_PART_MIN: smallest partition size the key sort may choose on the device
                                      // (a multiple of 256 in [1024, kOsPart]; kOsPart = fixed partitions)
+  // mesh pass
+  uint32_t meshWorkItems = 1u << 20;  // MGS_MESH_WORK_ITEMS=n: capacity of the large-triangle work list, 1 .. 2^26 chunks of 16 tiles
   // frame submission
   bool useGraph = true;  // MGS_GRAPH=0: plain kernel launches instead of replaying the captured frame graph
   // multi-GPU

@@ -48,6 +48,12 @@ static Tuning readTuning()
     if(x >= 1024 && x <= (int)kOsPart && x % 256 == 0)
       t.osPartMin = (uint32_t)x;
   }
+  if(const char* e = std::getenv("MGS_MESH_WORK_ITEMS"))
+  {
+    const long long x = std::atoll(e);
+    if(x >= 1 && x <= (1ll << 26))
+      t.meshWorkItems = (uint32_t)x;
+  }
   if(const char* e = std::getenv("MGS_RCCL_LIB"))
     t.rcclLib = e;
   return t;

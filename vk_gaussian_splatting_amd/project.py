@@ -7,8 +7,9 @@ interpreted: "renderer" (raster knobs), "camera" / "cameras", "splatsGlobals" (s
 degrees / scale, composed as T*R*S like computeTransform, src/utilities.h:170-199; "material" = the instance's splatMaterial,
 :252-260), "renderer.lightingMode" (and the legacy "lightingEnabled", :143-153) and "lights" in the three layouts the reader accepts
 (:616-770: assets / instances of version 3+, with the version 3 names "radius" / "position"; the flat list of versions 0-2).  The raw
-"lights" section is also kept in `extra` and written back unchanged.  Meshes, RTX and DLSS settings are carried through untouched on
-save but otherwise ignored (out of scope).
+"lights" section is also kept in `extra` and written back unchanged.  Meshes (:353-558) are read in both layouts, "meshAssets" +
+"meshInstances" of version 2+ and the "meshes" list of versions 0 / 1, and written back as read.  RTX and DLSS settings are carried
+through untouched on save but otherwise ignored (out of scope).
 """
 import json
 import os
@@ -43,6 +44,8 @@ class Project:
     instances: list = field(default_factory=list)       # [SplatInstance]
     extra: dict = field(default_factory=dict)           # sections written back as read (meshes, ..., and the raw "lights")
     lights: list = field(default_factory=list)          # "lights" interpreted: dicts with the field names of MgsLight
+    mesh_assets: dict = field(default_factory=dict)     # "meshAssets" interpreted: id -> absolute path of the .obj ("meshes": entry index)
+    mesh_instances: list = field(default_factory=list)  # "meshInstances" interpreted: dicts(asset, position, rotation, scale, materials)
 
     @property
     def lighting_mode(self):
@@ -99,7 +102,51 @@ class Project:
         scene.commit(self.sh_format, self.rgba_format)
         if self.lights:
             scene.set_lights([capi.make_light(**l) for l in self.lights])
+        self.add_meshes(scene)
         return scene
+
+    def resolve_meshes(self):
+        """loadMeshAssets / loadMeshInstances (vkgs_project_reader.cpp:353-454) on the host: (views, placed).  views: asset id -> the
+        arrays of Mesh.view(); a mesh file that cannot be loaded is skipped with a warning.  An instance's "materials" overwrite the
+        MESH's materials in order (they are shared by its instances, as in the reference: the last instance that carries them wins).
+        placed: (asset id, transform) of every instance whose asset was loaded, in file order; an instance of an unknown asset is skipped"""
+        import warnings
+        from . import capi
+        views = {}
+        for aid, path in self.mesh_assets.items():
+            try:
+                views[aid] = capi.Mesh.load_obj(path).view()
+            except capi.MgsError as e:
+                warnings.warn(f"mesh asset {aid} ({path}) skipped: {e}")
+        placed = []
+        for inst in self.mesh_instances:
+            v = views.get(inst["asset"])
+            if v is None:
+                continue
+            for k, item in enumerate(inst.get("materials") or []):
+                if k >= len(v["materials"]):
+                    break
+                for f in ("ambient", "diffuse", "specular", "emission"):
+                    if f in item:
+                        v["materials"][k][f] = tuple(float(x) for x in item[f])
+                if "shininess" in item:
+                    v["materials"][k]["shininess"] = float(item["shininess"])
+            M, _ = capi.compute_transform(inst["scale"], inst["rotation"], inst["position"])
+            placed.append((inst["asset"], M))
+        return views, placed
+
+    def add_meshes(self, scene):
+        """adds the mesh instances of resolve_meshes() to `scene`; returns their mesh instance ids"""
+        from . import capi
+        views, placed = self.resolve_meshes()
+        meshes, ids = {}, []
+        for aid, M in placed:
+            if aid not in meshes:
+                v = views[aid]
+                meshes[aid] = capi.Mesh.from_arrays(v["positions"], v["indices"], v["normals"], v["material_ids"],
+                                                    [capi.make_material(**m) for m in v["materials"]])
+            ids.append(scene.add_mesh_instance(meshes[aid], M))
+        return ids
 
 
 def _cam_from(item):
@@ -217,6 +264,26 @@ def load_project(path):
                 if k not in ("version", "renderer", "camera", "cameras", "splatsGlobals", "splatSets", "splats")}
     if "lights" in data:
         pr.lights = _lights_from(data["lights"], pr.version)
+    # loadMeshes (vkgs_project_reader.cpp:459-558); the sections stay in `extra` and are written back as read
+    def instance(it, asset):
+        return dict(asset=asset, name=it.get("name", ""), position=tuple(it.get("position", (0.0, 0.0, 0.0))),
+                    rotation=tuple(it.get("rotation", (0.0, 0.0, 0.0))), scale=tuple(it.get("scale", (1.0, 1.0, 1.0))),
+                    materials=it.get("materials"))
+    if pr.version >= 2 and "meshAssets" in data and "meshInstances" in data:  # separate assets and instances (:461-475)
+        for a in data["meshAssets"] if isinstance(data["meshAssets"], list) else []:
+            pr.mesh_assets[int(a["id"])] = os.path.normpath(os.path.join(base, a["path"]))
+        mi = data["meshInstances"]
+        items = mi["items"] if isinstance(mi, dict) and "items" in mi else mi if isinstance(mi, list) else []
+        for it in items:
+            pr.mesh_instances.append(instance(it, int(it["meshAssetId"])))
+    elif "meshes" in data:  # version 0 (a list) and version 1 ({"items": [...]}): every entry loads its own mesh and is its one instance (:476-553)
+        ms = data["meshes"]
+        items = ms["items"] if isinstance(ms, dict) and "items" in ms else ms if isinstance(ms, list) else []
+        for k, it in enumerate(items):
+            if not it.get("path"):
+                continue
+            pr.mesh_assets[k] = os.path.normpath(os.path.join(base, it["path"]))  # the entry's index stands in for an asset id
+            pr.mesh_instances.append(instance(it, k))
     return pr
 
 
