@@ -1,5 +1,5 @@
 """GPU parity tests (-m gpu) of the 3DGUT raster pipeline: unscented-transform projection +
-per-pixel particle response, HIP (k_gut.hip) through the C ABI against the CPU oracle (orc_render_gut_order, restated from
+per-pixel particle response, HIP (k_project_gut.hip, k_composite_gut.hip) through the C ABI against the CPU oracle (orc_render_gut_order, restated from
 threedgut_raster.{mesh,frag}.slang and cross-checked by an independent float64 restatement in the CPU tests).
 Bar: >= 50 dB PSNR and a per-channel absolute tolerance; strips bit-identical to the full frame."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The binning's column / row masks by a bit-matrix transpose (csrc/k_raster.hip: rectWord / transposeWords, k_dbin_count).
+"""The binning's column / row masks by a bit-matrix transpose (csrc/k_dbin.hip: rectWord / transposeWords, k_dbin_count).
 
 Host emulation of the wave-level algorithm — a splat's rectangle as a row of the (64 splats x binsX + binsY bits) matrix, five
 butterfly stages per half wave (partner = lane ^ d; keep-mask / rotate / merge exactly as the kernel's v_alignbit + v_bfi), the

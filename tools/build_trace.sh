@@ -1,5 +1,6 @@
 #!/bin/bash
-# trace build of the library (per-workgroup phase stamps in k_project and the sort passes) -> csrc/libmgs_trace.so
+# trace build of the library (per-workgroup phase stamps in k_project, the sort passes, k_dbin_emit of k_dbin.hip and k_composite of
+# k_composite.hip) -> csrc/libmgs_trace.so
 # (used by tools/trace_run.sh on the GPU box; objects in /tmp, the normal build is not touched)
 set -e
 C=$(cd "$(dirname "$0")/../vk_gaussian_splatting_amd/csrc" && pwd)

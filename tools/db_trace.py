@@ -1,4 +1,4 @@
-"""Debug-build experiment (csrc/k_raster.hip built with -DMGS_DB_TRACE): per-workgroup phase stamps of k_dbin_emit on the
+"""Debug-build experiment (csrc/k_dbin.hip built with -DMGS_DB_TRACE): per-workgroup phase stamps of k_dbin_emit on the
 garden-sized frame.  Usage: MGS_GRAPH=0 MGS_DB_TRACE_FILE=/tmp/d.bin python tools/db_trace.py [pose ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mgs.h"
+#include "composite_common.h"
 #include "launchers.h"
 #include "shade_direct.h"
 
@@ -45,25 +46,6 @@ __device__ __forceinline__ float4 loadPixel(const void* image, size_t o)
     return make_float4((float)(pk & 255u) / 255.0f, (float)((pk >> 8) & 255u) / 255.0f, (float)((pk >> 16) & 255u) / 255.0f, (float)(pk >> 24) / 255.0f);
   }
   return reinterpret_cast<const float4*>(image)[o];
-}
-template <int HALF>
-__device__ __forceinline__ void storePixel(void* image, size_t o, float4 c)
-{
-  if(HALF == 1)
-  {
-    const __half2 lo = __floats2half2_rn(c.x, c.y), hi = __floats2half2_rn(c.z, c.w);
-    uint2         pk;
-    pk.x = *reinterpret_cast<const uint32_t*>(&lo);
-    pk.y = *reinterpret_cast<const uint32_t*>(&hi);
-    reinterpret_cast<uint2*>(image)[o] = pk;
-  }
-  else if(HALF == 2)
-  {  // the compositors' UNORM conversion
-    auto q8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-    reinterpret_cast<uint32_t*>(image)[o] = q8(c.x) | (q8(c.y) << 8) | (q8(c.z) << 16) | (q8(c.w) << 24);
-  }
-  else
-    reinterpret_cast<float4*>(image)[o] = c;
 }
 
 }  // namespace
@@ -154,7 +136,7 @@ __global__ void __launch_bounds__(256) k_light(const LightArgs a)
       shadeDirect(h, worldPos, normal, mat, viewDir, color);
     }
   }
-  storePixel<HALF>(a.image, o, make_float4(color.x, color.y, color.z, 1.0f));
+  storePixel(a.image, HALF, o, color.x, color.y, color.z, 1.0f);
 }
 
 // depth_consolidate.frag.slang: the picked splat depth where it is valid and in front of the geometry (depth test LESS against the

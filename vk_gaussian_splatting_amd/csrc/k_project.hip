@@ -185,7 +185,7 @@ __device__ __forceinline__ bool projectSplat(const FrameConst& F, const Instance
   out.rect = (uint32_t)(x0 >> sx) | ((uint32_t)(y0 >> sy) << 8) | ((uint32_t)(x1 >> sx) << 16) | ((uint32_t)(y1 >> sy) << 24);
 
   // base colour, view direction and the SH sum (mesh.slang:205-207,240-243) are the compositor's business: it
-  // shades the records it stages (kernels_common.h: viewDirection, k_raster.hip: shading phase)
+  // shades the records it stages (kernels_common.h: viewDirection, k_composite.hip: shading phase)
   const float n1 = 2.0f * fastRcp(b1x * b1x + b1y * b1y), n2 = 2.0f * fastRcp(b2x * b2x + b2y * b2y);
   out.rec.cx  = pcx;
   out.rec.cy  = pcy;

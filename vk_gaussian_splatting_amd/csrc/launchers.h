@@ -12,11 +12,11 @@
 
 namespace mgs {
 
-// splats per workgroup of the project kernels, sorted splats per workgroup of the binning: k_project.hip and k_raster.hip
+// splats per workgroup of the project kernels, sorted splats per workgroup of the binning: k_project.hip, k_project_gut.hip and k_bin.hip
 // assert that their own constants equal it
 constexpr uint32_t kPart = 2048;
 
-// the project kernels (k_project.hip, k_gut.hip): cull, project, hand (key, id) pairs to the key sort (slot_emit.h)
+// the project kernels (k_project.hip, k_project_gut.hip): cull, project, hand (key, id) pairs to the key sort (slot_emit.h)
 struct ProjectLaunch
 {
   const FrameArgs* dArgs;            // the frame's constants on the device
@@ -37,7 +37,7 @@ struct ProjectLaunch
 void launchProject(hipStream_t stream, const ProjectLaunch& L);
 void launchProjectGut(hipStream_t stream, const ProjectLaunch& L);
 
-// the record + pair-sort path's binning (k_raster.hip)
+// the record + pair-sort path's binning (k_bin.hip)
 struct BinLaunch
 {
   const uint32_t* idsX;  // the sorted ids: planKeys->finalSel selects X or Y; the frame's key sort always ends in one buffer,
@@ -58,7 +58,7 @@ struct BinLaunch
 };
 void launchBinning(hipStream_t stream, const BinLaunch& L);
 
-// the direct binning of frames with at most 256 bins (k_raster.hip)
+// the direct binning of frames with at most 256 bins (k_dbin.hip)
 struct DirectBinLaunch
 {
   const uint32_t* idsX;  // as in BinLaunch
@@ -81,7 +81,7 @@ struct DirectBinLaunch
 bool directBinningSupported(int binsX, int binsY);
 void launchDirectBinning(hipStream_t stream, const DirectBinLaunch& L);
 
-// the compositors (k_raster.hip, k_gut.hip)
+// the compositors (k_composite.hip, k_composite_gut.hip)
 struct CompositeLaunch
 {
   const FrameArgs* A;      // host copy of the frame's constants: selects the kernel variant and the grid

@@ -1,4 +1,4 @@
-// partition_cull.h — the per-partition test of the project kernels (k_project.hip, k_gut.hip): can any splat of this workgroup's
+// partition_cull.h — the per-partition test of the project kernels (k_project.hip, k_project_gut.hip): can any splat of this workgroup's
 // 2048-splat partition survive the dist-stage cull / reach this device's strip?
 //
 // Storage order is Morton order, so a partition is a compact cell of space; its 8 AABB corners go through the same P*V*M.  The

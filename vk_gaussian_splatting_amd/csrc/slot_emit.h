@@ -1,4 +1,4 @@
-// slot_emit.h — the hand-over from the project kernels (k_project.hip, k_gut.hip) to the frame's key sort (k_osort.hip).
+// slot_emit.h — the hand-over from the project kernels (k_project.hip, k_project_gut.hip) to the frame's key sort (k_osort.hip).
 // A project workgroup owns one 2048-splat partition.  After its raster front end it hands the splats that can produce a
 // fragment to the sort in ITS OWN SLOT of the pair array — slot p = entries [2048 p, 2048 p + count_p) — and leaves count_p.
 // Nothing here waits for another workgroup.

@@ -152,7 +152,7 @@ size_t   osSortStatusWords(uint32_t maxParts);
 void     launchOsSortClearPlan(hipStream_t stream, OsPlan* plan);
 void     launchOsSort(hipStream_t stream, const OsLaunch& L);
 
-// ---- what the project kernels hand to the key sort (k_project.hip, k_gut.hip; device side in slot_emit.h) -----------------
+// ---- what the project kernels hand to the key sort (k_project.hip, k_project_gut.hip; device side in slot_emit.h) -----------------
 
 // The producer counts which values of key >> 16 it hands to the sort.  A partition is a compact cell of space, so its keys
 // span one to three values: every wave leaves a 32-word record (counts of the values lo .. lo + 24, header lo | span << 16

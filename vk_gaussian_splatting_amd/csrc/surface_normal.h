@@ -1,4 +1,4 @@
-// surface_normal.h — the per-splat world normal of NEED_SURFACE_INFO, shared by the 3DGS (k_raster.hip) and 3DGUT (k_gut.hip)
+// surface_normal.h — the per-splat world normal of NEED_SURFACE_INFO, shared by the 3DGS (k_composite.hip) and 3DGUT (k_composite_gut.hip)
 // compositors.
 #pragma once
 #include "kernels_common.h"
@@ -80,7 +80,7 @@ __device__ inline float4 splatWorldNormal(const FrameConst& F, const InstanceCon
     w0 = d0 / dl; w1 = d1 / dl; w2 = d2 / dl;
   }
   // .w = 1: two or more axes are degenerate and the normal is minus the RAY direction — the 3DGS mesh shader passes the
-  // direction to the splat centre (what was computed above), the 3DGUT fragment shader its pixel's ray (k_gut.hip)
+  // direction to the splat centre (what was computed above), the 3DGUT fragment shader its pixel's ray (k_composite_gut.hip)
   return make_float4(w0, w1, w2, smallCount >= 2 ? 1.0f : 0.0f);
 }
 
