@@ -38,8 +38,11 @@ extern "C" {
                                  mgs_compare_view_default, mgs_compare_composite, mgs_compare_download_composite;
                             meshes (MGS_HAS_MESHES below): entry points only, both numbers stay — mgs_mesh_from_arrays, mgs_mesh_load_obj, mgs_mesh_view,
                                  mgs_mesh_destroy, mgs_mesh_instance_add, mgs_mesh_instance_set_transform, mgs_mesh_instance_set_visible,
-                                 mgs_meshes_render, mgs_meshes_download */
+                                 mgs_meshes_render, mgs_meshes_download;
+                            ray-traced splats (MGS_HAS_TRACE below): entry points only, both numbers stay — mgs_trace_params_default,
+                                 mgs_render_traced, mgs_trace_download_hit_counts */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
@@ -521,6 +524,82 @@ int  mgs_meshes_render(MgsScene scene_or_context, const MgsFrameParams* params, 
  * uint32 (global: instances concatenated in creation order, visible or not; 0xFFFFFFFF = none).  MGS_ERR_STATE before any pass.
  * (The depth and colour images are the handle's owned occluder buffers: a later mgs_frame_upload_occluder overwrites them.) */
 int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, size_t bytes);
+
+/* ---- ray-traced splats (MGS_HAS_TRACE): primary rays of the reference's PIPELINE_RTX, the 3DGRT ray tracer, without fixed-function
+ * hardware.  Replaces GaussianSplatting::raytrace with shaders/threedgrt_raytrace.{rgen,rahit,rint}.slang (primary rays), the
+ * particle proxies of particle_as_build.comp.slang and the acceleration-structure managers: a hierarchy over the particles built on
+ * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
+ * Out of scope: meshes in the traced scene, shadows, lighting and bounces, the hybrid pipeline, the stochastic trace strategies,
+ * wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
+ * is not wired), trace profile feedback.
+ *
+ * Ray (threedgrt_raytrace.rgen.slang:159-196): pinhole = generatePinholeRay at the pixel centre (subPixelOffset 0.5,
+ * cameras.h.slang:27-44); fisheye = generateFisheyeRay of the pixel's integer coordinate, as written (:46-82), a pixel outside the
+ * field of view is written as (0,0,0,1); depth of field as depthOfField (:85-105) seeded with xxhash32(pixel, frame_sample_id)
+ * (rgen:193).  viewInverse and projInverse are computed on the host in double and rounded once (the lighting pass's rule; glm::inverse
+ * is not part of the reference tree: PARITY UNPINNED).  tMin = 0.001, tMax = 10000, epsT = 1e-9 (rgen:157,247-248).
+ * A hit of particle i on a ray: t_i = -dot(o,d)/dot(d,d) in the particle's canonical frame with the UNNORMALISED direction
+ * (particleDensityHitInstance, rint.slang:166-168; the reference's default is instances on), i.e. the world ray's parameter of the
+ * point of maximum response.  It exists for a pass when TMin < t_i < TMax and the response along the ray exceeds the response the
+ * reference circumscribes its proxy around (kernelScale, particle_as_build.comp.slang:74-87): min(kernel_min_response / density,
+ * 0.97) with kernel_adaptive_clamping, min(kernel_min_response, 0.97) without.  How far the reference's icosahedron or hardware box
+ * reaches beyond that ellipsoid, the entry-point t it reports in icosahedron mode and its traversal's tie order are PARITY UNPINNED;
+ * here ties in t resolve by ascending global id (caller's order).  It is ACCEPTED when particleProcessHit accepts it
+ * (threedgrt.h.slang:166-185: density > alpha_cull_threshold, alpha = min(alpha_clamp, response * density) > alpha_cull_threshold,
+ * response > kernel_min_response).  Model-space ray of a hit: origin through transformInverse, direction through
+ * transformRotScaleInverse (normalised; the host-double inverse of the mesh instances) (rgen:697-698); the SH direction is
+ * normalize(position - modelRayOrigin) (threedgrt.h.slang:193).
+ * Passes, as written (traceRayParticlesInsertionSort, rgen:615-819; insertion rahit.slang:152-167): each pass collects the
+ * samples_per_pass nearest hits with t in (tMin + epsT, tMax + epsT), walks them in order while the transmittance exceeds
+ * min_transmittance, sets tMin = max(tMin, t) after every walked slot, accepted or not, and the loop ends when a pass finds nothing,
+ * after max_passes, or when the transmittance test fails.  A hit that ties with the last slot, or lies within epsT of the last walked
+ * one, is therefore lost, here as there.  Integration as particleIntegrate (threedgrt.h.slang:226-235) with the transmittance in double.
+ * The frame's alpha is 1 - T, this library's MGS_ALPHA_COVERAGE meaning; the reference writes 1.0.
+ * kernel_min_response must be > 0 (at 0 the proxy is unbounded): MGS_ERR_INVALID_ARG. */
+typedef struct MgsTraceParams {
+  int32_t samples_per_pass;          /* PARTICLES_SPP, default 18 (parameters.h:218); 1..32 */
+  int32_t max_passes;                /* frameInfo.maxPasses, default 200 (shaderio.h:269); >= 1 */
+  float   min_transmittance;         /* default 0.01 (shaderio.h:272); [0, 1) */
+  int32_t kernel_adaptive_clamping;  /* default 1 (parameters.h:217); 0 / 1 */
+  float   depth_iso_threshold;       /* depthIsoThresholdRTX, default 0.7 (parameters.h:226); replaces MgsFrameParams::depth_iso_threshold */
+  uint32_t reserved[3];
+} MgsTraceParams;
+void mgs_trace_params_default(MgsTraceParams* p);
+typedef struct MgsTraceOut {
+  uint64_t leaves, nodes;            /* of the scene's hierarchy: particles with a leaf, nodes of all levels (leaves included) */
+  uint64_t node_visits;              /* nodes whose box was tested when taken from a ray's stack, summed over rays and passes */
+  uint64_t candidate_tests;          /* particles evaluated against a ray */
+  uint64_t accepted_hits;            /* sum of pixel.hitCount */
+  uint32_t max_passes_used;          /* the most passes any ray started */
+  uint32_t bvh_rebuilt;              /* 1: this call rebuilt the hierarchy */
+  float    build_ms, trace_ms;       /* HIP events around the build's launches (0 when not rebuilt) and around the traversal */
+} MgsTraceOut;
+/* One traced frame into the handle's frame buffer.  Reads of MgsFrameParams: view, proj, camera_pos, width, height, strip_row_begin,
+ * strip_row_end, sh_degree, alpha_cull_threshold, target_format, camera_model, fov_rad, kernel_degree, kernel_min_response,
+ * alpha_clamp, dof_mode, focus_dist, aperture, frame_sample_id, temporal_sampling, surface_outputs, normal_method,
+ * thin_particle_threshold, debug_flags (MGS_DEBUG_SH_ONLY and MGS_DEBUG_OPACITY_GAUSSIAN_DISABLED only); the rest is ignored, except:
+ * lighting_mode != 0, sort_mode == MGS_SORT_STOCHASTIC and a bound occluder each return MGS_ERR_UNSUPPORTED.  The ranges of both
+ * structs are checked before the handle is looked at.  `trace` NULL = the defaults; `out` non-NULL waits for the frame.
+ * Afterwards mgs_frame_download, mgs_frame_copy_strip, the image-compare entry points and temporal accumulation work as after
+ * mgs_render.  With surface_outputs = 1, mgs_frame_download_surface returns
+ *   which 0: ndc z of primaryHitPos = origin + t * direction of the first accepted hit after which the transmittance is below
+ *            depth_iso_threshold, as writeToGBuffers writes the depth buffer (rgen:1490-1502); 0 where nothing was picked — this
+ *            library's "none" value, NOT the reference's 1.0;
+ *   which 1: that particle's global id in the caller's order (0xFFFFFFFF where none);
+ *   which 2: integratedNormal in xyz (sum of normalWorld * weight, rgen:725; normal_method as computeEllipsoidNormalMaxDensityPlane /
+ *            computeEllipsoidNormal, threedgrt.h.slang:358-496, to world space by the inverse transpose, :218) and the sum of weight.x in w.
+ * The hierarchy (an implicit complete 8-ary tree over leaves in Morton order) covers all instances' particles in world
+ * space, belongs to the scene and is shared by its frame contexts.  It is rebuilt lazily by the next traced frame after
+ * mgs_scene_commit, mgs_instance_add, mgs_instance_set_transform, or a change of kernel_degree, kernel_min_response,
+ * kernel_adaptive_clamping or alpha_cull_threshold; a rebuild first waits for the frames in flight on all contexts (the rule of
+ * mgs_scene_set_lights).  Its bytes are part of scene_bytes of mgs_scene_memory_usage.  A leaf bound is the exact box of the affine
+ * image of the proxy ellipsoid, inflated by 8 ulps of the half extent plus 2 ulps of the centre; particles with density <=
+ * alpha_cull_threshold or a non-finite bound get no leaf and are never hit.  A scene without instances (committed or not) yields the
+ * frame (0,0,0) with alpha 0. */
+int mgs_render_traced(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
+                      MgsTraceOut* out /* may be NULL */);
+/* pixel.hitCount of the last traced frame of this handle, [height][width] uint32 (rows outside a strip frame's rows are stale); waits */
+int mgs_trace_download_hit_counts(MgsScene scene_or_context, uint32_t* host_dst, size_t count);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

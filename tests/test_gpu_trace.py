@@ -1,0 +1,91 @@
+"""mgs_render_traced on the device against the float64 restatement (np_trace.py), one child process per case.
+
+On the pixels the restatement does not mark fragile: the hit count and the picked id are EQUAL; over the whole frame the image's
+PSNR is at or above 50 dB, the floor the 3DGUT pipeline is held to (csrc/gut_common.h: the same arithmetic class).  The worst
+non-fragile pixel's absolute error is printed (DESIGN.md has the measured figures); no bound is fixed on it."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import np_trace
+import trace_cases as tc
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+CASES = sorted(tc.cases())
+
+
+def run_child(tmp_path, *args):
+    out = str(tmp_path / "out.npz")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_child_trace.py"), args[0], out, *args[1:]], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    return np.load(out)
+
+
+def compare(got_image, got_hits, ref, got_id=None, label=""):
+    ok = ~ref["fragile"]
+    psnr = np_trace.psnr_rgb(got_image, ref["image"])
+    err = np.abs(got_image.astype(np.float64) - ref["image"])[ok]
+    worst = float(err.max()) if err.size else 0.0
+    print(f"{label}: PSNR {psnr:.2f} dB, worst non-fragile pixel error {worst:.3e}, fragile {1 - ok.mean():.4f}, "
+          f"hit counts differ on {(got_hits[ok] != ref['hits'][ok]).sum()} non-fragile pixels")
+    assert np.array_equal(got_hits[ok], ref["hits"][ok])
+    if got_id is not None:
+        assert np.array_equal(got_id.astype(np.int64)[ok], ref["id"][ok])
+    assert psnr >= 50.0
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_traced_frame_matches_restatement(name, tmp_path):
+    got = run_child(tmp_path, "case", name)
+    ref = tc.restate(name)
+    case = tc.cases()[name]
+    compare(got["image"], got["hits"], ref, got["id"], name)
+    ok = ~ref["fragile"]
+    # side outputs: the picked depth follows the restatement within the per-pixel fp32 tolerance np_trace derives (ndc z is steep
+    # close to the camera: a ray that starts inside the cloud picks hits at t ~ 0.01, where 1e-7 in t is 1e-4 in z); the integrated
+    # normal is a sum of unit vectors with weights that add up to at most 1
+    excess = np.abs(got["depth"].astype(np.float64) - ref["depth"]) - ref["depth_tol"]
+    print(f"{name}: picked depth worst error {np.abs(got['depth'].astype(np.float64) - ref['depth'])[ok].max(initial=0.0):.3e}, "
+          f"largest tolerance {ref['depth_tol'][ok].max(initial=0.0):.3e}")
+    assert excess[ok].max(initial=0.0) <= 0.0
+    assert np.abs(got["normal"].astype(np.float64) - ref["normal"])[ok].max(initial=0.0) <= 2e-3
+    assert int(got["out_accepted_hits"]) == int(got["hits"].sum())
+    n_alive = sum(int(np_trace.prepare_set(a)["n"]) for a, _ in case["sets"])
+    assert int(got["out_leaves"]) <= n_alive
+    if name.startswith("e_leaves_"):
+        assert int(got["out_leaves"]) == int(name.rsplit("_", 1)[1])
+    if name == "l_no_leaf":
+        assert int(got["out_leaves"]) == 300 - 2
+    if name == "m_empty":
+        assert not got["image"].any() and int(got["out_leaves"]) == 0
+    if name == "g_out_of_passes":
+        assert int(got["out_max_passes_used"]) == 3
+    if name == "f_many_passes":
+        assert int(got["out_max_passes_used"]) > 3
+
+
+def test_determinism_strips_rebuilds_contexts_errors(tmp_path):
+    r = run_child(tmp_path, "extras")
+    assert r["first_rebuilt"] == 1 and r["second_rebuilt"] == 0          # an unchanged scene does not rebuild
+    assert r["same_frame_twice"] and r["same_after_rebuild"] and r["same_after_second_build"]  # bit-identical frames and builds
+    assert r["proxy_change_rebuilt"]
+    assert r["strip_equal"]                                             # strip rows [1, 2) == the same rows of the full frame
+    assert r["context_equal"] and r["context_rebuilt"] == 0             # a frame context traces over the scene's hierarchy
+    assert r["moved_rebuilt"] == 1 and r["moved_again_rebuilt"] == 0    # a transform change rebuilds, once
+    assert r["raster_unchanged"]                                        # mgs_render before == after a traced frame, bit for bit
+    assert r["scene_bytes_has_bvh"] > 0
+    assert (r["err_lighting"], r["err_stochastic"], r["err_occluder"]) == (-8, -8, -8)
+    assert (r["err_spp"], r["err_passes"], r["err_kmr"]) == (-1, -1, -1)
+    assert r["err_uncommitted"] == -6
+    # the moved scene follows the restatement
+    case = dict(tc.cases()["c_two_instances"])
+    sets = [(np_trace.prepare_set(a), M) for a, M in case["sets"]]
+    sets[1] = (sets[1][0], r["moved_M"])
+    ref = tc.restate_with(case, sets)
+    assert ref["fragile"].mean() <= 0.02
+    compare(r["moved_image"], r["moved_hits"], ref, label="moved instance")

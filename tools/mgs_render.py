@@ -6,6 +6,7 @@
                              [--occluder-depth FILE.npy [--background FILE.npy]]
                              [--mesh FILE.obj [--mesh-transform 16 floats]]...
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
+                             [--pipeline raster|trace [--samples-per-pass N --max-passes N --min-transmittance X]]
                              [--compare-with FRAME.npy [--flip-mode 0|1|2] [--compare-view OUT.png --split 0.5 --left capture --right diff-red-gray]]
 
 --occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
@@ -15,6 +16,9 @@ depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear co
 with the field names of MgsLight (type, color, intensity, position, range, direction, inner_cone_deg, outer_cone_deg,
 attenuation_mode; absent fields keep the reference's defaults); without it the headlight at the camera lights the scene.
 --material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
+
+--pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
+the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth, --mesh or --lighting 1.
 
 --compare-with: float32 [H, W, 3|4] frame made elsewhere (a reference screenshot, another build's frame), uploaded as the capture;
 prints MSE / PSNR / FLIP of the rendered frame against it, computed on the device (mgs_compare_metrics).  --compare-view writes
@@ -52,6 +56,10 @@ def main():
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
+    ap.add_argument("--pipeline", choices=["raster", "trace"], default="raster")
+    ap.add_argument("--samples-per-pass", type=int, default=18)
+    ap.add_argument("--max-passes", type=int, default=200)
+    ap.add_argument("--min-transmittance", type=float, default=0.01)
     ap.add_argument("--compare-with", default=None, metavar="FRAME.npy")
     ap.add_argument("--flip-mode", type=int, choices=[0, 1, 2], default=capi.FLIP_REFERENCE)
     ap.add_argument("--compare-view", default=None, metavar="OUT.png")
@@ -103,10 +111,22 @@ def main():
             scene.add_mesh_instance(mgs.Mesh.load_obj(path), m)
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
-    o = scene.render(p)
-    img = scene.download_frame(p).astype(np.float32)
-    print(f"{scene.splat_count} splats, {o.frustum_count} in frustum, {o.sorted_count} sorted, {o.tile_pairs} bin records, "
-          f"{o.stage_ms[5]:.3f} ms on the GPU" + (f" ({o.stage_ms[capi.STAGE_LIGHT]:.3f} ms lighting)" if a.lighting else ""))
+    if a.pipeline == "trace":
+        if a.occluder_depth or a.mesh or a.lighting:
+            ap.error("--pipeline trace renders splats alone: no --occluder-depth, --mesh or --lighting 1")
+        p.collect_timings = 0
+        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance)
+        o = scene.render_traced(p, t, want_stats=True)
+        img = scene.download_frame(p).astype(np.float32)
+        rays = W * H
+        print(f"{scene.splat_count} splats, {o.leaves} leaves in {o.nodes} nodes (build {o.build_ms:.3f} ms), {o.node_visits / rays:.1f} node visits and "
+              f"{o.candidate_tests / rays:.1f} candidate tests per ray, {o.accepted_hits / rays:.1f} hits per ray, at most {o.max_passes_used} passes, "
+              f"{o.trace_ms:.3f} ms on the GPU")
+    else:
+        o = scene.render(p)
+        img = scene.download_frame(p).astype(np.float32)
+        print(f"{scene.splat_count} splats, {o.frustum_count} in frustum, {o.sorted_count} sorted, {o.tile_pairs} bin records, "
+              f"{o.stage_ms[5]:.3f} ms on the GPU" + (f" ({o.stage_ms[capi.STAGE_LIGHT]:.3f} ms lighting)" if a.lighting else ""))
     if a.out.endswith(".npy"):
         np.save(a.out, img)
     else:

@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
+
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--json OUT.json]
+
+Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
+orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
+tests per ray, and writes everything as JSON.  Needs an MI355X.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vk_gaussian_splatting_amd as mgs  # noqa: E402
+from vk_gaussian_splatting_amd import capi, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scenes", nargs="+")
+    ap.add_argument("--size", type=int, nargs=2, default=[1920, 1080])
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--samples-per-pass", type=int, default=18)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    W, H = a.size
+    results = []
+    for name in a.scenes:
+        if not name.startswith("syn:"):
+            ap.error("scenes are syn:<n>")
+        n = int(name[4:])
+        scene = mgs.Scene(0)
+        scene.add_instance(mgs.SplatSet.from_arrays(**synth.make_scene(n)))
+        scene.commit()
+        eye = synth.orbit_pose(5)
+        V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, W, H)
+        p = capi.default_params(W, H)
+        capi.set_camera(p, V, P, eye)
+        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+        first = scene.render_traced(p, t, want_stats=True)
+        for _ in range(a.warmup):
+            scene.render_traced(p, t, want_stats=True)
+        ms = []
+        for _ in range(a.repeats):
+            o = scene.render_traced(p, t, want_stats=True)
+            ms.append(o.trace_ms)
+        rays = W * H
+        r = dict(scene=name, width=W, height=H, samples_per_pass=a.samples_per_pass, splats=n, leaves=int(o.leaves), nodes=int(o.nodes),
+                 build_ms=float(first.build_ms), first_trace_ms=float(first.trace_ms), trace_ms_median=float(np.median(ms)),
+                 trace_ms_min=float(min(ms)), trace_ms_max=float(max(ms)), repeats=a.repeats, warmup=a.warmup,
+                 node_visits_per_ray=o.node_visits / rays, candidate_tests_per_ray=o.candidate_tests / rays,
+                 accepted_hits_per_ray=o.accepted_hits / rays, max_passes_used=int(o.max_passes_used),
+                 scene_bytes=scene.memory_usage()[0])
+        print(json.dumps(r))
+        results.append(r)
+        scene.close()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -121,6 +121,22 @@ class MeshOut(C.Structure):
                 ("elapsed_ms", C.c_float), ("flags", C.c_uint32)]
 
 
+class TraceParams(C.Structure):
+    """MgsTraceParams: the knobs of the traced pipeline that MgsFrameParams has no room for"""
+    _fields_ = [("samples_per_pass", C.c_int32), ("max_passes", C.c_int32), ("min_transmittance", C.c_float),
+                ("kernel_adaptive_clamping", C.c_int32), ("depth_iso_threshold", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class TraceOut(C.Structure):
+    """MgsTraceOut: the hierarchy's size, the traversal's counters and the device times of one traced frame"""
+    _fields_ = [("leaves", C.c_uint64), ("nodes", C.c_uint64), ("node_visits", C.c_uint64), ("candidate_tests", C.c_uint64),
+                ("accepted_hits", C.c_uint64), ("max_passes_used", C.c_uint32), ("bvh_rebuilt", C.c_uint32),
+                ("build_ms", C.c_float), ("trace_ms", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CompareParams(C.Structure):
     """MgsCompareParams"""
     _fields_ = [("flip_mode", C.c_int32), ("pixels_per_degree", C.c_float)]
@@ -217,6 +233,9 @@ def load_library():
         "mgs_mesh_instance_set_visible": (C.c_int, [vp, C.c_int, C.c_int]),
         "mgs_meshes_render": (C.c_int, [vp, P(FrameParams), P(MeshOut)]),
         "mgs_meshes_download": (C.c_int, [vp, C.c_int, vp, C.c_size_t]),
+        "mgs_trace_params_default": (None, [P(TraceParams)]),
+        "mgs_render_traced": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceOut)]),
+        "mgs_trace_download_hit_counts": (C.c_int, [vp, P(C.c_uint32), C.c_size_t]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -271,6 +290,7 @@ EXPORTED_SYMBOLS = [
     "mgs_compare_view_default", "mgs_compare_composite", "mgs_compare_download_composite",
     "mgs_mesh_from_arrays", "mgs_mesh_load_obj", "mgs_mesh_view", "mgs_mesh_destroy", "mgs_mesh_instance_add",
     "mgs_mesh_instance_set_transform", "mgs_mesh_instance_set_visible", "mgs_meshes_render", "mgs_meshes_download",
+    "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -459,6 +479,17 @@ def default_params(width=1920, height=1080):
     return p
 
 
+def default_trace_params(**overrides):
+    """MgsTraceParams with the reference's defaults (mgs_trace_params_default); keyword arguments override fields"""
+    t = TraceParams()
+    load_library().mgs_trace_params_default(C.byref(t))
+    for k, v in overrides.items():
+        if k not in dict(TraceParams._fields_):
+            raise TypeError(f"default_trace_params: unknown field {k}")
+        setattr(t, k, v)
+    return t
+
+
 def set_camera(p, view, proj, camera_pos):
     """view/proj: 4x4 numpy in math (row, col) convention; stored glm column-major."""
     v = _f32(view).T.reshape(-1)
@@ -628,6 +659,22 @@ class Scene:
         _check(self._lib.mgs_render(self._h, C.byref(params), C.byref(out)))
         if want_stats and not params.collect_timings:
             _check(self._lib.mgs_frame_stats(self._h, C.byref(out)))
+        return out
+
+    def render_traced(self, params, trace=None, want_stats=False):
+        """mgs_render_traced: one ray-traced (3DGRT primary rays) frame into this handle's frame buffer; trace = a TraceParams or
+        None for the defaults; want_stats waits and returns a TraceOut"""
+        out = TraceOut()
+        self._sort_only = False
+        self._frame_wh = (params.width, params.height)
+        _check(self._lib.mgs_render_traced(self._h, C.byref(params), C.byref(trace) if trace is not None else None,
+                                           C.byref(out) if want_stats else None))
+        return out if want_stats else None
+
+    def trace_hit_counts(self, params):
+        """pixel.hitCount of the last traced frame, uint32[H,W]"""
+        out = np.zeros((params.height, params.width), np.uint32)
+        _check(self._lib.mgs_trace_download_hit_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
         return out
 
     def frame_stats(self):

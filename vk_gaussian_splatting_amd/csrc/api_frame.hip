@@ -198,6 +198,48 @@ __global__ void k_iota_u32(uint32_t* p, uint32_t n)
 }
 }  // extern "C"
 
+namespace mgs {
+void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* accum, void* image, int halfOut)
+{
+  hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, stream, dArgs, accum, image, halfOut);
+}
+}  // namespace mgs
+
+// the frame image (and side outputs, accumulator) of a frame that is made outside the frame graph (mgs_render_traced); captured
+// frames that point at a buffer that moved are dropped, as ensureFrameBuffers does
+int ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F)
+{
+  FrameBuffers& fb = s->fb;
+  int           rc = MGS_OK;
+  const size_t  pixels  = (size_t)F.width * F.height;
+  fb.imageRowBytes      = (size_t)F.width * targetLayout(p->target_format).pixelBytes;
+  fb.imageBytes         = fb.imageRowBytes * (size_t)F.height;
+  const void* before[5] = {fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
+  if(fb.image.n < fb.imageBytes)
+  {
+    if((rc = fb.image.ensure(fb.imageBytes))) return rc;
+    HIPCHK(hipMemsetAsync(fb.image.p, 0, fb.imageBytes, s->stream));
+  }
+  if(F.surfaceOutputs)
+  {
+    if((rc = s->surf.depth.ensure(pixels))) return rc;
+    if((rc = s->surf.id.ensure(pixels))) return rc;
+    if((rc = s->surf.normal.ensure(pixels))) return rc;
+  }
+  if(F.temporalSampling)
+    if((rc = fb.accum.ensure(pixels))) return rc;
+  s->surf.have         = F.surfaceOutputs != 0;
+  s->surf.lastOccDepth = nullptr;
+  s->surf.lastOccGone  = false;
+  const void* after[5] = {fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
+  if(std::memcmp(before, after, sizeof(before)) != 0 && !s->graphs.map.empty())
+  {
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->graphs.drop();
+  }
+  return MGS_OK;
+}
+
 // ---- adaptive bin size (BinPolicy, scene_state.h) ---------------------------------------------------------------------------
 // a sample taken 8 eligible frames ago is applied now
 int BinPolicy::apply()

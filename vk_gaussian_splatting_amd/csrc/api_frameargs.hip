@@ -44,7 +44,7 @@ void mgs_frame_params_default(MgsFrameParams* p)
 }
 
 // inverse of a glm column-major 4x4 in double (Gauss-Jordan with partial pivoting), rounded once to fp32
-static void mat4InverseDouble(const float m[16], float out[16])
+void mat4InverseDouble(const float m[16], float out[16])
 {
   double a[4][8];
   for(int r = 0; r < 4; ++r)

@@ -117,7 +117,7 @@ void mgs_mesh_destroy(MgsMesh mesh) { delete mesh; }
 
 // ---- the scene's mesh instances -----------------------------------------------------------------------------------------------
 // inverse(mat3(transform)) in double, rounded once (glm::inverse is not part of the reference tree: PARITY UNPINNED)
-static void rotScaleInverse(const float M[16], float out[9])
+void rotScaleInverse(const float M[16], float out[9])
 {
   double a[3][3];
   for(int r = 0; r < 3; ++r)

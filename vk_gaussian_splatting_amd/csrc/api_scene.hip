@@ -113,6 +113,7 @@ SceneData::~SceneData()
   for(auto& m : meshes)
     m.release();
   meshTab.release();
+  bvh.release();
 }
 
 void mgs_scene_destroy(MgsScene s)
@@ -137,6 +138,7 @@ void mgs_scene_destroy(MgsScene s)
   s->surf.release();
   s->cmp.release();
   s->mesh.release();
+  s->trace.release();
   s->rs.release();
   s->cpu.release();
   s->binPolicy.release();
@@ -220,7 +222,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   }
   if(sceneBytes)
   {
-    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes();
+    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes() + s->d->bvh.bytes();
     for(const auto& m : s->d->meshes)
       b += m.bytes();
     for(const auto& d : s->d->sets)
@@ -231,7 +233,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   {
     uint64_t b   = s->cpu.distDev.bytes();
     auto     add = [&](auto& buf) { b += buf.bytes(); };
-    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add);
+    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add); s->trace.eachBuffer(add);
     *workingBytes = b;
   }
   return MGS_OK;

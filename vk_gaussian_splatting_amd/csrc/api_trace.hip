@@ -1,0 +1,351 @@
+// api_trace.hip — the traced pipeline's host side: mgs_render_traced, the lazy build of the scene's hierarchy, the hit-count download.
+#include <array>
+#include <cmath>
+#include <memory>
+
+#include "scene_state.h"
+
+void mgs_trace_params_default(MgsTraceParams* p)
+{
+  if(!p)
+    return;
+  std::memset(p, 0, sizeof(*p));
+  p->samples_per_pass         = 18;     // PARTICLES_SPP, parameters.h:218
+  p->max_passes               = 200;    // shaderio.h:269
+  p->min_transmittance        = 0.01f;  // shaderio.h:272
+  p->kernel_adaptive_clamping = 1;      // parameters.h:217
+  p->depth_iso_threshold      = 0.7f;   // depthIsoThresholdRTX, parameters.h:226
+}
+
+static int failTrace(int code, const std::string& msg)
+{
+  setError(msg);
+  return code;
+}
+
+// what needs no device: the ranges of MgsTraceParams and of the MgsFrameParams fields the traced pipeline reads
+static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t)
+{
+  if(t.samples_per_pass < 1 || t.samples_per_pass > 32)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: samples_per_pass must be in [1, 32]");
+  if(t.max_passes < 1)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: max_passes must be at least 1");
+  if(!(t.min_transmittance >= 0.0f && t.min_transmittance < 1.0f))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: min_transmittance must be in [0, 1)");
+  if(!(t.depth_iso_threshold >= 0.0f && t.depth_iso_threshold <= 1.0f))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: depth_iso_threshold must be in [0, 1]");
+  if(t.kernel_adaptive_clamping != 0 && t.kernel_adaptive_clamping != 1)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: kernel_adaptive_clamping must be 0 or 1");
+  if(p->width <= 0 || p->height <= 0 || p->width > 8192 || p->height > 8192)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: width/height must be in [1,8192]");
+  if(p->target_format < MGS_TARGET_RGBA16F || p->target_format > MGS_TARGET_RGBA8)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: target_format must be MGS_TARGET_RGBA16F / RGBA32F / RGBA8");
+  if(p->camera_model < MGS_CAMERA_PINHOLE || p->camera_model > MGS_CAMERA_FISHEYE)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: camera_model out of range");
+  // kernel_min_response = 0 would make the proxy ellipsoid infinite (no finite bound, hence no leaf)
+  if(!(p->alpha_clamp > 1.0f / 255.0f && p->alpha_clamp <= 1.0f) || !(p->kernel_min_response > 0.0f && p->kernel_min_response < 1.0f))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: alpha_clamp must be in (1/255, 1] and kernel_min_response in (0, 1)");
+  if(!(p->alpha_cull_threshold >= 0.0f))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: alpha_cull_threshold must be >= 0");
+  if(p->kernel_degree != 8 && (p->kernel_degree < 0 || p->kernel_degree > 5))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: kernel_degree must be one of 0, 1, 2, 3, 4, 5, 8 (shaderio.h:112-119)");
+  if(p->normal_method != MGS_NORMAL_MAX_DENSITY_PLANE && p->normal_method != MGS_NORMAL_ISO_SURFACE)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: normal_method must be MGS_NORMAL_MAX_DENSITY_PLANE or MGS_NORMAL_ISO_SURFACE");
+  if(p->dof_mode < MGS_DOF_DISABLED || p->dof_mode > MGS_DOF_FIXED_FOCUS || p->frame_sample_id < 0)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: dof_mode / frame_sample_id out of range");
+  if(p->dof_mode != MGS_DOF_DISABLED && (!(p->aperture >= 0.0f) || !std::isfinite(p->aperture) || !(p->focus_dist > 0.0f) || !std::isfinite(p->focus_dist)))
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: depth of field needs a finite aperture >= 0 and a finite focus_dist > 0");
+  if(p->lighting_mode < MGS_LIGHTING_DISABLED || p->lighting_mode > MGS_LIGHTING_INDIRECT)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: lighting_mode out of range");
+  if(p->lighting_mode != MGS_LIGHTING_DISABLED)
+    return failTrace(MGS_ERR_UNSUPPORTED, "trace: lighting of traced frames is out of scope (primary rays only)");
+  if(p->sort_mode == MGS_SORT_STOCHASTIC)
+    return failTrace(MGS_ERR_UNSUPPORTED, "trace: the stochastic trace strategies are out of scope");
+  return MGS_OK;
+}
+
+// everything the hierarchy depends on, as bytes: a traced frame whose signature differs rebuilds
+static std::vector<uint8_t> bvhSignature(const SceneData& d, const TraceProxy& proxy)
+{
+  std::vector<uint8_t> sig;
+  auto put = [&](const void* p, size_t n) { sig.insert(sig.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
+  put(&d.epoch, sizeof(d.epoch));
+  put(&proxy, sizeof(proxy));
+  for(const Instance& I : d.instances)
+  {
+    put(&I.set, sizeof(I.set));
+    put(I.M, sizeof(I.M));
+  }
+  return sig;
+}
+
+// the frame in which the Morton codes are quantised: the union of the instances' transformed set boxes (finite centres only)
+static void sceneBox(const SceneData& d, float lo[3], float invExt[3])
+{
+  double wl[3] = {1e300, 1e300, 1e300}, wh[3] = {-1e300, -1e300, -1e300};
+  std::vector<std::array<float, 6>> setBox(d.sets.size());
+  for(size_t si = 0; si < d.sets.size(); ++si)
+  {
+    std::array<float, 6> b = {3e38f, 3e38f, 3e38f, -3e38f, -3e38f, -3e38f};
+    const auto&          pos = d.sets[si].host->positions;
+    for(size_t i = 0; i + 2 < pos.size(); i += 3)
+      if(std::isfinite(pos[i]) && std::isfinite(pos[i + 1]) && std::isfinite(pos[i + 2]))
+        for(int a = 0; a < 3; ++a)
+        {
+          b[a]     = std::min(b[a], pos[i + a]);
+          b[3 + a] = std::max(b[3 + a], pos[i + a]);
+        }
+    setBox[si] = b;
+  }
+  for(const Instance& I : d.instances)
+  {
+    const auto& b = setBox[I.set];
+    if(b[0] > b[3])
+      continue;
+    for(int corner = 0; corner < 8; ++corner)
+    {
+      const double x = (corner & 1) ? b[3] : b[0], y = (corner & 2) ? b[4] : b[1], z = (corner & 4) ? b[5] : b[2];
+      for(int a = 0; a < 3; ++a)
+      {
+        const double v = (double)I.M[a] * x + (double)I.M[4 + a] * y + (double)I.M[8 + a] * z + (double)I.M[12 + a];
+        if(std::isfinite(v))
+        {
+          wl[a] = std::min(wl[a], v);
+          wh[a] = std::max(wh[a], v);
+        }
+      }
+    }
+  }
+  for(int a = 0; a < 3; ++a)
+  {
+    const double ext = wh[a] - wl[a];
+    lo[a]            = wl[a] <= wh[a] ? (float)wl[a] : 0.0f;
+    invExt[a]        = (ext > 0.0 && std::isfinite(ext)) ? (float)(1.0 / ext) : 0.0f;
+  }
+}
+
+// (re)build the scene's hierarchy on handle s; the frame's constants A are already on the device (s->fb.dArgs)
+static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std::vector<uint8_t>&& sig, float* buildMs)
+{
+  SceneData&      d = *s->d;
+  TraceBvhState&  B = d.bvh;
+  TracePassState& t = s->trace;
+  hipStream_t     st = s->stream;
+  {  // the frames in flight on every context read the hierarchy this call rewrites: the rule of mgs_scene_set_lights
+    std::lock_guard<std::mutex> lk(d.mtx);
+    for(MgsScene_t* h : d.handles)
+      if(h != s)
+        HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  B.built = false;
+  const uint32_t n = d.totalSplats;
+  int            rc;
+  if((rc = B.inst.ensure(1))) return rc;
+  if((rc = B.callerId.ensure(n))) return rc;
+  if((rc = t.keys.ensure(n))) return rc;
+  if((rc = t.vals.ensure(n))) return rc;
+  if((rc = t.leafBox.ensure(2 * (size_t)n))) return rc;
+  if((rc = t.leafCount.ensure(1))) return rc;
+  {
+    auto tab = std::make_unique<TraceInstTable>();
+    std::memset(tab.get(), 0, sizeof(TraceInstTable));
+    std::vector<uint32_t> caller(n);
+    uint32_t              off = 0;
+    for(size_t k = 0; k < d.instances.size(); ++k)
+    {
+      rotScaleInverse(d.instances[k].M, tab->inst[k].rsInv);
+      const DeviceSet& ds = d.sets[d.instances[k].set];
+      for(uint32_t i = 0; i < ds.count; ++i)
+        caller[off + i] = off + ds.newToOld[i];
+      off += ds.count;
+    }
+    HIPCHK(hipMemcpyAsync(B.inst.p, tab.get(), sizeof(TraceInstTable), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(B.callerId.p, caller.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // the sources are locals
+  }
+  HIPCHK(hipEventRecord(t.ev[0], st));
+  BvhBuildArgs L{};
+  L.frame = s->fb.dArgs.p;
+  L.proxy = proxy;
+  sceneBox(d, L.sceneLo, L.sceneInvExt);
+  L.totalSplats = n;
+  L.keys        = t.keys.p;
+  L.vals        = t.vals.p;
+  L.leafBox     = t.leafBox.p;
+  launchBvhLeaves(st, L);
+  HIPCHK(hipGetLastError());
+  // the library's own (key, value) sort: LSD radix, stable, so equal Morton codes keep the order of the global storage ids
+  if((rc = mgs_radix_sort_u32(s, t.keys.p, t.vals.p, n, 0, 32, nullptr))) return rc;
+  HIPCHK(hipMemsetAsync(t.leafCount.p, 0, 4, st));
+  launchBvhCount(st, t.keys.p, n, t.leafCount.p);
+  uint32_t leaves = 0;
+  HIPCHK(hipMemcpyAsync(&leaves, t.leafCount.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  B.nLevels    = 0;
+  B.totalNodes = 0;
+  B.leaves     = leaves;
+  std::memset(B.levelOffset, 0, sizeof(B.levelOffset));
+  std::memset(B.levelCount, 0, sizeof(B.levelCount));
+  for(uint32_t c = leaves; c > 0 && B.nLevels < kBvhMaxLevels;)
+  {  // level 0: the leaves; then ceil(count / 8) until a level has one node
+    B.levelOffset[B.nLevels] = B.totalNodes;
+    B.levelCount[B.nLevels]  = c;
+    B.totalNodes += c;
+    ++B.nLevels;
+    if(c == 1)
+      break;
+    c = (c + 7u) / 8u;
+  }
+  if((rc = B.nodes.ensure(2 * (size_t)std::max<uint32_t>(B.totalNodes, 1u)))) return rc;
+  launchBvhGather(st, t.vals.p, t.leafBox.p, B.nodes.p, leaves);
+  for(int l = 1; l < B.nLevels; ++l)  // one plain kernel per level
+    launchBvhLevel(st, B.nodes.p + 2 * (size_t)B.levelOffset[l - 1], B.levelCount[l - 1], B.nodes.p + 2 * (size_t)B.levelOffset[l], B.levelCount[l]);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(t.ev[1], st));
+  HIPCHK(hipStreamSynchronize(st));  // other contexts may trace over it as soon as this call returns
+  HIPCHK(hipEventElapsedTime(buildMs, t.ev[0], t.ev[1]));
+  t.keys.release(), t.vals.release(), t.leafBox.release();
+  B.proxy     = proxy;
+  B.signature = std::move(sig);
+  B.built     = true;
+  return MGS_OK;
+}
+
+static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out)
+{
+  if(!p)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null params");
+  MgsTraceParams t;
+  if(tp)
+    t = *tp;
+  else
+    mgs_trace_params_default(&t);
+  if(int rc = validateTrace(p, t))  // (before the handle is looked at: the ranges can be checked without a device)
+    return rc;
+  if(!s)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null scene");
+  if(s->occ.depth)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: an occluder is bound (meshes in the traced scene are out of scope); unbind it with "
+                                          "mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
+  SceneData&  d     = *s->d;
+  const bool  empty = d.instances.empty();
+  if(!empty && !d.committed)
+    return failTrace(MGS_ERR_STATE, "mgs_render_traced: call mgs_scene_commit first");
+  HIPCHK(hipSetDevice(s->device));
+  if(!empty)
+    if(int wrc = ensureWorkingSet(s))
+      return wrc;
+  // the frame's constants as the raster pipelines build them: the 3DGUT fields carry the ray's parameters
+  MgsFrameParams q = *p;
+  q.pipeline       = MGS_PIPELINE_3DGUT;
+  q.sort_mode      = MGS_SORT_GPU_RADIX;
+  q.depth_iso_threshold = t.depth_iso_threshold;
+  auto A  = std::make_unique<FrameArgs>();
+  int  rc = buildFrameArgs(s, &q, *A);
+  if(rc)
+    return rc;
+  FrameConst& F = A->f;
+  mat4InverseDouble(p->view, F.lightViewInv);  // viewInverse / projInverse of the rays: host double, rounded once
+  mat4InverseDouble(p->proj, F.lightProjInv);
+  if((rc = ensureFrameImage(s, &q, F))) return rc;
+  TracePassState& ts = s->trace;
+  if(!ts.ev[0])
+    for(auto& e : ts.ev)
+      HIPCHK(hipEventCreate(&e));
+  const size_t pixels = (size_t)F.width * F.height;
+  if((rc = ts.hitCount.ensure(pixels))) return rc;
+  if((rc = ts.ctr.ensure(1))) return rc;
+  if((rc = uploadFrameState(s, *A, s->stream))) return rc;
+  const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
+  float            buildMs = 0.0f;
+  uint32_t         rebuilt = 0;
+  if(!empty)
+  {
+    std::vector<uint8_t> sig = bvhSignature(d, proxy);
+    if(!d.bvh.built || sig != d.bvh.signature)
+    {
+      if((rc = buildBvh(s, *A, proxy, std::move(sig), &buildMs))) return rc;
+      rebuilt = 1;
+    }
+  }
+  hipStream_t st = s->stream;
+  HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
+  HIPCHK(hipEventRecord(ts.ev[2], st));
+  TraceArgs L{};
+  L.frame    = s->fb.dArgs.p;
+  L.nodes    = d.bvh.nodes.p;
+  L.callerId = d.bvh.callerId.p;
+  L.inst     = d.bvh.inst.p;
+  L.ctr      = ts.ctr.p;
+  if(!empty)
+  {
+    std::memcpy(L.levelOffset, d.bvh.levelOffset, sizeof(L.levelOffset));
+    std::memcpy(L.levelCount, d.bvh.levelCount, sizeof(L.levelCount));
+    L.nLevels    = d.bvh.nLevels;
+    L.totalNodes = d.bvh.totalNodes;
+  }
+  L.proxy             = proxy;
+  L.samplesPerPass    = t.samples_per_pass;
+  L.maxPasses         = t.max_passes;
+  L.minTransmittance  = t.min_transmittance;
+  L.depthIsoThreshold = t.depth_iso_threshold;
+  L.image             = s->fb.image.p;
+  L.halfOut           = targetLayout(p->target_format).half;
+  L.hitCount          = ts.hitCount.p;
+  L.outDepth          = F.surfaceOutputs ? s->surf.depth.p : nullptr;
+  L.outId             = F.surfaceOutputs ? s->surf.id.p : nullptr;
+  L.outNormal         = F.surfaceOutputs ? s->surf.normal.p : nullptr;
+  launchTrace(st, L, F, d.shFormat);
+  if(F.temporalSampling)
+    launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.halfOut);
+  HIPCHK(hipEventRecord(ts.ev[3], st));
+  HIPCHK(hipGetLastError());
+  // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare)
+  LastFrame& last = s->last;
+  last.params                 = *p;
+  last.params.strip_row_begin = F.stripRow0;
+  last.params.strip_row_end   = F.stripRow1;
+  last.have         = true;
+  last.timed        = false;
+  last.wasSortOnly  = false;
+  last.listsPartial = true;  // no bin lists belong to this frame (mgs_frame_row_costs: MGS_ERR_STATE)
+  ts.w    = F.width;
+  ts.h    = F.height;
+  ts.have = true;
+  if(out)
+  {
+    std::memset(out, 0, sizeof(*out));
+    TraceCounters hc{};
+    HIPCHK(hipMemcpyAsync(&hc, ts.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out->leaves          = empty ? 0 : d.bvh.leaves;
+    out->nodes           = empty ? 0 : d.bvh.totalNodes;
+    out->node_visits     = hc.nodeVisits;
+    out->candidate_tests = hc.candidateTests;
+    out->accepted_hits   = hc.acceptedHits;
+    out->max_passes_used = hc.maxPassesUsed;
+    out->bvh_rebuilt     = rebuilt;
+    out->build_ms        = buildMs;
+    HIPCHK(hipEventElapsedTime(&out->trace_ms, ts.ev[2], ts.ev[3]));
+  }
+  return MGS_OK;
+}
+int mgs_render_traced(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out)
+{
+  return guarded("mgs_render_traced", [&] { return mgs_render_traced_impl(s, p, tp, out); });
+}
+
+int mgs_trace_download_hit_counts(MgsScene s, uint32_t* dst, size_t count)
+{
+  if(!s || !dst)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_hit_counts: null argument");
+  if(!s->trace.have)
+    return failTrace(MGS_ERR_STATE, "mgs_trace_download_hit_counts: no traced frame yet");
+  const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
+  if(count < n)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_hit_counts: destination too small");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipMemcpyAsync(dst, s->trace.hitCount.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return MGS_OK;
+}

@@ -281,6 +281,66 @@ struct MeshPassArgs
   uint32_t*          outPrim;
 };
 
+// ---- ray-traced splats (k_bvh.hip, k_trace.hip, api_trace.hip) ----
+// The hierarchy is an implicit complete 8-ary tree: level 0 holds the leaves (one per traceable particle, sorted by the 30-bit Morton
+// code of the leaf centre), node i of level L + 1 bounds the children [8i, 8i + 8) of level L.  A node is two float4: (lo.xyz, w) and
+// (hi.xyz, 0); a leaf's lo.w holds the particle's global STORAGE id as bits.  All levels live in one array.
+constexpr int      kBvhMaxLevels = 11;           // 8^10 = 2^30 leaves, the library's limit of global splats
+constexpr uint32_t kTraceInvalid = 0xFFFFFFFFu;  // PAYLOAD_INVALID_ID
+struct TraceInst
+{
+  float rsInv[9];  // transformRotScaleInverse = inverse(mat3(transform)), host double rounded once, glm column-major
+  float pad[3];
+};
+struct TraceInstTable
+{
+  TraceInst inst[kMaxInstances];
+};
+// what the leaf kernel and the traversal need to agree on: the proxy ellipsoid's threshold (particle_as_build.comp.slang:74-87)
+struct TraceProxy
+{
+  float   kernelMinResponse;
+  int32_t adaptiveClamping;
+  int32_t kernelDegree;
+  float   alphaCull;
+};
+struct BvhBuildArgs
+{
+  const FrameArgs* frame;       // instances (transforms, set buffers) of this frame's upload
+  TraceProxy       proxy;
+  float            sceneLo[3], sceneInvExt[3];  // Morton quantisation frame (host: the instances' transformed set boxes)
+  uint32_t         totalSplats;
+  uint32_t*        keys;        // [totalSplats] Morton code, kTraceInvalid = no leaf
+  uint32_t*        vals;        // [totalSplats] global storage id
+  float4*          leafBox;     // [2 * totalSplats]
+};
+struct TraceCounters
+{
+  unsigned long long nodeVisits, candidateTests, acceptedHits;
+  uint32_t           maxPassesUsed, pad;
+};
+// what the traversal kernel receives by value
+struct TraceArgs
+{
+  const FrameArgs*      frame;
+  const float4*         nodes;
+  const uint32_t*       callerId;   // [totalSplats] storage id -> caller's id (tie order)
+  const TraceInstTable* inst;
+  TraceCounters*        ctr;
+  uint32_t              levelOffset[kBvhMaxLevels], levelCount[kBvhMaxLevels];
+  int32_t               nLevels;    // 0: no leaf at all
+  uint32_t              totalNodes;
+  TraceProxy            proxy;
+  int32_t               samplesPerPass, maxPasses;
+  float                 minTransmittance, depthIsoThreshold;
+  void*                 image;
+  int32_t               halfOut;
+  uint32_t*             hitCount;   // [height][width]
+  float*                outDepth;   // side outputs, null unless surface_outputs
+  uint32_t*             outId;
+  float4*               outNormal;
+};
+
 // the caller's geometry as the compositors' launchers receive it
 struct Occluder
 {

@@ -112,6 +112,16 @@ void launchLight(hipStream_t stream, const LightArgs& a, int halfOut);
 // the mesh pass (k_mesh.hip): clear, set-up + small triangles, large triangles, resolve + shade
 // (totalTris: the grid of the set-up stage; largeBlocks: the fixed grid that strides over the device-side work list)
 void launchMeshPass(hipStream_t stream, const MeshPassArgs& a, uint32_t totalTris, uint32_t largeBlocks);
+// temporal accumulation of the handle's strip (api_frame.hip: k_post_accumulate), for frames made outside the frame graph
+void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* accum, void* image, int halfOut);
+// the hierarchy of the traced pipeline (k_bvh.hip): leaf bounds + Morton codes; the count of valid leaves behind the sort; the
+// gather of the sorted leaves into level 0; one plain kernel per upper level
+void launchBvhLeaves(hipStream_t stream, const BvhBuildArgs& a);
+void launchBvhCount(hipStream_t stream, const uint32_t* sortedKeys, uint32_t n, uint32_t* countOut);
+void launchBvhGather(hipStream_t stream, const uint32_t* sortedVals, const float4* leafBox, float4* level0, uint32_t nLeaves);
+void launchBvhLevel(hipStream_t stream, const float4* below, uint32_t nBelow, float4* level, uint32_t nLevel);
+// the traversal (k_trace.hip): one ray per lane, a wave64 = an 8 x 8 pixel tile
+void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 
 }  // namespace mgs

@@ -223,6 +223,24 @@ struct CpuSorter
   void shutdown();
 };
 
+// The hierarchy of the traced pipeline (mgs_render_traced; api_trace.hip, k_bvh.hip): all instances' particles in world space.  It
+// belongs to the SCENE and is shared by its frame contexts; rebuilt lazily by the next traced frame whose inputs (`signature`: the
+// commit epoch, the instances and their transforms, the proxy's parameters) differ from what it was built for.
+struct TraceBvhState
+{
+  DevBuf<float4>         nodes;     // all levels, two float4 per node (device_types.h)
+  DevBuf<uint32_t>       callerId;  // [totalSplats] storage id -> caller's id
+  DevBuf<TraceInstTable> inst;
+  uint32_t               levelOffset[kBvhMaxLevels] = {}, levelCount[kBvhMaxLevels] = {};
+  int                    nLevels = 0;
+  uint32_t               totalNodes = 0, leaves = 0;
+  TraceProxy             proxy{};
+  std::vector<uint8_t>   signature;
+  bool                   built = false;
+  uint64_t bytes() const { return nodes.bytes() + callerId.bytes() + inst.bytes(); }
+  void     release() { nodes.release(), callerId.release(), inst.release(); built = false; }
+};
+
 // What a commit produces: the resident splat buffers and the instance list.  ONE copy per scene, shared read-only by the scene
 // handle and every frame context created from it — the reference likewise keeps one copy of the splat buffers however many
 // frames are in flight, which is why processUpdateRequests waits for the device before it touches them
@@ -246,6 +264,7 @@ struct SceneData
   std::vector<MeshInstance> meshInstances;
   std::unique_ptr<MeshTable> meshHost;
   DevBuf<MeshTable>      meshTab;
+  TraceBvhState          bvh;            // mgs_render_traced
   uint64_t               epoch = 0;      // bumped by every commit: a context re-sizes its working set when it lags
   std::mutex             mtx;            // guards `handles`
   std::vector<MgsScene_t*> handles;      // the owning scene and its live frame contexts
@@ -449,6 +468,28 @@ struct MeshPassState
   }
 };
 
+// the traced pipeline's per-handle state (mgs_render_traced): hit counts and counters of the last traced frame, the scratch of a
+// hierarchy build this handle ran (freed when the build is done), the events around build and frame
+struct TracePassState
+{
+  DevBuf<uint32_t>      hitCount;
+  DevBuf<TraceCounters> ctr;
+  DevBuf<uint32_t>      keys, vals, leafCount;
+  DevBuf<float4>        leafBox;
+  int                   w = 0, h = 0;
+  bool                  have = false;
+  hipEvent_t            ev[4] = {};
+  template <class F>
+  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); }
+  void release()
+  {
+    eachBuffer([](auto& b) { b.release(); });
+    for(auto& e : ev)
+      if(e) (void)hipEventDestroy(e);
+    ev[0] = ev[1] = ev[2] = ev[3] = nullptr;
+  }
+};
+
 // scratch of the stand-alone sort (mgs_radix_sort_u32): owned by the handle (its device, its stream)
 struct SortScratch
 {
@@ -580,6 +621,7 @@ struct MgsScene_t
   SurfaceOutputs  surf;
   CompareState    cmp;
   MeshPassState   mesh;
+  TracePassState  trace;
   SortScratch     rs;
   CommState       comm;
   CpuSortState    cpu;
@@ -597,6 +639,9 @@ int  buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A);       //
 bool directBinning(const FrameConst& F);                                      // api_frameargs.hip
 bool binPolicyEligible(const MgsFrameParams* p);                              // api_frameargs.hip
 int  ensureFrameState(MgsScene s);                                            // api_frame.hip
+int  ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F);  // api_frame.hip: image, side outputs, accumulator
+void mat4InverseDouble(const float m[16], float out[16]);                     // api_frameargs.hip
+void rotScaleInverse(const float M[16], float out[9]);                        // api_mesh.hip
 int  uploadFrameState(MgsScene s, const FrameArgs& A, hipStream_t st);        // api_frame.hip
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip

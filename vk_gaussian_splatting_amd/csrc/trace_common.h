@@ -1,0 +1,59 @@
+// trace_common.h — what the hierarchy build (k_bvh.hip) and the traversal (k_trace.hip) must compute alike: the particle as the
+// 3DGRT shaders fetch it, the generalised-Gaussian response and the proxy ellipsoid's threshold and radius.
+#pragma once
+#include "kernels_common.h"
+
+namespace mgs {
+
+// ThreedgrtParticle (threedgrt.h.slang:42-48): centre, exp(scale), rotation of the normalised quaternion.  R is the rotation matrix
+// in row-major order (quatToMat3Transpose read as rows, quaternions.h.slang:56-73): canonical = diag(1/s) R^T (x - p).
+__device__ __forceinline__ void loadParticle(const InstanceConst& I, uint32_t li, float (&R)[9], float (&s)[3], float (&p)[3])
+{
+  p[0] = I.centers[3 * (size_t)li];
+  p[1] = I.centers[3 * (size_t)li + 1];
+  p[2] = I.centers[3 * (size_t)li + 2];
+  s[0] = expf(I.scales[3 * (size_t)li]);
+  s[1] = expf(I.scales[3 * (size_t)li + 1]);
+  s[2] = expf(I.scales[3 * (size_t)li + 2]);
+  const float4 rq = *reinterpret_cast<const float4*>(I.rotations + 4 * (size_t)li);  // (w,x,y,z)
+  const float  ql = sqrtf(rq.x * rq.x + rq.y * rq.y + rq.z * rq.z + rq.w * rq.w);
+  const float  w = rq.x / ql, x = rq.y / ql, y = rq.z / ql, z = rq.w / ql;
+  const float  xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
+  R[0] = 1.0f - 2.0f * (yy + zz); R[1] = 2.0f * (xy - wz);        R[2] = 2.0f * (xz + wy);
+  R[3] = 2.0f * (xy + wz);        R[4] = 1.0f - 2.0f * (xx + zz); R[5] = 2.0f * (yz - wx);
+  R[6] = 2.0f * (xz - wy);        R[7] = 2.0f * (yz + wx);        R[8] = 1.0f - 2.0f * (xx + yy);
+}
+
+// particleRayMaxKernelResponse<KERNEL_DEGREE> (threedgrt.h.slang:83-127); its argument is the SQUARED canonical distance
+__device__ __forceinline__ float kernelResponse(int degree, float dist2)
+{
+  switch(degree)
+  {
+    case 8: return __expf(-0.000685871056241f * (dist2 * dist2) * (dist2 * dist2));
+    case 5: return __expf(-0.0185185185185f * dist2 * dist2 * sqrtf(dist2));
+    case 4: return __expf(-0.0555555555556f * dist2 * dist2);
+    case 3: return __expf(-0.166666666667f * dist2 * sqrtf(dist2));
+    case 1: return __expf(-1.5f * sqrtf(dist2));
+    case 0: return fmaxf(1.0f + -0.329630334487f * sqrtf(dist2), 0.0f);
+    default: return __expf(-0.5f * dist2);
+  }
+}
+
+// the response the proxy ellipsoid is circumscribed around (kernelScale, particle_as_build.comp.slang:74-78)
+__device__ __forceinline__ float proxyThreshold(const TraceProxy& P, float density)
+{
+  return fminf(P.adaptiveClamping ? P.kernelMinResponse / density : P.kernelMinResponse, 0.97f);
+}
+
+// the canonical radius at which the response falls to `thr`: the inverse of kernelResponse in the distance (degree n >= 1:
+// exp(s d^n) with s = -4.5 / 3^n; degree 0: 1 + s0 d)
+__device__ __forceinline__ float proxyRadius(const TraceProxy& P, float thr)
+{
+  if(P.kernelDegree == 0)
+    return (1.0f - thr) / 0.329630334487f;
+  const float n = (float)P.kernelDegree;
+  const float s = -4.5f / powf(3.0f, n);
+  return powf(logf(thr) / s, 1.0f / n);
+}
+
+}  // namespace mgs
