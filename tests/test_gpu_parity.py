@@ -1199,6 +1199,24 @@ def test_frame_statistics_are_consistent(scene_small):
     assert a.scanned_entries <= a.tile_pairs * 64 * 4
 
 
+def test_escape_count_follows_the_ride(scene_small):
+    """mgs_frame_stats: escape_count counts the sorted splats whose bin rectangle rode through the key sort as the escape code —
+    deterministic, at most every sorted splat — and is every sorted splat where nothing rides (the CPU sort)"""
+    scene, sc = scene_small
+    W, H = 640, 360
+    eye = synth.orbit_pose(5)
+    V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, W, H)
+    p = capi.default_params(W, H)
+    capi.set_camera(p, V, P, eye)
+    a = scene.render(p, want_stats=True)
+    b = scene.render(p, want_stats=True)
+    assert a.error_flags == 0 and a.escape_count == b.escape_count
+    assert 0 <= a.escape_count <= a.sorted_count
+    p.sort_mode, p.cpu_sort_blocking = capi.SORT_CPU_ASYNC, 1
+    c = scene.render(p, want_stats=True)
+    assert c.error_flags == 0 and c.sorted_count > 0 and c.escape_count == c.sorted_count
+
+
 def test_bench_prints_one_strict_json_line_with_the_contract_keys():
     """bench.py is the driver's measurement hook: one strict-JSON line carrying the contract's keys"""
     import json

@@ -205,16 +205,19 @@ void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* ac
 }
 }  // namespace mgs
 
-// the frame image (and side outputs, accumulator) of a frame that is made outside the frame graph (mgs_render_traced); captured
-// frames that point at a buffer that moved are dropped, as ensureFrameBuffers does
-int ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F)
+// The frame image, side outputs and accumulator of a frame; one made by the frame graph (mgs_render) also sizes its range table
+// and names the occluder depth it is tested against, one made outside it (mgs_render_traced) has neither.  Captured frames that
+// point at a buffer that moved are dropped.
+int ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F, uint32_t rangeEntries, const float* occDepth)
 {
   FrameBuffers& fb = s->fb;
   int           rc = MGS_OK;
   const size_t  pixels  = (size_t)F.width * F.height;
   fb.imageRowBytes      = (size_t)F.width * targetLayout(p->target_format).pixelBytes;
   fb.imageBytes         = fb.imageRowBytes * (size_t)F.height;
-  const void* before[5] = {fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
+  const void* before[6] = {fb.ranges.p, fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
+  if(rangeEntries)
+    if((rc = fb.ranges.ensure(rangeEntries))) return rc;
   if(fb.image.n < fb.imageBytes)
   {
     if((rc = fb.image.ensure(fb.imageBytes))) return rc;
@@ -229,11 +232,11 @@ int ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F)
   if(F.temporalSampling)
     if((rc = fb.accum.ensure(pixels))) return rc;
   s->surf.have         = F.surfaceOutputs != 0;
-  s->surf.lastOccDepth = nullptr;
+  s->surf.lastOccDepth = occDepth;
   s->surf.lastOccGone  = false;
-  const void* after[5] = {fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
+  const void* after[6] = {fb.ranges.p, fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
   if(std::memcmp(before, after, sizeof(before)) != 0 && !s->graphs.map.empty())
-  {
+  {  // a buffer moved: captured frames point at the old one
     HIPCHK(hipStreamSynchronize(s->stream));
     s->graphs.drop();
   }
@@ -247,11 +250,9 @@ int BinPolicy::apply()
   if(!pending || (frames & 31u) != 24u)
     return MGS_OK;
   HIPCHK(hipEventSynchronize(ev));  // (eight frames of this context's stream ago: long done)
-  uint64_t scanned = 0;
-  for(uint32_t i = 0; i < kFrameStatSlots; ++i)
-    scanned += host[32u * i + 1u];
-  const uint64_t D = host[4];
-  pending          = false;
+  const FrameStatTotals tot     = foldFrameStats(host);
+  const uint64_t        scanned = tot.scanned, D = tot.listEntries;
+  pending                       = false;
   if(D > 0)
   {
     lastRatio = (float)((double)scanned / ((double)D * (double)sampledRegions));
@@ -266,13 +267,13 @@ int BinPolicy::apply()
   return MGS_OK;
 }
 // every 32nd eligible frame leaves a copy of its statistics lines (4 KB) for the frame eight later
-int BinPolicy::sample(const FrameConst& F, const uint32_t* statLines, hipStream_t st)
+int BinPolicy::sample(const FrameConst& F, const FrameStatLine* statLines, hipStream_t st)
 {
   if((frames & 31u) == 16u && !pending)
   {
     if(!host)
     {
-      if(hipHostMalloc((void**)&host, kFrameStatSlots * 32u * sizeof(uint32_t)) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+      if(hipHostMalloc((void**)&host, kFrameStatSlots * sizeof(FrameStatLine)) != hipSuccess || hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
       {
         (void)hipGetLastError();
         if(host) (void)hipHostFree(host);
@@ -281,7 +282,7 @@ int BinPolicy::sample(const FrameConst& F, const uint32_t* statLines, hipStream_
     }
     if(host)
     {
-      HIPCHK(hipMemcpyAsync(host, statLines, kFrameStatSlots * 32u * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(host, statLines, kFrameStatSlots * sizeof(FrameStatLine), hipMemcpyDeviceToHost, st));
       HIPCHK(hipEventRecord(ev, st));
       pending        = true;
       sampledFine    = (F.binShiftX == 3 && F.binShiftY == 3) ? 1 : 0;
@@ -361,7 +362,7 @@ struct FramePass
   uint32_t              nTiles;  // lists (and ranges) exist per bin
 };
 
-// the buffers this frame needs beyond the working set; captured frames that point at one that moved are dropped
+// the buffers this frame needs beyond the working set
 static int ensureFrameBuffers(const FramePass& fp)
 {
   MgsScene          s  = fp.s;
@@ -374,24 +375,6 @@ static int ensureFrameBuffers(const FramePass& fp)
   }
   if(fp.lit)
     if((rc = ensureLightTable(*s->d))) return rc;
-  const size_t pixels    = (size_t)F.width * F.height;
-  fb.imageRowBytes       = (size_t)F.width * targetLayout(fp.p->target_format).pixelBytes;
-  fb.imageBytes          = fb.imageRowBytes * (size_t)F.height;
-  const void* before[6] = {fb.ranges.p, fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
-  if((rc = fb.ranges.ensure(std::max<uint32_t>(fp.nTiles, 256u)))) return rc;
-  if(fb.image.n < fb.imageBytes)
-  {
-    if((rc = fb.image.ensure(fb.imageBytes))) return rc;
-    HIPCHK(hipMemsetAsync(fb.image.p, 0, fb.imageBytes, s->stream));
-  }
-  if(F.surfaceOutputs)
-  {
-    if((rc = s->surf.depth.ensure(pixels))) return rc;
-    if((rc = s->surf.id.ensure(pixels))) return rc;
-    if((rc = s->surf.normal.ensure(pixels))) return rc;
-  }
-  if(F.temporalSampling)
-    if((rc = fb.accum.ensure(pixels))) return rc;
   if(!directBinning(F) && fb.pairKey0.n < fb.pairCapacity)
   {  // first frame on the record + pair-sort path (> 256 bins, or forced): its buffers
     const uint64_t cap = fb.pairCapacity;
@@ -401,16 +384,7 @@ static int ensureFrameBuffers(const FramePass& fp)
     if((rc = fb.chunkStart.ensure(cap / kPart + 4))) return rc;
     if((rc = fb.splatOffset.ensure(s->d->totalSplats))) return rc;
   }
-  s->surf.have         = F.surfaceOutputs != 0;
-  s->surf.lastOccDepth = fp.occ.depth;
-  s->surf.lastOccGone  = false;
-  const void* after[6] = {fb.ranges.p, fb.image.p, s->surf.depth.p, s->surf.id.p, s->surf.normal.p, fb.accum.p};
-  if(std::memcmp(before, after, sizeof(before)) != 0 && !s->graphs.map.empty())
-  {  // a buffer moved: captured frames point at the old one
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->graphs.drop();
-  }
-  return MGS_OK;
+  return ensureFrameImage(s, fp.p, F, std::max<uint32_t>(fp.nTiles, 256u), fp.occ.depth);
 }
 
 // what both project kernels receive; mgs_sort_keys runs the 3DGS one with full = false over the whole frame
@@ -477,7 +451,7 @@ static int issueBinning(const FramePass& fp, hipStream_t st, hipEvent_t binEv)
     L.maxSplats     = s->d->totalSplats;
     L.binHist       = fb.partHist.p;
     L.pStride       = fb.pStride;
-    L.binTotal      = &planP->ghist[0][0];
+    L.tables        = directBinTables(planP);
     L.binList       = fb.pairVal1.p;
     L.ranges        = fb.ranges.p;
     L.ctr           = fb.ctr.p;
@@ -520,6 +494,11 @@ static int issueBinning(const FramePass& fp, hipStream_t st, hipEvent_t binEv)
   L.maxElems  = fb.pairCapacity;
   L.beginBit  = 0;
   L.endBit    = pairSortBits((int)fp.nTiles);
+  if(L.endBit > kPairSortMaxBits)
+  {  // (cannot happen: at most 256 x 256 bins.  A third pass would leave its totals where the compositors read binOrderValid)
+    setError("frame: the pair sort's key exceeds 16 bits");
+    return MGS_ERR_STATE;
+  }
   const bool onePass = L.endBit <= 8;  // <= 256 bins: the digit histogram IS the range table
   L.ranges    = onePass ? fb.ranges.p : nullptr;
   launchRadixSort(st, L);
@@ -654,8 +633,11 @@ static void recordLastFrame(const FramePass& fp, bool timed)
   last.timed        = timed;
   last.wasSortOnly  = false;
   last.listsPartial = false;
-  const int lr[5] = {F.rideShift, rideCodeBits(F), F.binsX, F.binsY, fp.cpuMode ? 0 : 1};
-  std::memcpy(last.ride, lr, sizeof(lr));
+  last.rideShift = F.rideShift;
+  last.codeBits  = rideCodeBits(F);
+  last.binsX     = F.binsX;
+  last.binsY     = F.binsY;
+  last.gpuSorted = !fp.cpuMode;
   last.binShift[0] = F.binShiftX;
   last.binShift[1] = F.binShiftY;
   if(timed)
@@ -709,7 +691,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   if((rc = uploadFrameState(s, A, s->stream))) return rc;
   if((rc = launchFrame(fp, timed))) return rc;
   if(policyFrame && directBinning(F))
-    if((rc = s->binPolicy.sample(F, &s->fb.plans.p->keys.ghist[0][0], s->stream))) return rc;
+    if((rc = s->binPolicy.sample(F, frameStatLines(&s->fb.plans.p->keys), s->stream))) return rc;
   // the counters stay on the device; mgs_frame_stats fetches them when somebody asks (two API calls per frame less
   // on the submitting thread, which spends ~6 us per call)
   HIPCHK(hipGetLastError());
@@ -786,22 +768,16 @@ int mgs_frame_stats(MgsScene s, MgsFrameOut* out)
   std::memset(out->stage_ms, 0, sizeof(out->stage_ms));
   out->rgba_device   = s->fb.image.p;
   out->rgba_bytes    = s->fb.imageBytes;
-  out->frustum_count = s->fb.hCtr->frustumCount;
-  out->sorted_count  = s->fb.hCtr->sortedCount;
-  out->tile_pairs    = s->fb.hCtr->pairCount;
-  out->error_flags   = s->fb.hCtr->errorFlags;
-  out->shaded_count  = 0;
-  out->scanned_entries = 0;
-  out->escape_count  = 0;
-  for(uint32_t i = 0; i < kFrameStatSlots; ++i)
-    {  // (sort_plan.h: frameStatSlot — the kernels' counts live in the keys plan's histogram rows, one 128-byte line per slot; after
-       //  mgs_sort_keys the plans were fetched by that call)
-      out->frustum_count += (&s->fb.hPlans->keys.ghist[0][0])[32u * i + 2u];
-      out->shaded_count += (&s->fb.hPlans->keys.ghist[0][0])[32u * i];
-      out->scanned_entries += (&s->fb.hPlans->keys.ghist[0][0])[32u * i + 1u];
-      out->escape_count += (&s->fb.hPlans->keys.ghist[0][0])[32u * i + 3u];
-    }
-  if(!s->last.wasSortOnly && s->last.ride[0] == 0)
+  // (the kernels' counts live on the statistics lines, frame_state.h; after mgs_sort_keys the plans were fetched by that call)
+  const FrameStatTotals tot = foldFrameStats(frameStatLines(&s->fb.hPlans->keys));
+  out->frustum_count   = tot.survivors;
+  out->sorted_count    = s->fb.hCtr->sortedCount;
+  out->tile_pairs      = s->fb.hCtr->pairCount;
+  out->error_flags     = s->fb.hCtr->errorFlags;
+  out->shaded_count    = tot.staged;
+  out->scanned_entries = tot.scanned;
+  out->escape_count    = tot.escapes;
+  if(!s->last.wasSortOnly && s->last.rideShift == 0)
     out->escape_count = out->sorted_count;  // nothing rode through the sort: every sorted splat's rectangle was stored and gathered by id
   if(s->last.timed && !s->last.wasSortOnly)
   {
@@ -956,7 +932,7 @@ static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, si
   std::vector<uint32_t> rect(s->d->totalSplats);
   HIPCHK(hipMemcpy(rec.data(), s->fb.rec.p, (size_t)s->d->totalSplats * sizeof(SplatRec), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(rect.data(), s->fb.rect.p, (size_t)s->d->totalSplats * 4, hipMemcpyDeviceToHost));
-  if(rectOut && s->last.ride[0] != 0 && s->last.ride[4] != 0)
+  if(rectOut && s->last.rideShift != 0 && s->last.gpuSorted)
   {  // the rectangles rode through the key sort as codes (kernels_common.h: rideEncode): rect[id] holds the escapes only, the
      // others are rebuilt from the code at the id's sorted position (they used to come back stale)
     FrameCounters c;
@@ -969,8 +945,8 @@ static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, si
       HIPCHK(hipMemcpy(sortedIds.data(), s->fb.idsA.p, (size_t)n * 4, hipMemcpyDeviceToHost));
       HIPCHK(hipMemcpy(codes.data(), s->fb.sortedCode16.p, (size_t)n * 2, hipMemcpyDeviceToHost));
     }
-    const int      bx = s->last.ride[2], by = s->last.ride[3], nb = bx * by;
-    const uint32_t escape = (1u << s->last.ride[1]) - 1u;
+    const int      bx = s->last.binsX, by = s->last.binsY, nb = bx * by;
+    const uint32_t escape = (1u << s->last.codeBits) - 1u;
     const uint32_t base[4] = {0u, (uint32_t)nb, (uint32_t)(nb + (bx - 1) * by), (uint32_t)(nb + (bx - 1) * by + bx * (by - 1))};
     for(uint32_t e = 0; e < n; ++e)
     {

@@ -177,6 +177,16 @@ int cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking)
   return MGS_OK;
 }
 
+// what mgs_sort_keys leaves for the queries behind it, whichever sorter ran
+static int recordSortOnly(MgsScene s, const MgsFrameParams* p, const MgsSortOut* out)
+{
+  s->last.sort        = *out;
+  s->last.wasSortOnly = true;
+  s->last.have        = true;
+  s->last.params      = *p;
+  return MGS_OK;
+}
+
 int mgs_sort_keys(MgsScene s, const MgsFrameParams* p, MgsSortOut* out)
 {
   if(!s || !p || !out)
@@ -201,11 +211,7 @@ int mgs_sort_keys(MgsScene s, const MgsFrameParams* p, MgsSortOut* out)
     out->count   = (uint32_t)s->cpu.indices.size();
     out->key_ms  = s->last.sort.key_ms;
     out->sort_ms = s->last.sort.sort_ms;
-    s->last.sort  = *out;
-    s->last.wasSortOnly = true;
-    s->last.have       = true;
-    s->last.params      = *p;
-    return MGS_OK;
+    return recordSortOnly(s, p, out);
   }
   FrameArgs A;
   int       rc = buildFrameArgs(s, p, A);
@@ -242,11 +248,7 @@ int mgs_sort_keys(MgsScene s, const MgsFrameParams* p, MgsSortOut* out)
   out->passes  = s->fb.hPlans->keys.passesRun;
   out->reserved[0] = s->fb.hPlans->os.remapOn;     // pass 2 sorted on the rank of key >> 16
   out->reserved[1] = s->fb.hPlans->os.remapCount;  // occurring values of key >> 16
-  s->last.sort  = *out;
-  s->last.wasSortOnly = true;
-  s->last.have       = true;
-  s->last.params      = *p;
-  return MGS_OK;
+  return recordSortOnly(s, p, out);
 }
 
 int mgs_sort_download(MgsScene s, uint32_t* keys, uint32_t* ids, uint32_t capacity)

@@ -377,16 +377,4 @@ struct alignas(16) GutRec
 };
 static_assert(sizeof(GutRec) == 96, "six 16-byte vectors");
 
-// device-resident counters of one frame
-struct FrameCounters
-{
-  uint32_t frustumCount;   // (zero since round 5: the dist stage's survivors are counted in the statistics lines, sort_plan.h: frameStatSlot)
-  uint32_t sortedCount;    // V: elements handed to the radix sort
-  uint32_t pairCount;      // D: (tile, splat) records
-  uint32_t errorFlags;
-  // (the compositors' statistics — staged records, scanned entries — and the project kernels' frustum survivors are counted on 32
-  //  lines of their own since round 5: sort_plan.h, frameStatSlot)
-  uint32_t pad[27];
-};
-
 }  // namespace mgs

@@ -139,13 +139,13 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const std::con
   int       ord      = (seq / perBin) * 8 + (int)(blockIdx.x & 7);  // bin ordinal
   const int inBin    = seq % perBin;
   // (compositeRegionGrid of composite_common.h is the grid of this mapping; k_composite_gut2 maps its workgroups the same way)
-  const bool ordered = plan->ghist[2][0] != 0u;  // the binning stage ranked the bins by list length (all bins of the frame)
+  const bool ordered = directBinTables(plan)->binOrderValid != 0u;  // the binning stage ranked the bins by list length (all bins of the frame)
   int cx2, ty;
   if(ordered)
   {
     if(ord >= F.binsX * F.binsY)
       return;
-    const int b = (int)plan->ghist[1][ord];
+    const int b = (int)directBinTables(plan)->binOrder[ord];
     cx2         = (b % F.binsX) * bw + inBin % bw;
     ty          = (b / F.binsX) * bh + inBin / bw;
   }
@@ -765,9 +765,9 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const std::con
 #endif
   if(t == 0)
   {  // frame statistics (mgs_frame_stats): two fire-and-forget adds per workgroup
-    uint32_t* stat = frameStatSlot(plan, blockIdx.x >> 3);  // (sort_plan.h: one 128-byte line per slot)
-    atomicAdd(&stat[0], statStaged);
-    atomicAdd(&stat[1], statScanned);
+    FrameStatLine* stat = frameStatLineFromPairs(plan, blockIdx.x >> 3);
+    atomicAdd(&stat->staged, statStaged);
+    atomicAdd(&stat->scanned, statScanned);
     // the bin's longest region, for the next frame of this context: regions that never saturate take twice as long as the
     // others, and starting them late is the kernel's tail; which ones they are is the same from one frame to the next
     atomicMax(&F.binCost[bin], (uint32_t)(wall_clock64() - costT0) + 1u);

@@ -371,9 +371,9 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
   }
   if(t == 0)
   {
-    uint32_t* stat = frameStatSlot(plan, blockIdx.x >> 3);  // (sort_plan.h: one 128-byte line per slot)
-    atomicAdd(&stat[1], statScanned);
-    atomicAdd(&stat[0], statStaged);
+    FrameStatLine* stat = frameStatLineFromPairs(plan, blockIdx.x >> 3);
+    atomicAdd(&stat->scanned, statScanned);
+    atomicAdd(&stat->staged, statStaged);
   }
   if(!inside)
     return;
@@ -454,13 +454,13 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
   const int seq      = (int)(blockIdx.x >> 3);
   const int ord      = (seq / perBin) * 8 + (int)(blockIdx.x & 7);  // bin ordinal
   const int inBin    = seq % perBin;
-  const bool ordered = plan->ghist[2][0] != 0u;
+  const bool ordered = directBinTables(plan)->binOrderValid != 0u;
   int cx2, ty;
   if(ordered)
   {
     if(ord >= F.binsX * F.binsY)
       return;
-    const int b = (int)plan->ghist[1][ord];
+    const int b = (int)directBinTables(plan)->binOrder[ord];
     cx2         = (b % F.binsX) * bw + inBin % bw;
     ty          = (b / F.binsX) * bh + inBin / bw;
   }
@@ -655,9 +655,9 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
   }
   if(t == 0)
   {
-    uint32_t* stat = frameStatSlot(plan, blockIdx.x >> 3);  // (sort_plan.h: one 128-byte line per slot)
-    atomicAdd(&stat[1], statScanned);
-    atomicAdd(&stat[0], statStaged);
+    FrameStatLine* stat = frameStatLineFromPairs(plan, blockIdx.x >> 3);
+    atomicAdd(&stat->scanned, statScanned);
+    atomicAdd(&stat->staged, statStaged);
   }
 #pragma unroll
   for(int h = 0; h < 2; ++h)

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void k_dbin_count(const uint32_t* __restrict__
   const int       t = threadIdx.x, lane = laneId(), w = t >> 6;
   const uint32_t* ids = plan->finalSel ? idsY : idsX;
   uint32_t        r[kDbCntMul][kDbRounds];
-  const uint32_t  ride = plan->reserved[0];
+  const uint32_t  ride = plan->rideInfo;
   const uint32_t  eW   = (uint32_t)w * (kDbRounds * 64) + (uint32_t)lane;
   if(ride != 0u)
   {  // the rectangles rode through the key sort as codes above the ids and lie in sorted order (kernels_common.h: rideEncode);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_dbin_count(const uint32_t* __restrict__
       for(int i = 0; i < kDbRounds; ++i)
         r[c][i] = (v[c][i] == escape) ? rect[id[c][i]] : rideDecode(v[c][i], dec);
     // how many rectangles did NOT fit a code (MgsFrameOut::escape_count: the only rect[id] stores / gathers of the frame): one
-    // fire-and-forget atomic per wave on the frame's statistics lines (sort_plan.h: frameStatSlot, word 3)
+    // fire-and-forget atomic per wave on the frame's statistics lines
     uint32_t esc = 0u;
 #pragma unroll
     for(int c = 0; c < kDbCntMul; ++c)
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void k_dbin_count(const uint32_t* __restrict__
       for(int i = 0; i < kDbRounds; ++i)
         esc += (uint32_t)__popcll(__ballot(v[c][i] == escape && (chunk0 + c) * (uint32_t)kDbChunk + eW + i * 64u < n));
     if(lane == 0 && esc != 0u)
-      atomicAdd(const_cast<uint32_t*>(&plan->ghist[0][0]) + 32u * ((blockIdx.x * 4u + (uint32_t)w) & (kFrameStatSlots - 1u)) + 3u, esc);
+      atomicAdd(&frameStatLineFromKeys(plan, blockIdx.x * 4u + (uint32_t)w)->escapes, esc);
   }
   else
   {
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void k_dbin_emit(const uint32_t* __restrict__ 
   }
   // the splats' own rectangles, where they rode through the key sort as codes (k_dbin_count has the story): lane == splat for the
   // walk below
-  const uint32_t ride = plan->reserved[0];
+  const uint32_t ride = plan->rideInfo;
   uint32_t       code[kDbRounds];
 #pragma unroll
   for(int i = 0; i < kDbRounds; ++i)
@@ -501,16 +501,16 @@ __global__ __launch_bounds__(256) void k_dbin_emit(const uint32_t* __restrict__ 
       binOrder[rank] = (uint32_t)t;
     }
     if(t == 0)
-      binOrder[256] = 1u;  // valid
+      *binOrderValidOf(binOrder) = 1u;
     if(t < nb)
       ranges[t] = wrapped ? make_uint2(0u, 0u)
                           : make_uint2(min(binBase, capacity), (uint32_t)min((uint64_t)binBase + btot, (uint64_t)capacity));
     if(t == 0)
     {
       ctr->pairCount = (uint32_t)min(D64, (uint64_t)capacity);
-      // (round 6) ... and beside the compositor's statistics (sort_plan.h: frameStatSlot, slot 0 word 4), so that ONE small copy
+      // ... and beside the compositor's statistics (line 0 of the statistics lines), so that ONE small copy
       // tells the host how much of their lists the regions scan: the adaptive bin size's input (api_frame.hip: BinPolicy)
-      const_cast<uint32_t*>(&plan->ghist[0][0])[4] = (uint32_t)min(D64, (uint64_t)capacity);
+      frameStatLineFromKeys(plan, 0u)->listEntries = (uint32_t)min(D64, (uint64_t)capacity);
       if(D64 > capacity)
         atomicOr(&ctr->errorFlags, kErrPairOverflow);
     }
@@ -677,7 +677,7 @@ void launchDirectBinning(hipStream_t stream, const DirectBinLaunch& L)
   // MGS_DB_TRANSPOSE=0: the rounds' masks by ballots everywhere (the masks are the same; the transpose path is the default)
   hipLaunchKernelGGL(k_dbin_count, dim3((maxChunks + kDbCntMul - 1) / kDbCntMul), dim3(256), 0, stream, L.idsX, L.idsY, L.planKeys, L.rect, L.sortedCode16,
                      L.maskBuf, L.binHist, L.pStride, L.binsX, L.binsY, tuning().dbTranspose);
-  hipLaunchKernelGGL(k_dbin_scan, dim3(L.binsX * L.binsY), dim3(256), 0, stream, L.planKeys, L.binHist, L.pStride, L.binTotal);
+  hipLaunchKernelGGL(k_dbin_scan, dim3(L.binsX * L.binsY), dim3(256), 0, stream, L.planKeys, L.binHist, L.pStride, L.tables->binTotal);
 #ifdef MGS_DB_TRACE
   static uint64_t* traceBuf = nullptr;
   const char*      tracePath = std::getenv("MGS_DB_TRACE_FILE");
@@ -692,7 +692,7 @@ void launchDirectBinning(hipStream_t stream, const DirectBinLaunch& L)
   }
 #endif
   hipLaunchKernelGGL(k_dbin_emit, dim3(maxChunks), dim3(256), 0, stream, L.idsX, L.idsY, L.planKeys, L.maskBuf, L.binHist, L.pStride,
-                     L.binTotal, L.binList, L.ranges, L.ctr, L.capacity, L.binsX, L.binsY, L.binTotal + 256, L.sortedCode16, L.binCost);
+                     L.tables->binTotal, L.binList, L.ranges, L.ctr, L.capacity, L.binsX, L.binsY, L.tables->binOrder, L.sortedCode16, L.binCost);
 #ifdef MGS_DB_TRACE
   if(tracePath)
   {

@@ -45,7 +45,7 @@
 #include <vector>
 
 #include "kernels_common.h"
-#include "sort_plan.h"
+#include "frame_state.h"
 
 namespace mgs {
 
@@ -484,7 +484,7 @@ struct OsPassArgs
   // clean ids for everybody, the codes in sorted order for the binning stage
   uint32_t        rideShift;   // bits of the id proper; 0 = nothing rides
   uint32_t        rideSplit;   // 1: the code's low 8 bits lie in the key's low byte, the rest above the id (slot_emit.h)
-  uint32_t        rideInfo;    // what planOut->reserved[0] tells k_dbin_count: shapes | code bits << 8
+  uint32_t        rideInfo;    // what planOut->rideInfo tells k_dbin_count: shapes | code bits << 8
   uint16_t*       dstCode16;
   const uint32_t* srcKeys;
   const uint32_t* srcVals;
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(kThreads, MGS_OS_WAVES) void k_os_pass(const OsPass
     a.planOut->finalSel  = 0u;
     a.planOut->passesRun = (uint32_t)a.pass + 1u;
     if(finalOut)
-      a.planOut->reserved[0] = a.rideShift != 0u ? a.rideInfo : 0u;  // the binning stage finds the rectangles in sorted order
+      a.planOut->rideInfo = a.rideShift != 0u ? a.rideInfo : 0u;  // the binning stage finds the rectangles in sorted order
   }
 
   // ---- load: wave w owns a contiguous quarter of the partition, lane-interleaved, so (wave, round, lane) is memory order.

@@ -403,7 +403,7 @@ __global__ __launch_bounds__(kPrjThreads, 6) void k_project(const FrameArgs* __r
     }
   __syncthreads();
   if(t == 0 && M)
-    atomicAdd(&frameStatSlotFromOs(osPlan, part)[2], M);  // (sort_plan.h: 32 slots on 32 lines, not the counters' one line)
+    atomicAdd(&frameStatLineFromOs(osPlan, part)->survivors, M);  // (32 lines, not the counters' one)
 
   MGS_PRJ_STAMP(3)
   if(M == 0u)

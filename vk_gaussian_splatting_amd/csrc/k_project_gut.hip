@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kGutThreads) void k_project_gut(const FrameArgs* __
     }
   __syncthreads();
   if(t == 0 && Mv)
-    atomicAdd(&frameStatSlotFromOs(osPlan, part)[2], Mv);  // (sort_plan.h: 32 slots on 32 lines, not the counters' one line)
+    atomicAdd(&frameStatLineFromOs(osPlan, part)->survivors, Mv);  // (32 lines, not the counters' one)
   // ---- 3DGUT front end over the survivors ----
   // The 96-byte records leave through LDS (as k_project's do): every lane builds one record, then the wave stores its 64 records
   // six lanes per record, so that a store instruction covers whole sectors wherever neighbouring ids both survive (a wave's

@@ -8,6 +8,7 @@
 
 #include "compare_types.h"
 #include "device_types.h"
+#include "frame_state.h"
 #include "sort_plan.h"
 
 namespace mgs {
@@ -70,7 +71,7 @@ struct DirectBinLaunch
   uint32_t        maxSplats;
   uint32_t*       binHist;
   uint32_t        pStride;
-  uint32_t*       binTotal;
+  DirectBinTables* tables;  // of the pairs plan (frame_state.h)
   uint32_t*       binList;
   uint2*          ranges;
   FrameCounters*  ctr;

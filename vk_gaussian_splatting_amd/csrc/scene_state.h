@@ -127,7 +127,7 @@ struct DevBuf
   uint64_t bytes() const { return (uint64_t)n * sizeof(T); }
 };
 
-// a typed window into memory somebody else owns (the members of FrameState below)
+// a typed window into memory somebody else owns (the members of FrameState, frame_state.h)
 template <class T>
 struct DevView
 {
@@ -153,17 +153,6 @@ struct MeshInstance
   int   mesh;  // index into SceneData::meshes
   float M[16];
   bool  visible = true;
-};
-
-// One device block per handle: the per-frame device state that every frame starts from zero (counters, sort plans), followed by
-// the frame's constants.  A frame begins with ONE upload that carries the zeros along with the constants — no kernel has to
-// sweep them (the frame's first kernel used to).
-struct FrameState
-{
-  FrameCounters ctr;
-  FramePlans    plans;  // keys, pairs, os (sort_plan.h)
-  FrameArgs     args;   // view / proj, instances, knobs: the kernels read them through this pointer, so a captured frame graph
-                        // replays with nothing but the upload
 };
 
 // compositor output mode of a target format (1 = RGBA16F, 0 = RGBA32F, 2 = RGBA8: linear UNORM, rounded once at the end; the
@@ -568,7 +557,9 @@ struct LastFrame
   MgsFrameParams params{};
   bool           have = false, timed = false, wasSortOnly = false;
   int            binShift[2] = {4, 3};  // the last frame's bin size (the adaptive policy may pick another one for the next frame)
-  int            ride[5] = {0, 0, 0, 0, 0};  // the last frame's rideShift, code bits, binsX, binsY, 1 if the GPU key sort ran (mgs_frame_download_projected)
+  int            rideShift = 0, codeBits = 0;      // of the last frame (0: nothing rode through the key sort) ...
+  int            binsX = 0, binsY = 0;             // ... its bins ...
+  bool           gpuSorted = false;                // ... and whether its GPU key sort ran (mgs_frame_download_projected)
   bool           listsPartial = false;  // the last frame came from mgs_render_gathered: its bin lists cover this rank's rows only
   MgsSortOut     sort{};
 };
@@ -589,11 +580,11 @@ struct BinPolicy
   int        sampledFine = 0, sampledRegions = 64;
   uint32_t   sampledRegionCount = 1;  // 32x16-px regions of the sampled frame (its strip)
   hipEvent_t ev = nullptr;
-  uint32_t*  host = nullptr;     // pinned, kFrameStatSlots x 32 words
+  FrameStatLine* host = nullptr;  // pinned, kFrameStatSlots lines
   float      lastRatio = 0.0f;
 
   int  apply();                                                                     // before an eligible frame (api_frame.hip)
-  int  sample(const FrameConst& F, const uint32_t* statLines, hipStream_t stream);  // behind an eligible frame
+  int  sample(const FrameConst& F, const FrameStatLine* statLines, hipStream_t stream);  // behind an eligible frame
   void release()
   {
     if(host) (void)hipHostFree(host);
@@ -639,7 +630,8 @@ int  buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A);       //
 bool directBinning(const FrameConst& F);                                      // api_frameargs.hip
 bool binPolicyEligible(const MgsFrameParams* p);                              // api_frameargs.hip
 int  ensureFrameState(MgsScene s);                                            // api_frame.hip
-int  ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F);  // api_frame.hip: image, side outputs, accumulator
+// api_frame.hip: image, side outputs, accumulator; a frame of the graph also sizes its range table and names its occluder depth
+int  ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F, uint32_t rangeEntries = 0, const float* occDepth = nullptr);
 void mat4InverseDouble(const float m[16], float out[16]);                     // api_frameargs.hip
 void rotScaleInverse(const float M[16], float out[9]);                        // api_mesh.hip
 int  uploadFrameState(MgsScene s, const FrameArgs& A, hipStream_t st);        // api_frame.hip

@@ -20,7 +20,7 @@
 //   pass-elision decision come from these; k_os_prepare folds them).
 #pragma once
 #include "kernels_common.h"
-#include "sort_plan.h"
+#include "frame_state.h"
 
 namespace mgs {
 

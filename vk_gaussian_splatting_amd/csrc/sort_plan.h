@@ -12,11 +12,14 @@
 
 namespace mgs {
 
+struct FrameCounters;  // frame_state.h
+
 struct SortPlan
 {
   uint32_t ghist[4][256];  // digit totals of every pass, written by that pass's scan kernel
   uint32_t skip[4];        // pass is the identity permutation (single occupied digit) -> its scatter exits
-  uint32_t reserved[4];
+  uint32_t rideInfo;       // written by the frame's key sort for the binning stage (OsLaunch::rideInfo); 0 = nothing rode
+  uint32_t reserved[3];
   uint32_t finalSel;       // result lives in X (0) or Y (1); written by the last pass
   uint32_t passesRun;
   uint32_t n;
@@ -62,13 +65,13 @@ constexpr uint32_t kRemapSpan = 4096;  // pass 2 of a depth-key sort indexes a 4
 struct OsPlan
 {
   uint32_t total[4][256];  // digit totals of every pass, complete before pass 0 starts (pass 2: per rank when remapOn)
-  uint32_t reserved4[4];   // (round 3 tried a start-order ticket per pass here: measured and dropped, k_osort.hip header)
+  uint32_t pad0[4];
   // Pass elision for depth keys: when at most 256 values of key >> 16 occur (within a span < 4096), pass 2 sorts on the RANK
   // of key >> 16 among them — an order-preserving 8-bit digit that covers the top 16 bits at once — and pass 3 does not run.
   uint32_t remapOn, remapCount, remapBase;
   uint32_t n;               // element count (copied from the device-side counter by k_os_prepare)
   uint32_t remapPadRank;    // pass 2 when remapOn: the rank of keys outside the table (padding lanes): the largest
-  uint32_t arrivedUnused;   // (rounds 3-4: arrival counter of k_os_prepare's reduce workgroups; the fold moved to k_os_pass<3>)
+  uint32_t pad1;
   uint32_t top16MinInv;     // 0x10000 - (smallest occurring value of key >> 16); 0 = none   } both kept as maxima: the plan
   uint32_t top16MaxP1;      // largest occurring value + 1; 0 = none                          } starts zeroed
   uint32_t pad[4];
@@ -88,7 +91,7 @@ struct OsLaunch
                                          // that value in the chunk's earlier slots | the group's start inside its slot << 16
   uint32_t        rideShift  = 0;        // frame only: the ids carry the bin rectangles' codes above bit rideShift (rideEncode) ...
   uint32_t        rideSplit  = 0;        // ... (1: split between the key's low byte and the id's spare bits, FrameConst::rideSplit) ...
-  uint32_t        rideInfo   = 0;        // ... shapes | code bits << 8, handed to the binning stage in planOut->reserved[0] ...
+  uint32_t        rideInfo   = 0;        // ... shapes | code bits << 8, handed to the binning stage in planOut->rideInfo ...
   uint16_t*       outCode16  = nullptr;  // ... and the final pass writes clean ids and, here, the codes in sorted order
   uint32_t*       prjOrderOut = nullptr; // [prjParts] the next frame's dispatch order of the project kernel: fullest slot first (k_os_prepare)
   uint32_t*       nOut       = nullptr;  // the frame's count of sorted pairs (== *nPtr afterwards), written by k_os_prepare
@@ -116,35 +119,6 @@ struct OsLaunch
   uint32_t        resSlots     = 0;    // workgroups of a pass the scene's device holds at once: CUs x MGS_OS_WAVES (126 VGPRs, 36-40 KB of LDS)
   uint32_t        flatLookback = 0;    // != 0: the flat level 2 of the look-back where it applies (k_osort.hip; Tuning::osFlat)
 };
-
-// the per-frame sort state of one context, contiguous so that the frame's first kernel zeroes it in one sweep
-struct FramePlans
-{
-  SortPlan keys;   // what the consumers of the sorted ids read (n, finalSel, passesRun)
-  SortPlan pairs;  // the record path's pair sort / the direct binning's per-bin totals
-  OsPlan   os;     // the key sort's own plan
-};
-
-static_assert(offsetof(FramePlans, pairs) == sizeof(SortPlan) && offsetof(FramePlans, os) == 2 * sizeof(SortPlan),
-              "frameStatSlot: the keys plan sits right before the pairs plan, the key sort's plan right behind it");
-// The compositors' frame statistics (staged records, scanned list entries; mgs_frame_stats): every region adds its two counts
-// with fire-and-forget atomics.  Rounds 1-4 kept 8 + 8 words for them in the frame counters — ONE 128-byte line; at 4K that is
-// 33 K atomics on one line, and the line's atomic unit (~90 per microsecond) was what the compositor's tail waited for (round 5
-// ablation: composite 361 -> 331 us at 4K, 118 -> 114 at 1080p without them).  Now 32 slots, one per 128-byte line of the KEYS
-// plan's histogram rows, which a frame's key sort does not use and the frame's upload zeroes: word 0 staged, word 1 scanned.
-constexpr uint32_t kFrameStatSlots = 32;
-#if defined(__HIPCC__)
-__device__ __forceinline__ uint32_t* frameStatSlot(const SortPlan* planPairs /* &FramePlans::pairs */, uint32_t slot)
-{
-  return const_cast<uint32_t*>(&(planPairs - 1)->ghist[0][0]) + 32u * (slot & (kFrameStatSlots - 1u));
-}
-// the same slots from the project kernels, which hold &FramePlans::os: word 2 = survivors of the dist-stage cull (one add per
-// partition: 22.8 K of them at configs[4] were 23 us of the frame counters' line)
-__device__ __forceinline__ uint32_t* frameStatSlotFromOs(const OsPlan* osPlan /* &FramePlans::os */, uint32_t slot)
-{
-  return frameStatSlot(reinterpret_cast<const SortPlan*>(osPlan) - 1, slot);
-}
-#endif
 
 uint32_t osSortMaxParts(uint32_t maxElems, uint32_t partMin);
 inline uint32_t osSortChunks(uint32_t prjParts) { return (prjParts + kOsChunk - 1u) / kOsChunk; }
