@@ -1,6 +1,8 @@
 """child process of test_gpu_trace.py: mgs_render_traced in a fresh process.   usage: _child_trace.py MODE OUT.npz [CASE]
 MODE case:   one case of trace_cases.py: the frame (RGBA32F), hit counts, side outputs and MgsTraceOut
-MODE extras: determinism, strips, rebuild rules, a frame context, the error codes, the raster path before and after"""
+MODE extras: determinism, strips, rebuild rules, a frame context, the error codes, the raster path before and after
+MODE formats: c_two_instances with quantised SH / colour storage at three K-buffer sizes, the three target formats, temporal
+             accumulation of four depth-of-field frames, and every strip row of a 36-row frame on its own"""
 import os
 import sys
 
@@ -45,8 +47,50 @@ if mode == "case":
     p = params(case)
     img, hits, o = traced(scene, case, p)
     depth, ids, nrm = scene.download_surface(p, normals=True)
-    np.savez(out, image=img, hits=hits, depth=depth, id=ids, normal=nrm, **{"out_" + k: v for k, v in o.as_dict().items()})
+    n0 = case["sets"][0][0]["positions"].shape[0] if case["sets"] else 0
+    order0 = scene.storage_order(0, n0) if n0 else np.zeros(0, np.uint32)  # instance 0: storage index -> caller's index
+    np.savez(out, image=img, hits=hits, depth=depth, id=ids, normal=nrm, storage_order_0=order0,
+             **{"out_" + k: v for k, v in o.as_dict().items()})
     scene.close()
+elif mode == "formats":
+    res = {}
+    case = tc.cases()["c_two_instances"]
+    p = params(case)
+    for tag, fmt in (("f16", capi.FORMAT_FLOAT16), ("u8", capi.FORMAT_UINT8)):
+        scene = mgs.Scene(0)
+        for arrays, M in case["sets"]:
+            scene.add_instance(mgs.SplatSet.from_arrays(**arrays), M)
+        scene.commit(fmt, fmt)
+        for k, (arrays, _) in enumerate(case["sets"]):
+            n, cpc = arrays["positions"].shape[0], arrays["f_rest"].shape[1] // 3
+            res[f"{tag}_rgba_{k}"] = scene.download_set(k, 2, 4 * n).reshape(n, 4)
+            sh = np.zeros((n, 15, 3), np.float32)  # the set's own stride is 3 * cpc floats per splat, [coef][rgb]
+            sh[:, :cpc] = scene.download_set(k, 3, 45 * n)[:3 * cpc * n].reshape(n, cpc, 3)
+            res[f"{tag}_sh_{k}"] = sh
+        for spp in (18, 4, 32):
+            img, hits, _ = traced(scene, case, p, samples_per_pass=spp)
+            _, ids = scene.download_surface(p)
+            res[f"{tag}_image_{spp}"], res[f"{tag}_hits_{spp}"], res[f"{tag}_id_{spp}"] = img, hits, ids
+        scene.close()
+    scene = build(case)
+    # the same frame to the three target formats
+    for tag, fmt in (("f32", capi.TARGET_RGBA32F), ("f16", capi.TARGET_RGBA16F), ("u8", capi.TARGET_RGBA8)):
+        res[f"target_{tag}"], res[f"target_{tag}_hits"], _ = traced(scene, case, params(case, target_format=fmt))
+    # temporal accumulation: four depth-of-field samples singly, then accumulated by the library
+    dof = dict(dof_mode=1, focus_dist=3.0, aperture=0.01)
+    res["dof_singles"] = np.stack([traced(scene, case, params(case, frame_sample_id=k, **dof))[0] for k in range(4)])
+    res["dof_accumulated"] = np.stack([traced(scene, case, params(case, frame_sample_id=k, temporal_sampling=1, **dof))[0] for k in range(4)])
+    # every strip row of the 36-row frame on its own (the last one is a partial tile row) against the full frame; the camera is
+    # tilted so that the splats reach the last rows (with the case's own camera rows 30..35 are empty)
+    tilted = dict(case, V=tc.lookat(case["eye"], (0.0, -0.9, 0.0)))
+    full_img, full_hits, _ = traced(scene, tilted)
+    for r in range(3):
+        s_img, s_hits, _ = traced(scene, tilted, params(tilted, strip_row_begin=r, strip_row_end=r + 1))
+        y0, y1 = 16 * r, min(16 * r + 16, case["H"])
+        res[f"strip_{r}"] = s_img[y0:y1].tobytes() == full_img[y0:y1].tobytes() and np.array_equal(s_hits[y0:y1], full_hits[y0:y1])
+    res["last_rows_hits"] = full_hits[32:].max(axis=1)
+    scene.close()
+    np.savez(out, **res)
 else:
     res = {}
     case = tc.cases()["c_two_instances"]

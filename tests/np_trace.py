@@ -25,6 +25,29 @@ margins, with x = om - p the model-space offset of the ray origin from the parti
     the pixel fragile (this covers the K-th slot and the epsT window: both are decided by the order of the hits).
   * transmittance: each accepted hit adds (alpha_hi - alpha_lo) / (1 - alpha) + 4 u to the relative uncertainty of T (kept in double
     on both sides); T within that of min_transmittance or of the iso threshold when it is tested makes the pixel fragile.
+  * iso-surface normal (normal_method = 1, computeEllipsoidNormal threedgrt.h.slang:423-537): rem = 9 - dist^2 moves by
+    2 dist d_d + d_d^2 (+ 16 u of the 9), half = sqrt(rem) by that over 2 half, the closest approach -b by d_d; rem within its
+    margin of 0, or the near root -b - half (or, when that is negative, the far root) within the sum of the two of 0, makes the
+    pixel fragile: each is a branch of raySphereIntersection.
+
+Exact ties.  The order margin above would mark every pair of coincident particles fragile, and the device's tie rule could never be
+tested.  But two candidates of one ray that belong to the SAME instance and whose centre, log-scale and quaternion are bit-identical
+are evaluated by the device from the same bits through the same instruction sequence (evalParticle: one ray, one instance transform,
+loadParticle of identical words), so their t is bit-identical on the device whatever it is, and here too.  Such a pair therefore does
+not make the pixel fragile through the order rule: its order is decided by the tie rule alone, (t, caller's global id) ascending
+(rahit.slang:152-167 inserts by distance; the library orders equal distances by the id in the caller's order), which the sort key of
+the candidate list encodes.  Every other margin (thresholds, range, the neighbours that are not its copy) still applies to each of
+the two.  A pass ends at tMin = the last walked t and the next collects t > tMin + epsT: the copy of a hit that was walked last in
+its pass is never a hit, on either side (at samples_per_pass = 1 no second copy ever is).
+
+Declared ties.  Copies of one particle are stored in the caller's order (the commit sort breaks equal codes by index), so they cannot
+tell an order by the caller's id from an order by the storage id.  Different particles can: on a ray whose model-space direction is
+(0, 0, dz) exactly, a particle with the identity quaternion has canonical direction (0, 0, dz / s_z), every product with its x and y
+components is +-0, and t = -(oc_z dc_z) / (dc_z dc_z) is computed from the ray, the centre's z and the log-scale's z alone: particles
+that share those two words have bit-identical t whatever their x, y and other scales (evalParticle: the same instruction sequence on
+the same bits; the zeros add exactly).  trace(exact_ties = [(y, x, instance, local ids)]) declares such a group for ONE pixel; there its
+members are an exact tie like copies are (their float64 t must be equal here too, which is asserted), and every other margin of
+theirs stays.  On every other pixel the group is treated like any particles.
 """
 import numpy as np
 
@@ -36,9 +59,11 @@ T_MIN, T_MAX, EPS_T = 0.001, 10000.0, 1e-9
 INVALID = 0xFFFFFFFF
 
 
-def prepare_set(arrays, rgba=None):
+def prepare_set(arrays, rgba=None, sh=None):
     """the particle data as the device holds it: centres, exp(scale), rotation rows, rgba (0.5 + C0 f_dc, sigmoid(opacity)) and the SH
-    record [n][15][3]; rgba may be handed in (what mgs_scene_download_set returns)"""
+    record [n][15][3]; rgba [n][4] and sh [n][15][3] (dequantised, caller's order, zero beyond the set's coefficients) may be handed
+    in: what mgs_scene_download_set returns for a set committed in a quantised format.  shape[n]: equal for two particles exactly
+    when centre, log-scale and quaternion are bit-identical (the exact-tie rule of the module docstring)."""
     pos = np.asarray(arrays["positions"], np.float32).astype(np.float64).reshape(-1, 3)
     n = pos.shape[0]
     s = np.exp(np.asarray(arrays["scale"], np.float32)).astype(np.float64).reshape(-1, 3)
@@ -58,11 +83,16 @@ def prepare_set(arrays, rgba=None):
     rgba = np.asarray(rgba, np.float32).astype(np.float64).reshape(-1, 4)
     fr = np.asarray(arrays["f_rest"], np.float32).astype(np.float64).reshape(n, -1)
     cpc = fr.shape[1] // 3
-    sh = np.zeros((n, 15, 3))
-    if cpc:
-        sh[:, :cpc, :] = fr.reshape(n, 3, cpc).transpose(0, 2, 1)
+    if sh is None:
+        sh = np.zeros((n, 15, 3))
+        if cpc:
+            sh[:, :cpc, :] = fr.reshape(n, 3, cpc).transpose(0, 2, 1)
+    else:
+        sh = np.asarray(sh, np.float32).astype(np.float64).reshape(n, 15, 3)
     degree = {0: 0, 3: 1, 8: 2, 15: 3}[cpc]
-    return dict(pos=pos, s=s, R=R, rgba=rgba, sh=sh, degree=degree, n=n)
+    raw = np.concatenate([np.asarray(arrays[k], np.float32).reshape(n, -1) for k in ("positions", "scale", "rotation")], 1)
+    shape = np.unique(np.ascontiguousarray(raw).view(np.uint32), axis=0, return_inverse=True)[1].reshape(-1) if n else np.zeros(0, np.int64)
+    return dict(pos=pos, s=s, R=R, rgba=rgba, sh=sh, degree=degree, n=n, shape=shape)
 
 
 def response(degree, d):
@@ -134,11 +164,14 @@ def _rand(state):
 
 def trace(instances, V, P, W, H, samples_per_pass=18, max_passes=200, min_transmittance=0.01, adaptive_clamping=True,
           depth_iso_threshold=0.7, kernel_degree=2, kernel_min_response=0.0113, alpha_clamp=0.99, alpha_cull=1.0 / 255.0, sh_degree=3,
-          fisheye=False, fov_rad=None, dof=None, thin=1e-6, rows=None, sh_only=False, no_gauss=False, single_sorted_walk=False):
+          fisheye=False, fov_rad=None, dof=None, thin=1e-6, rows=None, sh_only=False, no_gauss=False, single_sorted_walk=False, normal_method=0,
+          reverse_ties=False, exact_ties=()):
     """instances: [(prepared set, M 4x4 math)] in creation order.  Returns dict(image [H,W,4], hits [H,W], depth [H,W], id [H,W],
     normal [H,W,4], fragile [H,W], candidates [H,W], depth_tol [H,W]: the fp32 tolerance of
     the picked depth).  single_sorted_walk: ignore the pass structure, walk all candidates in order
-    (what the passes reduce to when K exceeds every ray's candidate count)."""
+    (what the passes reduce to when K exceeds every ray's candidate count).  normal_method: 0 the max-density plane, 1 the iso
+    surface; thin: thin_particle_threshold.  reverse_ties: order exact ties by DESCENDING id (the wrong rule; for the test that shows
+    a case can see the rule).  exact_ties: declared ties, see the module docstring.  tie_pair [H,W]: the walk accepted two bit-identical candidates one after the other."""
     V, P = np.asarray(V, np.float64), np.asarray(P, np.float64)
     kmr = float(np.float32(kernel_min_response))
     acull, aclamp = float(np.float32(alpha_cull)), float(np.float32(alpha_clamp))
@@ -153,6 +186,7 @@ def trace(instances, V, P, W, H, samples_per_pass=18, max_passes=200, min_transm
     nrm = np.zeros((H, W, 4))
     fragile = np.zeros((H, W), bool)
     ncand = np.zeros((H, W), np.int64)
+    tie_pair = np.zeros((H, W), bool)
     # per instance and pixel row: every particle against every ray of the row
     per_inst = []
     base = 0
@@ -207,23 +241,34 @@ def trace(instances, V, P, W, H, samples_per_pass=18, max_passes=200, min_transm
             if not ok_row[xp]:
                 img[y, xp] = (0, 0, 0, 1)
                 continue
-            c = sorted(cand[xp], key=lambda e: (e[0], e[1]))
+            c = sorted(cand[xp], key=lambda e: (e[0], -e[1] if reverse_ties else e[1]))
             ncand[y, xp] = len(c)
             fr = bool(frag_row[xp])
+
+            def same_bits(e, f):  # one instance, bit-identical centre, log-scale and quaternion: bit-identical t on the device
+                if e[2] == f[2] and per_inst[e[2]][0]["shape"][e[3]] == per_inst[e[2]][0]["shape"][f[3]]:
+                    return True
+                for ty, tx, tk, tids in exact_ties:  # a declared tie of this pixel
+                    if (ty, tx) == (y, xp) and e[2] == f[2] == tk and e[3] in tids and f[3] in tids:
+                        assert e[0] == f[0], "a declared exact tie has different t in the restatement"
+                        return True
+                return False
+
             for i in range(len(c) - 1):
-                if c[i + 1][0] - c[i][0] <= c[i][6] + c[i + 1][6]:
+                if c[i + 1][0] - c[i][0] <= c[i][6] + c[i + 1][6] and not same_bits(c[i], c[i + 1]):
                     fr = True
             T, relT = 1.0, 0.0
             rad = np.zeros(3)
             n_acc = np.zeros(3)
             wsum, iso_d, pick, hc, pick_dt = 0.0, 0.0, INVALID, 0, 0.0
             tmin = T_MIN
+            last_acc = None
 
             def near(Tv, lim):
                 return abs(Tv - lim) <= Tv * (relT + 4.0 * U)
 
             def walk(e):
-                nonlocal T, relT, rad, n_acc, wsum, iso_d, pick, pick_dt, hc, fr
+                nonlocal T, relT, rad, n_acc, wsum, iso_d, pick, pick_dt, hc, fr, last_acc
                 tt, gid, k, li, dist, d_d, d_t, om, dm = e
                 ps, M, Mi, Ri, dens, thr, alive, gbase = per_inst[k]
                 den = dens[li]
@@ -246,7 +291,12 @@ def trace(instances, V, P, W, H, samples_per_pass=18, max_passes=200, min_transm
                 T *= 1.0 - alpha
                 relT += (a_hi - a_lo) / max(1.0 - alpha, 1e-30) + 4.0 * U
                 hc += 1
-                n_acc += _normal_world(ps, li, om, dm, Ri, thin) * w
+                if last_acc is not None and last_acc[0] == tt and same_bits(last_acc, e):
+                    tie_pair[y, xp] = True
+                last_acc = e
+                nw, n_frag = _normal_world(ps, li, om, dm, Ri, thin, normal_method, d_d)
+                fr = fr or n_frag
+                n_acc += nw * w
                 wsum += w
                 if iso_d == 0.0:
                     if near(T, isoT):
@@ -292,27 +342,54 @@ def trace(instances, V, P, W, H, samples_per_pass=18, max_passes=200, min_transm
                 depth_tol[y, xp] = (max(abs(ndc_z(iso_d + dt)[0] - depth[y, xp]), abs(ndc_z(iso_d - dt)[0] - depth[y, xp]))
                                     + 8.0 * U * (np.abs(P[2]) @ np.abs(V @ np.append(o_row[xp] + iso_d * d_row[xp], 1.0))) / abs(clip[3]))
             fragile[y, xp] = fr
-    return dict(image=img, hits=hits, depth=depth, id=ids, normal=nrm, fragile=fragile, candidates=ncand, depth_tol=depth_tol)
+    return dict(image=img, hits=hits, depth=depth, id=ids, normal=nrm, fragile=fragile, candidates=ncand, depth_tol=depth_tol,
+                tie_pair=tie_pair)
 
 
-def _normal_world(ps, li, om, dm, Ri, thin):
-    """computeEllipsoidNormalMaxDensityPlane (threedgrt.h.slang:358-418) and the inverse-transpose to world space (:218)"""
+def _normal_world(ps, li, om, dm, Ri, thin, normal_method=0, d_d=0.0):
+    """computeEllipsoidNormalMaxDensityPlane (threedgrt.h.slang:358-418) or computeEllipsoidNormal (:423-496, raySphereIntersection
+    :502-537 with the canonical ray's NORMALISED direction, radius 3, range [0, inf)) and the inverse-transpose to world space (:218).
+    Returns (normal, fragile): fragile when a branch of the iso-surface intersection lies within the hit's fp32 margin d_d."""
     s, R, p = ps["s"][li], ps["R"][li], ps["pos"][li]
     local = om - p
-    small = s < thin
-    if small.sum() == 0:
+    iso = normal_method == 1
+    th = max(0.02 * s.max(), float(np.float32(thin))) if iso else float(np.float32(thin))
+    small = s < th
+    fragile = bool((np.abs(s - th) <= 8.0 * U * th).any())  # exp(scale) on the device may differ from numpy's by an ulp or two
+    fallback = -dm / np.linalg.norm(dm)
+    if small.sum() == 0 and not iso:
         g = R @ ((R.T @ local) / (s * s))
         n = g / np.linalg.norm(g)
         if n @ local < 0:
             n = -n
+    elif small.sum() == 0:
+        oc, dc = (R.T @ local) / s, (R.T @ dm) / s
+        dn = dc / np.linalg.norm(dc)
+        b = oc @ dn
+        cr = np.cross(dn, oc)
+        dist2 = cr @ cr
+        rem = 9.0 - dist2
+        m_rem = 2.0 * np.sqrt(dist2) * d_d + d_d * d_d + 16.0 * U * 9.0
+        fragile = fragile or abs(rem) <= m_rem
+        n = fallback
+        if rem >= 0.0:
+            half = np.sqrt(rem)
+            m_t = d_d + m_rem / max(2.0 * half, 1e-300) + 16.0 * U * (abs(b) + half)
+            t1, t2 = -b - half, -b + half
+            fragile = fragile or abs(t1) <= m_t or (t1 < 0.0 and abs(t2) <= m_t)
+            tq = t1 if t1 >= 0.0 else t2
+            if tq >= 0.0:
+                h = oc + tq * dn
+                g = R @ (h / np.linalg.norm(h) / s)
+                n = g / np.linalg.norm(g)
     elif small.sum() == 1:
         n = R[:, int(np.argmax(small))]
         if n @ local < 0:
             n = -n
     else:
-        n = -dm / np.linalg.norm(dm)
+        n = fallback
     wn = Ri.T @ n
-    return wn / np.linalg.norm(wn)
+    return wn / np.linalg.norm(wn), bool(fragile)
 
 
 def psnr_rgb(a, b):

@@ -59,6 +59,26 @@ def test_traced_frame_matches_restatement(name, tmp_path):
     assert int(got["out_leaves"]) <= n_alive
     if name.startswith("e_leaves_"):
         assert int(got["out_leaves"]) == int(name.rsplit("_", 1)[1])
+    if name == "o_dead_third":
+        assert int(got["out_leaves"]) == 13500 - 4500                   # the count boundary lies inside the third 4096-key partition
+    if name == "r_five_instances":
+        assert int(got["out_leaves"]) == 220 + 200 + 220 + 200          # the fourth instance contributes no leaf
+    if name == "q_axis_ring_ties":
+        # eight different particles with bit-identical t on the central ray, stored in (nearly) the reverse of the caller's order: the five
+        # that are hits, the picked one and the normal follow the order by the caller's id
+        order = got["storage_order_0"]
+        ring_in_storage = order[np.isin(order, np.arange(tc.RING))]
+        print(f"{name}: the ring's caller ids in storage order {ring_in_storage.tolist()}; centre pixel id {int(got['id'][12, 16])}, "
+              f"hits {int(got['hits'][12, 16])}, normal error {np.abs(got['normal'][12, 16] - ref['normal'][12, 16]).max():.3e}")
+        # the case can see the rule: by storage id another particle would come first and another five would be the hits
+        assert ring_in_storage[0] != 0 and set(ring_in_storage[:5].tolist()) != set(range(5))
+        assert ok[12, 16] and int(got["id"][12, 16]) == int(ref["id"][12, 16]) and int(got["hits"][12, 16]) == 5
+        assert np.abs(got["normal"][12, 16].astype(np.float64) - ref["normal"][12, 16]).max() <= 2e-3
+        assert np.abs(got["image"][12, 16].astype(np.float64) - ref["image"][12, 16]).max() <= 1e-5   # five hits, each alpha within the 16 u the restatement allows the hardware exponential, and ~10 roundings each
+    if name == "v_iso_threshold_0":
+        assert not got["depth"].any() and (got["id"] == np_trace.INVALID).all()   # nothing is picked
+    if name == "v_iso_threshold_1":                                     # the first accepted hit is picked on every ray that has one
+        assert np.array_equal((got["id"] != np_trace.INVALID)[ok], (ref["hits"] > 0)[ok]) and (ref["hits"] > 0).any()
     if name == "l_no_leaf":
         assert int(got["out_leaves"]) == 300 - 2
     if name == "m_empty":
@@ -89,3 +109,35 @@ def test_determinism_strips_rebuilds_contexts_errors(tmp_path):
     ref = tc.restate_with(case, sets)
     assert ref["fragile"].mean() <= 0.02
     compare(r["moved_image"], r["moved_hits"], ref, label="moved instance")
+
+
+def test_storage_formats_target_formats_accumulation_and_strips(tmp_path, ob):
+    r = run_child(tmp_path, "formats")
+    case = tc.cases()["c_two_instances"]
+    # quantised SH and colours: the restatement is fed what the device holds; all nine k_trace<SH format, KB> have then run against it
+    # (fp32 SH at 18 / 4 / 32 slots: the cases c_two_instances, f_many_passes, n_spp_32)
+    for tag in ("f16", "u8"):
+        sets = [(np_trace.prepare_set(a, rgba=r[f"{tag}_rgba_{k}"], sh=r[f"{tag}_sh_{k}"]), M) for k, (a, M) in enumerate(case["sets"])]
+        for spp in (18, 4, 32):
+            ref = tc.restate_with(dict(case, trace=dict(samples_per_pass=spp)), sets)
+            assert ref["fragile"].mean() <= 0.02
+            compare(r[f"{tag}_image_{spp}"], r[f"{tag}_hits_{spp}"], ref, r[f"{tag}_id_{spp}"], f"SH/colour {tag}, samples_per_pass {spp}")
+    # target formats: the kernel rounds the same accumulators, so no tolerance
+    f32 = r["target_f32"]
+    assert f32.dtype == np.float32 and f32[..., :3].any()
+    compare(f32, r["target_f32_hits"], tc.restate("c_two_instances"), label="RGBA32F target")
+    assert r["target_f16"].dtype == np.float16 and r["target_f16"].tobytes() == f32.astype(np.float16).tobytes()
+    want8 = np.floor(np.clip(f32, np.float32(0), np.float32(1)) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+    assert r["target_u8"].dtype == np.uint8 and np.array_equal(r["target_u8"], want8)
+    # temporal accumulation after a traced frame: the running mean of the four samples traced singly (the bar of
+    # test_gpu_stochastic.py::test_temporal_accumulation_matches_post_comp)
+    singles, acc = r["dof_singles"].astype(np.float32), r["dof_accumulated"].astype(np.float32)
+    assert not np.array_equal(singles[0], singles[3])
+    main = np.zeros_like(singles[0])
+    for k in range(4):
+        main = ob.post_accumulate(main, singles[k], k)
+        err = float(np.abs(acc[k] - main).max())
+        print(f"temporal accumulation, sample {k}: worst error {err:.3e}")
+        assert err <= 1e-3, k
+    # strips: every strip row on its own == the same rows of the full frame, the partial last tile row (rows 32..35) included
+    assert (r["last_rows_hits"] > 0).all() and r["strip_0"] and r["strip_1"] and r["strip_2"]
