@@ -40,9 +40,12 @@ extern "C" {
                                  mgs_mesh_destroy, mgs_mesh_instance_add, mgs_mesh_instance_set_transform, mgs_mesh_instance_set_visible,
                                  mgs_meshes_render, mgs_meshes_download;
                             ray-traced splats (MGS_HAS_TRACE below): entry points only, both numbers stay — mgs_trace_params_default,
-                                 mgs_render_traced, mgs_trace_download_hit_counts */
+                                 mgs_render_traced, mgs_trace_download_hit_counts;
+                            lit traced frames (MGS_HAS_TRACE_LIGHTING below): entry points only, both numbers stay —
+                                 mgs_trace_light_params_default, mgs_render_traced_lit, mgs_trace_download_shadow_hits */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
@@ -529,8 +532,9 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * hardware.  Replaces GaussianSplatting::raytrace with shaders/threedgrt_raytrace.{rgen,rahit,rint}.slang (primary rays), the
  * particle proxies of particle_as_build.comp.slang and the acceleration-structure managers: a hierarchy over the particles built on
  * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
- * Out of scope: meshes in the traced scene, shadows, lighting and bounces, the hybrid pipeline, the stochastic trace strategies,
- * wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
+ * Direct lighting with hard shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
+ * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, the hybrid pipeline, the stochastic trace
+ * strategies, wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
  * is not wired), trace profile feedback.
  *
  * Ray (threedgrt_raytrace.rgen.slang:159-196): pinhole = generatePinholeRay at the pixel centre (subPixelOffset 0.5,
@@ -600,6 +604,69 @@ int mgs_render_traced(MgsScene scene_or_context, const MgsFrameParams* params, c
                       MgsTraceOut* out /* may be NULL */);
 /* pixel.hitCount of the last traced frame of this handle, [height][width] uint32 (rows outside a strip frame's rows are stale); waits */
 int mgs_trace_download_hit_counts(MgsScene scene_or_context, uint32_t* host_dst, size_t count);
+
+/* ---- lit traced frames (MGS_HAS_TRACE_LIGHTING): the traced frame's splat surface under the scene's lights and the instances'
+ * materials (mgs_scene_set_lights, mgs_instance_set_material), each light shadowed by one more ray through the same particle
+ * hierarchy.  Replaces surfaceFinalFiltering, evaluateLightingAndShadingParticles, traceShadowRayForLight and
+ * traceShadowRayParticle of shaders/threedgrt_raytrace.rgen.slang (:991-1009, :1082-1144, :1262-1292, :1344-1464) with
+ * computeLightToSurfaceVector and wavefrontComputeShadingDirectOnly (shaders/wavefront.h.slang:33-70, :233-280).  No mesh is in the
+ * traced scene, so every mesh branch of those functions is its meshCount == 0 branch.
+ * Primary rays: exactly mgs_render_traced with surface outputs on (NEED_SURFACE_INFO is 1 whenever lighting is on).
+ * surfaceFinalFiltering (:991-1009): an integrated normal of length <= 0.2 is replaced by -rayDirection; a pixel without an
+ * iso-surface hit is discarded (discardSplatContribution :468-491: radiance 0, transmittance 1), here rgb 0 and alpha 0; otherwise
+ * the normal is normalised.  A fisheye pixel outside the field of view stays (0,0,0,1).
+ * Shading (:1082-1144): the material is the picked hit's instance's.  radiance restarts at radiance * emission, and that alone is the
+ * pixel when the material's needShading is 0 (the default material).  ambient, diffuse and specular are the pixel's fp32 radiance
+ * (the accumulator of the primary walk, not the pixel as stored in an RGBA16F / RGBA8 target) times the material's.  Position =
+ * origin + t_iso * direction, the view direction is the ray's.  Per light computeLightToSurfaceVector: directional lightDist = 1e10;
+ * a point or spot light farther away than its range is SKIPPED ENTIRELY and adds no ambient term — unlike the deferred raster pass
+ * (lighting_mode of mgs_render), whose shading adds the ambient term once per light, in range or not.  With no lights: a headlight
+ * at camera_pos, never shadowed.  A surface point that coincides with a point or spot light has no light direction (0 / 0): the
+ * pixel is NaN, there as here.
+ * Shadow ray (hard shadows, :1344-1464): origin = position + lightDir * particle_shadow_offset, TMin 0.0, TMax lightDist - 0.001, no
+ * epsT.  ONE collection of the samples_per_pass nearest hits through the same proxies with the tie rule of the primary rays; there
+ * is no second pass, so occluders beyond the samples_per_pass-th are not seen, there as here.  The slots are walked in order, slots
+ * with t >= lightDist skipped, particleProcessHit / particleIntegrate with the transmittance in double; after each slot a
+ * transmittance below particle_shadow_transmittance_threshold becomes 0 and ends the walk.  Then (:1453-1460) T = saturate(T),
+ * scaledT = saturate((T - threshold) / (1 - threshold)), normalizedColor = shadowRadiance / max component (1 when that is <= 0.001),
+ * transmittance = saturate(scaledT * lerp(1, normalizedColor, particle_shadow_color_strength * (1 - scaledT))).  light.color is
+ * multiplied by it; inShadow = its max component < 0.001 (:1126-1127) returns from the shading after the ambient term.
+ * Alpha stays 1 - T of the primary walk (the reference writes 1.0).
+ * Soft shadows (MGS_SHADOWS_SOFT) are MGS_ERR_UNSUPPORTED: sampleDisk draws from nvshaders/random.h.slang, which is not part of the
+ * reference tree, and MgsLight has no radius: PARITY UNPINNED. */
+#define MGS_SHADOWS_DISABLED 0 /* default (parameters.h:167) */
+#define MGS_SHADOWS_HARD 1
+#define MGS_SHADOWS_SOFT 2     /* MGS_ERR_UNSUPPORTED */
+typedef struct MgsTraceLightParams {
+  int32_t  shadows_mode;                            /* MGS_SHADOWS_*, default MGS_SHADOWS_DISABLED */
+  float    particle_shadow_offset;                  /* default 0.2 (parameters.h:222); finite, >= 0 */
+  float    particle_shadow_transmittance_threshold; /* default 0.8 (parameters.h:223); [0, 1): at 1 the ramp divides by zero */
+  float    particle_shadow_color_strength;          /* default 0.0 (parameters.h:224); [0, 1] */
+  uint32_t reserved[4];
+} MgsTraceLightParams;
+void mgs_trace_light_params_default(MgsTraceLightParams* p);
+typedef struct MgsTraceLightOut {
+  uint64_t shadow_rays;            /* shadow rays traced: pixels with a surface and a shaded material x lights in range (0 with shadows off) */
+  uint64_t shadow_node_visits;     /* as MgsTraceOut::node_visits, of the shadow rays */
+  uint64_t shadow_candidate_tests; /* particles evaluated against a shadow ray's window */
+  uint64_t shadow_accepted_hits;   /* hits the shadow walks accepted */
+  float    light_ms;               /* HIP events around the light pass */
+  uint32_t reserved;
+} MgsTraceLightOut;
+/* One lit traced frame into the handle's frame buffer.  Reads everything mgs_render_traced reads, plus lighting_mode, which must be
+ * MGS_LIGHTING_DIRECT: MGS_LIGHTING_INDIRECT needs bounces and returns MGS_ERR_UNSUPPORTED, MGS_LIGHTING_DISABLED or any other value
+ * MGS_ERR_INVALID_ARG.  The ranges of the three structs are checked before the handle is looked at.  `trace` / `light` NULL = the
+ * defaults; `out` or `light_out` non-NULL waits for the frame.  Afterwards mgs_frame_download, mgs_frame_copy_strip,
+ * mgs_frame_download_surface (always: lighting turns the surface outputs on), mgs_trace_download_hit_counts, the image-compare entry
+ * points, temporal accumulation, strip rows and frame contexts work as after mgs_render_traced.  Lights and materials keep their
+ * rules: one table per scene, rewritten after waiting for the frames in flight; neither rebuilds the hierarchy.  The light pass's
+ * per-pixel scratch (ray parameter, fp32 radiance, shadow hits) belongs to the handle and counts into working_bytes. */
+int mgs_render_traced_lit(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
+                          const MgsTraceLightParams* light /* NULL = defaults */, MgsTraceOut* out /* may be NULL */,
+                          MgsTraceLightOut* light_out /* may be NULL */);
+/* shadow hits accepted for the pixel, summed over the lights, of the last lit traced frame of this handle: [height][width] uint32
+ * (rows outside a strip frame's rows are stale); waits.  MGS_ERR_STATE unless the handle's last traced frame was a lit one. */
+int mgs_trace_download_shadow_hits(MgsScene scene_or_context, uint32_t* host_dst, size_t count);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

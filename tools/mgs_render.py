@@ -6,7 +6,8 @@
                              [--occluder-depth FILE.npy [--background FILE.npy]]
                              [--mesh FILE.obj [--mesh-transform 16 floats]]...
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
-                             [--pipeline raster|trace [--samples-per-pass N --max-passes N --min-transmittance X]]
+                             [--pipeline raster|trace [--samples-per-pass N --max-passes N --min-transmittance X]
+                              [--lighting 1 [--shadows 1] [--shadow-offset X --shadow-threshold X --shadow-color-strength X]]]
                              [--compare-with FRAME.npy [--flip-mode 0|1|2] [--compare-view OUT.png --split 0.5 --left capture --right diff-red-gray]]
 
 --occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
@@ -17,6 +18,7 @@ with the field names of MgsLight (type, color, intensity, position, range, direc
 attenuation_mode; absent fields keep the reference's defaults); without it the headlight at the camera lights the scene.
 --material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
 
+--pipeline trace --lighting 1 [--shadows 1]: a lit traced frame (mgs_render_traced_lit), --lights / --material as for the raster pipelines.
 --pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
 the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth, --mesh or --lighting 1.
 
@@ -57,6 +59,10 @@ def main():
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
     ap.add_argument("--pipeline", choices=["raster", "trace"], default="raster")
+    ap.add_argument("--shadows", type=int, choices=[0, 1], default=0)  # --pipeline trace --lighting 1: hard shadow rays through the splats
+    ap.add_argument("--shadow-offset", type=float, default=0.2)
+    ap.add_argument("--shadow-threshold", type=float, default=0.8)
+    ap.add_argument("--shadow-color-strength", type=float, default=0.0)
     ap.add_argument("--samples-per-pass", type=int, default=18)
     ap.add_argument("--max-passes", type=int, default=200)
     ap.add_argument("--min-transmittance", type=float, default=0.01)
@@ -112,11 +118,20 @@ def main():
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
     if a.pipeline == "trace":
-        if a.occluder_depth or a.mesh or a.lighting:
-            ap.error("--pipeline trace renders splats alone: no --occluder-depth, --mesh or --lighting 1")
+        if a.occluder_depth or a.mesh:
+            ap.error("--pipeline trace renders splats alone: no --occluder-depth or --mesh")
         p.collect_timings = 0
         t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance)
-        o = scene.render_traced(p, t, want_stats=True)
+        if a.lighting:  # mgs_render_traced_lit: --lights / --material as for the raster pipelines, shadows by one more ray per light
+            lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
+                                                 particle_shadow_transmittance_threshold=a.shadow_threshold,
+                                                 particle_shadow_color_strength=a.shadow_color_strength)
+            o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
+            sr = max(int(lo.shadow_rays), 1)
+            print(f"light pass {lo.light_ms:.3f} ms on the GPU, {lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, "
+                  f"{lo.shadow_candidate_tests / sr:.1f} candidate tests and {lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
+        else:
+            o = scene.render_traced(p, t, want_stats=True)
         img = scene.download_frame(p).astype(np.float32)
         rays = W * H
         print(f"{scene.splat_count} splats, {o.leaves} leaves in {o.nodes} nodes (build {o.build_ms:.3f} ms), {o.node_visits / rays:.1f} node visits and "

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--lit] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
-tests per ray, and writes everything as JSON.  Needs an MI355X.
+tests per ray, and writes everything as JSON.  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
+lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  Needs an MI355X.
 """
 import argparse
 import json
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--samples-per-pass", type=int, default=18)
+    ap.add_argument("--lit", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -56,6 +58,26 @@ def main():
                  node_visits_per_ray=o.node_visits / rays, candidate_tests_per_ray=o.candidate_tests / rays,
                  accepted_hits_per_ray=o.accepted_hits / rays, max_passes_used=int(o.max_passes_used),
                  scene_bytes=scene.memory_usage()[0])
+        if a.lit:
+            p.lighting_mode = 1
+            scene.set_material(0, capi.make_material(ambient=(0.1, 0.1, 0.1), diffuse=(0.8, 0.8, 0.8), emission=(0.0, 0.0, 0.0)))
+            spots = [(4.0, 6.0, 3.0), (-5.0, 5.0, 2.0), (2.0, 7.0, -5.0), (-3.0, 4.0, -4.0)]
+            r["lit"] = []
+            for nl in (0, 1, 4):
+                scene.set_lights([capi.make_light(position=q, range=1000.0, attenuation_mode=0) for q in spots[:nl]])
+                for shadows in (0, 1):
+                    lp = capi.default_trace_light_params(shadows_mode=shadows)
+                    lms = []
+                    for k in range(a.warmup + a.repeats):
+                        _, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
+                        if k >= a.warmup:
+                            lms.append(lo.light_ms)
+                    sr = max(int(lo.shadow_rays), 1)
+                    r["lit"].append(dict(lights=nl, shadows=shadows, light_ms_median=float(np.median(lms)), light_ms_min=float(min(lms)),
+                                         shadow_rays=int(lo.shadow_rays), node_visits_per_shadow_ray=lo.shadow_node_visits / sr,
+                                         candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
+                                         accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr))
+            p.lighting_mode = 0
         print(json.dumps(r))
         results.append(r)
         scene.close()

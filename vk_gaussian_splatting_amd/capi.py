@@ -127,6 +127,21 @@ class TraceParams(C.Structure):
                 ("kernel_adaptive_clamping", C.c_int32), ("depth_iso_threshold", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+class TraceLightParams(C.Structure):
+    """MgsTraceLightParams: the shadow rays of a lit traced frame (mgs_render_traced_lit)"""
+    _fields_ = [("shadows_mode", C.c_int32), ("particle_shadow_offset", C.c_float), ("particle_shadow_transmittance_threshold", C.c_float),
+                ("particle_shadow_color_strength", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class TraceLightOut(C.Structure):
+    """MgsTraceLightOut: the shadow rays' counters and the light pass's device time of one lit traced frame"""
+    _fields_ = [("shadow_rays", C.c_uint64), ("shadow_node_visits", C.c_uint64), ("shadow_candidate_tests", C.c_uint64),
+                ("shadow_accepted_hits", C.c_uint64), ("light_ms", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class TraceOut(C.Structure):
     """MgsTraceOut: the hierarchy's size, the traversal's counters and the device times of one traced frame"""
     _fields_ = [("leaves", C.c_uint64), ("nodes", C.c_uint64), ("node_visits", C.c_uint64), ("candidate_tests", C.c_uint64),
@@ -236,6 +251,9 @@ def load_library():
         "mgs_trace_params_default": (None, [P(TraceParams)]),
         "mgs_render_traced": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceOut)]),
         "mgs_trace_download_hit_counts": (C.c_int, [vp, P(C.c_uint32), C.c_size_t]),
+        "mgs_trace_light_params_default": (None, [P(TraceLightParams)]),
+        "mgs_render_traced_lit": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceLightParams), P(TraceOut), P(TraceLightOut)]),
+        "mgs_trace_download_shadow_hits": (C.c_int, [vp, P(C.c_uint32), C.c_size_t]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -291,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "mgs_mesh_from_arrays", "mgs_mesh_load_obj", "mgs_mesh_view", "mgs_mesh_destroy", "mgs_mesh_instance_add",
     "mgs_mesh_instance_set_transform", "mgs_mesh_instance_set_visible", "mgs_meshes_render", "mgs_meshes_download",
     "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
+    "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -490,6 +509,17 @@ def default_trace_params(**overrides):
     return t
 
 
+def default_trace_light_params(**overrides):
+    """MgsTraceLightParams with the reference's defaults (mgs_trace_light_params_default); keyword arguments override fields"""
+    t = TraceLightParams()
+    load_library().mgs_trace_light_params_default(C.byref(t))
+    for k, v in overrides.items():
+        if k not in dict(TraceLightParams._fields_):
+            raise TypeError(f"default_trace_light_params: unknown field {k}")
+        setattr(t, k, v)
+    return t
+
+
 def set_camera(p, view, proj, camera_pos):
     """view/proj: 4x4 numpy in math (row, col) convention; stored glm column-major."""
     v = _f32(view).T.reshape(-1)
@@ -670,6 +700,24 @@ class Scene:
         _check(self._lib.mgs_render_traced(self._h, C.byref(params), C.byref(trace) if trace is not None else None,
                                            C.byref(out) if want_stats else None))
         return out if want_stats else None
+
+    def render_traced_lit(self, params, trace=None, light=None, want_stats=False):
+        """mgs_render_traced_lit: one traced frame under the scene's lights with shadow rays through the splats (params.lighting_mode
+        must be MGS_LIGHTING_DIRECT); trace / light = a TraceParams / TraceLightParams or None for the defaults; want_stats waits
+        and returns (TraceOut, TraceLightOut)"""
+        out, lout = TraceOut(), TraceLightOut()
+        self._sort_only = False
+        self._frame_wh = (params.width, params.height)
+        _check(self._lib.mgs_render_traced_lit(self._h, C.byref(params), C.byref(trace) if trace is not None else None,
+                                               C.byref(light) if light is not None else None,
+                                               C.byref(out) if want_stats else None, C.byref(lout) if want_stats else None))
+        return (out, lout) if want_stats else None
+
+    def trace_shadow_hits(self, params):
+        """shadow hits accepted per pixel of the last lit traced frame, summed over the lights, uint32[H,W]"""
+        out = np.zeros((params.height, params.width), np.uint32)
+        _check(self._lib.mgs_trace_download_shadow_hits(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out
 
     def trace_hit_counts(self, params):
         """pixel.hitCount of the last traced frame, uint32[H,W]"""

@@ -1,4 +1,5 @@
-// api_trace.hip — the traced pipeline's host side: mgs_render_traced, the lazy build of the scene's hierarchy, the hit-count download.
+// api_trace.hip — the traced pipeline's host side: mgs_render_traced and mgs_render_traced_lit, the lazy build of the scene's
+// hierarchy, the hit-count and shadow-hit downloads.
 #include <array>
 #include <cmath>
 #include <memory>
@@ -17,6 +18,17 @@ void mgs_trace_params_default(MgsTraceParams* p)
   p->depth_iso_threshold      = 0.7f;   // depthIsoThresholdRTX, parameters.h:226
 }
 
+void mgs_trace_light_params_default(MgsTraceLightParams* p)
+{
+  if(!p)
+    return;
+  std::memset(p, 0, sizeof(*p));
+  p->shadows_mode                            = MGS_SHADOWS_DISABLED;  // parameters.h:167
+  p->particle_shadow_offset                  = 0.2f;                  // parameters.h:222
+  p->particle_shadow_transmittance_threshold = 0.8f;                  // parameters.h:223
+  p->particle_shadow_color_strength          = 0.0f;                  // parameters.h:224
+}
+
 static int failTrace(int code, const std::string& msg)
 {
   setError(msg);
@@ -24,7 +36,8 @@ static int failTrace(int code, const std::string& msg)
 }
 
 // what needs no device: the ranges of MgsTraceParams and of the MgsFrameParams fields the traced pipeline reads
-static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t)
+// (lit: the checks of mgs_render_traced_lit, whose lighting_mode rule differs)
+static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr)
 {
   if(t.samples_per_pass < 1 || t.samples_per_pass > 32)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: samples_per_pass must be in [1, 32]");
@@ -55,10 +68,30 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: dof_mode / frame_sample_id out of range");
   if(p->dof_mode != MGS_DOF_DISABLED && (!(p->aperture >= 0.0f) || !std::isfinite(p->aperture) || !(p->focus_dist > 0.0f) || !std::isfinite(p->focus_dist)))
     return failTrace(MGS_ERR_INVALID_ARG, "trace: depth of field needs a finite aperture >= 0 and a finite focus_dist > 0");
-  if(p->lighting_mode < MGS_LIGHTING_DISABLED || p->lighting_mode > MGS_LIGHTING_INDIRECT)
-    return failTrace(MGS_ERR_INVALID_ARG, "trace: lighting_mode out of range");
-  if(p->lighting_mode != MGS_LIGHTING_DISABLED)
-    return failTrace(MGS_ERR_UNSUPPORTED, "trace: lighting of traced frames is out of scope (primary rays only)");
+  if(lit)
+  {
+    if(lit->shadows_mode < MGS_SHADOWS_DISABLED || lit->shadows_mode > MGS_SHADOWS_SOFT)
+      return failTrace(MGS_ERR_INVALID_ARG, "trace: shadows_mode must be MGS_SHADOWS_DISABLED, MGS_SHADOWS_HARD or MGS_SHADOWS_SOFT");
+    if(!(lit->particle_shadow_offset >= 0.0f) || !std::isfinite(lit->particle_shadow_offset))
+      return failTrace(MGS_ERR_INVALID_ARG, "trace: particle_shadow_offset must be finite and >= 0");
+    if(!(lit->particle_shadow_transmittance_threshold >= 0.0f && lit->particle_shadow_transmittance_threshold < 1.0f))
+      return failTrace(MGS_ERR_INVALID_ARG, "trace: particle_shadow_transmittance_threshold must be in [0, 1)");
+    if(!(lit->particle_shadow_color_strength >= 0.0f && lit->particle_shadow_color_strength <= 1.0f))
+      return failTrace(MGS_ERR_INVALID_ARG, "trace: particle_shadow_color_strength must be in [0, 1]");
+    if(p->lighting_mode == MGS_LIGHTING_INDIRECT)
+      return failTrace(MGS_ERR_UNSUPPORTED, "trace: indirect lighting needs bounces, which are out of scope");
+    if(p->lighting_mode != MGS_LIGHTING_DIRECT)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_lit: lighting_mode must be MGS_LIGHTING_DIRECT");
+    if(lit->shadows_mode == MGS_SHADOWS_SOFT)
+      return failTrace(MGS_ERR_UNSUPPORTED, "trace: soft shadows are out of scope (hard shadows only)");
+  }
+  else
+  {
+    if(p->lighting_mode < MGS_LIGHTING_DISABLED || p->lighting_mode > MGS_LIGHTING_INDIRECT)
+      return failTrace(MGS_ERR_INVALID_ARG, "trace: lighting_mode out of range");
+    if(p->lighting_mode != MGS_LIGHTING_DISABLED)
+      return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: lighting_mode != 0 is mgs_render_traced_lit's");
+  }
   if(p->sort_mode == MGS_SORT_STOCHASTIC)
     return failTrace(MGS_ERR_UNSUPPORTED, "trace: the stochastic trace strategies are out of scope");
   return MGS_OK;
@@ -211,7 +244,9 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
   return MGS_OK;
 }
 
-static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out)
+// lit: the frame of mgs_render_traced_lit (lp NULL = the defaults); otherwise lp and lout are not looked at
+static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out, bool lit = false,
+                                  const MgsTraceLightParams* lp = nullptr, MgsTraceLightOut* lout = nullptr)
 {
   if(!p)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null params");
@@ -220,7 +255,12 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
     t = *tp;
   else
     mgs_trace_params_default(&t);
-  if(int rc = validateTrace(p, t))  // (before the handle is looked at: the ranges can be checked without a device)
+  MgsTraceLightParams lt;
+  if(lit && lp)
+    lt = *lp;
+  else
+    mgs_trace_light_params_default(&lt);
+  if(int rc = validateTrace(p, t, lit ? &lt : nullptr))  // (before the handle is looked at: the ranges can be checked without a device)
     return rc;
   if(!s)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null scene");
@@ -255,6 +295,14 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   const size_t pixels = (size_t)F.width * F.height;
   if((rc = ts.hitCount.ensure(pixels))) return rc;
   if((rc = ts.ctr.ensure(1))) return rc;
+  if(lit)
+  {
+    if((rc = ts.isoDist.ensure(pixels))) return rc;
+    if((rc = ts.radiance.ensure(pixels))) return rc;
+    if((rc = ts.shadowHits.ensure(pixels))) return rc;
+    if((rc = ts.lctr.ensure(1))) return rc;
+    if((rc = ensureLightTable(d))) return rc;
+  }
   if((rc = uploadFrameState(s, *A, s->stream))) return rc;
   const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
   float            buildMs = 0.0f;
@@ -295,10 +343,37 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   L.outDepth          = F.surfaceOutputs ? s->surf.depth.p : nullptr;
   L.outId             = F.surfaceOutputs ? s->surf.id.p : nullptr;
   L.outNormal         = F.surfaceOutputs ? s->surf.normal.p : nullptr;
+  L.outIsoDist        = lit ? ts.isoDist.p : nullptr;
+  L.outRadiance       = lit ? ts.radiance.p : nullptr;
   launchTrace(st, L, F, d.shFormat);
+  if(lit)
+  {  // the light pass rewrites the frame's pixels from the fp32 radiance k_trace left
+    HIPCHK(hipEventRecord(ts.ev[3], st));
+    HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
+    HIPCHK(hipEventRecord(ts.ev[4], st));
+    TraceLightArgs G{};
+    G.t                   = L;
+    G.isoDist             = ts.isoDist.p;
+    G.pickId              = s->surf.id.p;
+    G.normal              = s->surf.normal.p;
+    G.radiance            = ts.radiance.p;
+    G.table               = d.lightTab.p;
+    G.shadowHits          = ts.shadowHits.p;
+    G.lctr                = ts.lctr.p;
+    G.shadowsMode         = lt.shadows_mode;
+    G.shFormat            = d.shFormat == 0 ? 0 : d.shFormat == 1 ? 1 : 2;
+    G.shadowOffset        = lt.particle_shadow_offset;
+    G.shadowThreshold     = lt.particle_shadow_transmittance_threshold;
+    G.shadowColorStrength = lt.particle_shadow_color_strength;
+    launchTraceLight(st, G, F);
+    HIPCHK(hipEventRecord(ts.ev[5], st));
+  }
   if(F.temporalSampling)
     launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.halfOut);
-  HIPCHK(hipEventRecord(ts.ev[3], st));
+  if(!lit)
+  {
+    HIPCHK(hipEventRecord(ts.ev[3], st));
+  }
   HIPCHK(hipGetLastError());
   // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare)
   LastFrame& last = s->last;
@@ -312,6 +387,19 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   ts.w    = F.width;
   ts.h    = F.height;
   ts.have = true;
+  ts.haveLit = lit;  // the shadow hits are those of the last traced frame only when that frame was lit
+  if(lit && lout)
+  {
+    std::memset(lout, 0, sizeof(*lout));
+    TraceLightCounters hc{};
+    HIPCHK(hipMemcpyAsync(&hc, ts.lctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    lout->shadow_rays            = hc.shadowRays;
+    lout->shadow_node_visits     = hc.nodeVisits;
+    lout->shadow_candidate_tests = hc.candidateTests;
+    lout->shadow_accepted_hits   = hc.acceptedHits;
+    HIPCHK(hipEventElapsedTime(&lout->light_ms, ts.ev[4], ts.ev[5]));
+  }
   if(out)
   {
     std::memset(out, 0, sizeof(*out));
@@ -333,6 +421,27 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
 int mgs_render_traced(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out)
 {
   return guarded("mgs_render_traced", [&] { return mgs_render_traced_impl(s, p, tp, out); });
+}
+
+int mgs_render_traced_lit(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsTraceLightParams* lp, MgsTraceOut* out,
+                          MgsTraceLightOut* lout)
+{
+  return guarded("mgs_render_traced_lit", [&] { return mgs_render_traced_impl(s, p, tp, out, true, lp, lout); });
+}
+
+int mgs_trace_download_shadow_hits(MgsScene s, uint32_t* dst, size_t count)
+{
+  if(!s || !dst)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_shadow_hits: null argument");
+  if(!s->trace.haveLit)
+    return failTrace(MGS_ERR_STATE, "mgs_trace_download_shadow_hits: the handle's last traced frame was not a lit one");
+  const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
+  if(count < n || s->trace.shadowHits.n < n)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_shadow_hits: destination too small, or the last traced frame was not lit at this size");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipMemcpyAsync(dst, s->trace.shadowHits.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return MGS_OK;
 }
 
 int mgs_trace_download_hit_counts(MgsScene s, uint32_t* dst, size_t count)

@@ -339,6 +339,29 @@ struct TraceArgs
   float*                outDepth;   // side outputs, null unless surface_outputs
   uint32_t*             outId;
   float4*               outNormal;
+  float*                outIsoDist;   // a lit frame's inputs of the light pass (mgs_render_traced_lit), null otherwise: the ray
+  float4*               outRadiance;  // parameter of the iso-surface hit (0 = none) and the pixel in fp32 (rgb, 1 - T)
+};
+// the shadow rays' statistics (MgsTraceLightOut)
+struct TraceLightCounters
+{
+  unsigned long long shadowRays, nodeVisits, candidateTests, acceptedHits;
+};
+// what the light pass of a lit traced frame (k_trace_light.hip) receives by value.  Its per-pixel inputs are plain buffers: the
+// primary surface may come from another producer than k_trace.
+struct TraceLightArgs
+{
+  TraceArgs           t;            // hierarchy, frame, proxy, samplesPerPass, image, halfOut as the primary rays had them
+  const float*        isoDist;      // [height][width] ray parameter of the surface, 0 = none (discarded)
+  const uint32_t*     pickId;       // [height][width] global storage id of the picked particle
+  const float4*       normal;       // [height][width] integrated normal (unnormalised) and weight
+  const float4*       radiance;     // [height][width] fp32 radiance and alpha of the primary walk
+  const LightTable*   table;
+  uint32_t*           shadowHits;   // [height][width] accepted shadow hits, summed over the lights
+  TraceLightCounters* lctr;
+  int32_t             shadowsMode;  // MGS_SHADOWS_*
+  int32_t             shFormat;     // storage format of the SH records (read when shadowColorStrength != 0)
+  float               shadowOffset, shadowThreshold, shadowColorStrength;
 };
 
 // the caller's geometry as the compositors' launchers receive it

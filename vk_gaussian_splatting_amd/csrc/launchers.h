@@ -123,6 +123,7 @@ void launchBvhGather(hipStream_t stream, const uint32_t* sortedVals, const float
 void launchBvhLevel(hipStream_t stream, const float4* below, uint32_t nBelow, float4* level, uint32_t nLevel);
 // the traversal (k_trace.hip): one ray per lane, a wave64 = an 8 x 8 pixel tile
 void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat);
+void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameConst& F);  // k_trace_light.hip
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 
 }  // namespace mgs

@@ -465,17 +465,24 @@ struct TracePassState
   DevBuf<TraceCounters> ctr;
   DevBuf<uint32_t>      keys, vals, leafCount;
   DevBuf<float4>        leafBox;
+  // a lit frame's scratch (mgs_render_traced_lit): what k_trace leaves for the light pass, and the light pass's own outputs
+  DevBuf<float>              isoDist;
+  DevBuf<float4>             radiance;
+  DevBuf<uint32_t>           shadowHits;
+  DevBuf<TraceLightCounters> lctr;
   int                   w = 0, h = 0;
-  bool                  have = false;
-  hipEvent_t            ev[4] = {};
+  bool                  have = false, haveLit = false;
+  hipEvent_t            ev[6] = {};  // build begin / end, traversal begin / end, light pass begin / end
   template <class F>
-  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); }
+  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); }
   void release()
   {
     eachBuffer([](auto& b) { b.release(); });
     for(auto& e : ev)
+    {
       if(e) (void)hipEventDestroy(e);
-    ev[0] = ev[1] = ev[2] = ev[3] = nullptr;
+      e = nullptr;
+    }
   }
 };
 

@@ -1,7 +1,8 @@
-// shade_direct.h — the direct shading both the deferred lighting pass (k_light.hip) and the mesh pass (k_mesh.hip) evaluate:
-// wavefrontComputeShadingDirectOnly with wavefrontComputeSpecular (shaders/wavefront.h.slang:233-280,388-403) in their own order of
-// operations, the material and light types it reads, and the small vector helpers.  Device code only; every kernel file that
-// includes it gets its own inlined copy.
+// shade_direct.h — the direct shading the deferred lighting pass (k_light.hip), the mesh pass (k_mesh.hip) and the light pass of a
+// traced frame (k_trace_light.hip) evaluate: wavefrontComputeShadingDirectOnly with wavefrontComputeSpecular
+// (shaders/wavefront.h.slang:233-280,388-403) in their own order of operations, the material and light types it reads, the small
+// vector helpers, and for the traced pass computeLightToSurfaceVector (:33-70) with the shadow's factor on the light's colour.
+// Device code only; every kernel file that includes it gets its own inlined copy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,11 +46,36 @@ __device__ __forceinline__ float attenuate(int mode, float distance, float range
   return attenuation;
 }
 
-// wavefrontComputeShadingDirectOnly (wavefront.h.slang:233-280) with inShadow = false, transmittance = 1
-__device__ __forceinline__ void shadeDirect(const LightDev& light, V3 worldPos, V3 n, const Mat& mat, V3 viewDir, V3& radiance)
+// computeLightToSurfaceVector (wavefront.h.slang:33-70), hard shadows: the direction to the light and its distance; false when a
+// point or spot light is farther away than its range.  The traced pass SKIPS such a light entirely (rgen.slang:1120-1121), ambient
+// term included; the deferred raster pass calls shadeDirect for every light, which adds the ambient term and no more.  A point that
+// coincides with the light divides 0 by 0 as normalize(toLight) does in the reference: the pixel is NaN there and here.
+__device__ __forceinline__ bool lightToSurface(const LightDev& light, V3 worldPos, V3& lightDir, float& lightDist)
+{
+  if(light.type == MGS_LIGHT_DIRECTIONAL)
+  {
+    lightDir  = -load3(light.dirN);
+    lightDist = 1e10f;
+    return true;
+  }
+  const V3 toLight = load3(light.pos) - worldPos;
+  lightDist        = sqrtf(dot3(toLight, toLight));
+  if(lightDist > light.range)
+    return false;
+  lightDir = toLight * (1.0f / lightDist);
+  return true;
+}
+
+// wavefrontComputeShadingDirectOnly (wavefront.h.slang:233-280) with transmittance = 1.  SHADOWED: light.color was multiplied by
+// the shadow ray's transmittance `shadowT` before the call (rgen.slang:1126), and inShadow returns after the ambient term (:252).
+template <bool SHADOWED>
+__device__ __forceinline__ void shadeDirectT(const LightDev& light, V3 worldPos, V3 n, const Mat& mat, V3 viewDir, V3 shadowT,
+                                             bool inShadow, V3& radiance)
 {
   radiance = radiance + mat.ambient;  // ambient once per light, as written
-  const V3 lightColor = load3(light.color);
+  if(SHADOWED && inShadow)
+    return;
+  const V3 lightColor = SHADOWED ? load3(light.color) * shadowT : load3(light.color);
   V3       L;
   V3       lightDiffuse = {0.0f, 0.0f, 0.0f};
   if(light.type == MGS_LIGHT_DIRECTIONAL)
@@ -94,6 +120,11 @@ __device__ __forceinline__ void shadeDirect(const LightDev& light, V3 worldPos, 
   const float specular             = kEnergyConservation * powf(fmaxf(dot3(V, R), 0.0f), kShininess);
   const V3    specularContribution = mat.specular * specular * lightColor * light.intensity;
   radiance                         = radiance + (fragDiffuse + specularContribution);
+}
+// ... with inShadow = false and an unshadowed light: the raster passes
+__device__ __forceinline__ void shadeDirect(const LightDev& light, V3 worldPos, V3 n, const Mat& mat, V3 viewDir, V3& radiance)
+{
+  shadeDirectT<false>(light, worldPos, n, mat, viewDir, V3{1.0f, 1.0f, 1.0f}, false, radiance);
 }
 
 }  // namespace
