@@ -772,7 +772,7 @@ int mgs_sort_keys(MgsScene scene, const MgsFrameParams* params, MgsSortOut* out)
 int mgs_sort_download(MgsScene scene, uint32_t* keys, uint32_t* ids, uint32_t capacity);
 
 /* sort an arbitrary device-resident (key,value) u32 array (LSD radix): the full key width on the frame's single-kernel pass
- * sort (k_osort.hip), partial bit ranges on the generic sort (k_sort.hip)
+ * sort (k_osort_pass.hip), partial bit ranges on the generic sort (k_sort.hip)
  * (keys_device/values_device are overwritten with the result) — used by the sort parity tests
  * and the sorted-Gsplats/s microbenchmark. */
 int mgs_radix_sort_u32(MgsScene scene, void* keys_device, void* values_device, uint32_t count,

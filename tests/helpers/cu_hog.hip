@@ -1,7 +1,7 @@
 // cu_hog.hip — test helper (NOT part of libmgs): a kernel that does nothing but hold compute-unit resources for a while, so that
 // a test can make the key sort's single-kernel passes run OVERSUBSCRIBED: with LDS-heavy workgroups of this kernel resident on
 // every CU, only part of a pass's workgroups find a slot at a time and the rest start as the hogs retire — the situation in
-// which the look-back of k_os_pass leans on "a 1-D grid is dispatched in index order" (k_osort.hip header).  The test asserts a
+// which the look-back of k_os_pass leans on "a 1-D grid is dispatched in index order" (k_osort_pass.hip header).  The test asserts a
 // correct order (or kErrSpinTimeout reported as an error), never a hang.
 // Built in-tree by __graft_entry__.build() into tests/helpers/libcuhog.so; loaded with ctypes.
 #include <hip/hip_runtime.h>

@@ -157,7 +157,7 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
         assert "SORTS_OK" in r.stdout, r.stdout[-3000:]
         out[mode] = [l for l in r.stdout.splitlines() if l.startswith("FRAMES_SHA1")]
         print(mode, [l for l in r.stdout.splitlines() if l.startswith("STATS")])
-    # (gather: the bin rectangles looked up by id instead of riding through the sort above the ids, k_osort.hip)
+    # (gather: the bin rectangles looked up by id instead of riding through the sort above the ids, k_osort_pass.hip)
     assert out["default"] and out["default"] == out["plain"] == out["generic"] == out["gather"]
     assert out["default"] == out["split"]
     # fullproducts: P*V*M without the exact shortcuts of round 5 (products with exact zeros dropped): the same frames to the bit
@@ -165,7 +165,7 @@ def test_key_sort_variants_are_bit_identical_to_the_stable_sort():
     # ballotmasks: the binning's column / row masks by ballots instead of the bit-matrix transpose (k_dbin_count): the same lists
     assert out["default"] == out["ballotmasks"]
     # chain: the sort passes' level-2 look-back as the chain of group prefixes of rounds 3-5 instead of round 6's counted sums
-    # (k_osort.hip: flat level 2; sorts of more than 1 024 partitions always take the chain)
+    # (k_osort_pass.hip: flat level 2; sorts of more than 1 024 partitions always take the chain)
     assert out["default"] == out["chain"]
     # fixedpart / part1024: the sort's partitions fixed at 4 096 pairs / chosen on the device down to 1 024 (default: down to 1 536)
     assert out["default"] == out["fixedpart"] == out["part1024"]
@@ -201,7 +201,7 @@ def test_adaptive_bin_size_is_scheduling_only_and_follows_the_scan_ratio(kind):
 
 def test_key_sort_oversubscribed_by_a_co_running_kernel():
     """The look-back of k_os_pass waits for lower-numbered workgroups and leans on the dispatcher starting a 1-D grid in index
-    order (k_osort.hip header); all partitions of a frame-sized sort are usually resident at once, which hides the question.
+    order (k_osort_pass.hip header); all partitions of a frame-sized sort are usually resident at once, which hides the question.
     Here a second stream fills the compute units with LDS-heavy workgroups that retire at 16 different times
     (tests/helpers/cu_hog.hip), so the passes run in instalments: 18 sorts / frames / stand-alone sorts must equal the
     undisturbed ones bit for bit; a wait that ran into its bound must come back as an error naming kErrSpinTimeout (ADVICE r3:
@@ -249,7 +249,7 @@ def test_depth_keys_cull_and_sort_bit_exact(scene_small, ob, pose, flip):
 @pytest.mark.parametrize("shape", ["one key", "two keys", "few splats", "camera inside", "plane + cloud"])
 def test_frame_sort_degenerate_key_distributions(ob, shape):
     """The frame's key sort never runs its first LSD pass: the project kernels write their slots grouped by the key's low byte
-    and the sort's first kernel gathers in that order through run tables (slot_emit.h, k_osort.hip).  The stand-alone sort's
+    and the sort's first kernel gathers in that order through run tables (slot_emit.h, k_osort_pass.hip).  The stand-alone sort's
     adversarial battery does not go through that path, so here are the frame-path degenerates: every key equal (ONE run of up to
     2048 pairs per slot: the wave-cooperative expansion; every id a tie, resolved in storage order), two key values, a handful of
     splats (one partition spanning hundreds of digit-0 values, most of them empty), the camera inside the cloud (hundreds of values
@@ -290,7 +290,7 @@ def test_frame_sort_degenerate_key_distributions(ob, shape):
     assert so.count == oks.size and so.count > (30 if shape == "few splats" else 30_000)
     if shape == "camera inside":  # keys on both sides of zero: slots that span far more than the 24 values a wave record holds
         top = np.unique(gk >> 16)
-        rank_digit = top.size <= 256 and int(top[-1]) - int(top[0]) < 4095  # what k_os_prepare decides (k_osort.hip)
+        rank_digit = top.size <= 256 and int(top[-1]) - int(top[0]) < 4095  # what foldTop16 decides (k_osort_pass.hip)
         assert top.size > 100 and ((so.reserved[0] == 1 and so.passes == 3) if rank_digit else (so.reserved[0] == 0 and so.passes == 4))
     if shape == "one key":
         assert np.unique(gk).size == 1
@@ -1642,7 +1642,7 @@ def test_full_size_eight_instances_unified_sort():
     assert np.array_equal(part[480:608], full[480:608])
     # a needle of a frustum (0.7 degrees): ~6 800 survivors spread over the 22 775 slots of the project kernels, 0.3 per slot —
     # the sort's first pass gathers a partition of 4096 pairs from more than 8192 slots (the path that searches the prefix of
-    # the slot counts itself, k_osort.hip) and a ragged second one
+    # the slot counts itself, k_osort_prepare.hip) and a ragged second one
     Vn, Pn = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 0.7, 0.1, 2000.0, W, H)
     pn = capi.default_params(W, H)
     capi.set_camera(pn, Vn, Pn, eye)

@@ -1,5 +1,5 @@
-"""Debug-build experiment (csrc/k_osort.hip built with -DMGS_OS_TRACE): per-workgroup phase stamps of the key sort's passes on
-the garden-sized frame.  Usage: MGS_GRAPH=0 MGS_OS_TRACE_FILE=/tmp/o.bin python tools/os_trace.py [pose ...]"""
+"""Debug-build experiment (the key sort, csrc/k_osort_*.hip and osort_launch.hip, built with -DMGS_OS_TRACE): per-workgroup phase
+stamps of the key sort's passes on the garden-sized frame.  Usage: MGS_GRAPH=0 MGS_OS_TRACE_FILE=/tmp/o.bin python tools/os_trace.py [pose ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

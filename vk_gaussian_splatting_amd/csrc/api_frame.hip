@@ -791,7 +791,7 @@ int mgs_frame_stats(MgsScene s, MgsFrameOut* out)
     return MGS_ERR_OVERFLOW;
   }
   if(out->error_flags & kErrSpinTimeout)
-  {  // a look-back wait of the key sort ran into its bound (k_osort.hip): the sorted order, hence the frame, is not to be trusted
+  {  // a look-back wait of the key sort ran into its bound (k_osort_pass.hip): the sorted order, hence the frame, is not to be trusted
     setError("frame: a look-back wait of the key sort gave up (kErrSpinTimeout); the frame is invalid");
     return MGS_ERR_DEVICE;
   }

@@ -272,7 +272,7 @@ static int mgs_instance_add_impl(MgsScene s, MgsSplatSet set, const float m[16],
     total += s->d->sets[I.set].host->size();
   total += set->data->size();
   if(total >= kOsMaxPairs)
-  {  // the reference's ids are u32; this build's key sort carries 30-bit digit prefixes in its look-back words (k_osort.hip)
+  {  // the reference's ids are u32; this build's key sort carries 30-bit digit prefixes in its look-back words (osort_common.h)
     // (ADVICE r4 asked for the generic sort as a fall-back here instead.  Not built: a scene that large cannot be resident — 2^30
     //  splats are >= 107 GB of splat data in the smallest storage formats plus >= 200 B per splat of working set per frame in
     //  flight, beyond the 288 GB of one MI355X — so the limit that binds first is memory, and this one is never the reason.)
@@ -701,7 +701,7 @@ int sizeWorkingSet(MgsScene s)
   // frame that died between the two kernels cannot leak counts into the next scene
   if((rc = s->fb.top16Count.ensure(65536u))) return rc;
   HIPCHK(hipMemset(s->fb.top16Count.p, 0, 65536u * 4u));
-  {  // look-back words of the key sort's passes: zero once, the passes clear them for their successors (k_osort.hip)
+  {  // look-back words of the key sort's passes: zero once, the passes clear them for their successors (osort_launch.hip)
     // (the three sets' offsets depend on the element bound: a re-sized working set starts from zeroed words)
     const size_t words = 3u * osSortStatusWords(osSortMaxParts((uint32_t)total, tuning().osPartMin));
     if((rc = s->fb.osStatus.ensure(words))) return rc;

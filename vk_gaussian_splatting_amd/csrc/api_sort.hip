@@ -73,7 +73,15 @@ void CpuSorter::shutdown()
   started = false;
 }
 
-// the frame's key sort (k_osort.hip): slots of the project kernel -> sorted ids in idsA (keys in keysA when wanted).  Its pass
+// what every launch of the key sort's kernels takes from the scene's device and tuning() (OsLaunch: required, no defaults)
+static void setOsTuning(MgsScene s, OsLaunch& L)
+{
+  L.partMin      = tuning().osPartMin;
+  L.resSlots     = s->osResSlots;
+  L.flatLookback = tuning().osFlat;
+}
+
+// the frame's key sort (osort_launch.hip): slots of the project kernel -> sorted ids in idsA (keys in keysA when wanted).  Its pass
 // elision (sort_plan.h) is on unless MGS_SORT_REMAP=0.  It leaves the project kernels' next dispatch order in prjOrder: fullest
 // slot of this frame first (scheduling only).
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride)
@@ -100,9 +108,7 @@ void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride)
   L.status       = s->fb.osStatus.p;
   L.ctr          = s->fb.ctr.p;
   L.allowRemap   = tuning().sortRemap;
-  L.partMin      = tuning().osPartMin;
-  L.resSlots     = s->osResSlots;
-  L.flatLookback = tuning().osFlat;
+  setOsTuning(s, L);
   if(ride != nullptr && ride->rideShift != 0 && !wantKeys)
   {
     L.rideShift = (uint32_t)ride->rideShift;
@@ -331,7 +337,7 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
   if((rc = hist.ensure(256ull * parts))) return rc;
   if((rc = nDev.ensure(1))) return rc;
   if((rc = plan.ensure(1))) return rc;
-  // a full-width sort runs on the frame key sort's kernels (k_osort.hip, uniform input, four plain passes): the battery of
+  // a full-width sort runs on the frame key sort's kernels (osort_launch.hip: uniform input, four plain passes): the battery of
   // the stand-alone sort tests exercises exactly what the frame uses; partial bit ranges take the generic sort (k_sort.hip).
   // MGS_RAW_SORT=generic forces the generic one for every range.
   // (2^30 pairs or more: the look-back words of k_os_pass hold 30-bit prefixes — the generic sort has no such limit)
@@ -341,7 +347,7 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
     if((rc = s->rs.pairA.ensure(count))) return rc;
     if((rc = s->rs.pairB.ensure(count))) return rc;
     if((rc = s->rs.osPlan.ensure(1))) return rc;
-    // the passes keep the three sets of look-back words zeroed for each other (k_osort.hip); the sets' offsets depend on
+    // the passes keep the three sets of look-back words zeroed for each other (osort_launch.hip); the sets' offsets depend on
     // the count, so a sort of another size starts from freshly zeroed words
     const uint32_t maxParts = osSortMaxParts(count, tuning().osPartMin);
     const size_t   words    = 3u * osSortStatusWords(maxParts);
@@ -376,9 +382,7 @@ int mgs_radix_sort_u32(MgsScene s, void* keysDev, void* valsDev, uint32_t count,
     O.ctr      = s->fb.ctr.p;
     O.status   = s->rs.status.p;
     O.allowRemap = false;
-    O.partMin    = tuning().osPartMin;
-    O.resSlots   = s->osResSlots;
-    O.flatLookback = tuning().osFlat;
+    setOsTuning(s, O);
     HIPCHK(hipMemsetAsync(&s->fb.ctr.p->errorFlags, 0, sizeof(uint32_t), st));  // whatever an earlier frame left there is not this sort's
     launchOsSort(st, O);
   }

@@ -1,6 +1,6 @@
 // k_sort.hip — generic stable LSD radix sort of (u32 key, u32 value) pairs for gfx950: any bit range, device-side count.
 // Users: the record-path pair sort of the binning fallback (> 256 bins) and the stand-alone sort API with a partial bit
-// range.  The frame's depth-key sort is k_osort.hip (single-kernel passes).
+// range.  The frame's depth-key sort is k_osort_pass.hip (single-kernel passes; osort_common.h).
 //
 // Behavioural spec: vrdxCmdSortKeyValueIndirect (3rdparty/vrdx/include/vk_radix_sort.h:73-78,
 // 3rdparty/vrdx/src/vk_radix_sort.cc:262-416): stable, ascending, 8-bit digits, element count read on

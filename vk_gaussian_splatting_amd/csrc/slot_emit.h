@@ -1,4 +1,4 @@
-// slot_emit.h — the hand-over from the project kernels (k_project.hip, k_project_gut.hip) to the frame's key sort (k_osort.hip).
+// slot_emit.h — the hand-over from the project kernels (k_project.hip, k_project_gut.hip) to the frame's key sort (osort_common.h).
 // A project workgroup owns one 2048-splat partition.  After its raster front end it hands the splats that can produce a
 // fragment to the sort in ITS OWN SLOT of the pair array — slot p = entries [2048 p, 2048 p + count_p) — and leaves count_p.
 // Nothing here waits for another workgroup.
@@ -8,7 +8,7 @@
 // while the keys are on chip: where pair (slot s, digit d, i-th of its group) stands after a stable pass on bits 0-7 is
 //     D[d] + sum over slots s' < s of count[s'][d] + i        (D = exclusive scan of the digit totals),
 // a function of the groups' counts alone — so that pass is never run: the sort's first kernel (bits 8-15) reads its dense
-// partitions straight from the slots, in digit-0 order, through k_os_prepare's tables of those sums (k_osort.hip, "virtual
+// partitions straight from the slots, in digit-0 order, through k_os_prepare's tables of those sums (k_osort_pass.hip, "virtual
 // pass 0").  Round 3 wrote the slot in id order and ran pass 0 as a kernel of its own (38 us of a 118 us sort); the ranking
 // it did there (8 ballots per key) is done here instead, and its load / look-back / re-order / scatter are gone.
 //

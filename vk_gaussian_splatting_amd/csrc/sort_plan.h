@@ -1,6 +1,7 @@
 // sort_plan.h — device-resident plans of the radix sorts and the host-side launch descriptors.
 //   k_sort.hip   generic reduce-then-scan LSD sort (any bit range; the record-path pair sort, the stand-alone sort API)
-//   k_osort.hip  the frame's depth-key sort: single-kernel passes with an in-kernel two-level look-back; its pass 0 is virtual
+//   k_osort_prepare.hip, k_osort_pass.hip, osort_launch.hip (shared: osort_common.h)
+//                the frame's depth-key sort: single-kernel passes with an in-kernel two-level look-back; its pass 0 is virtual
 //                (done by the project kernels' hand-over, slot_emit.h)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,7 +47,7 @@ struct SortLaunch
 void launchSortClearPlan(hipStream_t stream, SortPlan* plan);
 void launchRadixSort(hipStream_t stream, const SortLaunch& s);
 
-// ---- the frame's key sort (k_osort.hip) -------------------------------------------------------------------------------
+// ---- the frame's key sort (osort_common.h) ----------------------------------------------------------------------------
 #ifndef MGS_OS_PART
 #define MGS_OS_PART 4096
 #endif
@@ -114,10 +115,10 @@ struct OsLaunch
   FrameCounters*  ctr      = nullptr;  // errorFlags |= kErrSpinTimeout if a look-back wait ever gives up
   bool            allowRemap = true;
   // required: every caller fills these from its scene and tuning() (no defaults here)
-  uint32_t        partMin      = 0;    // smallest partition size the passes may choose on the device (k_osort.hip: osPartOf; Tuning::osPartMin,
+  uint32_t        partMin      = 0;    // smallest partition size the passes may choose on the device (osort_common.h: osPartOf; Tuning::osPartMin,
                                        // default 1 536; kOsPart = fixed partitions); the status words were sized by osSortMaxParts with it
   uint32_t        resSlots     = 0;    // workgroups of a pass the scene's device holds at once: CUs x MGS_OS_WAVES (126 VGPRs, 36-40 KB of LDS)
-  uint32_t        flatLookback = 0;    // != 0: the flat level 2 of the look-back where it applies (k_osort.hip; Tuning::osFlat)
+  uint32_t        flatLookback = 0;    // != 0: the flat level 2 of the look-back where it applies (k_osort_pass.hip; Tuning::osFlat)
 };
 
 uint32_t osSortMaxParts(uint32_t maxElems, uint32_t partMin);
