@@ -1,6 +1,6 @@
 """The scenes of the fragment-count tests, shared by tests/test_fragments_cpu.py (which holds the oracle to the float64 count of
 tests/np_fragments.py and establishes the borderline share and EPS_FRAG from the CPU side alone), tests/test_gpu_fragments.py (which
-holds the compositor to the same counts) and tests/_child_fragments.py.
+holds the compositor to the same counts), tests/_child_fragments.py and tests/_child_fragment_grids.py.
 
 The compositor works on 32x16-px regions (one workgroup), 16x8-px quarters (one wave) and, in the additive-alpha mode, 128x64-px
 bins (one depth-ordered list each).  Every case is chosen for a place where a fragment can get lost or counted twice."""
@@ -109,16 +109,212 @@ def hand_made(clamped=True):
     # 512 = one stage-A round of 256 * MGS_SUM_ENTRIES entries, 513 = one more
     for n, (cx, cy), d in STACKS:
         sp += [(cx, cy, 1.9, 1.6, 0.5, d)] * n
+    return _discs(sp, HW, HH, HAND_EYE_Z)
+
+
+def _discs(sp, w, h, eye_z):
+    """(x px, y px, sigma1 px, sigma2 px, angle, distance) rows -> the arrays of a splat set: flat discs facing a camera on +z whose
+    focal length is h pixels (hand_camera, grid_camera)"""
     a = np.asarray(sp, np.float64)
     d = a[:, 5]
-    unit = d / HH   # world units per pixel at distance d
-    pos = np.stack([(a[:, 0] - HW / 2) * unit, (a[:, 1] - HH / 2) * unit, HAND_EYE_Z - d], 1)
+    unit = d / h   # world units per pixel at distance d
+    pos = np.stack([(a[:, 0] - w / 2) * unit, (a[:, 1] - h / 2) * unit, eye_z - d], 1)
     scale = np.log(np.stack([a[:, 2] * unit, a[:, 3] * unit, np.full(d.shape, 1e-4)], 1))
     rot = np.stack([np.cos(a[:, 4] / 2), np.zeros_like(d), np.zeros_like(d), np.sin(a[:, 4] / 2)], 1)
     n = a.shape[0]
     r = np.random.default_rng(9)
     return dict(positions=pos.astype(np.float32), f_dc=r.standard_normal((n, 3)).astype(np.float32), f_rest=np.zeros((n, 0), np.float32),
                 opacity=np.full(n, 2.0, np.float32), scale=scale.astype(np.float32), rotation=rot.astype(np.float32))
+
+
+# ---- bin grids: one frame per regime of the binning stage (k_dbin_count / k_dbin_scan / k_dbin_emit, the record path of k_bin) ----
+GRID_EYE_Z = 5.0
+OVERSIZED = (900.0, 800.0, 0.17)   # sigma px along / across, angle: both axes at the 2048-px clamp, as in hand_made
+
+
+def grid_camera(w, h):
+    """hand_camera for a frame of w x h px: the focal length is h pixels"""
+    eye = np.array([0.0, 0.0, GRID_EYE_Z], np.float32)
+    return lookat(eye, (0, 0, 0)), persp(0.5, w / h, 0.1, 100.0), eye
+
+
+def _box(s1, s2, angle):
+    """half width and half height in px of the footprint box of a disc (sigma px along / across, angle), as the reference builds its
+    extent basis (threedgs.h.slang:60-121): 0.3 px^2 of dilation, and the 0.1 floor under the discriminant, which gives a small round
+    splat axes of sqrt(8 (sigma^2 + 0.3 +- 0.316)) along (1, 0.316) and across"""
+    c, n = np.cos(angle), np.sin(angle)
+    a, b, d = s1 * s1 * c * c + s2 * s2 * n * n + 0.3, (s1 * s1 - s2 * s2) * c * n, s1 * s1 * n * n + s2 * s2 * c * c + 0.3
+    half = 0.5 * (a + d)
+    t = np.sqrt(max(0.1, half * half - (a * d - b * b)))
+    ev1, ev2 = half + t, half - t
+    e = np.array([1.0 if abs(b) < 0.001 else b, ev1 - a])
+    e /= np.hypot(*e)
+    l1, l2 = min(np.sqrt(8.0 * ev1), 2048.0), min(np.sqrt(8.0 * ev2), 2048.0)
+    return float(np.hypot(e[0] * l1, e[1] * l2)), float(np.hypot(e[1] * l1, e[0] * l2))
+
+
+def grid_case(bins_x, bins_y, bin_w, bin_h, ragged):
+    """A frame of bins_x x bins_y bins of bin_w x bin_h px (ragged: 5 px narrower and 3 px lower, or a (dw, dh) pair: the last bin,
+    region column and tile row are partial) with flat camera-facing discs placed for the binning stage: a splat inside each of a
+    bin (at its centre, and three more layers off it), splats on bin corners and edges and half a pixel to either side
+    (the coded 2x1, 1x2, 2x2 rectangles) and footprints that end between the last pixel centre of a bin and the first of the next,
+    escapes (3x1, 1x3, 3x3, a rectangle over every bin column, one over every bin row, one splat larger than the frame) and centres
+    outside the frame on all four sides.  Every group lies at a distance of its own.  Sizes scale with the bins (bin_h / 16).
+    Returns dict(arrays, W, H, bins, bin_px, tags: group name -> splat indices)."""
+    cut = (5, 3) if ragged is True else (tuple(ragged) if ragged else (0, 0))
+    w, h = bins_x * bin_w - cut[0], bins_y * bin_h - cut[1]
+    s, nb = bin_h / 16.0, bins_x * bins_y
+    sp, tags = [], {}
+
+    def add(tag, *rows):
+        tags.setdefault(tag, []).extend(range(len(sp), len(sp) + len(rows)))
+        sp.extend(rows)
+
+    def mid_x(i):   # the centre of what the frame holds of bin column i
+        return (i * bin_w + min((i + 1) * bin_w, w)) / 2.0
+
+    def mid_y(j):
+        return (j * bin_h + min((j + 1) * bin_h, h)) / 2.0
+
+    # inside every bin (layer 0: at its centre, one bin each), and three more layers a fifth of a bin off the centre, which reach
+    # into the neighbours: four waves of rounds on the larger grids, and a second chunk on those of 256 bins and more
+    sig = [(1.6, 1.6), (2.2, 1.2), (1.4, 2.3)]
+    for layer, (fx, fy) in enumerate(((0.0, 0.0), (0.22, 0.2), (-0.22, 0.15), (0.18, -0.2))):
+        for b in range(nb):
+            s1, s2 = sig[(b + layer) % 3]
+            add("inside" if layer == 0 else "layers", (mid_x(b % bins_x) + fx * bin_w, mid_y(b // bins_x) + fy * bin_h, s1 * s, s2 * s,
+                                                       0.3 + 0.31 * ((b + layer) % 4), 5.0 - 0.02 * layer))
+    # bin corners: 2x2
+    sig = [(1.3, 1.3), (2.7, 1.1), (1.9, 3.1)]
+    corners = sorted({(i, j) for i, j in ((1, 1), (bins_x - 1, bins_y - 1), (bins_x // 2, bins_y // 2)) if 1 <= i < bins_x and 1 <= j < bins_y})
+    for ci, cj in corners:
+        for i, dx in enumerate((0.0, -0.5, 0.5)):
+            for j, dy in enumerate((0.0, -0.5, 0.5)):
+                s1, s2 = sig[(i + j) % 3]
+                add("corner", (ci * bin_w + dx, cj * bin_h + dy, s1 * s, s2 * s, 0.37 * (i + 3 * j), 5.1))
+    # bin edges: 2x1 and 1x2, and footprints that end 0.25 px short of / 0.75 px past the pixel centres on either side of an edge
+    lx, ly = _box(1.3 * s, 1.3 * s, 0.0)
+    if bins_x >= 2:
+        for i in sorted({1, bins_x - 1}):
+            for dx in (0.0, -0.5, 0.5):
+                add("edge_x", (i * bin_w + dx, mid_y(bins_y // 2), 1.3 * s, 1.3 * s, 0.0, 5.2))
+        e, y = float(bin_w), mid_y(bins_y - 1)
+        add("ends_x_1", (e - lx - 0.25, y, 1.3 * s, 1.3 * s, 0.0, 5.25), (e + lx + 0.25, y, 1.3 * s, 1.3 * s, 0.0, 5.25))
+        add("ends_x_2", (e - lx + 0.75, y, 1.3 * s, 1.3 * s, 0.0, 5.25), (e + lx - 0.75, y, 1.3 * s, 1.3 * s, 0.0, 5.25))
+    if bins_y >= 2:
+        for j in sorted({1, bins_y - 1}):
+            for dy in (0.0, -0.5, 0.5):
+                add("edge_y", (mid_x(bins_x // 2), j * bin_h + dy, 1.3 * s, 1.3 * s, 0.0, 5.3))
+        e, x = float((bins_y - 1) * bin_h), mid_x(bins_x - 1)
+        add("ends_y_1", (x, e - ly - 0.25, 1.3 * s, 1.3 * s, 0.0, 5.35), (x, e + ly + 0.25, 1.3 * s, 1.3 * s, 0.0, 5.35))
+        add("ends_y_2", (x, e - ly + 0.75, 1.3 * s, 1.3 * s, 0.0, 5.35), (x, e + ly - 0.75, 1.3 * s, 1.3 * s, 0.0, 5.35))
+    # escapes (more than 2 x 2 bins).  The long ones are tilted off the axes (no BASIS_ULPS needed) and keep sigma1 / sigma2 < 10.
+    i0, j0 = min(bins_x - 3, bins_x // 2), min(bins_y - 3, bins_y // 2)
+    if bins_x >= 3:
+        add("3x1", ((i0 + 1.5) * bin_w, mid_y(min(1, bins_y - 1)), 0.45 * bin_w, 0.05 * bin_w, 0.1, 5.4))
+    if bins_y >= 3:
+        add("1x3", (mid_x(min(1, bins_x - 1)), (j0 + 1.5) * bin_h, 0.45 * bin_h, 0.06 * bin_h, np.pi / 2 - 0.1, 5.5))
+    if bins_x >= 3 and bins_y >= 3:
+        add("3x3", ((i0 + 1.5) * bin_w, (j0 + 1.5) * bin_h, np.sqrt(50.0 * s * s - 0.3), np.sqrt(50.0 * s * s - 0.3), 0.0, 5.6))
+    # every bin column / every bin row: an axis of 0.56 of the frame (the other a tenth of it: on a wide grid the rectangle is
+    # several bin rows high — an eigenvalue ratio under 100 allows no less)
+    if bins_x >= 2:
+        add("all_columns", (w / 2.0 + 1.3, mid_y(bins_y // 2), 0.56 * w / np.sqrt(8.0), 0.56 * w / np.sqrt(8.0) / 9.6, 0.04, 5.7))
+    if bins_y >= 2:
+        add("all_rows", (mid_x(bins_x // 2), h / 2.0 + 1.3, 0.56 * h / np.sqrt(8.0), 0.56 * h / np.sqrt(8.0) / 9.6, np.pi / 2 - 0.04, 5.8))
+    add("oversized", (w / 2.0 + 3.0, h / 2.0 + 2.0) + OVERSIZED + (6.0,))
+    # centres outside the frame whose footprints reach in (the dist stage keeps a centre up to 20 % of the half frame outside)
+    ox, oy = min(5.0, 0.06 * w), min(5.0, 0.06 * h)
+    add("outside", (-ox, 0.4 * h, 5.0 * s, 3.0 * s, 0.3, 4.9), (w + ox, 0.6 * h, 4.0 * s, 4.5 * s, 1.1, 4.9),
+        (0.3 * w, -oy, 3.0 * s, 5.0 * s, 0.5, 4.9), (0.7 * w, h + oy, 4.5 * s, 4.0 * s, 0.8, 4.9))
+    return dict(arrays=_discs(sp, w, h, GRID_EYE_Z), W=w, H=h, bins=(bins_x, bins_y), bin_px=(bin_w, bin_h), tags=tags)
+
+
+# name -> (bins_x, bins_y, ragged): 32x16-px bins (MGS_BIN_SHIFT=1,0; tests/_child_fragment_grids.py).  21x12 (252 bins) is the one
+# grid of sum 33 — the first that takes the ballots by default — which the direct binning takes (17x16 goes to the records)
+GRIDS = {}
+for _bx, _by in ((32, 8), (8, 32), (25, 10), (21, 12), (17, 16), (16, 16), (17, 15), (31, 1), (1, 31), (33, 4), (1, 1)):
+    GRIDS[f"grid_{_bx}x{_by}"] = (_bx, _by, False)
+    GRIDS[f"grid_{_bx}x{_by}_ragged"] = (_bx, _by, (12, 7) if (_bx, _by) == (1, 1) else True)   # (1x1 ragged: 20x9 px)
+RECORD_GRIDS = ("grid_17x16", "grid_33x4")   # no direct binning: 272 bins; 33 bin columns (plain and ragged alike)
+# the stage's default 128x64-px additive-alpha bins, rendered by the default process
+DEFAULT_BIN_GRIDS = {"bins128_16x16": (16, 16), "bins128_32x8": (32, 8)}
+
+# chunks of kDbChunk = 1024 sorted splats and k_dbin_emit's stage of kDbStage = 3072 entries, on the 16x16 grid: stacks of identical
+# footprints, each at a distance of its own (far to near = the sorted stream)
+SW, SH = 512, 256
+_OVER = (SW / 2 + 3.0, SH / 2 + 2.0) + OVERSIZED
+
+
+def _one_bin(bx, by):
+    return (bx * 32 + 16.0, by * 16 + 8.0, 1.6, 1.6, 0.0)
+
+
+def _three_bins(bx, by):   # bins bx .. bx + 2 of row by
+    return ((bx + 1.5) * 32, by * 16 + 8.0, 14.4, 1.6, 0.1)
+
+
+def _four_bins(i, j):      # the bins around corner (i, j)
+    return (i * 32.0, j * 16.0, 1.3, 1.3, 0.0)
+
+
+# name -> [(splats, footprint, distance)], far to near
+STACK_CASES = {
+    # 1 + 400 + 300 + 200 + 123 = 1024 sorted splats: one full chunk; one more, the nearest, is a last chunk of one splat
+    "chunks_1024": [(1, _OVER, 6.0), (400, _one_bin(3, 2), 5.8), (300, _four_bins(9, 5), 5.6), (200, _three_bins(6, 11), 5.4), (123, _one_bin(13, 14), 5.2)],
+    "chunks_1025": [(1, _OVER, 6.0), (400, _one_bin(3, 2), 5.8), (300, _four_bins(9, 5), 5.6), (200, _three_bins(6, 11), 5.4), (123, _one_bin(13, 14), 5.2),
+                    (1, _one_bin(15, 15), 4.6)],
+    "chunks_4097": [(1, _OVER, 6.0), (1500, _one_bin(3, 2), 5.8), (1200, _four_bins(9, 5), 5.6), (800, _three_bins(6, 11), 5.4), (595, _one_bin(13, 14), 5.2),
+                    (1, _one_bin(15, 15), 4.6)],
+    # chunk 0: 1024 x 256 entries (unstaged, every bin's run 1024 long); chunk 1: 1024 x 3 = 3072 = kDbStage (the last staged size,
+    # all escapes); chunk 2: 1023 x 3 + 4 = 3073 (the first unstaged size); chunk 3: 1024 x 1
+    "stage_edge": [(1024, _OVER, 6.0), (1024, _three_bins(2, 3), 5.6), (1023, _three_bins(7, 8), 5.2), (1, _four_bins(12, 12), 5.19),
+                   (1024, _one_bin(5, 12), 4.8)],
+}
+STAGE_EDGE_ENTRIES = [1024 * 256, 3072, 3073, 1024]   # list entries per chunk of "stage_edge"
+
+
+def stack_case(name):
+    sp = []
+    for n, foot, d in STACK_CASES[name]:
+        sp += [foot + (d,)] * n
+    return dict(arrays=_discs(sp, SW, SH, GRID_EYE_Z), W=SW, H=SH, bins=(16, 16), bin_px=(32, 16), tags={"oversized": [0]})
+
+
+GRID_CASES = list(GRIDS) + list(STACK_CASES)   # what tests/_child_fragment_grids.py renders, with 32x16-px bins
+
+
+def bin_rects(table, w, h, bin_w, bin_h):
+    """the bin rectangle (x0, y0, x1, y1) per row of a Fragments.table, from the footprint box alone (the pixel centres inside
+    centre +- the ellipse's bounding box, clipped to the frame), and whether the box has such a pixel at all"""
+    ex, ey = np.hypot(table["b1"][:, 0], table["b2"][:, 0]), np.hypot(table["b1"][:, 1], table["b2"][:, 1])
+    x0, x1 = np.ceil(table["c"][:, 0] - ex - 0.5), np.floor(table["c"][:, 0] + ex - 0.5)
+    y0, y1 = np.ceil(table["c"][:, 1] - ey - 0.5), np.floor(table["c"][:, 1] + ey - 0.5)
+    hit = (x1 >= x0) & (y1 >= y0) & (x1 >= 0) & (x0 <= w - 1) & (y1 >= 0) & (y0 <= h - 1)
+    r = np.stack([np.clip(x0, 0, w - 1) // bin_w, np.clip(y0, 0, h - 1) // bin_h, np.clip(x1, 0, w - 1) // bin_w, np.clip(y1, 0, h - 1) // bin_h], 1)
+    return r.astype(np.int64), hit
+
+
+def unpack_rects(rect):
+    """download_projected's packed rectangles -> int64[n, 4] (x0, y0, x1, y1) in bins"""
+    r = np.asarray(rect, np.uint32).astype(np.int64)
+    return np.stack([r & 255, (r >> 8) & 255, (r >> 16) & 255, r >> 24], 1)
+
+
+def rect_entries(r):
+    """list entries per rectangle: (x1 - x0 + 1) (y1 - y0 + 1)"""
+    return (r[:, 2] - r[:, 0] + 1) * (r[:, 3] - r[:, 1] + 1)
+
+
+def direct_binning_takes(bx, by):
+    """the grids k_dbin_* take (directBinningSupported): at most 32 bins along an axis, 256 bins, binsX + binsY <= 40"""
+    return bx <= 32 and by <= 32 and bx * by <= 256 and bx + by <= 40
+
+
+def bin_grid(w, h, shift_x, shift_y):
+    """the frame's bin grid: bins of (16 << shift_x) x (16 << shift_y) px over 16-px tiles"""
+    tx, ty = (w + 15) // 16, (h + 15) // 16
+    return (tx + (1 << shift_x) - 1) >> shift_x, (ty + (1 << shift_y) - 1) >> shift_y
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------------
@@ -150,6 +346,14 @@ CHILD_CASES = ["dense", "hand_made"]                                 # what test
 @functools.lru_cache(maxsize=None)
 def case(name):
     """name -> dict(sets=[(arrays, transform or None)], cam=(V, P, eye), W, H)"""
+    if name in GRIDS or name in DEFAULT_BIN_GRIDS or name in STACK_CASES:
+        if name in STACK_CASES:
+            g = stack_case(name)
+        elif name in GRIDS:
+            g = grid_case(GRIDS[name][0], GRIDS[name][1], 32, 16, GRIDS[name][2])
+        else:
+            g = grid_case(DEFAULT_BIN_GRIDS[name][0], DEFAULT_BIN_GRIDS[name][1], 128, 64, False)
+        return dict(sets=[(g["arrays"], None)], cam=grid_camera(g["W"], g["H"]), W=g["W"], H=g["H"], bins=g["bins"], bin_px=g["bin_px"], tags=g["tags"])
     if name in ("hand_made", "hand_made_open"):   # "open": without the splat that covers the whole frame, for the coverage test
         return dict(sets=[(hand_made(clamped=name == "hand_made"), None)], cam=hand_camera(), W=HW, H=HH)
     crowded = name in ("crowded", "crowded_opaque")

@@ -115,14 +115,21 @@ def fragments(projected, survivors, W, H, gaussian=False, delta=1e-4, depth=None
     x1 = np.minimum(W - 1, np.ceil(t["c"][:, 0] + pad * ex - 0.5)).astype(np.int64)
     y0 = np.maximum(0, np.floor(t["c"][:, 1] - pad * ey - 0.5)).astype(np.int64)
     y1 = np.minimum(H - 1, np.ceil(t["c"][:, 1] + pad * ey - 0.5)).astype(np.int64)
+    # a stack of identical splats is evaluated once.  `row` below holds every per-splat quantity the loop body reads (centre, basis,
+    # opacity, theta, depth; the window follows from them): extend it if another one enters the loop
+    same, last = None, None
     for i in np.flatnonzero((x1 >= x0) & (y1 >= y0)):
-        yy, xx = np.mgrid[y0[i]:y1[i] + 1, x0[i]:x1[i] + 1]
-        A, alpha = _eval(t["c"][i], t["b1"][i], t["b2"][i], t["opacity"][i], xx + 0.5, yy + 0.5, gaussian)
-        keep, edge = _rule(A, alpha, gaussian, delta, _turn(t["c"][i], t["b1"][i], t["b2"][i], t["theta"][i], xx + 0.5, yy + 0.5) if t["theta"][i] else 0.0)
-        win = (slice(y0[i], y1[i] + 1), slice(x0[i], x1[i] + 1))
-        if D is not None:
-            seen = t["z"][i] <= D[win]
-            keep, edge = keep & seen, edge & seen
+        row = (t["c"][i].tobytes(), t["b1"][i].tobytes(), t["b2"][i].tobytes(), float(t["opacity"][i]), float(t["theta"][i]), float(t["z"][i]))
+        if row != same:
+            yy, xx = np.mgrid[y0[i]:y1[i] + 1, x0[i]:x1[i] + 1]
+            A, alpha = _eval(t["c"][i], t["b1"][i], t["b2"][i], t["opacity"][i], xx + 0.5, yy + 0.5, gaussian)
+            keep, edge = _rule(A, alpha, gaussian, delta, _turn(t["c"][i], t["b1"][i], t["b2"][i], t["theta"][i], xx + 0.5, yy + 0.5) if t["theta"][i] else 0.0)
+            win = (slice(y0[i], y1[i] + 1), slice(x0[i], x1[i] + 1))
+            if D is not None:
+                seen = t["z"][i] <= D[win]
+                keep, edge = keep & seen, edge & seen
+            same, last = row, (keep, edge, alpha, win)
+        keep, edge, alpha, win = last
         out.count[win] += keep
         out.alpha_sum[win] += np.where(keep, alpha, 0.0)
         out.borderline_count[win] += edge

@@ -7,7 +7,8 @@ import pytest
 import fragment_cases as fc
 import np_fragments as nf
 
-ALL_CASES = ["dense", "sparse", "hand_made", "hand_made_open", "opaque_gaussian", "two_instances", "crowded", "crowded_opaque"]
+ALL_CASES = (["dense", "sparse", "hand_made", "hand_made_open", "opaque_gaussian", "two_instances", "crowded", "crowded_opaque"]
+             + fc.GRID_CASES + list(fc.DEFAULT_BIN_GRIDS))
 
 
 def oracle_alpha(ob, ref, order, **kw):
@@ -56,6 +57,69 @@ def test_hand_made_case_covers_what_it_is_made_for(ob):
     assert not ((fr.count >= 449) & ~in_regions).any()
     assert fr.count.min() == 1 and fr.count.max() >= 513  # (the splat at the clamp covers the frame)
     assert (fc.reference(ob, "hand_made_open").fragments().count == 0).mean() > 0.5
+
+
+def rects_by_id(ref):
+    """the bin rectangles of a grid case's splats from the restatement's footprint boxes, indexed by splat id (every splat is drawn)"""
+    c, t = ref.c, ref.fragments().table
+    assert np.array_equal(t["id"], np.arange(ref.total)), "a splat of the case is culled"
+    r, hit = fc.bin_rects(t, c["W"], c["H"], *c["bin_px"])
+    assert hit.all()
+    return r
+
+
+@pytest.mark.parametrize("name", list(fc.GRIDS) + list(fc.DEFAULT_BIN_GRIDS))
+def test_grid_case_reaches_its_regime(ob, name):
+    """each grid case's premise from reference data alone: the bin grid that W, H and the shifts give, whether the direct binning takes
+    it, and the rectangles its groups were placed for (float64 footprint boxes)"""
+    ref = fc.reference(ob, name)
+    c, tags = ref.c, ref.c["tags"]
+    (bx, by), (bw, bh) = c["bins"], c["bin_px"]
+    assert fc.bin_grid(c["W"], c["H"], {32: 1, 128: 3}[bw], {16: 0, 64: 2}[bh]) == (bx, by)
+    if name in fc.GRIDS:
+        assert (bx, by) == fc.GRIDS[name][:2]
+        assert fc.direct_binning_takes(bx, by) == (not name.startswith(fc.RECORD_GRIDS)), name
+    r = rects_by_id(ref)
+    wide, high = r[:, 2] - r[:, 0] + 1, r[:, 3] - r[:, 1] + 1
+    assert tuple(r[tags["oversized"][0]]) == (0, 0, bx - 1, by - 1)
+    inside = {int(r[i, 1] * bx + r[i, 0]) for i in tags["inside"] if wide[i] == 1 and high[i] == 1}
+    assert inside == set(range(bx * by)), inside   # every bin, the four corner bins and bin nb - 1 among them
+    shapes = {"corner": (2, 2), "edge_x": (2, 1), "edge_y": (1, 2), "ends_x_2": (2, 1), "ends_y_2": (1, 2), "3x1": (3, 1), "1x3": (1, 3), "3x3": (3, 3)}
+    for tag, (nx, ny) in shapes.items():
+        for i in tags.get(tag, ()):
+            assert (wide[i], high[i]) == (nx, ny), (tag, i, r[i])
+    for tag in ("ends_x_1", "ends_y_1"):   # one bin, up to the last (from the first) pixel of it
+        for i in tags.get(tag, ()):
+            assert (wide[i], high[i]) == (1, 1), (tag, i, r[i])
+    assert ("corner" in tags) == (bx >= 2 and by >= 2) and ("3x1" in tags) == (bx >= 3) and ("1x3" in tags) == (by >= 3)
+    assert all(wide[i] == bx for i in tags.get("all_columns", ())) and ("all_columns" in tags) == (bx >= 2)
+    assert all(high[i] == by for i in tags.get("all_rows", ())) and ("all_rows" in tags) == (by >= 2)
+    cpx = ref.projected[0]["center_px"][tags["outside"]]
+    assert cpx[0, 0] < 0 and cpx[1, 0] > c["W"] and cpx[2, 1] < 0 and cpx[3, 1] > c["H"]
+    n_esc = int(((wide > 2) | (high > 2)).sum())
+    print(f"fragments {name}: {c['W']}x{c['H']} px, {bx}x{by} bins (sum {bx + by}), {ref.total} splats, {n_esc} escapes, "
+          f"{int(fc.rect_entries(r).sum())} list entries")
+
+
+@pytest.mark.parametrize("name", list(fc.STACK_CASES))
+def test_stack_case_fills_its_chunks(ob, name):
+    """the chunk and stage premises from the oracle's sorted order and the restatement's footprint boxes: the sorted count, and the
+    list entries of every chunk of 1024 sorted splats"""
+    ref = fc.reference(ob, name)
+    assert fc.bin_grid(ref.c["W"], ref.c["H"], 1, 0) == (16, 16)
+    r = rects_by_id(ref)
+    keys, ids = ob.key_cull(ob.make_frame(**ref.frame_kw), ref.inst)
+    _, order = ob.sort_stable(keys, ids)
+    assert order.size == ref.total == sum(n for n, _, _ in fc.STACK_CASES[name])
+    entries = fc.rect_entries(r)[order]
+    per_chunk = [int(entries[i:i + 1024].sum()) for i in range(0, order.size, 1024)]
+    print(f"fragments {name}: {order.size} sorted splats, list entries per chunk {per_chunk}")
+    assert tuple(r[order[0]]) == (0, 0, 15, 15)
+    if name == "stage_edge":
+        assert per_chunk == fc.STAGE_EDGE_ENTRIES and per_chunk[1] == 3072 and per_chunk[2] == 3073 and per_chunk[0] > 3072
+    else:
+        assert order.size == int(name.split("_")[1]) and len(per_chunk) == (order.size + 1023) // 1024
+        assert name == "chunks_1024" or entries[1024 * (len(per_chunk) - 1):].size == 1   # a last chunk of one splat
 
 
 def test_staged_records_per_region(ob):

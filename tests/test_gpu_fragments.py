@@ -13,7 +13,12 @@ whose basis the oracle's own fp32 puts 3.9e-4 rad from the float64 one.
 
 Every walk of k_composite has to arrive at the same number: the additive mode's own walks (per-wave sum walk, the all-saturated
 batches' polynomial walk), the general walk (surface outputs, occluder), and — as coverage — the default mode's early-out walk; on
-both binning paths and with the smallest bins."""
+both binning paths and with the smallest bins.
+
+The last section holds the binning stage to the same counts on every bin grid at which it changes its path: the limits of the direct
+binning (32 bins along an axis, 256 bins, binsX + binsY = 40), masks by ballots and by transpose at their edges, the frames that fall
+to the record path, the three placement paths of k_dbin_emit around its stage of 3072 entries, chunk boundaries, and strips that begin
+and end inside a bin."""
 import os
 import subprocess
 import sys
@@ -156,3 +161,125 @@ def test_binning_paths_give_the_same_counts(default_hashes, env):
     assert r.returncode == 0 and "CHILD_DONE" in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
     got = {l.split()[1]: l.split()[2] for l in r.stdout.splitlines() if l.startswith("ALPHA_SHA1")}
     assert got == default_hashes, (env, got, default_hashes)
+
+
+# ---- every bin-grid regime of the binning stage --------------------------------------------------------------------------------------
+# What the binning hands the compositor, exactly, on the grids where k_dbin_count / k_dbin_emit change their path
+# (fragment_cases.GRIDS, STACK_CASES; test_fragments_cpu.py shows from the CPU side that each case reaches its regime).
+def check_binning(what, name, ref, stats, ids, rects, rides):
+    """the frame's statistics against the sorted splats' own rectangles: every list entry counted once (exactly), the over-sized
+    splat over the whole grid (the frame had the grid the case was built for), the escapes where the rectangles ride"""
+    sorted_count, tile_pairs, escape_count, error_flags = (int(v) for v in stats)
+    bx, by = ref.c["bins"]
+    assert error_flags == 0, (what, error_flags)
+    assert sorted_count == ref.total == ids.size, (what, sorted_count, ref.total)
+    entries = fc.rect_entries(rects)
+    assert tile_pairs == int(entries.sum()), (what, tile_pairs, int(entries.sum()))
+    over = rects[ids == ref.c["tags"]["oversized"][0]]
+    assert over.shape[0] == 1 and tuple(over[0]) == (0, 0, bx - 1, by - 1), (what, over)
+    escapes = int(((rects[:, 2] - rects[:, 0] > 1) | (rects[:, 3] - rects[:, 1] > 1)).sum())
+    if rides:
+        assert escape_count == escapes, (what, escape_count, escapes)
+    per_chunk = [int(entries[i:i + 1024].sum()) for i in range(0, ids.size, 1024)]
+    print(f"fragments {what}: {sorted_count} sorted, {tile_pairs} list entries, {escapes} escapes, entries per chunk {per_chunk}")
+    if name == "stage_edge":
+        assert per_chunk == fc.STAGE_EDGE_ENTRIES, (what, per_chunk)
+
+
+@pytest.mark.parametrize("name", list(fc.DEFAULT_BIN_GRIDS))
+def test_counts_default_bins(scenes, ob, name):
+    """2048x1024 (16x16) and 4096x512 (32x8) at the additive alpha's own 128x64-px bins: no switch set"""
+    ref = fc.reference(ob, name)
+    fr = ref.fragments()
+    alpha, out = gf.render_counts(scenes(name), name)
+    check_counts(f"{name}, default bins", fr, alpha, out)
+    ids, rects = gf.sorted_rects(scenes(name), out)
+    check_binning(name, name, ref, (out.sorted_count, out.tile_pairs, out.escape_count, out.error_flags), ids, rects, rides=True)
+
+
+class Rows:
+    """the pixel rows [y0, y1) of a Fragments, for check_counts"""
+
+    def __init__(self, fr, y0, y1):
+        self.fr, self.y0 = fr, y0
+        self.count, self.borderline_count = fr.count[y0:y1], fr.borderline_count[y0:y1]
+        self.borderline = self.borderline_count > 0
+
+    def covering(self, x, y):
+        return self.fr.covering(x, y + self.y0)
+
+
+@pytest.mark.parametrize("strip", [(0, 1), (1, 6), (5, 7), (7, 64), (8, 12)], ids=lambda s: f"rows_{s[0]}_{s[1]}")
+def test_counts_of_strips_inside_bins(scenes, ob, strip):
+    """tile rows [r0, r1) of the 16x16 default-bin frame (a bin is 4 tile rows: the strips begin and end inside bins, (8, 12) is one
+    bin row): the strip's own pixel rows hold the full frame's counts"""
+    name = "bins128_16x16"
+    fr = fc.reference(ob, name).fragments()
+    assert (fc.case(name)["H"] + 15) // 16 == 64
+    y0, y1 = 16 * strip[0], 16 * strip[1]
+    # the frame buffer outlives a frame: first fill it with a frame that is no count anywhere on the strip's rows (the same frame with
+    # the gaussian on: every pixel lies under the over-sized splat and gets a non-integer alpha), so that a pixel the strip's frame
+    # does not write cannot pass
+    before, _ = gf.render_alpha(scenes(name), name, alpha_mode=capi.ALPHA_SUM)
+    assert (before[y0:y1] != fr.count[y0:y1]).all() and (before[y0:y1] != np.floor(before[y0:y1])).all()
+    alpha, out = gf.render_alpha(scenes(name), name, strip=strip, alpha_mode=capi.ALPHA_SUM, debug_flags=4)
+    check_counts(f"{name}, tile rows {strip}", Rows(fr, y0, y1), alpha[y0:y1], out)
+
+
+GRID_ENVS = {"default": {}, "ballots": {"MGS_DB_TRANSPOSE": "0"}, "gather": {"MGS_RECT_RIDE": "0"}, "split": {"MGS_RIDE_SPLIT": "2"},
+             "records": {"MGS_DIRECT_BIN": "0"}}
+
+
+@pytest.fixture(scope="module")
+def grid_children(tmp_path_factory):
+    """one child per environment (all with 32x16-px bins), started on first use: name -> the child's npz as a dict"""
+    done = {}
+
+    def get(env_id):
+        if env_id not in done:
+            import time
+            child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_child_fragment_grids.py")
+            out = str(tmp_path_factory.mktemp("grids") / f"{env_id}.npz")
+            e = {k: v for k, v in os.environ.items() if k not in ("MGS_DIRECT_BIN", "MGS_BIN_SHIFT", "MGS_DB_TRANSPOSE", "MGS_RECT_RIDE", "MGS_RIDE_SPLIT")}
+            e.update(GRID_ENVS[env_id], MGS_BIN_SHIFT="1,0")
+            t0 = time.perf_counter()
+            r = subprocess.run([sys.executable, child, out], env=e, capture_output=True, text=True, timeout=300)
+            print(f"fragments grids, {env_id}: child took {time.perf_counter() - t0:.1f} s")
+            assert r.returncode == 0 and "CHILD_DONE" in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+            with np.load(out) as z:
+                done[env_id] = {k: z[k] for k in z.files}
+        return done[env_id]
+
+    return get
+
+
+@pytest.mark.parametrize("env_id", list(GRID_ENVS))
+def test_grid_counts(grid_children, ob, env_id):
+    """every grid, chunk and stage case with 32x16-px bins against the float64 counts, and the frame's statistics against the sorted
+    splats' rectangles: masks by transpose or ballots as the grid decides with the rectangles riding (default), ballots everywhere,
+    every rectangle gathered by id (staged without ride), the codes split, and the record + pair-sort path.  A frame of 257 bin
+    columns is refused and the scene's next frame holds its counts."""
+    got = grid_children(env_id)
+    for name in fc.GRID_CASES:
+        ref = fc.reference(ob, name)
+        what = f"{name}, {env_id}"
+        check_counts(what, ref.fragments(), got[name + "/alpha"])
+        rides = env_id in ("default", "ballots", "split") and fc.direct_binning_takes(*ref.c["bins"])
+        check_binning(what, name, ref, got[name + "/stats"], got[name + "/ids"], got[name + "/rects"], rides)
+    # the refused frame: the buffer held a frame that is no count anywhere (the gaussian on) when it was refused, the frame after it
+    # holds the counts again
+    first = fc.GRID_CASES[0]
+    fr = fc.reference(ob, first).fragments()
+    assert int(got["invalid/code"]) == capi.ERR_INVALID_ARG
+    assert (got["invalid/alpha_before"] != fr.count).all()
+    check_counts(f"{first}, {env_id}, after the refused frame", fr, got["invalid/alpha_after"])
+    assert np.array_equal(got["invalid/alpha_after"].view(np.uint32), got[first + "/alpha"].view(np.uint32))
+
+
+def test_grid_counts_identical_across_settings(grid_children):
+    """the five settings' alpha planes are the same bit for bit"""
+    base = grid_children("default")
+    for env_id in GRID_ENVS:
+        got = grid_children(env_id)
+        for name in fc.GRID_CASES:
+            assert np.array_equal(got[name + "/alpha"].view(np.uint32), base[name + "/alpha"].view(np.uint32)), (env_id, name)
