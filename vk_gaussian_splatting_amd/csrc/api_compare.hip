@@ -6,7 +6,7 @@
 // (ImageCompare, src/image_compare.cpp)
 // The capture, the planes of the FLIP reference passes and the composite output belong to the handle; nothing here is touched by
 // a frame, and a frame touches nothing here.
-// (CmpImage::fmt is the compositors' output mode, targetLayout().half; a capture keeps its pixel size next to it)
+// (CmpImage::fmt is the compositors' output mode, targetLayout().fmt; a capture keeps its pixel size next to it)
 
 // the handle's last complete frame as a compare image, or the reason there is none
 static int cmpCurrentImage(MgsScene s, const char* who, CmpImage& img)
@@ -25,7 +25,7 @@ static int cmpCurrentImage(MgsScene s, const char* who, CmpImage& img)
   img.p   = s->fb.image.p;
   img.w   = q.width;
   img.h   = q.height;
-  img.fmt = targetLayout(q.target_format).half;
+  img.fmt = targetLayout(q.target_format).fmt;
   return MGS_OK;
 }
 

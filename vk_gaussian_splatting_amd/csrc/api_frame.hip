@@ -123,88 +123,6 @@ static int pairSortBits(int nTiles)
   return ((bits + 7) / 8) * 8;
 }
 
-// the frame's four small kernels (C names, as a profile lists them)
-extern "C" {
-__global__ void k_set_plan_n(SortPlan* plan, FrameCounters* ctr, uint32_t n)
-{
-  plan->n         = n;
-  plan->finalSel  = 0;
-  plan->passesRun = 0;
-  ctr->sortedCount = n;
-}
-__global__ void k_fill_u32(uint32_t* p, uint32_t v, uint32_t n)
-{
-  for(uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    p[i] = v;
-}
-// post.comp.slang:29-43: main = lerp(main, aux1, 1 / (frameSampleId + 1)) — aux1 is the frame just rendered, main the
-// accumulated image.  Here the accumulator is a separate fp32 image and the result is written back over the frame in the
-// target's format, so the caller reads the running mean where it reads every frame.
-__global__ void k_post_accumulate(const FrameArgs* __restrict__ Ap, float4* __restrict__ acc, void* __restrict__ image, int halfOut)
-{
-  const FrameConst& F  = Ap->f;
-  const int         y0 = F.stripRow0 * kTilePx, y1 = min(F.stripRow1 * kTilePx, F.height);
-  const size_t      n  = (size_t)(y1 - y0) * (size_t)F.width;
-  const float       a  = 1.0f / (float)(F.frameSampleId + 1);
-  for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-  {
-    const size_t o = (size_t)y0 * F.width + i;
-    float4       c;
-    if(halfOut == 1)
-    {
-      const uint2   pk = reinterpret_cast<const uint2*>(image)[o];
-      const float2  lo = __half22float2(*reinterpret_cast<const __half2*>(&pk.x)), hi = __half22float2(*reinterpret_cast<const __half2*>(&pk.y));
-      c = make_float4(lo.x, lo.y, hi.x, hi.y);
-    }
-    else if(halfOut == 2)
-    {
-      const uint32_t pk = reinterpret_cast<const uint32_t*>(image)[o];
-      c = make_float4((float)(pk & 255u) / 255.0f, (float)((pk >> 8) & 255u) / 255.0f, (float)((pk >> 16) & 255u) / 255.0f, (float)(pk >> 24) / 255.0f);
-    }
-    else
-      c = reinterpret_cast<const float4*>(image)[o];
-    float4 m = acc[o];
-    if(F.frameSampleId <= 0)
-      m = c;  // lerp(main, aux1, 1) without touching what the accumulator held (it may be uninitialised)
-    else
-    {  // lerp(x, y, s) = x + s * (y - x)
-      m.x = m.x + a * (c.x - m.x);
-      m.y = m.y + a * (c.y - m.y);
-      m.z = m.z + a * (c.z - m.z);
-      m.w = m.w + a * (c.w - m.w);
-    }
-    acc[o] = m;
-    if(halfOut == 1)
-    {
-      const __half2 lo = __floats2half2_rn(m.x, m.y), hi = __floats2half2_rn(m.z, m.w);
-      uint2         pk;
-      pk.x = *reinterpret_cast<const uint32_t*>(&lo);
-      pk.y = *reinterpret_cast<const uint32_t*>(&hi);
-      reinterpret_cast<uint2*>(image)[o] = pk;
-    }
-    else if(halfOut == 2)
-    {
-      auto q8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-      reinterpret_cast<uint32_t*>(image)[o] = q8(m.x) | (q8(m.y) << 8) | (q8(m.z) << 16) | (q8(m.w) << 24);
-    }
-    else
-      reinterpret_cast<float4*>(image)[o] = m;
-  }
-}
-__global__ void k_iota_u32(uint32_t* p, uint32_t n)
-{
-  for(uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    p[i] = i;
-}
-}  // extern "C"
-
-namespace mgs {
-void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* accum, void* image, int halfOut)
-{
-  hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, stream, dArgs, accum, image, halfOut);
-}
-}  // namespace mgs
-
 // The frame image, side outputs and accumulator of a frame; one made by the frame graph (mgs_render) also sizes its range table
 // and names the occluder depth it is tested against, one made outside it (mgs_render_traced) has neither.  Captured frames that
 // point at a buffer that moved are dropped.
@@ -356,7 +274,7 @@ struct FramePass
   MgsScene              s;
   const MgsFrameParams* p;
   const FrameArgs*      A;
-  int                   half;  // compositor output mode (targetLayout)
+  int                   fmt;   // the image's format as the kernels name it (targetLayout)
   bool                  gut, lit, cpuMode;
   Occluder              occ;
   uint32_t              nTiles;  // lists (and ranges) exist per bin
@@ -427,8 +345,8 @@ static int issueSort(const FramePass& fp, hipStream_t st)
     HIPCHK(hipMemcpyAsync(s->fb.idsA.p, s->cpu.storageIds.data(), (size_t)s->d->totalSplats * 4, hipMemcpyHostToDevice, st));
   }
   else  // no result yet: the reference draws with whatever the index buffer holds; we use identity order
-    hipLaunchKernelGGL(k_iota_u32, dim3(1024), dim3(256), 0, st, s->fb.idsA.p, s->d->totalSplats);
-  hipLaunchKernelGGL(k_set_plan_n, dim3(1), dim3(1), 0, st, &s->fb.plans.p->keys, s->fb.ctr.p, s->d->totalSplats);
+    launchIotaU32(st, s->fb.idsA.p, s->d->totalSplats);
+  launchSetPlanN(st, &s->fb.plans.p->keys, s->fb.ctr.p, s->d->totalSplats);
   return MGS_OK;
 }
 
@@ -521,7 +439,7 @@ static int issueFrame(const FramePass& fp, bool withEvents)
     launchFrameInit(st, fb.ranges.p, fp.nTiles);  // record path: tiles without entries keep an empty range
   if(withEvents) HIPCHK(hipEventRecord(fev[6], st));  // MGS_STAGE_CULL ends here; it is part of MGS_STAGE_PROJECT too
   if(fp.cpuMode)  // rejected splats must look empty to the binning stage: rect with x0 > x1
-    hipLaunchKernelGGL(k_fill_u32, dim3(1024), dim3(256), 0, st, fb.rect.p, 1u, s->d->totalSplats);
+    launchFillU32(st, fb.rect.p, 1u, s->d->totalSplats);
   const ProjectLaunch P = projectLaunch(s, *fp.A, true, !fp.cpuMode);
   if(fp.gut)
     launchProjectGut(st, P);
@@ -544,7 +462,7 @@ static int issueFrame(const FramePass& fp, bool withEvents)
   C.rec        = fb.rec.p;
   C.recGut     = fb.recGut.p;
   C.image      = fb.image.p;
-  C.halfOut    = fp.half;
+  C.fmt        = fp.fmt;
   C.shFormat   = s->d->shFormat;
   C.ctr        = fb.ctr.p;
   C.outDepth   = F.surfaceOutputs ? s->surf.depth.p : nullptr;
@@ -570,11 +488,11 @@ static int issueFrame(const FramePass& fp, bool withEvents)
     L.width  = F.width;
     L.row0   = F.stripRow0 * kTilePx;
     L.row1   = std::min(F.stripRow1 * kTilePx, F.height);
-    launchLight(st, L, fp.half);
+    launchLight(st, L, fp.fmt);
     if(withEvents) HIPCHK(hipEventRecord(fev[8], st));
   }
   if(F.temporalSampling)
-    hipLaunchKernelGGL(k_post_accumulate, dim3(2048), dim3(256), 0, st, fb.dArgs.p, fb.accum.p, fb.image.p, fp.half);
+    launchPostAccumulate(st, fb.dArgs.p, fb.accum.p, fb.image.p, fp.fmt);
   if(withEvents) HIPCHK(hipEventRecord(fev[5], st));
   return MGS_OK;
 }
@@ -589,7 +507,7 @@ static GraphCache::Key graphKey(const FramePass& fp)
   std::memcpy(&isoBits, &F.depthIsoThreshold, 4);
   // everything the compositor receives by value (CompositeArgs) must be part of the key
   const int32_t kv[16] = {F.width, F.height, F.stripRow0, F.stripRow1, F.binShiftX, F.binShiftY, F.partitionCull, F.alphaMode,
-                          F.debugFlags & (2 | 4), F.surfaceOutputs, fp.half, F.nInstances, F.shDegree, isoBits,
+                          F.debugFlags & (2 | 4), F.surfaceOutputs, fp.fmt, F.nInstances, F.shDegree, isoBits,
                           F.pipeline, F.stochastic | (F.dofMode << 1) | (F.temporalSampling << 2) | ((F.pipeline == 1 && F.kernelDegree != 2) ? 8 : 0) |
                               ((F.pipeline == 1 && F.normalMethod == 1) ? 16 : 0) |
                               (F.lightingMode << 5) |  // 0..2: the lighting pass is a launch of its own; what it gets by value is in this key or moves with the buffers
@@ -674,7 +592,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   fp.s       = s;
   fp.p       = p;
   fp.A       = &A;
-  fp.half    = targetLayout(p->target_format).half;
+  fp.fmt     = targetLayout(p->target_format).fmt;
   fp.gut     = p->pipeline == MGS_PIPELINE_3DGUT;
   fp.lit     = p->lighting_mode != MGS_LIGHTING_DISABLED;
   fp.cpuMode = p->sort_mode == MGS_SORT_CPU_ASYNC;

@@ -338,7 +338,7 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   L.minTransmittance  = t.min_transmittance;
   L.depthIsoThreshold = t.depth_iso_threshold;
   L.image             = s->fb.image.p;
-  L.halfOut           = targetLayout(p->target_format).half;
+  L.fmt               = targetLayout(p->target_format).fmt;
   L.hitCount          = ts.hitCount.p;
   L.outDepth          = F.surfaceOutputs ? s->surf.depth.p : nullptr;
   L.outId             = F.surfaceOutputs ? s->surf.id.p : nullptr;
@@ -369,7 +369,7 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
     HIPCHK(hipEventRecord(ts.ev[5], st));
   }
   if(F.temporalSampling)
-    launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.halfOut);
+    launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.fmt);
   if(!lit)
   {
     HIPCHK(hipEventRecord(ts.ev[3], st));

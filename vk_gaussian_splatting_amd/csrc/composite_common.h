@@ -1,8 +1,9 @@
-// composite_common.h — what the compositors share: k_composite's mode bits, the grid size of the packed compositors (k_composite.hip,
-// k_composite_gut.hip) and the store of a finished pixel (k_composite.hip, k_light.hip).
+// composite_common.h — what the compositors share: k_composite's mode bits and the grid size of the packed compositors (k_composite.hip,
+// k_composite_gut.hip).  A finished pixel goes into the frame through target_pixel.h.
 #pragma once
-#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
+
+#include "target_pixel.h"
 
 namespace mgs {
 
@@ -28,26 +29,6 @@ inline int compositeRegionGrid(const Args& F)
 {
   const int nBins = F.binsX * F.binsY;
   return ((nBins + 7) / 8) * (1 << (F.binShiftX - 1 + F.binShiftY)) * 8;  // a multiple of 8: the same count on every XCD
-}
-
-// ---- a finished pixel into the frame: halfOut 0 RGBA32F, 1 RGBA16F, 2 RGBA8 UNORM (clamp, scale, round to nearest) -----------------
-__device__ __forceinline__ void storePixel(void* image, int halfOut, size_t o, float r, float g, float b, float a)
-{
-  if(halfOut == 1)
-  {
-    const __half2 lo = __floats2half2_rn(r, g), hi = __floats2half2_rn(b, a);
-    uint2         pk;
-    pk.x = *reinterpret_cast<const uint32_t*>(&lo);
-    pk.y = *reinterpret_cast<const uint32_t*>(&hi);
-    reinterpret_cast<uint2*>(image)[o] = pk;
-  }
-  else if(halfOut == 2)
-  {
-    auto q8 = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-    reinterpret_cast<uint32_t*>(image)[o] = q8(r) | (q8(g) << 8) | (q8(b) << 16) | (q8(a) << 24);
-  }
-  else
-    reinterpret_cast<float4*>(image)[o] = make_float4(r, g, b, a);
 }
 
 }  // namespace mgs

@@ -9,6 +9,12 @@ constexpr int kMaxInlineInstances = 16;   // SH-table entries the compositor car
 constexpr int kMaxLights          = 64;   // == MGS_MAX_LIGHTS: entries of the scene's light table (LightTable)
 constexpr int kTilePx             = 16;  // compositing tile edge in pixels (one workgroup; 8x8 pixels per wave)
 
+// the frame image's pixel format as the kernels and their launch structs carry it (`fmt`; scene_state.h: targetLayout() maps
+// MgsFrameParams::target_format to it; CmpImage::fmt has the same numbering); target_pixel.h loads and stores a pixel in it
+constexpr int kTargetF32 = 0;  // RGBA32F
+constexpr int kTargetF16 = 1;  // RGBA16F
+constexpr int kTargetU8  = 2;  // RGBA8 UNORM, linear
+
 // error bits reported through MgsFrameOut.error_flags
 enum : uint32_t {
   kErrPairOverflow  = 1u << 0,  // tile-pair capacity exceeded
@@ -334,7 +340,7 @@ struct TraceArgs
   int32_t               samplesPerPass, maxPasses;
   float                 minTransmittance, depthIsoThreshold;
   void*                 image;
-  int32_t               halfOut;
+  int32_t               fmt;
   uint32_t*             hitCount;   // [height][width]
   float*                outDepth;   // side outputs, null unless surface_outputs
   uint32_t*             outId;
@@ -351,7 +357,7 @@ struct TraceLightCounters
 // primary surface may come from another producer than k_trace.
 struct TraceLightArgs
 {
-  TraceArgs           t;            // hierarchy, frame, proxy, samplesPerPass, image, halfOut as the primary rays had them
+  TraceArgs           t;            // hierarchy, frame, proxy, samplesPerPass, image, fmt as the primary rays had them
   const float*        isoDist;      // [height][width] ray parameter of the surface, 0 = none (discarded)
   const uint32_t*     pickId;       // [height][width] global storage id of the picked particle
   const float4*       normal;       // [height][width] integrated normal (unnormalised) and weight

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "compare_types.h"
+#include "target_pixel.h"
 
 #pragma clang fp contract(off)
 
@@ -36,18 +37,7 @@ struct C3
 __device__ __forceinline__ float4 cmpLoad(const CmpImage& im, int x, int y)
 {
   const size_t o = (size_t)y * (size_t)im.w + (size_t)x;
-  if(im.fmt == 1)
-  {
-    const uint2  pk = reinterpret_cast<const uint2*>(im.p)[o];
-    const float2 lo = __half22float2(*reinterpret_cast<const __half2*>(&pk.x)), hi = __half22float2(*reinterpret_cast<const __half2*>(&pk.y));
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  }
-  if(im.fmt == 2)
-  {
-    const uint32_t pk = reinterpret_cast<const uint32_t*>(im.p)[o];
-    return make_float4((float)(pk & 255u) / 255.0f, (float)((pk >> 8) & 255u) / 255.0f, (float)((pk >> 16) & 255u) / 255.0f, (float)(pk >> 24) / 255.0f);
-  }
-  return reinterpret_cast<const float4*>(im.p)[o];
+  return loadPixel(im.p, im.fmt, o);
 }
 
 // Texture2D::Load outside the image: zero (robust image access)

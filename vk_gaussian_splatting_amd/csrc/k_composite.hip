@@ -91,7 +91,7 @@ template <int MODE, int SHF>
 __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const std::conditional_t<occ_lds(MODE), CompositeArgsOcc, CompositeArgs> F, const uint2* __restrict__ ranges,
                                                    const uint32_t* __restrict__ valX, const uint32_t* __restrict__ valY,
                                                    const SortPlan* __restrict__ plan, const SplatRec* __restrict__ rec,
-                                                   void* __restrict__ outImage, int halfOut, FrameCounters* __restrict__ ctr,
+                                                   void* __restrict__ outImage, int fmt, FrameCounters* __restrict__ ctr,
                                                    float* __restrict__ outDepth, uint32_t* __restrict__ outSplatId,
                                                    const FrameArgs* __restrict__ Ap, float4* __restrict__ outNormal)
 {
@@ -794,7 +794,7 @@ __global__ __launch_bounds__(256, MGS_CMP_WAVES) void k_composite(const std::con
             ao += bg.w;
         }
       }
-      storePixel(outImage, halfOut, o, r, g, b, ao);
+      storePixel(outImage, fmt, o, r, g, b, ao);
       if constexpr(surf)
       {
         outDepth[o]   = h ? pickZ.y : pickZ.x;
@@ -841,7 +841,7 @@ static void launchCompositeMode(hipStream_t stream, const CompositeLaunch& L, co
 {
 #define MGS_CMP_SHF(SHF)                                                                                                      \
   hipLaunchKernelGGL((k_composite<MODE, SHF>), dim3(grid), dim3(256), 0, stream, C, L.ranges, L.valX, L.valY, L.planPairs, L.rec, \
-                     L.image, L.halfOut, L.ctr, L.outDepth, L.outSplatId, L.dArgs, L.outNormal)
+                     L.image, L.fmt, L.ctr, L.outDepth, L.outSplatId, L.dArgs, L.outNormal)
   switch(L.shFormat)
   {
     case 0: MGS_CMP_SHF(0); break;

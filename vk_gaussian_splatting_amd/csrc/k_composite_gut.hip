@@ -22,43 +22,6 @@
 
 namespace mgs {
 
-// world-space ray direction of the pixel whose centre is (pcx, pcy) (threedgut_raster.frag.slang:101-111); false: outside the
-// fisheye's field of view (the fragment is discarded)
-__device__ __forceinline__ bool gutPixelRay(const FrameConst& F, float pcx, float pcy, float& dxw, float& dyw, float& dzw)
-{
-  const float* Vi = F.viewInv;
-  float        cx, cy, cz;
-  bool         rayOk = true;
-  if(F.cameraModel == 1)
-  {  // generateFisheyeRay(position.xy, viewport, fovRad, principal 0, viewInverse), cameras.h.slang:46-82
-    const float u = (pcx / ((float)F.width - 1.0f)) * 2.0f - 1.0f, v = (pcy / ((float)F.height - 1.0f)) * 2.0f - 1.0f;
-    const float r = sqrtf(u * u + v * v);
-    rayOk         = !(r > 1.0f);
-    float phiCos  = fabsf(r) > 1e-9f ? u / r : 0.0f;
-    phiCos        = fminf(fmaxf(phiCos, -1.0f), 1.0f);
-    float phi     = acosf(phiCos);
-    phi           = v < 0.0f ? -phi : phi;
-    const float theta = r * F.fovRad * 0.5f;
-    cx = cosf(phi) * sinf(theta);
-    cy = -sinf(phi) * sinf(theta);
-    cz = -cosf(theta);
-  }
-  else
-  {  // generatePinholeRay(position.xy, float2(0.5), ...): the 0.5 is added to SV_Position, as the reference writes it
-    const float ux = ((pcx + 0.5f) / (float)F.width) * 2.0f - 1.0f, uy = ((pcy + 0.5f) / (float)F.height) * 2.0f - 1.0f;
-    const float* Pi = F.projInv;
-    cx = Pi[0] * ux + Pi[4] * uy + Pi[8] + Pi[12];
-    cy = Pi[1] * ux + Pi[5] * uy + Pi[9] + Pi[13];
-    cz = Pi[2] * ux + Pi[6] * uy + Pi[10] + Pi[14];
-  }
-  dxw = Vi[0] * cx + Vi[4] * cy + Vi[8] * cz;
-  dyw = Vi[1] * cx + Vi[5] * cy + Vi[9] * cz;
-  dzw = Vi[2] * cx + Vi[6] * cy + Vi[10] * cz;
-  const float l = rsqrtf(dxw * dxw + dyw * dyw + dzw * dzw);
-  dxw *= l; dyw *= l; dzw *= l;
-  return rayOk;
-}
-
 // ---- compositor: one workgroup per 16x16 tile, one pixel per thread -------------------------------------------------------
 constexpr int kGutBatch = 256;  // list entries scanned per round == staging capacity
 
@@ -80,7 +43,7 @@ template <int SHF, int XT, bool OCC = false, class... OccArg>
 __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restrict__ Ap, const uint2* __restrict__ ranges,
                                                        const uint32_t* __restrict__ valX, const uint32_t* __restrict__ valY,
                                                        const SortPlan* __restrict__ plan, const GutRec* __restrict__ rec,
-                                                       void* __restrict__ outImage, int halfOut, FrameCounters* __restrict__ ctr,
+                                                       void* __restrict__ outImage, int fmt, FrameCounters* __restrict__ ctr,
                                                        float* __restrict__ outDepth, uint32_t* __restrict__ outSplatId,
                                                        float4* __restrict__ outNormal, const OccArg... occArg)
 {
@@ -123,18 +86,7 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
   {
     seedPx = rngXxhash32((uint32_t)px, (uint32_t)py, (uint32_t)F.frameSampleId);  // int(position.x), int(position.y), frameSampleId
     if(F.dofMode != 0)
-    {
-      uint32_t    seed = seedPx;
-      const float r1 = rngRand(seed) * 6.28318530717958647692f, r2 = rngRand(seed) * F.aperture;
-      const float* Vi = F.viewInv;  // camRight = mul(float4(1,0,0,0), viewInverse), camUp = mul(float4(0,1,0,0), viewInverse)
-      const float c = cosf(r1), sn = sinf(r1), sq = sqrtf(r2);
-      lensX = (c * Vi[0] + sn * Vi[4]) * sq;
-      lensY = (c * Vi[1] + sn * Vi[5]) * sq;
-      lensZ = (c * Vi[2] + sn * Vi[6]) * sq;
-      float fx = dxw * F.focusDist - lensX, fy = dyw * F.focusDist - lensY, fz = dzw * F.focusDist - lensZ;
-      const float l = rsqrtf(fx * fx + fy * fy + fz * fz);
-      dxw = fx * l; dyw = fy * l; dzw = fz * l;
-    }
+      gutLensSample<false>(F, seedPx, lensX, lensY, lensZ, dxw, dyw, dzw);
   }
   const bool  early   = F.alphaMode == 0;
   const bool  noGauss = (F.debugFlags & 4) != 0;
@@ -166,22 +118,16 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
       r1 = rp[1];
     }
     const bool     ok  = have && fabsf(r0.x - bcx) <= r1.z + 7.5f && fabsf(r0.y - bcy) <= r1.w + 7.5f;
-    const uint64_t bal = __ballot(ok);
-    if(lane == 0)
-      s_wc[w] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t base = 0;
-    if(w > 0) base += s_wc[0];
-    if(w > 1) base += s_wc[1];
-    if(w > 2) base += s_wc[2];
-    const uint32_t fill = s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
+    uint32_t       fill;
+    const uint32_t pos = gutCompactSlot(ok, s_wc, lane, w, fill);
     if(ok)
     {
-      const uint32_t pos = base + lanesBelow(bal);
       const float4*  rp  = reinterpret_cast<const float4*>(rec + g);
       const float4   r2 = rp[2], r3 = rp[3], r4 = rp[4];
       float4         c5 = rp[5];
-      // deferred shading (mesh.slang:142-148): base colour + SH in the splat's model coordinates, once per staged record
+      // deferred shading (mesh.slang:142-148): base colour + SH in the splat's model coordinates, once per staged record.  The same
+      // text as in k_composite_gut2, written out in both: as a shared function it changes the VGPR count of this kernel's
+      // XT >= 2 instantiations, which use I and li below
       int k = 0;
       for(int i = 1; i < F.nInstances; ++i)
         if(g >= Ap->inst[i].globalOffset)
@@ -275,18 +221,8 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
       const float dist2 = (kx * kx + ky * ky + kz * kz) * gRcp(gx * gx + gy * gy + gz * gz);
       float resp = __expf(-0.5f * dist2);                            // quadratic kernel, :127-131
       if constexpr(XT >= 2)
-      {  // particleRayMaxKernelResponse<KERNEL_DEGREE>, threedgrt.h.slang:83-127 (its argument is the squared distance)
-        switch(F.kernelDegree)
-        {
-          case 8: resp = __expf(-0.000685871056241f * (dist2 * dist2) * (dist2 * dist2)); break;
-          case 5: resp = __expf(-0.0185185185185f * dist2 * dist2 * sqrtf(dist2)); break;
-          case 4: resp = __expf(-0.0555555555556f * dist2 * dist2); break;
-          case 3: resp = __expf(-0.166666666667f * dist2 * sqrtf(dist2)); break;
-          case 1: resp = __expf(-1.5f * sqrtf(dist2)); break;
-          case 0: resp = fmaxf(1.0f + -0.329630334487f * sqrtf(dist2), 0.0f); break;
-          default: break;
-        }
-      }
+        if(F.kernelDegree != 2)  // degree 2 is the line above (kernelResponse's default); calling without the test changes the VGPR count
+          resp = kernelResponse(F.kernelDegree, dist2);
       const float al    = fminf(F.alphaClamp, resp * c4.w);          // :263
       bool        hit   = inQuad && resp > a1.z && T >= tMin;
       if constexpr(OCC)
@@ -401,22 +337,7 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
       outNormal[pix]  = make_float4(nx, ny, nz, 1.0f - ((inside && rayOk) ? T : 1.0f));
     }
   }
-  // (not storePixel of composite_common.h: this kernel takes every format but 0 and 1 as RGBA8, and its code stays as it is)
-  if(halfOut == 1)
-  {
-    const __half2 lo = __floats2half2_rn(cr, cg), hi2 = __floats2half2_rn(cb, alphaOut);
-    uint2         o;
-    o.x = *reinterpret_cast<const uint32_t*>(&lo);
-    o.y = *reinterpret_cast<const uint32_t*>(&hi2);
-    reinterpret_cast<uint2*>(outImage)[pix] = o;
-  }
-  else if(halfOut == 0)
-    reinterpret_cast<float4*>(outImage)[pix] = make_float4(cr, cg, cb, alphaOut);
-  else
-  {
-    auto q = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-    reinterpret_cast<uint32_t*>(outImage)[pix] = q(cr) | (q(cg) << 8) | (q(cb) << 16) | (q(alphaOut) << 24);
-  }
+  storePixel(outImage, fmt, pix, cr, cg, cb, alphaOut);
 }
 
 
@@ -436,7 +357,7 @@ template <int SHF, int XT>
 __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restrict__ Ap, const uint2* __restrict__ ranges,
                                                         const uint32_t* __restrict__ valX, const uint32_t* __restrict__ valY,
                                                         const SortPlan* __restrict__ plan, const GutRec* __restrict__ rec,
-                                                        void* __restrict__ outImage, int halfOut, FrameCounters* __restrict__ ctr)
+                                                        void* __restrict__ outImage, int fmt, FrameCounters* __restrict__ ctr)
 {
   __shared__ float4   s_r[kGut2Cap][6];
   __shared__ uint8_t  s_m[kGut2Cap];
@@ -498,19 +419,13 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
     seed1 = rngXxhash32((uint32_t)px + 8u, (uint32_t)py, (uint32_t)F.frameSampleId);
     if(F.dofMode != 0)
     {
-      const float* Vi = F.viewInv;
 #pragma unroll
       for(int h = 0; h < 2; ++h)
       {
-        uint32_t    sd = h ? seed1 : seed0;
-        const float r1 = rngRand(sd) * 6.28318530717958647692f, r2 = rngRand(sd) * F.aperture;
-        const float c = cosf(r1), sn = sinf(r1), sq = gSqrt(r2);
-        const float lx = (c * Vi[0] + sn * Vi[4]) * sq, ly = (c * Vi[1] + sn * Vi[5]) * sq, lz = (c * Vi[2] + sn * Vi[6]) * sq;
-        const float dx0 = h ? dxw.y : dxw.x, dy0 = h ? dyw.y : dyw.x, dz0 = h ? dzw.y : dzw.x;
-        const float fx = dx0 * F.focusDist - lx, fy = dy0 * F.focusDist - ly, fz = dz0 * F.focusDist - lz;
-        const float l  = rsqrtf(fx * fx + fy * fy + fz * fz);
-        if(h) { lensX.y = lx; lensY.y = ly; lensZ.y = lz; dxw.y = fx * l; dyw.y = fy * l; dzw.y = fz * l; }
-        else  { lensX.x = lx; lensY.x = ly; lensZ.x = lz; dxw.x = fx * l; dyw.x = fy * l; dzw.x = fz * l; }
+        float lx, ly, lz, dx = h ? dxw.y : dxw.x, dy = h ? dyw.y : dyw.x, dz = h ? dzw.y : dzw.x;
+        gutLensSample<true>(F, h ? seed1 : seed0, lx, ly, lz, dx, dy, dz);
+        if(h) { lensX.y = lx; lensY.y = ly; lensZ.y = lz; dxw.y = dx; dyw.y = dy; dzw.y = dz; }
+        else  { lensX.x = lx; lensY.x = ly; lensZ.x = lz; dxw.x = dx; dyw.x = dy; dzw.x = dz; }
       }
     }
   }
@@ -538,22 +453,14 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
     }
     // pixel centres of the region span bcx +- 15.5, bcy +- 7.5
     const bool     ok  = have && fabsf(r0.x - bcx) <= r1.z + 15.5f && fabsf(r0.y - bcy) <= r1.w + 7.5f;
-    const uint64_t bal = __ballot(ok);
-    if(lane == 0)
-      s_wc[w] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t base = 0;
-    if(w > 0) base += s_wc[0];
-    if(w > 1) base += s_wc[1];
-    if(w > 2) base += s_wc[2];
-    const uint32_t fill = s_wc[0] + s_wc[1] + s_wc[2] + s_wc[3];
+    uint32_t       fill;
+    const uint32_t pos = gutCompactSlot(ok, s_wc, lane, w, fill);
     if(ok)
     {
-      const uint32_t pos = base + lanesBelow(bal);
       const float4*  rp  = reinterpret_cast<const float4*>(rec + g);
       const float4   r2 = rp[2], r3 = rp[3], r4 = rp[4];
       float4         c5 = rp[5];
-      // deferred shading (mesh.slang:142-148): base colour + SH in the splat's model coordinates, once per staged record
+      // deferred shading, as in k_composite_gut (which says why it is no function of gut_common.h)
       int k = 0;
       for(int i = 1; i < F.nInstances; ++i)
         if(g >= Ap->inst[i].globalOffset)
@@ -668,21 +575,7 @@ __global__ __launch_bounds__(256) void k_composite_gut2(const FrameArgs* __restr
     const float r = h ? cr.y : cr.x, g = h ? cg.y : cg.x, b = h ? cb.y : cb.x;
     const float alphaOut = 1.0f - (rok ? (h ? T.y : T.x) : 1.0f);
     const size_t pix = (size_t)py * F.width + (size_t)(px + 8 * h);
-    if(halfOut == 1)
-    {
-      const __half2 lo = __floats2half2_rn(r, g), hi2 = __floats2half2_rn(b, alphaOut);
-      uint2         o;
-      o.x = *reinterpret_cast<const uint32_t*>(&lo);
-      o.y = *reinterpret_cast<const uint32_t*>(&hi2);
-      reinterpret_cast<uint2*>(outImage)[pix] = o;
-    }
-    else if(halfOut == 0)
-      reinterpret_cast<float4*>(outImage)[pix] = make_float4(r, g, b, alphaOut);
-    else
-    {
-      auto q = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-      reinterpret_cast<uint32_t*>(outImage)[pix] = q(r) | (q(g) << 8) | (q(b) << 16) | (q(alphaOut) << 24);
-    }
+    storePixel(outImage, fmt, pix, r, g, b, alphaOut);
   }
 }
 
@@ -700,11 +593,11 @@ static void launchGutVariant(hipStream_t stream, const CompositeLaunch& L, int t
   {
     const GutOccArgs occArgs{L.occ.depth, reinterpret_cast<const float4*>(L.occ.color), L.occ.sortedByKey ? 1 : 0};
     hipLaunchKernelGGL((k_composite_gut<SHF, XT, true, GutOccArgs>), dim3(tiles), dim3(256), 0, stream, L.dArgs, L.ranges, L.valX, L.valY,
-                       L.planPairs, L.recGut, L.image, L.halfOut, L.ctr, L.outDepth, L.outSplatId, L.outNormal, occArgs);
+                       L.planPairs, L.recGut, L.image, L.fmt, L.ctr, L.outDepth, L.outSplatId, L.outNormal, occArgs);
   }
   else
     hipLaunchKernelGGL((k_composite_gut<SHF, XT>), dim3(tiles), dim3(256), 0, stream, L.dArgs, L.ranges, L.valX, L.valY, L.planPairs,
-                       L.recGut, L.image, L.halfOut, L.ctr, L.outDepth, L.outSplatId, L.outNormal);
+                       L.recGut, L.image, L.fmt, L.ctr, L.outDepth, L.outSplatId, L.outNormal);
 }
 
 void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L)
@@ -721,7 +614,7 @@ void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L)
   {
 #define MGS_GUT2(SHF, XT) case(SHF) * 2 + (XT):                                                                                       \
     hipLaunchKernelGGL((k_composite_gut2<SHF, XT>), dim3(compositeRegionGrid(F)), dim3(256), 0, stream, L.dArgs, L.ranges, L.valX, L.valY, \
-                       L.planPairs, L.recGut, L.image, L.halfOut, L.ctr);                                                             \
+                       L.planPairs, L.recGut, L.image, L.fmt, L.ctr);                                                                 \
     return;
     switch(shf * 2 + (lens ? 1 : 0))
     {

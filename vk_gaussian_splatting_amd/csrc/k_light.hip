@@ -12,9 +12,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mgs.h"
-#include "composite_common.h"
 #include "launchers.h"
 #include "shade_direct.h"
+#include "target_pixel.h"
 
 namespace mgs {
 
@@ -31,27 +31,10 @@ __device__ __forceinline__ float4 mulMat(const float* __restrict__ m, float4 v)
   return r;
 }
 
-template <int HALF>
-__device__ __forceinline__ float4 loadPixel(const void* image, size_t o)
-{
-  if(HALF == 1)
-  {
-    const uint2  pk = reinterpret_cast<const uint2*>(image)[o];
-    const float2 lo = __half22float2(*reinterpret_cast<const __half2*>(&pk.x)), hi = __half22float2(*reinterpret_cast<const __half2*>(&pk.y));
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  }
-  if(HALF == 2)
-  {
-    const uint32_t pk = reinterpret_cast<const uint32_t*>(image)[o];
-    return make_float4((float)(pk & 255u) / 255.0f, (float)((pk >> 8) & 255u) / 255.0f, (float)((pk >> 16) & 255u) / 255.0f, (float)(pk >> 24) / 255.0f);
-  }
-  return reinterpret_cast<const float4*>(image)[o];
-}
-
 }  // namespace
 
-// HALF: the target format as the compositors name it (0 RGBA32F, 1 RGBA16F, 2 RGBA8)
-template <int HALF>
+// FMT: the target format (kTargetF32, kTargetF16, kTargetU8)
+template <int FMT>
 __global__ void __launch_bounds__(256) k_light(const LightArgs a)
 {
   const uint32_t W = (uint32_t)a.width;
@@ -64,7 +47,7 @@ __global__ void __launch_bounds__(256) k_light(const LightArgs a)
   const float4   normalData    = a.normal[o];
   const float    ndcDepth      = a.depth[o];
   const uint32_t globalSplatId = a.id[o];
-  const float4   baseColor     = loadPixel<HALF>(a.image, o);
+  const float4   baseColor     = loadPixel(a.image, FMT, o);
   if(normalData.w < 0.001f)
     return;  // no surface: colour and alpha pass through
 
@@ -136,7 +119,7 @@ __global__ void __launch_bounds__(256) k_light(const LightArgs a)
       shadeDirect(h, worldPos, normal, mat, viewDir, color);
     }
   }
-  storePixel(a.image, HALF, o, color.x, color.y, color.z, 1.0f);
+  storePixel(a.image, FMT, o, color.x, color.y, color.z, 1.0f);
 }
 
 // depth_consolidate.frag.slang: the picked splat depth where it is valid and in front of the geometry (depth test LESS against the
@@ -151,18 +134,18 @@ __global__ void __launch_bounds__(256) k_depth_consolidate(const float* __restri
   out[i]        = (p > 0.0001f && p < D) ? p : D;
 }
 
-void launchLight(hipStream_t stream, const LightArgs& a, int halfOut)
+void launchLight(hipStream_t stream, const LightArgs& a, int fmt)
 {
   const uint32_t n = (uint32_t)(a.row1 - a.row0) * (uint32_t)a.width;
   if(n == 0)
     return;
   const dim3 grid((n + 255u) / 256u), block(256);
-  if(halfOut == 1)
-    hipLaunchKernelGGL(k_light<1>, grid, block, 0, stream, a);
-  else if(halfOut == 2)
-    hipLaunchKernelGGL(k_light<2>, grid, block, 0, stream, a);
+  if(fmt == kTargetF16)
+    hipLaunchKernelGGL(k_light<kTargetF16>, grid, block, 0, stream, a);
+  else if(fmt == kTargetU8)
+    hipLaunchKernelGGL(k_light<kTargetU8>, grid, block, 0, stream, a);
   else
-    hipLaunchKernelGGL(k_light<0>, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(k_light<kTargetF32>, grid, block, 0, stream, a);
 }
 
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n)

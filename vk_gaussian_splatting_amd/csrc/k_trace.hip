@@ -14,11 +14,11 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "composite_common.h"
 #include "gut_common.h"
 #include "kernels_common.h"
 #include "launchers.h"
 #include "sh_eval.h"
+#include "target_pixel.h"
 #include "trace_common.h"
 #include "trace_traverse.h"
 
@@ -204,21 +204,7 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
     a.outIsoDist[pix]  = isoDist;
     a.outRadiance[pix] = make_float4(cr, cg, cb, alphaOut);
   }
-  if(a.halfOut == 1)
-  {
-    const __half2 lo = __floats2half2_rn(cr, cg), hi2 = __floats2half2_rn(cb, alphaOut);
-    uint2         o;
-    o.x = *reinterpret_cast<const uint32_t*>(&lo);
-    o.y = *reinterpret_cast<const uint32_t*>(&hi2);
-    reinterpret_cast<uint2*>(a.image)[pix] = o;
-  }
-  else if(a.halfOut == 0)
-    reinterpret_cast<float4*>(a.image)[pix] = make_float4(cr, cg, cb, alphaOut);
-  else
-  {
-    auto q = [](float v) { return (uint32_t)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
-    reinterpret_cast<uint32_t*>(a.image)[pix] = q(cr) | (q(cg) << 8) | (q(cb) << 16) | (q(alphaOut) << 24);
-  }
+  storePixel(a.image, a.fmt, pix, cr, cg, cb, alphaOut);
   // statistics: integer sums, so the totals do not depend on the order of arrival
   atomicAdd(&a.ctr->nodeVisits, nodeVisits);
   atomicAdd(&a.ctr->candidateTests, candTests);

@@ -94,7 +94,7 @@ struct CompositeLaunch
   const SplatRec*  rec;     // launchComposite
   const GutRec*    recGut;  // launchCompositeGut
   void*            image;
-  int              halfOut;
+  int              fmt;  // kTargetF32 / kTargetF16 / kTargetU8
   int              shFormat;
   FrameCounters*   ctr;
   float*           outDepth;  // the three side outputs: null unless the frame has surface outputs
@@ -109,12 +109,16 @@ void launchCompositeGut(hipStream_t stream, const CompositeLaunch& L);
 
 void launchFrameInit(hipStream_t stream, uint2* ranges, uint32_t nTiles);
 void launchTileRanges(hipStream_t stream, const uint32_t* keyX, const uint32_t* keyY, const SortPlan* planPairs, uint2* ranges);
-void launchLight(hipStream_t stream, const LightArgs& a, int halfOut);
+void launchLight(hipStream_t stream, const LightArgs& a, int fmt);
 // the mesh pass (k_mesh.hip): clear, set-up + small triangles, large triangles, resolve + shade
 // (totalTris: the grid of the set-up stage; largeBlocks: the fixed grid that strides over the device-side work list)
 void launchMeshPass(hipStream_t stream, const MeshPassArgs& a, uint32_t totalTris, uint32_t largeBlocks);
-// temporal accumulation of the handle's strip (api_frame.hip: k_post_accumulate), for frames made outside the frame graph
-void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* accum, void* image, int halfOut);
+// the frame's small kernels (k_frame.hip): the key plan's count of a frame sorted on the CPU, fill and iota of n words,
+// and the temporal accumulation of the handle's strip
+void launchSetPlanN(hipStream_t stream, SortPlan* plan, FrameCounters* ctr, uint32_t n);
+void launchFillU32(hipStream_t stream, uint32_t* p, uint32_t v, uint32_t n);
+void launchIotaU32(hipStream_t stream, uint32_t* p, uint32_t n);
+void launchPostAccumulate(hipStream_t stream, const FrameArgs* dArgs, float4* accum, void* image, int fmt);
 // the hierarchy of the traced pipeline (k_bvh.hip): leaf bounds + Morton codes; the count of valid leaves behind the sort; the
 // gather of the sorted leaves into level 0; one plain kernel per upper level
 void launchBvhLeaves(hipStream_t stream, const BvhBuildArgs& a);

@@ -155,18 +155,18 @@ struct MeshInstance
   bool  visible = true;
 };
 
-// compositor output mode of a target format (1 = RGBA16F, 0 = RGBA32F, 2 = RGBA8: linear UNORM, rounded once at the end; the
-// numbering of CmpImage::fmt too) and the bytes of one pixel
+// the kernels' name of a target format (device_types.h: kTargetF32 / kTargetF16 / kTargetU8, the numbering of CmpImage::fmt too; RGBA8
+// is linear UNORM, rounded once at the end) and the bytes of one pixel
 struct TargetLayout
 {
-  int    half;
+  int    fmt;
   size_t pixelBytes;
 };
 inline TargetLayout targetLayout(int targetFormat)
 {
   if(targetFormat == MGS_TARGET_RGBA16F)
-    return {1, 8};
-  return targetFormat == MGS_TARGET_RGBA8 ? TargetLayout{2, 4} : TargetLayout{0, 16};
+    return {kTargetF16, 8};
+  return targetFormat == MGS_TARGET_RGBA8 ? TargetLayout{kTargetU8, 4} : TargetLayout{kTargetF32, 16};
 }
 
 // bits of the bin-rectangle codes that ride through the key sort (0: nothing rides; chooseRide, api_frameargs.hip)

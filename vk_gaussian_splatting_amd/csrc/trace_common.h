@@ -1,6 +1,8 @@
 // trace_common.h — what the hierarchy build (k_bvh.hip) and the traversal (k_trace.hip) must compute alike: the particle as the
-// 3DGRT shaders fetch it, the generalised-Gaussian response and the proxy ellipsoid's threshold and radius.
+// 3DGRT shaders fetch it and the proxy ellipsoid's threshold and radius (the generalised-Gaussian response itself: kernelResponse,
+// gut_common.h, shared with the 3DGUT compositor).
 #pragma once
+#include "gut_common.h"
 #include "kernels_common.h"
 
 namespace mgs {
@@ -22,21 +24,6 @@ __device__ __forceinline__ void loadParticle(const InstanceConst& I, uint32_t li
   R[0] = 1.0f - 2.0f * (yy + zz); R[1] = 2.0f * (xy - wz);        R[2] = 2.0f * (xz + wy);
   R[3] = 2.0f * (xy + wz);        R[4] = 1.0f - 2.0f * (xx + zz); R[5] = 2.0f * (yz - wx);
   R[6] = 2.0f * (xz - wy);        R[7] = 2.0f * (yz + wx);        R[8] = 1.0f - 2.0f * (xx + yy);
-}
-
-// particleRayMaxKernelResponse<KERNEL_DEGREE> (threedgrt.h.slang:83-127); its argument is the SQUARED canonical distance
-__device__ __forceinline__ float kernelResponse(int degree, float dist2)
-{
-  switch(degree)
-  {
-    case 8: return __expf(-0.000685871056241f * (dist2 * dist2) * (dist2 * dist2));
-    case 5: return __expf(-0.0185185185185f * dist2 * dist2 * sqrtf(dist2));
-    case 4: return __expf(-0.0555555555556f * dist2 * dist2);
-    case 3: return __expf(-0.166666666667f * dist2 * sqrtf(dist2));
-    case 1: return __expf(-1.5f * sqrtf(dist2));
-    case 0: return fmaxf(1.0f + -0.329630334487f * sqrtf(dist2), 0.0f);
-    default: return __expf(-0.5f * dist2);
-  }
 }
 
 // the response the proxy ellipsoid is circumscribed around (kernelScale, particle_as_build.comp.slang:74-78)
