@@ -42,10 +42,12 @@ extern "C" {
                             ray-traced splats (MGS_HAS_TRACE below): entry points only, both numbers stay — mgs_trace_params_default,
                                  mgs_render_traced, mgs_trace_download_hit_counts;
                             lit traced frames (MGS_HAS_TRACE_LIGHTING below): entry points only, both numbers stay —
-                                 mgs_trace_light_params_default, mgs_render_traced_lit, mgs_trace_download_shadow_hits */
+                                 mgs_trace_light_params_default, mgs_render_traced_lit, mgs_trace_download_shadow_hits;
+                            hybrid frames (MGS_HAS_HYBRID below): one entry point, both numbers stay — mgs_render_hybrid */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
@@ -533,7 +535,8 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * particle proxies of particle_as_build.comp.slang and the acceleration-structure managers: a hierarchy over the particles built on
  * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
  * Direct lighting with hard shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
- * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, the hybrid pipeline, the stochastic trace
+ * A rasterised primary surface under the same light pass is mgs_render_hybrid (MGS_HAS_HYBRID, below).
+ * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, the stochastic trace
  * strategies, wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
  * is not wired), trace profile feedback.
  *
@@ -667,6 +670,47 @@ int mgs_render_traced_lit(MgsScene scene_or_context, const MgsFrameParams* param
 /* shadow hits accepted for the pixel, summed over the lights, of the last lit traced frame of this handle: [height][width] uint32
  * (rows outside a strip frame's rows are stale); waits.  MGS_ERR_STATE unless the handle's last traced frame was a lit one. */
 int mgs_trace_download_shadow_hits(MgsScene scene_or_context, uint32_t* host_dst, size_t count);
+
+/* ---- hybrid frames (MGS_HAS_HYBRID): the rasterised splat surface lit with traced shadow rays — the reference's PIPELINE_HYBRID
+ * (params->pipeline = MGS_PIPELINE_3DGS) and PIPELINE_HYBRID_3DGUT (MGS_PIPELINE_3DGUT) without meshes
+ * (doc/hybrid_rendering_3d_gaussians.md, doc/lighting_and_shadows.md section 5).  The raster pass supplies radiance, picked depth, picked
+ * id and integrated normal "in place of first-bounce ray tracing"; everything after that is the ray tracer's.  Three steps:
+ * 1. Primary surface: exactly the frame mgs_render makes from *params with lighting_mode = 0 and surface_outputs = 1 (the deferred
+ *    shading pass is off in hybrid mode, NEED_SURFACE_INFO is on).  depth_iso_threshold is MgsFrameParams'; `out` is filled as
+ *    mgs_render fills it.  MgsTraceParams::depth_iso_threshold and max_passes are NOT READ (there is no primary walk), not even
+ *    range-checked.
+ * 2. Hand-over (initRtxStateFromRasterPass, shaders/threedgrt_raytrace.rgen.slang:346-460), per pixel of the handle's strip rows:
+ *    radiance = the frame's pixel as stored in its target format (what the reference and the deferred pass read), alpha = that
+ *    pixel's alpha, kept in the output (1 - T, this library's convention; the reference writes 1.0).  validDepth = picked ndc depth
+ *    > 0.0001.  Pinhole: position = the unprojection of (pixel centre, picked depth) through the host-double inverses of proj and
+ *    view, rounded once (the deferred pass's reconstructWorldPos, operation for operation), ray parameter = length(position - ray
+ *    origin).  Fisheye (3DGUT only, :402-419): view z of the picked depth through the inverse projection, ray parameter = view z /
+ *    (view-space ray direction).z.  The ray is the traced pipeline's (mgs_render_traced, "Ray"), depth of field included for 3DGUT;
+ *    the reference's 3DGS hybrid skips the lens (rgen:191), so MGS_PIPELINE_3DGS with dof_mode != 0 is MGS_ERR_UNSUPPORTED
+ *    (mgs_render's code) and with a fisheye camera MGS_ERR_INVALID_ARG.  normal = normalize(normal.xyz) when normal.w > 0.001,
+ *    else 0; the pixel is DISCARDED when !validDepth or length(normal) < 0.001: rgb 0 and alpha 0 (this library's convention for a
+ *    discarded lit pixel; the reference writes (0,0,0,1)).  The traced path's "length <= 0.2 -> -rayDirection" fallback is NOT part
+ *    of hybrid: surfaceFinalFiltering is only called from the particle trace, which hybrid skips at bounce 0.  A pixel with a valid
+ *    depth and normal whose picked id is 0xFFFFFFFF keeps its raster colour unlit (splatIsClosest && isoSurfSplatSetId != INVALID
+ *    fails, :1047-1049), as does a fisheye pixel outside the field of view.  A ray parameter that is not > 0 discards the pixel.
+ * 3. Shading and shadows: exactly what mgs_render_traced_lit documents for one pixel — material of the picked id's instance,
+ *    emission, the range rule without the ambient term, headlight with no lights, one samples_per_pass collection per light through
+ *    the scene's hierarchy, the transmittance ramp and the tint — at position = ray origin + ray parameter * ray direction, which
+ *    is also where the shadow ray starts (the reference shades at the unprojected position, :1110).
+ * Temporal accumulation runs after the light pass.  The hierarchy is the scene's, built lazily under mgs_render_traced's rules and
+ * shared with traced frames; its proxy is kernel_degree, kernel_min_response, alpha_cull_threshold of `params` and
+ * kernel_adaptive_clamping of `trace`, whichever raster pipeline runs (kernel_min_response must be > 0).  Afterwards
+ * mgs_frame_download, mgs_frame_copy_strip, the image-compare entry points and mgs_trace_download_shadow_hits work as after a lit
+ * traced frame (mgs_trace_download_hit_counts: MGS_ERR_STATE, there is no primary walk); mgs_frame_download_surface returns the
+ * raster pass's outputs untouched.  Strip rows and frame contexts work; mgs_render_gathered is not wired.  The normalised normal is
+ * a 16 B / pixel scratch of the handle and counts into working_bytes.
+ * The ranges of the three structs are checked before the handle is looked at.  lighting_mode == MGS_LIGHTING_INDIRECT:
+ * MGS_ERR_UNSUPPORTED; 0 or any other value: MGS_ERR_INVALID_ARG (a hybrid frame without lighting is mgs_render's);
+ * MGS_SHADOWS_SOFT, MGS_SORT_STOCHASTIC and a bound occluder (shadowing mesh pixels needs meshes in the traced scene): MGS_ERR_UNSUPPORTED.
+ * `trace` / `light` NULL = the defaults; `light_out` non-NULL waits for the frame. */
+int mgs_render_hybrid(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
+                      const MgsTraceLightParams* light /* NULL = defaults */, MgsFrameOut* out /* may be NULL */,
+                      MgsTraceLightOut* light_out /* may be NULL */);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

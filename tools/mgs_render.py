@@ -6,8 +6,9 @@
                              [--occluder-depth FILE.npy [--background FILE.npy]]
                              [--mesh FILE.obj [--mesh-transform 16 floats]]...
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
-                             [--pipeline raster|trace [--samples-per-pass N --max-passes N --min-transmittance X]
+                             [--pipeline raster|trace|hybrid [--samples-per-pass N --max-passes N --min-transmittance X]
                               [--lighting 1 [--shadows 1] [--shadow-offset X --shadow-threshold X --shadow-color-strength X]]]
+                             [--raster-pipeline 3dgs|3dgut]
                              [--compare-with FRAME.npy [--flip-mode 0|1|2] [--compare-view OUT.png --split 0.5 --left capture --right diff-red-gray]]
 
 --occluder-depth: float32 [H, W] window depth of opaque geometry rasterised with the same camera (1.0 = none); the splats are
@@ -19,6 +20,9 @@ attenuation_mode; absent fields keep the reference's defaults); without it the h
 --material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
 
 --pipeline trace --lighting 1 [--shadows 1]: a lit traced frame (mgs_render_traced_lit), --lights / --material as for the raster pipelines.
+--pipeline hybrid --lighting 1 [--shadows 1]: a hybrid frame (mgs_render_hybrid): the rasterised frame of --raster-pipeline as the
+primary surface, lit and shadowed by the traced light pass; --lights / --material / --shadow-* as above, --samples-per-pass of the
+shadow rays.  Not combinable with --occluder-depth or --mesh.  --raster-pipeline: 3DGS (default) or 3DGUT, of --pipeline raster and hybrid.
 --pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
 the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth, --mesh or --lighting 1.
 
@@ -58,7 +62,8 @@ def main():
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
-    ap.add_argument("--pipeline", choices=["raster", "trace"], default="raster")
+    ap.add_argument("--pipeline", choices=["raster", "trace", "hybrid"], default="raster")  # hybrid: the raster surface lit with traced shadow rays
+    ap.add_argument("--raster-pipeline", choices=["3dgs", "3dgut"], default="3dgs")  # of --pipeline raster and hybrid
     ap.add_argument("--shadows", type=int, choices=[0, 1], default=0)  # --pipeline trace --lighting 1: hard shadow rays through the splats
     ap.add_argument("--shadow-offset", type=float, default=0.2)
     ap.add_argument("--shadow-threshold", type=float, default=0.8)
@@ -87,6 +92,12 @@ def main():
     p = capi.default_params(W, H)
     capi.set_camera(p, V, P, a.eye)
     p.collect_timings = 1
+    if a.pipeline != "trace":
+        p.pipeline = capi.PIPELINE_3DGUT if a.raster_pipeline == "3dgut" else capi.PIPELINE_3DGS
+    if a.pipeline == "hybrid" and (a.occluder_depth or a.mesh):
+        ap.error("--pipeline hybrid lights and shadows splats alone (meshes in the traced scene are out of scope): no --occluder-depth or --mesh")
+    if a.pipeline == "hybrid" and not a.lighting:
+        ap.error("--pipeline hybrid needs --lighting 1 (without lighting it is --pipeline raster)")
     if a.background and not a.occluder_depth:
         ap.error("--background needs --occluder-depth")
     if a.occluder_depth:
@@ -137,6 +148,17 @@ def main():
         print(f"{scene.splat_count} splats, {o.leaves} leaves in {o.nodes} nodes (build {o.build_ms:.3f} ms), {o.node_visits / rays:.1f} node visits and "
               f"{o.candidate_tests / rays:.1f} candidate tests per ray, {o.accepted_hits / rays:.1f} hits per ray, at most {o.max_passes_used} passes, "
               f"{o.trace_ms:.3f} ms on the GPU")
+    elif a.pipeline == "hybrid":  # mgs_render_hybrid: the frame of --raster-pipeline as the primary surface, then the traced light pass
+        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+        lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
+                                             particle_shadow_transmittance_threshold=a.shadow_threshold,
+                                             particle_shadow_color_strength=a.shadow_color_strength)
+        o, lo = scene.render_hybrid(p, t, lp, want_stats=True)
+        img = scene.download_frame(p).astype(np.float32)
+        sr = max(int(lo.shadow_rays), 1)
+        print(f"{scene.splat_count} splats, {o.sorted_count} sorted, raster frame {o.stage_ms[5]:.3f} ms and light pass {lo.light_ms:.3f} ms on the GPU, "
+              f"{lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, {lo.shadow_candidate_tests / sr:.1f} candidate tests and "
+              f"{lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
     else:
         o = scene.render(p)
         img = scene.download_frame(p).astype(np.float32)

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--lit] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--lit] [--hybrid] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
 tests per ray, and writes everything as JSON.  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
-lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  Needs an MI355X.
+lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  --hybrid (with --lit) renders the same lit
+scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and the shadow counters beside the traced ones.  Needs an MI355X.
 """
 import argparse
 import json
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--samples-per-pass", type=int, default=18)
     ap.add_argument("--lit", action="store_true")
+    ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -77,6 +79,21 @@ def main():
                                          shadow_rays=int(lo.shadow_rays), node_visits_per_shadow_ray=lo.shadow_node_visits / sr,
                                          candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
                                          accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr))
+                    if a.hybrid:  # the same lights over the rasterised (3DGS) surface
+                        p.collect_timings = 1
+                        hms, fms = [], []
+                        for k in range(a.warmup + a.repeats):
+                            fo, lo = scene.render_hybrid(p, t, lp, want_stats=True)
+                            if k >= a.warmup:
+                                hms.append(lo.light_ms)
+                                fms.append(fo.stage_ms[5])
+                        p.collect_timings = 0
+                        sr = max(int(lo.shadow_rays), 1)
+                        r["lit"][-1]["hybrid"] = dict(raster_ms_median=float(np.median(fms)), light_ms_median=float(np.median(hms)),
+                                                      light_ms_min=float(min(hms)), shadow_rays=int(lo.shadow_rays),
+                                                      node_visits_per_shadow_ray=lo.shadow_node_visits / sr,
+                                                      candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
+                                                      accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr)
             p.lighting_mode = 0
         print(json.dumps(r))
         results.append(r)

@@ -264,6 +264,7 @@ def load_library():
         "mgs_scene_storage_order": (C.c_int, [vp, C.c_int, P(C.c_uint32), C.c_size_t]),
         "mgs_frame_params_default": (None, [P(FrameParams)]),
         "mgs_render": (C.c_int, [vp, P(FrameParams), P(FrameOut)]),
+        "mgs_render_hybrid": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceLightParams), P(FrameOut), P(TraceLightOut)]),
         "mgs_frame_stats": (C.c_int, [vp, P(FrameOut)]),
         "mgs_timings_query": (C.c_int, [vp, C.c_uint32, P(F)]),
         "mgs_frame_download": (C.c_int, [vp, vp, C.c_size_t]),
@@ -309,7 +310,7 @@ EXPORTED_SYMBOLS = [
     "mgs_mesh_from_arrays", "mgs_mesh_load_obj", "mgs_mesh_view", "mgs_mesh_destroy", "mgs_mesh_instance_add",
     "mgs_mesh_instance_set_transform", "mgs_mesh_instance_set_visible", "mgs_meshes_render", "mgs_meshes_download",
     "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
-    "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits",
+    "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits", "mgs_render_hybrid",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -712,6 +713,23 @@ class Scene:
                                                C.byref(light) if light is not None else None,
                                                C.byref(out) if want_stats else None, C.byref(lout) if want_stats else None))
         return (out, lout) if want_stats else None
+
+    def render_hybrid(self, params, trace=None, light=None, want_stats=False):
+        """mgs_render_hybrid: the rasterised frame of params.pipeline (3DGS or 3DGUT) as the primary surface, lit by the scene's
+        lights with shadow rays through the splats (params.lighting_mode must be MGS_LIGHTING_DIRECT); trace / light = a TraceParams /
+        TraceLightParams or None for the defaults; want_stats waits and returns (FrameOut with the raster frame's statistics,
+        TraceLightOut)"""
+        out, lout = FrameOut(), TraceLightOut()
+        self._sort_only = False
+        self._frame_wh = (params.width, params.height)
+        _check(self._lib.mgs_render_hybrid(self._h, C.byref(params), C.byref(trace) if trace is not None else None,
+                                           C.byref(light) if light is not None else None,
+                                           C.byref(out) if want_stats else None, C.byref(lout) if want_stats else None))
+        if not want_stats:
+            return None
+        if not params.collect_timings:
+            _check(self._lib.mgs_frame_stats(self._h, C.byref(out)))
+        return out, lout
 
     def trace_shadow_hits(self, params):
         """shadow hits accepted per pixel of the last lit traced frame, summed over the lights, uint32[H,W]"""

@@ -276,6 +276,7 @@ struct FramePass
   const FrameArgs*      A;
   int                   fmt;   // the image's format as the kernels name it (targetLayout)
   bool                  gut, lit, cpuMode;
+  bool                  hybrid;  // a frame of mgs_render_hybrid: its tail folds the frame into the running mean, behind its light pass
   Occluder              occ;
   uint32_t              nTiles;  // lists (and ranges) exist per bin
 };
@@ -491,7 +492,7 @@ static int issueFrame(const FramePass& fp, bool withEvents)
     launchLight(st, L, fp.fmt);
     if(withEvents) HIPCHK(hipEventRecord(fev[8], st));
   }
-  if(F.temporalSampling)
+  if(F.temporalSampling && !fp.hybrid)
     launchPostAccumulate(st, fb.dArgs.p, fb.accum.p, fb.image.p, fp.fmt);
   if(withEvents) HIPCHK(hipEventRecord(fev[5], st));
   return MGS_OK;
@@ -511,6 +512,7 @@ static GraphCache::Key graphKey(const FramePass& fp)
                           F.pipeline, F.stochastic | (F.dofMode << 1) | (F.temporalSampling << 2) | ((F.pipeline == 1 && F.kernelDegree != 2) ? 8 : 0) |
                               ((F.pipeline == 1 && F.normalMethod == 1) ? 16 : 0) |
                               (F.lightingMode << 5) |  // 0..2: the lighting pass is a launch of its own; what it gets by value is in this key or moves with the buffers
+                              (fp.hybrid ? 128 : 0) |  // a hybrid frame's graph ends before the accumulation
                               (F.rideShift << 8) | (F.rideShapes << 16) | (F.rideSplit << 24)};  // ... and everything that selects a kernel variant or a launch argument
   std::memcpy(key.v, kv, sizeof(kv));
   key.p[0] = fp.s->fb.image.p;
@@ -565,7 +567,8 @@ static void recordLastFrame(const FramePass& fp, bool timed)
   }
 }
 
-static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out)
+// tail: what mgs_render_hybrid hangs onto the frame (scene_state.h), null for mgs_render
+int renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail* tail)
 {
   if(!s || !p)
   {
@@ -588,6 +591,12 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   if((rc = buildFrameArgs(s, p, A))) return rc;
   const FrameConst& F = A.f;
   if((rc = validateFrameParams(p, F, s->occ))) return rc;
+  if(tail)
+  {  // the rays of the tail's kernels: what a lit frame's constants carry (the raster kernels read none of it)
+    std::memcpy(A.f.cameraPos, p->camera_pos, sizeof(A.f.cameraPos));
+    mat4InverseDouble(p->view, A.f.lightViewInv);
+    mat4InverseDouble(p->proj, A.f.lightProjInv);
+  }
   FramePass fp{};
   fp.s       = s;
   fp.p       = p;
@@ -596,6 +605,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   fp.gut     = p->pipeline == MGS_PIPELINE_3DGUT;
   fp.lit     = p->lighting_mode != MGS_LIGHTING_DISABLED;
   fp.cpuMode = p->sort_mode == MGS_SORT_CPU_ASYNC;
+  fp.hybrid  = tail != nullptr;
   fp.nTiles  = (uint32_t)(F.binsX * F.binsY);
   if(s->occ.depth)
   {
@@ -607,7 +617,11 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
   const bool timed = p->collect_timings != 0;
   // this frame's constants, and its counters and plans zeroed: one 18 KB upload
   if((rc = uploadFrameState(s, A, s->stream))) return rc;
+  if(tail)
+    if((rc = tail->afterUpload(A))) return rc;
   if((rc = launchFrame(fp, timed))) return rc;
+  if(tail)
+    if((rc = tail->afterFrame(A, fp.fmt))) return rc;
   if(policyFrame && directBinning(F))
     if((rc = s->binPolicy.sample(F, frameStatLines(&s->fb.plans.p->keys), s->stream))) return rc;
   // the counters stay on the device; mgs_frame_stats fetches them when somebody asks (two API calls per frame less
@@ -626,7 +640,7 @@ static int mgs_render_impl(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out
 }
 int mgs_render(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out)
 {
-  return guarded("mgs_render", [&] { return mgs_render_impl(s, p, out); });
+  return guarded("mgs_render", [&] { return renderFrame(s, p, out, nullptr); });
 }
 
 int mgs_timings_query(MgsScene s, uint32_t framesBack, float* stageMs)

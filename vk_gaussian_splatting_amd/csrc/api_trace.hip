@@ -1,5 +1,5 @@
 // api_trace.hip — the traced pipeline's host side: mgs_render_traced and mgs_render_traced_lit, the lazy build of the scene's
-// hierarchy, the hit-count and shadow-hit downloads.
+// hierarchy, the hit-count and shadow-hit downloads; and mgs_render_hybrid, whose primary surface is a frame of mgs_render.
 #include <array>
 #include <cmath>
 #include <memory>
@@ -36,16 +36,17 @@ static int failTrace(int code, const std::string& msg)
 }
 
 // what needs no device: the ranges of MgsTraceParams and of the MgsFrameParams fields the traced pipeline reads
-// (lit: the checks of mgs_render_traced_lit, whose lighting_mode rule differs)
-static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr)
+// (lit: the checks of mgs_render_traced_lit, whose lighting_mode rule differs; hybrid: those of mgs_render_hybrid, which has no
+// primary walk and takes its surface from one of the raster pipelines)
+static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr, bool hybrid = false)
 {
   if(t.samples_per_pass < 1 || t.samples_per_pass > 32)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: samples_per_pass must be in [1, 32]");
-  if(t.max_passes < 1)
+  if(!hybrid && t.max_passes < 1)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: max_passes must be at least 1");
   if(!(t.min_transmittance >= 0.0f && t.min_transmittance < 1.0f))
     return failTrace(MGS_ERR_INVALID_ARG, "trace: min_transmittance must be in [0, 1)");
-  if(!(t.depth_iso_threshold >= 0.0f && t.depth_iso_threshold <= 1.0f))
+  if(!hybrid && !(t.depth_iso_threshold >= 0.0f && t.depth_iso_threshold <= 1.0f))
     return failTrace(MGS_ERR_INVALID_ARG, "trace: depth_iso_threshold must be in [0, 1]");
   if(t.kernel_adaptive_clamping != 0 && t.kernel_adaptive_clamping != 1)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: kernel_adaptive_clamping must be 0 or 1");
@@ -68,6 +69,16 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const
     return failTrace(MGS_ERR_INVALID_ARG, "trace: dof_mode / frame_sample_id out of range");
   if(p->dof_mode != MGS_DOF_DISABLED && (!(p->aperture >= 0.0f) || !std::isfinite(p->aperture) || !(p->focus_dist > 0.0f) || !std::isfinite(p->focus_dist)))
     return failTrace(MGS_ERR_INVALID_ARG, "trace: depth of field needs a finite aperture >= 0 and a finite focus_dist > 0");
+  if(hybrid)
+  {
+    if(p->pipeline != MGS_PIPELINE_3DGS && p->pipeline != MGS_PIPELINE_3DGUT)
+      return failTrace(MGS_ERR_INVALID_ARG, "hybrid: pipeline must be MGS_PIPELINE_3DGS or MGS_PIPELINE_3DGUT");
+    // the 3DGS hybrid's rays skip the lens (rgen.slang:191), and its raster pass knows neither lens nor fisheye rays
+    if(p->pipeline == MGS_PIPELINE_3DGS && p->dof_mode != MGS_DOF_DISABLED)
+      return failTrace(MGS_ERR_UNSUPPORTED, "hybrid: depth of field is a feature of the 3DGUT pipeline (per-pixel rays); the 3DGS pipeline has none");
+    if(p->pipeline == MGS_PIPELINE_3DGS && p->camera_model != MGS_CAMERA_PINHOLE)
+      return failTrace(MGS_ERR_INVALID_ARG, "hybrid: a fisheye camera needs MGS_PIPELINE_3DGUT (the 3DGS surface is a pinhole one)");
+  }
   if(lit)
   {
     if(lit->shadows_mode < MGS_SHADOWS_DISABLED || lit->shadows_mode > MGS_SHADOWS_SOFT)
@@ -81,7 +92,8 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const
     if(p->lighting_mode == MGS_LIGHTING_INDIRECT)
       return failTrace(MGS_ERR_UNSUPPORTED, "trace: indirect lighting needs bounces, which are out of scope");
     if(p->lighting_mode != MGS_LIGHTING_DIRECT)
-      return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_lit: lighting_mode must be MGS_LIGHTING_DIRECT");
+      return failTrace(MGS_ERR_INVALID_ARG, hybrid ? "mgs_render_hybrid: lighting_mode must be MGS_LIGHTING_DIRECT (a hybrid frame without lighting is mgs_render's)"
+                                                   : "mgs_render_traced_lit: lighting_mode must be MGS_LIGHTING_DIRECT");
     if(lit->shadows_mode == MGS_SHADOWS_SOFT)
       return failTrace(MGS_ERR_UNSUPPORTED, "trace: soft shadows are out of scope (hard shadows only)");
   }
@@ -244,6 +256,106 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
   return MGS_OK;
 }
 
+// the scene's hierarchy for this frame's proxy: rebuilt when its signature differs (the frame's constants are on the device)
+static int ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt)
+{
+  SceneData& d = *s->d;
+  *buildMs = 0.0f;
+  *rebuilt = 0;
+  if(d.instances.empty())
+    return MGS_OK;
+  std::vector<uint8_t> sig = bvhSignature(d, proxy);
+  if(d.bvh.built && sig == d.bvh.signature)
+    return MGS_OK;
+  *rebuilt = 1;
+  return buildBvh(s, A, proxy, std::move(sig), buildMs);
+}
+
+static int ensureTraceEvents(TracePassState& ts)
+{
+  if(!ts.ev[0])
+    for(auto& e : ts.ev)
+      HIPCHK(hipEventCreate(&e));
+  return MGS_OK;
+}
+
+// a light pass's scratch and the scene's light table
+static int ensureLightScratch(MgsScene s, size_t pixels)
+{
+  TracePassState& ts = s->trace;
+  int             rc;
+  if((rc = ts.isoDist.ensure(pixels))) return rc;
+  if((rc = ts.radiance.ensure(pixels))) return rc;
+  if((rc = ts.shadowHits.ensure(pixels))) return rc;
+  if((rc = ts.lctr.ensure(1))) return rc;
+  return ensureLightTable(*s->d);
+}
+
+// what every kernel of the traced pipeline receives: frame, hierarchy, proxy, the rays' knobs, the image (the outputs stay null)
+static TraceArgs traceArgs(MgsScene s, const TraceProxy& proxy, const MgsTraceParams& t, int fmt)
+{
+  SceneData& d = *s->d;
+  TraceArgs  L{};
+  L.frame    = s->fb.dArgs.p;
+  L.nodes    = d.bvh.nodes.p;
+  L.callerId = d.bvh.callerId.p;
+  L.inst     = d.bvh.inst.p;
+  L.ctr      = s->trace.ctr.p;
+  if(!d.instances.empty())
+  {
+    std::memcpy(L.levelOffset, d.bvh.levelOffset, sizeof(L.levelOffset));
+    std::memcpy(L.levelCount, d.bvh.levelCount, sizeof(L.levelCount));
+    L.nLevels    = d.bvh.nLevels;
+    L.totalNodes = d.bvh.totalNodes;
+  }
+  L.proxy             = proxy;
+  L.samplesPerPass    = t.samples_per_pass;
+  L.maxPasses         = t.max_passes;
+  L.minTransmittance  = t.min_transmittance;
+  L.depthIsoThreshold = t.depth_iso_threshold;
+  L.image             = s->fb.image.p;
+  L.fmt               = fmt;
+  return L;
+}
+
+// the light pass over the surface in the handle's scratch (ray parameter, fp32 radiance), the picked ids and the given normals
+static TraceLightArgs traceLightArgs(MgsScene s, const TraceArgs& L, const MgsTraceLightParams& lt, const uint32_t* pickId, const float4* normal)
+{
+  SceneData&      d  = *s->d;
+  TracePassState& ts = s->trace;
+  TraceLightArgs  G{};
+  G.t                   = L;
+  G.isoDist             = ts.isoDist.p;
+  G.pickId              = pickId;
+  G.normal              = normal;
+  G.radiance            = ts.radiance.p;
+  G.table               = d.lightTab.p;
+  G.shadowHits          = ts.shadowHits.p;
+  G.lctr                = ts.lctr.p;
+  G.shadowsMode         = lt.shadows_mode;
+  G.shFormat            = d.shFormat == 0 ? 0 : d.shFormat == 1 ? 1 : 2;
+  G.shadowOffset        = lt.particle_shadow_offset;
+  G.shadowThreshold     = lt.particle_shadow_transmittance_threshold;
+  G.shadowColorStrength = lt.particle_shadow_color_strength;
+  return G;
+}
+
+// the shadow rays' counters and the time between the light pass's events; waits
+static int readLightOut(MgsScene s, MgsTraceLightOut* lout)
+{
+  TracePassState& ts = s->trace;
+  std::memset(lout, 0, sizeof(*lout));
+  TraceLightCounters hc{};
+  HIPCHK(hipMemcpyAsync(&hc, ts.lctr.p, sizeof(hc), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  lout->shadow_rays            = hc.shadowRays;
+  lout->shadow_node_visits     = hc.nodeVisits;
+  lout->shadow_candidate_tests = hc.candidateTests;
+  lout->shadow_accepted_hits   = hc.acceptedHits;
+  HIPCHK(hipEventElapsedTime(&lout->light_ms, ts.ev[4], ts.ev[5]));
+  return MGS_OK;
+}
+
 // lit: the frame of mgs_render_traced_lit (lp NULL = the defaults); otherwise lp and lout are not looked at
 static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out, bool lit = false,
                                   const MgsTraceLightParams* lp = nullptr, MgsTraceLightOut* lout = nullptr)
@@ -289,56 +401,21 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   mat4InverseDouble(p->proj, F.lightProjInv);
   if((rc = ensureFrameImage(s, &q, F))) return rc;
   TracePassState& ts = s->trace;
-  if(!ts.ev[0])
-    for(auto& e : ts.ev)
-      HIPCHK(hipEventCreate(&e));
+  if((rc = ensureTraceEvents(ts))) return rc;
   const size_t pixels = (size_t)F.width * F.height;
   if((rc = ts.hitCount.ensure(pixels))) return rc;
   if((rc = ts.ctr.ensure(1))) return rc;
   if(lit)
-  {
-    if((rc = ts.isoDist.ensure(pixels))) return rc;
-    if((rc = ts.radiance.ensure(pixels))) return rc;
-    if((rc = ts.shadowHits.ensure(pixels))) return rc;
-    if((rc = ts.lctr.ensure(1))) return rc;
-    if((rc = ensureLightTable(d))) return rc;
-  }
+    if((rc = ensureLightScratch(s, pixels))) return rc;
   if((rc = uploadFrameState(s, *A, s->stream))) return rc;
   const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
   float            buildMs = 0.0f;
   uint32_t         rebuilt = 0;
-  if(!empty)
-  {
-    std::vector<uint8_t> sig = bvhSignature(d, proxy);
-    if(!d.bvh.built || sig != d.bvh.signature)
-    {
-      if((rc = buildBvh(s, *A, proxy, std::move(sig), &buildMs))) return rc;
-      rebuilt = 1;
-    }
-  }
+  if((rc = ensureHierarchy(s, *A, proxy, &buildMs, &rebuilt))) return rc;
   hipStream_t st = s->stream;
   HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
   HIPCHK(hipEventRecord(ts.ev[2], st));
-  TraceArgs L{};
-  L.frame    = s->fb.dArgs.p;
-  L.nodes    = d.bvh.nodes.p;
-  L.callerId = d.bvh.callerId.p;
-  L.inst     = d.bvh.inst.p;
-  L.ctr      = ts.ctr.p;
-  if(!empty)
-  {
-    std::memcpy(L.levelOffset, d.bvh.levelOffset, sizeof(L.levelOffset));
-    std::memcpy(L.levelCount, d.bvh.levelCount, sizeof(L.levelCount));
-    L.nLevels    = d.bvh.nLevels;
-    L.totalNodes = d.bvh.totalNodes;
-  }
-  L.proxy             = proxy;
-  L.samplesPerPass    = t.samples_per_pass;
-  L.maxPasses         = t.max_passes;
-  L.minTransmittance  = t.min_transmittance;
-  L.depthIsoThreshold = t.depth_iso_threshold;
-  L.image             = s->fb.image.p;
-  L.fmt               = targetLayout(p->target_format).fmt;
+  TraceArgs L = traceArgs(s, proxy, t, targetLayout(p->target_format).fmt);
   L.hitCount          = ts.hitCount.p;
   L.outDepth          = F.surfaceOutputs ? s->surf.depth.p : nullptr;
   L.outId             = F.surfaceOutputs ? s->surf.id.p : nullptr;
@@ -351,21 +428,7 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
     HIPCHK(hipEventRecord(ts.ev[3], st));
     HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
     HIPCHK(hipEventRecord(ts.ev[4], st));
-    TraceLightArgs G{};
-    G.t                   = L;
-    G.isoDist             = ts.isoDist.p;
-    G.pickId              = s->surf.id.p;
-    G.normal              = s->surf.normal.p;
-    G.radiance            = ts.radiance.p;
-    G.table               = d.lightTab.p;
-    G.shadowHits          = ts.shadowHits.p;
-    G.lctr                = ts.lctr.p;
-    G.shadowsMode         = lt.shadows_mode;
-    G.shFormat            = d.shFormat == 0 ? 0 : d.shFormat == 1 ? 1 : 2;
-    G.shadowOffset        = lt.particle_shadow_offset;
-    G.shadowThreshold     = lt.particle_shadow_transmittance_threshold;
-    G.shadowColorStrength = lt.particle_shadow_color_strength;
-    launchTraceLight(st, G, F);
+    launchTraceLight(st, traceLightArgs(s, L, lt, s->surf.id.p, s->surf.normal.p), F);
     HIPCHK(hipEventRecord(ts.ev[5], st));
   }
   if(F.temporalSampling)
@@ -389,17 +452,7 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   ts.have = true;
   ts.haveLit = lit;  // the shadow hits are those of the last traced frame only when that frame was lit
   if(lit && lout)
-  {
-    std::memset(lout, 0, sizeof(*lout));
-    TraceLightCounters hc{};
-    HIPCHK(hipMemcpyAsync(&hc, ts.lctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    lout->shadow_rays            = hc.shadowRays;
-    lout->shadow_node_visits     = hc.nodeVisits;
-    lout->shadow_candidate_tests = hc.candidateTests;
-    lout->shadow_accepted_hits   = hc.acceptedHits;
-    HIPCHK(hipEventElapsedTime(&lout->light_ms, ts.ev[4], ts.ev[5]));
-  }
+    if((rc = readLightOut(s, lout))) return rc;
   if(out)
   {
     std::memset(out, 0, sizeof(*out));
@@ -427,6 +480,99 @@ int mgs_render_traced_lit(MgsScene s, const MgsFrameParams* p, const MgsTracePar
                           MgsTraceLightOut* lout)
 {
   return guarded("mgs_render_traced_lit", [&] { return mgs_render_traced_impl(s, p, tp, out, true, lp, lout); });
+}
+
+// ---- hybrid frames: the raster pass supplies the primary surface, the light pass of the traced pipeline shades and shadows it ----
+namespace {
+struct HybridTail : FrameTail
+{
+  MgsScene                   s = nullptr;
+  const MgsFrameParams*      p = nullptr;  // the caller's
+  MgsTraceParams             t;
+  MgsTraceLightParams        lt;
+  float                      buildMs = 0.0f;
+  uint32_t                   rebuilt = 0;
+
+  TraceProxy proxy() const { return TraceProxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold}; }
+  int        afterUpload(const FrameArgs& A) override
+  {
+    TracePassState& ts = s->trace;
+    int             rc;
+    if((rc = ensureTraceEvents(ts))) return rc;
+    const size_t pixels = (size_t)A.f.width * A.f.height;
+    if((rc = ts.hybridNormal.ensure(pixels))) return rc;
+    if((rc = ensureLightScratch(s, pixels))) return rc;
+    return ensureHierarchy(s, A, proxy(), &buildMs, &rebuilt);
+  }
+  int afterFrame(const FrameArgs& A, int fmt) override
+  {
+    TracePassState&   ts = s->trace;
+    const FrameConst& F  = A.f;
+    hipStream_t       st = s->stream;
+    HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
+    HIPCHK(hipEventRecord(ts.ev[4], st));
+    HybridSurfaceArgs H{};
+    H.frame       = s->fb.dArgs.p;
+    H.image       = s->fb.image.p;
+    H.depth       = s->surf.depth.p;
+    H.id          = s->surf.id.p;
+    H.normal      = s->surf.normal.p;
+    H.outIsoDist  = ts.isoDist.p;
+    H.outNormal   = ts.hybridNormal.p;
+    H.outRadiance = ts.radiance.p;
+    launchHybridSurface(st, H, F, fmt);
+    launchTraceLight(st, traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p), F);
+    HIPCHK(hipEventRecord(ts.ev[5], st));
+    if(F.temporalSampling)  // the lit sample is what the running mean folds in
+      launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, fmt);
+    HIPCHK(hipGetLastError());
+    return MGS_OK;
+  }
+};
+}  // namespace
+
+static int mgs_render_hybrid_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsTraceLightParams* lp, MgsFrameOut* out,
+                                  MgsTraceLightOut* lout)
+{
+  if(!p)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_hybrid: null params");
+  HybridTail tail;
+  if(tp)
+    tail.t = *tp;
+  else
+    mgs_trace_params_default(&tail.t);
+  if(lp)
+    tail.lt = *lp;
+  else
+    mgs_trace_light_params_default(&tail.lt);
+  if(int rc = validateTrace(p, tail.t, &tail.lt, true))  // (before the handle is looked at)
+    return rc;
+  if(!s)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_hybrid: null scene");
+  if(s->occ.depth)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: an occluder is bound (shadowing mesh pixels needs meshes in the traced scene, which are out of "
+                                          "scope); unbind it with mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
+  tail.s = s;
+  tail.p = p;
+  // step 1: exactly mgs_render's unlit frame with the surface outputs on (the deferred pass is off in hybrid mode, NEED_SURFACE_INFO on)
+  MgsFrameParams q  = *p;
+  q.lighting_mode   = MGS_LIGHTING_DISABLED;
+  q.surface_outputs = 1;
+  if(int rc = renderFrame(s, &q, out, &tail))
+    return rc;
+  s->last.params.lighting_mode = p->lighting_mode;  // (surface_outputs stays 1: the raster pass's outputs are there to download)
+  TracePassState& ts = s->trace;
+  ts.w       = p->width;
+  ts.h       = p->height;
+  ts.have    = false;  // no primary walk: there are no hit counts
+  ts.haveLit = true;
+  if(lout)
+    return readLightOut(s, lout);
+  return MGS_OK;
+}
+int mgs_render_hybrid(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsTraceLightParams* lp, MgsFrameOut* out, MgsTraceLightOut* lout)
+{
+  return guarded("mgs_render_hybrid", [&] { return mgs_render_hybrid_impl(s, p, tp, lp, out, lout); });
 }
 
 int mgs_trace_download_shadow_hits(MgsScene s, uint32_t* dst, size_t count)

@@ -358,7 +358,7 @@ struct TraceLightCounters
 struct TraceLightArgs
 {
   TraceArgs           t;            // hierarchy, frame, proxy, samplesPerPass, image, fmt as the primary rays had them
-  const float*        isoDist;      // [height][width] ray parameter of the surface, 0 = none (discarded)
+  const float*        isoDist;      // [height][width] ray parameter of the surface, 0 = none (discarded), < 0 = settled by the producer (left alone)
   const uint32_t*     pickId;       // [height][width] global storage id of the picked particle
   const float4*       normal;       // [height][width] integrated normal (unnormalised) and weight
   const float4*       radiance;     // [height][width] fp32 radiance and alpha of the primary walk
@@ -368,6 +368,21 @@ struct TraceLightArgs
   int32_t             shadowsMode;  // MGS_SHADOWS_*
   int32_t             shFormat;     // storage format of the SH records (read when shadowColorStrength != 0)
   float               shadowOffset, shadowThreshold, shadowColorStrength;
+};
+
+// what the hand-over of a hybrid frame (k_hybrid.hip, mgs_render_hybrid) receives by value: the raster pass's pixel and side outputs
+// in, the light pass's per-pixel inputs (TraceLightArgs) out
+struct HybridSurfaceArgs
+{
+  const FrameArgs* frame;
+  void*            image;        // the frame as the compositor left it, in the target format (read; never written)
+  const float*     depth;        // picked ndc depth                       } the raster side outputs,
+  const uint32_t*  id;           // picked splat (global storage id)       } left as they are
+  const float4*    normal;       // integrated normal and weight           }
+  float*           outIsoDist;   // ray parameter of the surface; 0: discarded; < 0: the pixel is settled, the light pass leaves it alone
+                                 // (the light pass reads the raster pass's picked ids as they are: the ray parameter alone filters)
+  float4*          outNormal;    // the normalised normal (the handle's own scratch)
+  float4*          outRadiance;  // the stored pixel in fp32: rgb and alpha
 };
 
 // the caller's geometry as the compositors' launchers receive it

@@ -128,6 +128,8 @@ void launchBvhLevel(hipStream_t stream, const float4* below, uint32_t nBelow, fl
 // the traversal (k_trace.hip): one ray per lane, a wave64 = an 8 x 8 pixel tile
 void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat);
 void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameConst& F);  // k_trace_light.hip
+// the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
+void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 
 }  // namespace mgs

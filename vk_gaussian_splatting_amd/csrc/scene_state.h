@@ -470,11 +470,12 @@ struct TracePassState
   DevBuf<float4>             radiance;
   DevBuf<uint32_t>           shadowHits;
   DevBuf<TraceLightCounters> lctr;
+  DevBuf<float4>             hybridNormal;  // a hybrid frame's normalised normal (mgs_render_hybrid): the raster side outputs stay as they are
   int                   w = 0, h = 0;
   bool                  have = false, haveLit = false;
   hipEvent_t            ev[6] = {};  // build begin / end, traversal begin / end, light pass begin / end
   template <class F>
-  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); }
+  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); f(hybridNormal); }
   void release()
   {
     eachBuffer([](auto& b) { b.release(); });
@@ -642,6 +643,15 @@ int  ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F, 
 void mat4InverseDouble(const float m[16], float out[16]);                     // api_frameargs.hip
 void rotScaleInverse(const float M[16], float out[9]);                        // api_mesh.hip
 int  uploadFrameState(MgsScene s, const FrameArgs& A, hipStream_t st);        // api_frame.hip
+// What mgs_render_hybrid (api_trace.hip) hangs onto a frame of mgs_render: the frame's constants then also carry the camera position
+// and the rays' inverses, temporal accumulation is left to afterFrame, and the captured graph ends at the compositor.
+struct FrameTail
+{
+  virtual int afterUpload(const FrameArgs& A) = 0;          // the constants are on the device, nothing of the frame is launched yet
+  virtual int afterFrame(const FrameArgs& A, int fmt) = 0;  // behind the frame's launches on the handle's stream
+  virtual ~FrameTail() = default;
+};
+int  renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail* tail);  // api_frame.hip: mgs_render's frame
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip
 int  cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking);         // api_sort.hip
