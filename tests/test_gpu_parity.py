@@ -491,6 +491,50 @@ def test_storage_formats_match_oracle_with_same_quantisation(ob, shf, rgbaf, tol
     scene.close()
 
 
+def test_commit_planes_roundtrip(ob):
+    """one scene of two different splat sets (4100 splats with f_rest 45: two full partitions and a partial one; 300 with f_rest
+    9) committed in the three storage formats in turn: every commit releases both sets and rebuilds them, and the fp32 colours
+    are the colour plane itself (fp32) or a plane of their own (fp16, u8), in both directions.  After each commit the planes come
+    back as the oracle prepares them, bit for bit, and the scene holds exactly the bytes of its planes."""
+    scs = [synth.make_scene(4100, seed=61), synth.make_scene(300, seed=62, sh_coeffs_per_channel=3)]
+    M1, _ = mgs.compute_transform([1.0, 1.0, 1.0], [0.0, 30.0, 0.0], [1.5, 0.2, -0.5])
+
+    def build(fmt):
+        scene = mgs.Scene(0)
+        for sc, M in zip(scs, (None, M1)):
+            scene.add_instance(mgs.SplatSet.from_arrays(**sc), M)
+        scene.commit(fmt, fmt)
+        return scene
+
+    def set_bytes(n, sh_stride, fmt):  # the planes of one set
+        esz = {capi.FORMAT_FLOAT32: 4, capi.FORMAT_FLOAT16: 2, capi.FORMAT_UINT8: 1}[fmt]
+        b = n * (12 + 24 + 4 + 4 + 12 + 16) + ((n + 2047) // 2048) * 32   # centres, cov6, alpha, maxScale, scales, rotations, boxes
+        b += n * 4 * esz + (n * 16 if fmt != capi.FORMAT_FLOAT32 else 0)  # colours as stored, and read back as fp32
+        return b + (n * 48 * esz if sh_stride else 0)                     # padded SH records
+
+    p, *_ = camera(9, 64, 48)
+    scene = build(capi.FORMAT_UINT8)
+    for fmt in (capi.FORMAT_UINT8, capi.FORMAT_FLOAT32, capi.FORMAT_FLOAT16):
+        scene.commit(fmt, fmt)
+        want_bytes = 2 * 32                                               # the compositor's instance table
+        for k, sc in enumerate(scs):
+            ps = ob.PreparedSet(sc, sh_format=fmt, rgba_format=fmt)
+            n = ps.count
+            assert ps.sh_stride == (45, 9)[k]
+            for which, want in enumerate((ps.positions, ps.cov6, ps.rgba, ps.sh[: ps.sh_stride * n])):
+                assert np.array_equal(scene.download_set(k, which, want.size), want), (fmt, k, which)
+            assert np.array_equal(np.sort(scene.storage_order(k, n)), np.arange(n))
+            want_bytes += set_bytes(n, ps.sh_stride, fmt)
+        assert scene.memory_usage()[0] == want_bytes, fmt
+    scene.render(p)
+    got = scene.download_frame(p)
+    fresh = build(capi.FORMAT_FLOAT16)
+    fresh.render(p)
+    assert np.array_equal(got.view(np.uint16), fresh.download_frame(p).view(np.uint16))
+    scene.close()
+    fresh.close()
+
+
 def test_multi_instance_unified_sort_and_golden_frame(ob):
     g = np.load(os.path.join(GOLDEN, "frame_two_instances.npz"))
     sc = synth.make_scene(3000, seed=42)

@@ -381,6 +381,28 @@ def test_file_readers_survive_mutated_files_under_sanitizers(tmp_path):
     assert len(lines) >= 9 and all("no crash / sanitizer report" in l for l in lines)
 
 
+@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"]], ids=["plain", "asan_ubsan"])
+def test_packed_planes_roundtrip_and_match_the_recorded_digests(tmp_path, flags):
+    """tests/helpers/pack_roundtrip.cpp over csrc/host_model.cpp: the program asserts the layout of every plane of a packed splat
+    set (4100 splats, f_rest 0 / 9 / 24 / 45, all nine format pairs) and prints a digest per plane.  The digests must equal
+    tests/golden/pack_digests.txt, which the same program printed when the planes came from the commit path of 53dfea5 (the
+    loops then in api_scene.hip, built by the device compiler's host side, writing to host memory instead of the device)."""
+    import subprocess
+    csrc = os.path.join(ROOT, "vk_gaussian_splatting_amd", "csrc")
+    exe = str(tmp_path / "pack_roundtrip")
+    r = subprocess.run(["g++", *flags, "-std=c++17", "-ffp-contract=off", "-Wall", "-I" + csrc, os.path.join(ROOT, "tests", "helpers", "pack_roundtrip.cpp"),
+                        os.path.join(csrc, "host_model.cpp"), "-lz", "-lpthread", "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, UBSAN_OPTIONS="halt_on_error=1"))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    got = r.stdout.splitlines()
+    assert got[-1] == "pack_roundtrip ok"
+    want = open(os.path.join(GOLDEN, "pack_digests.txt")).read().splitlines()
+    assert len(want) == 4 * 9 * 12
+    differ = [f"{g}  (recorded: {w})" for g, w in zip(got[:-1], want) if g != w]
+    assert len(got) - 1 == len(want) and not differ, "\n".join(differ[:10])
+
+
 def test_camera_set_presets_and_project_camera_fields(tmp_path):
     """class CameraSet (src/camera_set.h:65-190): home preset, duplicate presets collapse (operator== ignores the DoF fields),
     the last preset cannot be erased; the .vkgs camera carries model / dofMode (old files: dofEnabled) / focusDist / aperture

@@ -175,16 +175,16 @@ static int chooseBinGrid(MgsScene s, const MgsFrameParams* p, FrameConst& F)
 // an instance's buffers and what the kernels need of its transform (offsets and blocks are the caller's running sums)
 static void fillInstanceConst(const MgsFrameParams* p, const Instance& I, const DeviceSet& d, InstanceConst& C)
 {
-  C.centers = d.centers;
-  C.cov6    = d.cov6;
-  C.rgba    = d.rgba;
-  C.sh      = d.sh;
-  C.partBox = d.partBox;
-  C.maxScale = d.maxScale;
-  C.scales    = d.scales;
-  C.alpha     = d.alpha;
-  C.rgbaF32   = d.rgbaF32;
-  C.rotations = d.rotations;
+  C.centers = d.centers.p;
+  C.cov6    = d.cov6.p;
+  C.rgba    = d.rgba.p;
+  C.sh      = d.sh.p;
+  C.partBox = d.partBox.p;
+  C.maxScale = d.maxScale.p;
+  C.scales    = d.scales.p;
+  C.alpha     = d.alpha.p;
+  C.rgbaF32   = d.rgbaF32();
+  C.rotations = d.rotations.p;
   {
     auto len3 = [&](int c) { return std::sqrt((I.M[4 * c] * I.M[4 * c] + I.M[4 * c + 1] * I.M[4 * c + 1]) + I.M[4 * c + 2] * I.M[4 * c + 2]); };
     C.modelAxisMax = std::max(len3(0), std::max(len3(1), len3(2)));

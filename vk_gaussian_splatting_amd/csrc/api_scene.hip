@@ -85,29 +85,11 @@ int mgs_scene_create(int device, MgsScene* out)
   return guarded("mgs_scene_create", [&] { return mgs_scene_create_impl(device, out); });
 }
 
-static void freeSet(DeviceSet& d)
-{
-  if(d.centers) (void)hipFree(d.centers);
-  if(d.cov6) (void)hipFree(d.cov6);
-  if(d.rgba) (void)hipFree(d.rgba);
-  if(d.sh) (void)hipFree(d.sh);
-  if(d.partBox) (void)hipFree(d.partBox);
-  if(d.maxScale) (void)hipFree(d.maxScale);
-  if(d.alpha) (void)hipFree(d.alpha);
-  if(d.rgbaF32 && (void*)d.rgbaF32 != d.rgba) (void)hipFree(d.rgbaF32);
-  d.rgbaF32 = nullptr;
-  if(d.scales) (void)hipFree(d.scales);
-  if(d.rotations) (void)hipFree(d.rotations);
-  d.centers = d.cov6 = d.partBox = d.maxScale = d.scales = d.rotations = d.alpha = nullptr;
-  d.rgba = d.sh = nullptr;
-  d.shFormat = d.rgbaFormat = -1;  // a freed (or half-built) set never matches a requested format: commit rebuilds it
-}
-
 SceneData::~SceneData()
 {  // the last handle (scene or context) is gone: every stream that read these buffers was synchronised by its handle's destroy
   (void)hipSetDevice(device);
   for(auto& d : sets)
-    freeSet(d);
+    d.release();
   compInst.release();
   lightTab.release();
   for(auto& m : meshes)
@@ -202,17 +184,6 @@ int mgs_scene_set_list_capacity(MgsScene s, uint64_t entries)
   return MGS_OK;
 }
 
-static uint64_t setBytes(const DeviceSet& d)
-{
-  if(!d.centers)
-    return 0;
-  const uint64_t n   = d.count;
-  const uint64_t fmt[3] = {4, 2, 1};
-  uint64_t       b   = n * (12 + 24 + 4 + 4 + 12 + 16) + ((n + kPart - 1) / kPart) * 32;  // centres, cov6, alpha, maxScale, scales, rotations, partBox
-  b += n * 4 * fmt[d.rgbaFormat] + (d.rgbaFormat != MGS_FORMAT_FLOAT32 ? n * 16 : 0);
-  b += d.sh ? n * (uint64_t)d.shPitch * fmt[d.shFormat] : 0;
-  return b;
-}
 int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBytes)
 {
   if(!s)
@@ -226,7 +197,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
     for(const auto& m : s->d->meshes)
       b += m.bytes();
     for(const auto& d : s->d->sets)
-      b += setBytes(d);
+      b += d.bytes();
     *sceneBytes = b;
   }
   if(workingBytes)
@@ -445,37 +416,49 @@ uint64_t mgs_scene_splat_count(MgsScene s)
   return total;
 }
 
-static int uploadFormatted(const std::vector<float>& src, int format, bool isSh, void** dev)
+// the only way a plane of a splat set reaches the device
+template <typename T>
+static int uploadPlane(DevBuf<T>& dst, const std::vector<T>& src)
 {
-  const size_t n = src.size();
-  if(n == 0)
+  if(int rc = dst.ensure(src.size()))
+    return rc;
+  if(!src.empty())
+    HIPCHK(hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return MGS_OK;
+}
+static int uploadSet(const PackedSplatSet& P, DeviceSet& d)
+{
+  int rc = MGS_OK;
+  if((rc = uploadPlane(d.centers, P.centers))) return rc;
+  if((rc = uploadPlane(d.partBox, P.partBox))) return rc;
+  if((rc = uploadPlane(d.maxScale, P.maxScale))) return rc;
+  if((rc = uploadPlane(d.scales, P.scales))) return rc;
+  if((rc = uploadPlane(d.rotations, P.rotations))) return rc;
+  if((rc = uploadPlane(d.cov6, P.cov6))) return rc;
+  if((rc = uploadPlane(d.rgba, P.rgba))) return rc;
+  if((rc = uploadPlane(d.rgbaRead, P.rgbaRead))) return rc;
+  if((rc = uploadPlane(d.alpha, P.alpha))) return rc;
+  return uploadPlane(d.sh, P.sh);
+}
+// Releases the set, then builds it in the requested formats.  The new planes become the set's only when all of them have arrived:
+// a failure leaves it released and unbuilt, and the next commit starts over.
+static int commitSet(DeviceSet& d, int shFormat, int rgbaFormat)
+{
+  d.release();
+  PackedSplatSet P;
+  packSplatSet(*d.host, shFormat, rgbaFormat, P);
+  DeviceSet fresh;
+  fresh.host = d.host;
+  fresh.count = P.count, fresh.shDegree = P.shDegree, fresh.shStride = P.shStride, fresh.shPitch = P.shPitch;
+  fresh.shFormat = shFormat, fresh.rgbaFormat = rgbaFormat;
+  if(int rc = uploadSet(P, fresh))
   {
-    *dev = nullptr;
-    return MGS_OK;
+    fresh.release();
+    return rc;
   }
-  const size_t esz = format == MGS_FORMAT_FLOAT32 ? 4 : format == MGS_FORMAT_FLOAT16 ? 2 : 1;
-  if(hipMalloc(dev, n * esz) != hipSuccess)
-  {
-    setError("commit: device allocation failed");
-    return MGS_ERR_OOM;
-  }
-  if(format == MGS_FORMAT_FLOAT32)
-  {
-    HIPCHK(hipMemcpy(*dev, src.data(), n * 4, hipMemcpyHostToDevice));
-  }
-  else if(format == MGS_FORMAT_FLOAT16)
-  {
-    std::vector<uint16_t> tmp(n);
-    parallelBatches(n, [&](size_t i) { tmp[i] = floatToHalf(src[i]); });
-    HIPCHK(hipMemcpy(*dev, tmp.data(), n * 2, hipMemcpyHostToDevice));
-  }
-  else
-  {
-    std::vector<uint8_t> tmp(n);
-    const float          lo = isSh ? -1.f : 0.f;
-    parallelBatches(n, [&](size_t i) { tmp[i] = toUint8(src[i], lo, 1.f); });
-    HIPCHK(hipMemcpy(*dev, tmp.data(), n, hipMemcpyHostToDevice));
-  }
+  fresh.newToOld = std::move(P.newToOld), fresh.oldToNew = std::move(P.oldToNew);
+  fresh.built    = true;
+  d              = std::move(fresh);
   return MGS_OK;
 }
 
@@ -509,174 +492,37 @@ static int mgs_scene_commit_impl(MgsScene s, int shFormat, int rgbaFormat)
       HIPCHK(hipStreamSynchronize(h->stream));
   }
   s->graphs.drop();  // captured frames hold the old buffers and grid sizes (contexts drop theirs when they see the new epoch)
+  s->d->committed = false;  // until every set below is whole
   for(auto& d : s->d->sets)
-  {
-    if(d.centers && d.shFormat == shFormat && d.rgbaFormat == rgbaFormat)
-      continue;  // idempotent
-    freeSet(d);
-    const HostSplatSet& h = *d.host;
-    const size_t        n = h.size();
-    d.count               = (uint32_t)n;
-    d.shDegree            = std::max(0, h.maxShDegree());
-    d.shStride            = shStride(h.fRestPerSplat());
-    // storage order: Morton order of the centres.  Global ids used inside the pipeline are STORAGE ids; the
-    // API maps them back (mgs_sort_download, mgs_scene_download_set, mgs_scene_storage_order).  Ties between
-    // equal depth keys resolve in storage order — the reference's tie order is nondeterministic
-    // (dist.comp.slang:137-139).
-    std::vector<float> cov;
-    buildCov6(h, cov);
-    {
-      std::vector<float> radius(n);
-      parallelBatches(n, [&](size_t i) { radius[i] = std::sqrt(8.0f * (cov[6 * i] + cov[6 * i + 3] + cov[6 * i + 5])); });
-      mortonOrder(h, &radius, d.newToOld);
-    }
-    d.oldToNew.resize(n);
-    parallelBatches(n, [&](size_t i) { d.oldToNew[d.newToOld[i]] = (uint32_t)i; });
-    const uint32_t* perm = d.newToOld.data();
-    // a4: SplatSetVk::initDataBuffers (src/splat_set_vk.cpp:188-480), host loops like the reference
-    {
-      std::vector<float> pos(n * 3);
-      parallelBatches(n, [&](size_t i) { std::memcpy(&pos[3 * i], &h.positions[3 * (size_t)perm[i]], 12); });
-      HIPCHK(hipMalloc((void**)&d.centers, n * 3 * sizeof(float)));
-      HIPCHK(hipMemcpy(d.centers, pos.data(), n * 3 * sizeof(float), hipMemcpyHostToDevice));
-      // per-partition bounds (model space): AABB of the centres and rmax = sqrt(8 * max trace(Sigma3D)),
-      // an upper bound of the sqrt(8)-sigma footprint radius of any splat of the partition
-      const size_t       np = (n + kPart - 1) / kPart;
-      std::vector<float> box(np * 8);
-      parallelBatches(np, [&](size_t pIdx) {
-        float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f}, tr = 0.f;
-        bool  bad = false;
-        for(size_t i = pIdx * kPart; i < std::min(n, (pIdx + 1) * kPart); ++i)
-        {
-          for(int a = 0; a < 3; ++a)
-          {
-            const float v = pos[3 * i + a];
-            if(!std::isfinite(v)) bad = true;
-            mn[a] = std::min(mn[a], v);
-            mx[a] = std::max(mx[a], v);
-          }
-          const float* c = &cov[6 * (size_t)perm[i]];
-          const float  t = c[0] + c[3] + c[5];
-          if(!std::isfinite(t)) bad = true;
-          tr = std::max(tr, t);
-        }
-        float* b = &box[8 * pIdx];
-        for(int a = 0; a < 3; ++a)
-        {
-          b[a]     = mn[a];
-          b[3 + a] = mx[a];
-        }
-        b[6] = std::sqrt(8.0f * tr);
-        b[7] = bad ? 1.0f : 0.0f;  // non-finite data: never cull this partition
-      });
-      HIPCHK(hipMalloc((void**)&d.partBox, np * 8 * sizeof(float)));
-      HIPCHK(hipMemcpy(d.partBox, box.data(), np * 8 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {  // size culling (dist.comp.slang:93-134) needs max(exp(scale)): 4 B/splat, exp() on the host like the oracle
-      std::vector<float> ms(n);
-      parallelBatches(n, [&](size_t i) {
-        const float* sc = &h.scale[3 * (size_t)perm[i]];
-        ms[i]           = std::max(std::exp(sc[0]), std::max(std::exp(sc[1]), std::exp(sc[2])));
-      });
-      HIPCHK(hipMalloc((void**)&d.maxScale, n * sizeof(float)));
-      HIPCHK(hipMemcpy(d.maxScale, ms.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {  // raw scales / rotations (splat_set_vk.cpp:221-251): 28 B/splat, read by the surface normal only
-      std::vector<float> sc(n * 3), rq(n * 4);
-      parallelBatches(n, [&](size_t i) {
-        std::memcpy(&sc[3 * i], &h.scale[3 * (size_t)perm[i]], 12);
-        std::memcpy(&rq[4 * i], &h.rotation[4 * (size_t)perm[i]], 16);
-      });
-      HIPCHK(hipMalloc((void**)&d.scales, n * 3 * sizeof(float)));
-      HIPCHK(hipMemcpy(d.scales, sc.data(), n * 3 * sizeof(float), hipMemcpyHostToDevice));
-      HIPCHK(hipMalloc((void**)&d.rotations, n * 4 * sizeof(float)));
-      HIPCHK(hipMemcpy(d.rotations, rq.data(), n * 4 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {
-      std::vector<float> planar(n * 6);
-      // HBM layout: float4 covA[n] = (S00,S01,S02,S11) followed by float2 covB[n] = (S12,S22)
-      parallelBatches(n, [&](size_t i) {
-        std::memcpy(&planar[4 * i], &cov[6 * (size_t)perm[i]], 16);
-        std::memcpy(&planar[4 * n + 2 * i], &cov[6 * (size_t)perm[i] + 4], 8);
-      });
-      HIPCHK(hipMalloc((void**)&d.cov6, n * 6 * sizeof(float)));
-      HIPCHK(hipMemcpy(d.cov6, planar.data(), n * 6 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {
-      std::vector<float> rgba, re(n * 4);
-      buildRgba(h, rgba);
-      parallelBatches(n, [&](size_t i) { std::memcpy(&re[4 * i], &rgba[4 * (size_t)perm[i]], 16); });
-      int rc = uploadFormatted(re, rgbaFormat, false, &d.rgba);
-      if(rc != MGS_OK)
+    if(!(d.built && d.shFormat == shFormat && d.rgbaFormat == rgbaFormat))
+      if(int rc = commitSet(d, shFormat, rgbaFormat))
         return rc;
-      // the colours exactly as fetchColor reads them back from the formatted buffer (threedgs_particle_buffers.h.slang:
-      // 72-90): fp32 for the compositor's shading phase, and the opacity as a plane of its own — all the projection needs
-      std::vector<float> al(n);
-      if(rgbaFormat != MGS_FORMAT_FLOAT32)
-        parallelBatches(n * 4, [&](size_t i) {
-          re[i] = rgbaFormat == MGS_FORMAT_FLOAT16 ? halfToFloat(floatToHalf(re[i])) : (float)toUint8(re[i], 0.f, 1.f) / 255.0f;
-        });
-      parallelBatches(n, [&](size_t i) { al[i] = re[4 * i + 3]; });
-      if(rgbaFormat == MGS_FORMAT_FLOAT32)
-        d.rgbaF32 = static_cast<float*>(d.rgba);
-      else
-      {
-        HIPCHK(hipMalloc((void**)&d.rgbaF32, n * 4 * sizeof(float)));
-        HIPCHK(hipMemcpy(d.rgbaF32, re.data(), n * 4 * sizeof(float), hipMemcpyHostToDevice));
-      }
-      HIPCHK(hipMalloc((void**)&d.alpha, n * sizeof(float)));
-      HIPCHK(hipMemcpy(d.alpha, al.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if(d.shStride)
-    {
-      std::vector<float> sh, padded;
-      buildShInterleaved(h, sh);
-      // one 48-element record per (storage) splat, [coef][rgb] like the reference, zero padded: the compositor
-      // fetches whole records of the splats it stages (192 B fp32 = three 64-byte sectors)
-      d.shPitch = 48;
-      padded.assign(n * (size_t)d.shPitch, 0.f);
-      const int stride = d.shStride;
-      parallelBatches(n, [&](size_t i) {
-        std::memcpy(&padded[i * (size_t)d.shPitch], &sh[(size_t)perm[i] * (size_t)stride], sizeof(float) * stride);
-      });
-      int rc = uploadFormatted(padded, shFormat, true, &d.sh);
-      if(rc != MGS_OK)
-        return rc;
-    }
-    d.shFormat   = shFormat;
-    d.rgbaFormat = rgbaFormat;
-  }
   s->d->shFormat   = shFormat;
   s->d->rgbaFormat = rgbaFormat;
 
   // global id space + partitions (a5: rebuildGlobalIndexTables, splat_set_manager_vk.cpp:2304-2360,
   // here a closed-form prefix instead of an 8-byte-per-splat table)
-  uint64_t total = 0, parts = 0;
-  for(const auto& I : s->d->instances)
+  // and the compositor's SH table of all instances (it carries the first 16 by value)
+  uint64_t                         total = 0, parts = 0;
+  std::vector<CompositeArgs::Inst> tab(s->d->instances.size());
+  s->d->instOffset.clear();
+  for(size_t k = 0; k < s->d->instances.size(); ++k)
   {
-    const uint32_t c = s->d->sets[I.set].count;
-    total += c;
-    parts += (c + kPart - 1) / kPart;
+    const DeviceSet& d  = s->d->sets[s->d->instances[k].set];
+    tab[k].sh           = d.sh.p;
+    tab[k].rgba         = reinterpret_cast<const float4*>(d.rgbaF32());
+    tab[k].centers      = d.centers.p;
+    tab[k].globalOffset = (uint32_t)total;
+    tab[k].shDegree     = d.shDegree;
+    s->d->instOffset.push_back((uint32_t)total);
+    total += d.count;
+    parts += (d.count + kPart - 1) / kPart;
   }
+  s->d->instOffset.push_back((uint32_t)total);
   s->d->totalSplats = (uint32_t)total;
   s->d->totalParts  = (uint32_t)parts;
-  int rc = MGS_OK;
-  {  // the compositor's SH table of all instances (it carries the first 16 by value)
-    std::vector<CompositeArgs::Inst> tab(s->d->instances.size());
-    uint32_t                         off = 0;
-    for(size_t k = 0; k < s->d->instances.size(); ++k)
-    {
-      const DeviceSet& d  = s->d->sets[s->d->instances[k].set];
-      tab[k].sh           = d.sh;
-      tab[k].rgba         = reinterpret_cast<const float4*>(d.rgbaF32);
-      tab[k].centers      = d.centers;
-      tab[k].globalOffset = off;
-      tab[k].shDegree     = d.shDegree;
-      off += d.count;
-    }
-    if((rc = s->d->compInst.ensure(tab.size()))) return rc;
-    HIPCHK(hipMemcpy(s->d->compInst.p, tab.data(), tab.size() * sizeof(tab[0]), hipMemcpyHostToDevice));
-  }
+  if(int rc = uploadPlane(s->d->compInst, tab))
+    return rc;
   s->d->committed = true;
   s->d->epoch += 1;
   return sizeWorkingSet(s);
@@ -798,13 +644,12 @@ int mgs_scene_download_set(MgsScene s, int instance, int which, float* dst, size
   size_t           need;
   const void*      src;
   int              fmt = MGS_FORMAT_FLOAT32;
-  bool             isSh = false, isCov = false;
   switch(which)
   {
-    case 0: need = 3 * n; src = d.centers; break;
-    case 1: need = 6 * n; src = d.cov6; isCov = true; break;
-    case 2: need = 4 * n; src = d.rgba; fmt = d.rgbaFormat; break;
-    case 3: need = (size_t)d.shStride * n; src = d.sh; fmt = d.shFormat; isSh = true; break;
+    case 0: need = 3 * n; src = d.centers.p; break;
+    case 1: need = 6 * n; src = d.cov6.p; break;
+    case 2: need = 4 * n; src = d.rgba.p; fmt = d.rgbaFormat; break;
+    case 3: need = (size_t)d.shStride * n; src = d.sh.p; fmt = d.shFormat; break;
     default: setError("mgs_scene_download_set: unknown buffer"); return MGS_ERR_INVALID_ARG;
   }
   if(count < need)
@@ -814,84 +659,23 @@ int mgs_scene_download_set(MgsScene s, int instance, int which, float* dst, size
   }
   if(need == 0)
     return MGS_OK;
-  const uint32_t* n2o = d.newToOld.data();  // storage index -> caller's index
-  if(isCov)
-  {  // planar (float4 covA[n], float2 covB[n]) in storage order -> the reference's 6 floats per splat, caller's order
-    std::vector<float> raw(need);
-    HIPCHK(hipMemcpy(raw.data(), src, need * 4, hipMemcpyDeviceToHost));
-    for(size_t i = 0; i < n; ++i)
-    {
-      std::memcpy(dst + 6 * (size_t)n2o[i], &raw[4 * i], 16);
-      std::memcpy(dst + 6 * (size_t)n2o[i] + 4, &raw[4 * n + 2 * i], 8);
-    }
-    return MGS_OK;
-  }
-  if(isSh)
-  {  // padded records in storage order: fetch, dequantise, restore [splat][coef][rgb] in the caller's order
-    const size_t         tot = (size_t)d.shPitch * n;
-    const size_t         esz = fmt == MGS_FORMAT_FLOAT32 ? 4 : fmt == MGS_FORMAT_FLOAT16 ? 2 : 1;
-    std::vector<uint8_t> raw(tot * esz);
-    HIPCHK(hipMemcpy(raw.data(), src, raw.size(), hipMemcpyDeviceToHost));
-    for(size_t i = 0; i < n; ++i)
-      for(int k = 0; k < d.shStride; ++k)
-      {
-        const size_t j = i * (size_t)d.shPitch + (size_t)k;
-        float        v;
-        if(fmt == MGS_FORMAT_FLOAT32)
-          std::memcpy(&v, raw.data() + 4 * j, 4);
-        else if(fmt == MGS_FORMAT_FLOAT16)
-        {
-          uint16_t hv;
-          std::memcpy(&hv, raw.data() + 2 * j, 2);
-          v = halfToFloat(hv);
-        }
-        else
-          v = (float)raw[j] / 255.0f * 2.0f - 1.0f;
-        dst[(size_t)n2o[i] * (size_t)d.shStride + k] = v;
-      }
-    return MGS_OK;
-  }
-  {  // centres (3 floats) and rgba (4 elements): fetch in storage order, dequantise, scatter to the caller's order
-    const size_t       w = (which == 0) ? 3 : 4;
-    std::vector<float> tmp(need);
-    if(fmt == MGS_FORMAT_FLOAT32)
-      HIPCHK(hipMemcpy(tmp.data(), src, need * 4, hipMemcpyDeviceToHost));
-    else if(fmt == MGS_FORMAT_FLOAT16)
-    {
-      std::vector<uint16_t> raw(need);
-      HIPCHK(hipMemcpy(raw.data(), src, need * 2, hipMemcpyDeviceToHost));
-      for(size_t i = 0; i < need; ++i)
-        tmp[i] = halfToFloat(raw[i]);
-    }
-    else
-    {
-      std::vector<uint8_t> raw(need);
-      HIPCHK(hipMemcpy(raw.data(), src, need, hipMemcpyDeviceToHost));
-      for(size_t i = 0; i < need; ++i)
-        tmp[i] = (float)raw[i] / 255.0f;
-    }
-    for(size_t i = 0; i < n; ++i)
-      std::memcpy(dst + w * (size_t)n2o[i], &tmp[w * i], w * sizeof(float));
-    return MGS_OK;
-  }
+  std::vector<uint8_t> raw(packedPlaneBytes(which, n, d.shPitch, fmt));
+  HIPCHK(hipMemcpy(raw.data(), src, raw.size(), hipMemcpyDeviceToHost));
+  unpackPlane(which, raw.data(), fmt, d.newToOld, d.shStride, d.shPitch, dst);
+  return MGS_OK;
 }
 
 // storage global id <-> caller global id.  Instances are concatenated in creation order in both spaces;
 // only the index inside a splat set is permuted.
 static void mapIds(MgsScene s, uint32_t* ids, size_t n, std::vector<uint32_t> DeviceSet::*perm)
 {
-  std::vector<uint32_t> offs;
-  uint32_t              o = 0;
-  for(const auto& I : s->d->instances)
-  {
-    offs.push_back(o);
-    o += s->d->sets[I.set].count;
-  }
-  offs.push_back(o);
+  const std::vector<uint32_t>& offs = s->d->instOffset;  // of the last commit
+  if(offs.empty())
+    return;
   parallelBatches(n, [&](size_t i) {
     const uint32_t g = ids[i];
     size_t         k = 0;
-    while(k + 1 < s->d->instances.size() && g >= offs[k + 1])
+    while(k + 2 < offs.size() && g >= offs[k + 1])
       ++k;
     ids[i] = offs[k] + (s->d->sets[s->d->instances[k].set].*perm)[g - offs[k]];
   });

@@ -926,6 +926,154 @@ float halfToFloat(uint16_t h)
   return f;
 }
 
+// ------------------------------------------------------------------------------------ the committed planes
+void quantise(const float* src, size_t n, int format, bool isSh, uint8_t* dst)
+{
+  const float lo = isSh ? -1.f : 0.f;
+  if(format == MGS_FORMAT_FLOAT32)
+    std::memcpy(dst, src, n * 4);
+  else if(format == MGS_FORMAT_FLOAT16)
+    for(size_t i = 0; i < n; ++i)
+    {
+      const uint16_t hv = floatToHalf(src[i]);
+      std::memcpy(dst + 2 * i, &hv, 2);
+    }
+  else
+    for(size_t i = 0; i < n; ++i)
+      dst[i] = toUint8(src[i], lo, 1.f);
+}
+void dequantise(const uint8_t* src, size_t n, int format, bool isSh, float* dst)
+{
+  if(format == MGS_FORMAT_FLOAT32)
+    std::memcpy(dst, src, n * 4);
+  else if(format == MGS_FORMAT_FLOAT16)
+    for(size_t i = 0; i < n; ++i)
+    {
+      uint16_t hv;
+      std::memcpy(&hv, src + 2 * i, 2);
+      dst[i] = halfToFloat(hv);
+    }
+  else if(isSh)
+    for(size_t i = 0; i < n; ++i)
+      dst[i] = (float)src[i] / 255.0f * 2.0f - 1.0f;
+  else
+    for(size_t i = 0; i < n; ++i)
+      dst[i] = (float)src[i] / 255.0f;
+}
+
+void packSplatSet(const HostSplatSet& h, int shFormat, int rgbaFormat, PackedSplatSet& out)
+{
+  const size_t n = h.size();
+  out.count      = (uint32_t)n;
+  out.shDegree   = std::max(0, h.maxShDegree());
+  out.shStride   = shStride(h.fRestPerSplat());
+  out.shPitch    = out.shStride ? 48 : 0;
+  std::vector<float> cov;
+  buildCov6(h, cov);
+  {
+    std::vector<float> radius(n);
+    parallelBatches(n, [&](size_t i) { radius[i] = std::sqrt(8.0f * (cov[6 * i] + cov[6 * i + 3] + cov[6 * i + 5])); });
+    mortonOrder(h, &radius, out.newToOld);
+  }
+  out.oldToNew.resize(n);
+  parallelBatches(n, [&](size_t i) { out.oldToNew[out.newToOld[i]] = (uint32_t)i; });
+  const uint32_t* perm = out.newToOld.data();
+
+  out.centers.resize(n * 3), out.cov6.resize(n * 6), out.maxScale.resize(n), out.scales.resize(n * 3), out.rotations.resize(n * 4);
+  parallelBatches(n, [&](size_t i) {
+    const size_t o = perm[i];
+    std::memcpy(&out.centers[3 * i], &h.positions[3 * o], 12);
+    std::memcpy(&out.cov6[4 * i], &cov[6 * o], 16);
+    std::memcpy(&out.cov6[4 * n + 2 * i], &cov[6 * o + 4], 8);
+    const float* sc = &h.scale[3 * o];
+    out.maxScale[i] = std::max(std::exp(sc[0]), std::max(std::exp(sc[1]), std::exp(sc[2])));
+    std::memcpy(&out.scales[3 * i], sc, 12);
+    std::memcpy(&out.rotations[4 * i], &h.rotation[4 * o], 16);
+  });
+  // per-partition bounds (model space): AABB of the centres and rmax = sqrt(8 * max trace(Sigma3D)), an upper bound of the
+  // sqrt(8)-sigma footprint radius of any splat of the partition
+  const size_t np = (n + kPackPart - 1) / kPackPart;
+  out.partBox.resize(np * 8);
+  parallelBatches(np, [&](size_t pIdx) {
+    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f}, tr = 0.f;
+    bool  bad = false;
+    for(size_t i = pIdx * kPackPart; i < std::min(n, (pIdx + 1) * kPackPart); ++i)
+    {
+      for(int a = 0; a < 3; ++a)
+      {
+        const float v = out.centers[3 * i + a];
+        if(!std::isfinite(v)) bad = true;
+        mn[a] = std::min(mn[a], v);
+        mx[a] = std::max(mx[a], v);
+      }
+      const float* c = &cov[6 * (size_t)perm[i]];
+      const float  t = c[0] + c[3] + c[5];
+      if(!std::isfinite(t)) bad = true;
+      tr = std::max(tr, t);
+    }
+    float* b = &out.partBox[8 * pIdx];
+    for(int a = 0; a < 3; ++a)
+    {
+      b[a]     = mn[a];
+      b[3 + a] = mx[a];
+    }
+    b[6] = std::sqrt(8.0f * tr);
+    b[7] = bad ? 1.0f : 0.0f;  // non-finite data: never cull this partition
+  });
+  {
+    std::vector<float> rgba;
+    buildRgba(h, rgba);
+    const size_t esz = formatBytes(rgbaFormat);
+    out.rgba.resize(n * 4 * esz), out.rgbaRead.resize(rgbaFormat == MGS_FORMAT_FLOAT32 ? 0 : n * 4), out.alpha.resize(n);
+    parallelBatches(n, [&](size_t i) {
+      uint8_t* q = &out.rgba[4 * i * esz];
+      float    back[4];
+      quantise(&rgba[4 * (size_t)perm[i]], 4, rgbaFormat, false, q);
+      dequantise(q, 4, rgbaFormat, false, back);
+      if(!out.rgbaRead.empty())
+        std::memcpy(&out.rgbaRead[4 * i], back, 16);
+      out.alpha[i] = back[3];
+    });
+  }
+  out.sh.clear();
+  if(out.shStride)
+  {
+    std::vector<float> sh;
+    buildShInterleaved(h, sh);
+    const size_t esz = formatBytes(shFormat), stride = (size_t)out.shStride, pitch = (size_t)out.shPitch;
+    const std::vector<float> zeros(pitch - stride, 0.f);
+    out.sh.resize(n * pitch * esz);
+    parallelBatches(n, [&](size_t i) {
+      uint8_t* rec = &out.sh[i * pitch * esz];
+      quantise(&sh[(size_t)perm[i] * stride], stride, shFormat, true, rec);
+      quantise(zeros.data(), zeros.size(), shFormat, true, rec + stride * esz);
+    });
+  }
+}
+
+size_t packedPlaneBytes(int which, size_t count, int shPitch, int format)
+{
+  const size_t elems[4] = {3, 6, 4, (size_t)shPitch};
+  return count * elems[which] * formatBytes(format);
+}
+void unpackPlane(int which, const uint8_t* raw, int format, const std::vector<uint32_t>& newToOld, int shStride, int shPitch, float* dst)
+{
+  const size_t n = newToOld.size(), esz = formatBytes(format);
+  if(which == 1)
+  {  // float4 covA[n], float2 covB[n] -> the reference's 6 floats per splat
+    for(size_t i = 0; i < n; ++i)
+    {
+      std::memcpy(dst + 6 * (size_t)newToOld[i], raw + 16 * i, 16);
+      std::memcpy(dst + 6 * (size_t)newToOld[i] + 4, raw + 16 * n + 8 * i, 8);
+    }
+    return;
+  }
+  // records of `w` logical elements every `pitch` stored ones: dequantise, scatter to the caller's order
+  const size_t w = which == 0 ? 3 : which == 2 ? 4 : (size_t)shStride, pitch = which == 3 ? (size_t)shPitch : w;
+  for(size_t i = 0; i < n; ++i)
+    dequantise(raw + i * pitch * esz, w, format, which == 3, dst + w * (size_t)newToOld[i]);
+}
+
 }  // namespace mgs
 
 // ---- triangle meshes: the OBJ subset of mgs_mesh_load_obj (include/mgs.h) ------------------------------------------------------

@@ -72,6 +72,45 @@ uint8_t  toUint8(float v, float lo, float hi);  // src/splat_set_vk.cpp:85-89
 // set by a few outliers.
 void mortonOrder(const HostSplatSet& s, const std::vector<float>* radius, std::vector<uint32_t>& newToOld);
 
+// ---- the planes of a committed splat set, as they lie in device memory (mgs_scene_commit uploads them as they are) ----
+// Storage formats are include/mgs.h's MGS_FORMAT_FLOAT32 / FLOAT16 / UINT8 (0 / 1 / 2).  UINT8 maps [0,1] (colours) or [-1,1] (SH).
+constexpr uint32_t kPackPart = 2048;  // splats per partition (= kPart of the kernels)
+inline size_t formatBytes(int format) { return format == 0 ? 4 : format == 1 ? 2 : 1; }
+void quantise(const float* src, size_t n, int format, bool isSh, uint8_t* dst);    // the ONE float -> storage format ...
+void dequantise(const uint8_t* src, size_t n, int format, bool isSh, float* dst);  // ... and the ONE way back (fetchColor's read)
+
+struct PackedSplatSet
+{
+  // storage order (size classes, then Morton order of the centres) <-> caller's order.  Ids inside the pipeline are STORAGE ids; ties
+  // between equal depth keys resolve in storage order (the reference's tie order is nondeterministic, dist.comp.slang:137-139)
+  std::vector<uint32_t> newToOld, oldToNew;
+  // everything below in storage order
+  std::vector<float>   centers;    // [count*3]
+  std::vector<float>   cov6;       // planar: float4 covA[count] = (S00,S01,S02,S11) then float2 covB[count] = (S12,S22)
+  std::vector<float>   partBox;    // [ceil(count/2048)][8]: min xyz, max xyz of the centres, rmax = sqrt(8 * max trace(Sigma)), and
+                                   // 1.0 where the partition holds non-finite data (never culled)
+  std::vector<float>   maxScale;   // [count] max(exp(scale)): size culling (dist.comp.slang:93-134), exp() on the host like the oracle
+  std::vector<float>   scales;     // [count*3] log scales   } as stored (splat_set_vk.cpp:221-251), read by the surface normal only
+  std::vector<float>   rotations;  // [count*4] (w,x,y,z)    }
+  std::vector<uint8_t> rgba;       // [count*4] in the colour format
+  std::vector<float>   rgbaRead;   // [count*4] `rgba` as fetchColor reads it back (threedgs_particle_buffers.h.slang:72-90); empty
+                                   // when `rgba` is stored as fp32 and is that plane itself
+  std::vector<float>   alpha;      // [count] the fourth component of rgbaF32(): all the projection needs
+  std::vector<uint8_t> sh;         // [count] records of shPitch elements in the SH format, [coef][rgb] like the reference then
+                                   // zeros: the compositor fetches whole records (192 B fp32 = three 64-byte sectors)
+  uint32_t count = 0;
+  int      shDegree = 0, shStride = 0;  // logical SH elements per splat (0/9/24/45)
+  int      shPitch = 0;                 // stored ones (48, or 0 without SH)
+  // [count*4] the colours as the shaders read them back
+  const float* rgbaF32() const { return rgbaRead.empty() ? reinterpret_cast<const float*>(rgba.data()) : rgbaRead.data(); }
+};
+// a4: SplatSetVk::initDataBuffers (src/splat_set_vk.cpp:188-480), host loops like the reference
+void packSplatSet(const HostSplatSet& h, int shFormat, int rgbaFormat, PackedSplatSet& out);
+// the inverse for the planes mgs_scene_download_set names (0 centres, 1 cov6 as 6 floats per splat, 2 rgba, 3 SH as
+// [splat][coef][rgb]): `raw` is the plane as stored, `dst` fp32 in the caller's order
+size_t packedPlaneBytes(int which, size_t count, int shPitch, int format);
+void   unpackPlane(int which, const uint8_t* raw, int format, const std::vector<uint32_t>& newToOld, int shStride, int shPitch, float* dst);
+
 // parallel-for over [0,n) in batches of 8192 (START_PAR_LOOP, src/utilities.h:52-59)
 template <typename F>
 void parallelBatches(size_t n, F&& fn);

@@ -70,32 +70,6 @@ struct MgsSplatSet_t
   std::shared_ptr<HostSplatSet> data;
 };
 
-struct DeviceSet
-{
-  std::shared_ptr<HostSplatSet> host;
-  float*   centers = nullptr;
-  float*   cov6    = nullptr;
-  void*    rgba    = nullptr;
-  void*    sh      = nullptr;
-  uint32_t count   = 0;
-  int      shDegree = 0, shStride = 0;  // logical elements per splat (0/9/24/45)
-  int      shPitch = 0;                  // stored elements per splat: shStride padded to a 16-byte multiple
-  int      shFormat = -1, rgbaFormat = -1;
-  float*   maxScale = nullptr;             // [count] max(exp(scale)), storage order
-  float*   rgbaF32 = nullptr;              // [count*4] colours as the shaders read them back (== rgba when stored as fp32)
-  float*   alpha = nullptr;                // [count] dequantised opacity, storage order (the projection's view of rgba)
-  float*   scales = nullptr;               // [count*3] log scales, storage order   } integrated-normal side output
-  float*   rotations = nullptr;            // [count*4] (w,x,y,z), storage order    }
-  float*   partBox = nullptr;              // [ceil(count/2048)][8]: AABB of the centres + footprint radius bound
-  std::vector<uint32_t> newToOld, oldToNew;  // storage order (Morton) <-> caller's order
-};
-
-struct Instance
-{
-  int   set;  // index into sets
-  float M[16];
-};
-
 template <typename T>
 struct DevBuf
 {
@@ -125,6 +99,43 @@ struct DevBuf
     n = 0;
   }
   uint64_t bytes() const { return (uint64_t)n * sizeof(T); }
+};
+
+// A committed splat set on the device: the planes of PackedSplatSet (host_model.h), uploaded as they are.  Built whole or not at all
+// (commitSet, api_scene.hip); `host` stays when the planes are released.
+struct DeviceSet
+{
+  std::shared_ptr<HostSplatSet> host;
+  DevBuf<float>   centers, cov6, partBox, maxScale, scales, rotations, alpha;
+  DevBuf<uint8_t> rgba, sh;   // as stored: fp32 | fp16 | u8 (`sh` stays empty for a set without SH)
+  DevBuf<float>   rgbaRead;   // `rgba` read back as fp32, for the formats where `rgba` itself is not that
+  uint32_t count   = 0;
+  int      shDegree = 0, shStride = 0, shPitch = 0;  // PackedSplatSet's
+  int      shFormat = -1, rgbaFormat = -1;
+  bool     built = false;
+  std::vector<uint32_t> newToOld, oldToNew;  // storage order (Morton) <-> caller's order
+
+  // [count*4] the colours as the shaders read them back
+  const float* rgbaF32() const { return rgbaFormat == MGS_FORMAT_FLOAT32 ? reinterpret_cast<const float*>(rgba.p) : rgbaRead.p; }
+  uint64_t bytes() const
+  {
+    return centers.bytes() + cov6.bytes() + partBox.bytes() + maxScale.bytes() + scales.bytes() + rotations.bytes() + alpha.bytes()
+           + rgba.bytes() + sh.bytes() + rgbaRead.bytes();
+  }
+  void release()
+  {
+    centers.release(), cov6.release(), partBox.release(), maxScale.release(), scales.release(), rotations.release(), alpha.release();
+    rgba.release(), sh.release(), rgbaRead.release();
+    shFormat = rgbaFormat = -1;
+    built = false;
+  }
+};
+static_assert(kPackPart == kPart, "the host pack and the kernels agree on the partition size");
+
+struct Instance
+{
+  int   set;  // index into sets
+  float M[16];
 };
 
 // a typed window into memory somebody else owns (the members of FrameState, frame_state.h)
@@ -242,6 +253,7 @@ struct SceneData
   bool                   committed = false;
   int                    shFormat = 0, rgbaFormat = 0;
   uint32_t               totalSplats = 0, totalParts = 0;
+  std::vector<uint32_t>  instOffset;     // [instances + 1] first global id of each instance (the same in storage and caller's ids)
   DevBuf<CompositeArgs::Inst> compInst;  // SH table of all instances for the compositor (scenes with > 16 instances)
   // lights and per-instance materials of the lighting pass (mgs_scene_set_lights, mgs_instance_set_material): the host copy, and
   // the device block every context's pass reads (allocated once: its address is baked into captured frames)
