@@ -43,12 +43,15 @@ extern "C" {
                                  mgs_render_traced, mgs_trace_download_hit_counts;
                             lit traced frames (MGS_HAS_TRACE_LIGHTING below): entry points only, both numbers stay —
                                  mgs_trace_light_params_default, mgs_render_traced_lit, mgs_trace_download_shadow_hits;
-                            hybrid frames (MGS_HAS_HYBRID below): one entry point, both numbers stay — mgs_render_hybrid */
+                            hybrid frames (MGS_HAS_HYBRID below): one entry point, both numbers stay — mgs_render_hybrid;
+                            3DGUT record hook (MGS_HAS_PROJECTED_GUT below): one entry point, both numbers stay —
+                                 mgs_frame_download_projected_gut */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -796,6 +799,14 @@ int  mgs_compare_download_composite(MgsScene scene_or_context, void* host_dst, s
  * opacity (after MS antialiasing), conservative half extents x/y of the visible footprint (pixels), 0 };
  * rect_out[i] (may be NULL) = the footprint's bin rectangle x0 | y0<<8 | x1<<16 | y1<<24. */
 int mgs_frame_download_projected(MgsScene scene, const uint32_t* global_ids, size_t count, float* out10, uint32_t* rect_out);
+/* the same hook for a 3DGUT frame (MGS_HAS_PROJECTED_GUT; threedgut_raster.mesh.slang:111-254, whose per-quad outputs the
+ * reference never stores either): out24[i] = the record the 3DGUT front end built for the id, as the compositors read it:
+ * { centre_px.x, centre_px.y (the unscented mean), q1.xy, q2.xy (quad half axis h / |h|^2, 1 / pixels: the pixel centre c + d is
+ * inside the quad where |d.q1| <= 1 and |d.q2| <= 1), half extents x/y of the quad's bounding box (pixels, culling only),
+ * B[9] (row-major 3x3: canonical ray direction ~ B * world direction, B = S^-1 R^T * (M^-1)3x3), ro[3] (canonical ray origin of
+ * the camera), r, g, b (0: the compositors shade), opacity (after MS antialiasing) }; rect_out as above.  Valid after a full
+ * 3DGUT frame only (MGS_ERR_STATE otherwise); meaningful only for ids that frame sorted. */
+int mgs_frame_download_projected_gut(MgsScene scene, const uint32_t* global_ids, size_t count, float* out24, uint32_t* rect_out);
 int mgs_sync(MgsScene scene);
 
 /* ---- sort only (metric hook): vrdxCmdSortKeyValueIndirect (3rdparty/vrdx/include/vk_radix_sort.h:73-78)

@@ -94,5 +94,17 @@ def test_every_rejection_of_mgs_render_leaves_the_handle_as_it_was():
                 scene.clear_occluder()
             after = render_bits(scene, valid_params(pipeline))
             assert np.array_equal(after, before[pipeline]), f"{name}: the valid frame after the rejected call differs"
+        # the record hooks answer for a frame of their own pipeline only, and for the scene's ids only
+        for pl, own, other in ((GS, scene.download_projected, scene.download_projected_gut), (GUT, scene.download_projected_gut, scene.download_projected)):
+            render_bits(scene, valid_params(pl))
+            rec, rect = own([0, 999])
+            assert rec.shape == (2, 24 if pl == GUT else 10) and rect.shape == (2,)
+            with pytest.raises(mgs.MgsError) as e:
+                other([0])
+            assert e.value.code == capi.ERR_STATE and "frame rendered yet" in lib.mgs_last_error().decode()
+            with pytest.raises(mgs.MgsError) as e:
+                own([0, 1000])
+            assert e.value.code == INVALID_ARG and "id out of range" in lib.mgs_last_error().decode()
+            assert np.array_equal(render_bits(scene, valid_params(pl)), before[pl])
     finally:
         scene.close()

@@ -272,6 +272,7 @@ def load_library():
         "mgs_frame_copy_strip": (C.c_int, [vp, vp, C.c_size_t]),
         "mgs_sync": (C.c_int, [vp]),
         "mgs_frame_download_projected": (C.c_int, [vp, P(C.c_uint32), C.c_size_t, P(F), P(C.c_uint32)]),
+        "mgs_frame_download_projected_gut": (C.c_int, [vp, P(C.c_uint32), C.c_size_t, P(F), P(C.c_uint32)]),
         "mgs_loader_create": (C.c_int, [P(vp)]),
         "mgs_loader_destroy": (None, [vp]),
         "mgs_loader_push": (C.c_int, [vp, C.c_char_p]),
@@ -312,7 +313,7 @@ EXPORTED_SYMBOLS = [
     "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
     "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits", "mgs_render_hybrid",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
-    "mgs_frame_download_projected", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
+    "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
     "mgs_loader_create", "mgs_loader_destroy", "mgs_loader_push", "mgs_loader_status", "mgs_loader_take", "mgs_sort_keys", "mgs_sort_download", "mgs_radix_sort_u32", "mgs_radix_sort_host",
     "mgs_camera_lookat_perspective", "mgs_compute_transform"]
@@ -868,6 +869,16 @@ class Scene:
         rect = np.zeros(ids.size, np.uint32)
         _check(self._lib.mgs_frame_download_projected(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size,
                                                       _fp(out), rect.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out, rect
+
+    def download_projected_gut(self, global_ids):
+        """debug hook: (records[n,24] float32 — cx, cy, q1, q2, bex, bey, B[9], ro[3], r, g, b, a —, rect[n] uint32) of the last
+        3DGUT frame for the given global ids"""
+        ids = np.ascontiguousarray(global_ids, np.uint32)
+        out = np.zeros((ids.size, 24), np.float32)
+        rect = np.zeros(ids.size, np.uint32)
+        _check(self._lib.mgs_frame_download_projected_gut(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size,
+                                                          _fp(out), rect.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out, rect
 
     def sort_keys(self, params):

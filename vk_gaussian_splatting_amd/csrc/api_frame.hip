@@ -5,6 +5,7 @@
 // counts stay on the device (IndirectParams, shaders/shaderio.h:343-356) and are read back only
 // for statistics, like readBackIndirectParametersIfNeeded (:1536).
 #include <cmath>
+#include <string>
 
 #include "scene_state.h"
 
@@ -837,34 +838,37 @@ int mgs_frame_copy_strip(MgsScene s, void* dst, size_t bytes)
   return MGS_OK;
 }
 
-// test/debug hook: the projected records of the last full frame for the given global ids (caller's id space)
-static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, size_t count, float* out10, uint32_t* rectOut)
+// what the two record hooks below share: the checks (`what` names the hook, `pipeline` the frame it needs), the ids in storage
+// space (sid) and, where wanted, the bin rectangle of every storage id (rect)
+static int projectedHookBegin(MgsScene s, const char* what, int pipeline, const uint32_t* ids, size_t count, const float* out,
+                              bool wantRect, std::vector<uint32_t>& sid, std::vector<uint32_t>& rect)
 {
-  if(!s || !ids || !out10)
+  const std::string name(what);
+  if(!s || !ids || !out)
   {
-    setError("mgs_frame_download_projected: null argument");
+    setError((name + ": null argument").c_str());
     return MGS_ERR_INVALID_ARG;
   }
-  if(!s->last.have || s->last.wasSortOnly || s->last.params.pipeline != MGS_PIPELINE_3DGS)
+  if(!s->last.have || s->last.wasSortOnly || s->last.params.pipeline != pipeline)
   {
-    setError("mgs_frame_download_projected: no 3DGS frame rendered yet");
+    setError((name + (pipeline == MGS_PIPELINE_3DGUT ? ": no 3DGUT frame rendered yet" : ": no 3DGS frame rendered yet")).c_str());
     return MGS_ERR_STATE;
   }
   for(size_t i = 0; i < count; ++i)
     if(ids[i] >= s->d->totalSplats)
     {
-      setError("mgs_frame_download_projected: id out of range");
+      setError((name + ": id out of range").c_str());
       return MGS_ERR_INVALID_ARG;
     }
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream));
-  std::vector<uint32_t> sid(ids, ids + count);
+  sid.assign(ids, ids + count);
   mapIdsToStorage(s, sid.data(), count);
-  std::vector<SplatRec> rec(s->d->totalSplats);
-  std::vector<uint32_t> rect(s->d->totalSplats);
-  HIPCHK(hipMemcpy(rec.data(), s->fb.rec.p, (size_t)s->d->totalSplats * sizeof(SplatRec), hipMemcpyDeviceToHost));
+  if(!wantRect)
+    return MGS_OK;
+  rect.resize(s->d->totalSplats);
   HIPCHK(hipMemcpy(rect.data(), s->fb.rect.p, (size_t)s->d->totalSplats * 4, hipMemcpyDeviceToHost));
-  if(rectOut && s->last.rideShift != 0 && s->last.gpuSorted)
+  if(s->last.rideShift != 0 && s->last.gpuSorted)
   {  // the rectangles rode through the key sort as codes (kernels_common.h: rideEncode): rect[id] holds the escapes only, the
      // others are rebuilt from the code at the id's sorted position (they used to come back stale)
     FrameCounters c;
@@ -891,6 +895,18 @@ static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, si
       rect[sortedIds[e]] = x0 | (y0 << 8) | ((x0 + dx) << 16) | ((y0 + dy) << 24);
     }
   }
+  return MGS_OK;
+}
+
+// test/debug hook: the projected records of the last full frame for the given global ids (caller's id space)
+static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, size_t count, float* out10, uint32_t* rectOut)
+{
+  std::vector<uint32_t> sid, rect;
+  const int rc = projectedHookBegin(s, "mgs_frame_download_projected", MGS_PIPELINE_3DGS, ids, count, out10, rectOut != nullptr, sid, rect);
+  if(rc != MGS_OK)
+    return rc;
+  std::vector<SplatRec> rec(s->d->totalSplats);
+  HIPCHK(hipMemcpy(rec.data(), s->fb.rec.p, (size_t)s->d->totalSplats * sizeof(SplatRec), hipMemcpyDeviceToHost));
   for(size_t i = 0; i < count; ++i)
   {
     const SplatRec& r = rec[sid[i]];
@@ -917,4 +933,32 @@ static int mgs_frame_download_projected_impl(MgsScene s, const uint32_t* ids, si
 int mgs_frame_download_projected(MgsScene s, const uint32_t* ids, size_t count, float* out10, uint32_t* rectOut)
 {
   return guarded("mgs_frame_download_projected", [&] { return mgs_frame_download_projected_impl(s, ids, count, out10, rectOut); });
+}
+
+// the same for a 3DGUT frame: the GutRecs of k_project_gut.hip as they are, 24 floats in struct order
+static int mgs_frame_download_projected_gut_impl(MgsScene s, const uint32_t* ids, size_t count, float* out24, uint32_t* rectOut)
+{
+  std::vector<uint32_t> sid, rect;
+  const int rc = projectedHookBegin(s, "mgs_frame_download_projected_gut", MGS_PIPELINE_3DGUT, ids, count, out24, rectOut != nullptr, sid, rect);
+  if(rc != MGS_OK)
+    return rc;
+  if(!s->fb.recGut.p)
+  {
+    setError("mgs_frame_download_projected_gut: no 3DGUT frame rendered yet");
+    return MGS_ERR_STATE;
+  }
+  static_assert(sizeof(GutRec) == 24 * sizeof(float), "out24 is the record itself");
+  std::vector<GutRec> rec(s->d->totalSplats);
+  HIPCHK(hipMemcpy(rec.data(), s->fb.recGut.p, (size_t)s->d->totalSplats * sizeof(GutRec), hipMemcpyDeviceToHost));
+  for(size_t i = 0; i < count; ++i)
+  {
+    std::memcpy(out24 + 24 * i, &rec[sid[i]], sizeof(GutRec));
+    if(rectOut)
+      rectOut[i] = rect[sid[i]];
+  }
+  return MGS_OK;
+}
+int mgs_frame_download_projected_gut(MgsScene s, const uint32_t* ids, size_t count, float* out24, uint32_t* rectOut)
+{
+  return guarded("mgs_frame_download_projected_gut", [&] { return mgs_frame_download_projected_gut_impl(s, ids, count, out24, rectOut); });
 }

@@ -94,7 +94,9 @@ __global__ __launch_bounds__(256) void k_composite_gut(const FrameArgs* __restri
   const uint32_t* vals = plan->finalSel ? valY : valX;
   const int      bin   = (ty >> F.binShiftY) * F.binsX + (tx >> F.binShiftX);
   const uint2    range = ranges[bin];
-  float T = (inside && rayOk) ? 1.0f : 0.0f, cr = 0.f, cg = 0.f, cb = 0.f, asum = 0.f;
+  // a pixel without a ray (outside the image, outside the fisheye's field of view: frag.slang:96-100 discards) starts below every
+  // tMin, the additive-alpha mode's -1 included, so that no record hits it: its count is 0 as its coverage is
+  float T = (inside && rayOk) ? 1.0f : -2.0f, cr = 0.f, cg = 0.f, cb = 0.f, asum = 0.f;
   float occD = 0.0f;          // this pixel's bound depth (-inf outside the image; NaN passes nothing)
   bool  occBehind = !inside;  // the last record seen lies behind it
   if constexpr(OCC)
