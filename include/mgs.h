@@ -45,10 +45,14 @@ extern "C" {
                                  mgs_trace_light_params_default, mgs_render_traced_lit, mgs_trace_download_shadow_hits;
                             hybrid frames (MGS_HAS_HYBRID below): one entry point, both numbers stay — mgs_render_hybrid;
                             3DGUT record hook (MGS_HAS_PROJECTED_GUT below): one entry point, both numbers stay —
-                                 mgs_frame_download_projected_gut */
+                                 mgs_frame_download_projected_gut;
+                            trace strategies (MGS_HAS_TRACE_STRATEGIES below): no entry point, both numbers stay — MgsTraceParams::reserved[0] is
+                                 named trace_strategy (0 = what it was), MGS_TRACE_STRATEGY_* */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_TRACE_STRATEGIES 1 /* feature macro: MgsTraceParams::trace_strategy and MGS_TRACE_STRATEGY_* exist (within ABI 5.1: the first reserved word
+                                     of MgsTraceParams is named, 0 = what it was; no struct size or default changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
@@ -539,8 +543,7 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
  * Direct lighting with hard shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
  * A rasterised primary surface under the same light pass is mgs_render_hybrid (MGS_HAS_HYBRID, below).
- * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, the stochastic trace
- * strategies, wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
+ * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
  * is not wired), trace profile feedback.
  *
  * Ray (threedgrt_raytrace.rgen.slang:159-196): pinhole = generatePinholeRay at the pixel centre (subPixelOffset 0.5,
@@ -565,14 +568,52 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * after max_passes, or when the transmittance test fails.  A hit that ties with the last slot, or lies within epsT of the last walked
  * one, is therefore lost, here as there.  Integration as particleIntegrate (threedgrt.h.slang:226-235) with the transmittance in double.
  * The frame's alpha is 1 - T, this library's MGS_ALPHA_COVERAGE meaning; the reference writes 1.0.
- * kernel_min_response must be > 0 (at 0 the proxy is unbounded): MGS_ERR_INVALID_ARG. */
+ * kernel_min_response must be > 0 (at 0 the proxy is unbounded): MGS_ERR_INVALID_ARG.
+ *
+ * Trace strategies (MGS_HAS_TRACE_STRATEGIES; RTX_TRACE_STRATEGY_*, shaderio.h:122-124, parameters.h:219).  The above is
+ * MGS_TRACE_STRATEGY_FULL_ANYHIT, the default.  The other two trade noise for speed and converge under temporal accumulation
+ * (frame_sample_id = 0, 1, ... with temporal_sampling = 1; the reference switches its automatic temporal sampling on for them,
+ * gaussian_splatting.cpp:311-316).  They share with strategy 0: the ray and its lens (whose draws come from their own seed, rgen:193,
+ * and do not advance the strategies' seedRayPass = xxhash32(pixel, frame_sample_id), rgen:228), tMin / tMax / epsT, what a hit is and
+ * when it is accepted, radiance and normals, debug flags, strips, contexts, target formats, the surface outputs, the hit counts and the
+ * hierarchy (a change of trace_strategy does not rebuild it).  A particle's id that enters a hash is its global id in the CALLER's order.
+ *   MGS_TRACE_STRATEGY_PASS_STOCHASTIC (rgen:615-819 with kStochasticPass): the passes of strategy 0, unchanged; the pixel state
+ *     (radiance, transmittance, hit count, normal, pick) is snapshot before a pass's walk (:669-673).  After the walk of a pass that found
+ *     a hit: opacity = float(1 - T); if rand(seedRayPass) < opacity the radiance is divided by opacity, a pixel without an iso-surface
+ *     pick takes the last payload slot that was valid and walked while the transmittance test held, accepted or not (lastValidHitIdx,
+ *     :684-687, :772-790), T = 0 (the frame's alpha is 1) and tracing ends; otherwise the pixel returns to the snapshot (tMin does
+ *     not) and the next pass follows (:765-801).  A ray whose passes are all rejected is an untouched pixel: (0,0,0,0), hit count 0,
+ *     nothing picked.  max_passes_used and accepted_hits keep their meaning (the sum of the hit counts as written to the pixels).
+ *   MGS_TRACE_STRATEGY_STOCHASTIC_ANYHIT (rahit.slang:94-150, rgen:823-961, PARTICLES_SPP forced to 1, gaussian_splatting.cpp:1693):
+ *     ONE traversal of (tMin + epsT, tMax + epsT) and one payload slot, initially (inf, none).  Every hit with t < slot.t is evaluated
+ *     by particleProcessHit; an accepted one draws u = rand(xxhash32(rngSeed, id ^ floatBits(t), 0)) with rngSeed = xxhash32(pixel,
+ *     frame_sample_id) (rand consumes the hashed value as its state, rahit:131-133) and becomes the slot when u < alpha.  With one
+ *     slot the IgnoreHit rule of rahit:147-150 cannot lose a hit that would have won, and a hit's draw depends on nothing but the
+ *     pixel, the sample, the particle and t: the result is the NEAREST KEPT HIT, whatever the order of traversal (which may therefore
+ *     cut subtrees beyond slot.t).  Two kept hits with bit-identical t resolve to the lower id in the caller's order; the reference
+ *     keeps whichever its traversal met first: PARITY UNPINNED.  The t whose bits are hashed is this library's t of the point of
+ *     maximum response; the reference hashes RayTCurrent() of its hardware intersection: PARITY UNPINNED (another random stream of the
+ *     same distribution).  Pixel (rgen:951-960): with a kept hit rgb = its radiance, alpha = 1, hit count 1, the pick is that hit
+ *     (id; ndc z of origin + t * direction), the normal is the normalised sample normal (0 if its length is 0) with w = 1; without
+ *     one (0,0,0,0), hit count 0, nothing picked, normal 0.  samples_per_pass, max_passes, min_transmittance and depth_iso_threshold
+ *     are range-checked but NOT READ; max_passes_used is 1 wherever a ray was traced.
+ * As in every unlit traced frame surfaceFinalFiltering is not applied (it belongs to the lit path).  Any other value of trace_strategy is
+ * MGS_ERR_INVALID_ARG.  mgs_render_traced_lit and mgs_render_hybrid take trace_strategy 0 only and return MGS_ERR_UNSUPPORTED
+ * otherwise (before the handle is looked at): the reference also randomises the shadow rays under the any-hit strategy
+ * (rgen:1364-1400), which is later work. */
+typedef enum MgsTraceStrategy {
+  MGS_TRACE_STRATEGY_FULL_ANYHIT       = 0, /* RTX_TRACE_STRATEGY_FULL_ANYHIT: sorted passes until the transmittance is used up (default) */
+  MGS_TRACE_STRATEGY_PASS_STOCHASTIC   = 1, /* RTX_TRACE_STRATEGY_PASS_STOCHASTIC: Russian roulette on every pass's opacity */
+  MGS_TRACE_STRATEGY_STOCHASTIC_ANYHIT = 2  /* RTX_TRACE_STRATEGY_STOCHASTIC_ANYHIT: one traversal, the nearest hit kept with probability alpha */
+} MgsTraceStrategy;
 typedef struct MgsTraceParams {
   int32_t samples_per_pass;          /* PARTICLES_SPP, default 18 (parameters.h:218); 1..32 */
   int32_t max_passes;                /* frameInfo.maxPasses, default 200 (shaderio.h:269); >= 1 */
   float   min_transmittance;         /* default 0.01 (shaderio.h:272); [0, 1) */
   int32_t kernel_adaptive_clamping;  /* default 1 (parameters.h:217); 0 / 1 */
   float   depth_iso_threshold;       /* depthIsoThresholdRTX, default 0.7 (parameters.h:226); replaces MgsFrameParams::depth_iso_threshold */
-  uint32_t reserved[3];
+  int32_t trace_strategy;            /* MGS_TRACE_STRATEGY_*, default MGS_TRACE_STRATEGY_FULL_ANYHIT (parameters.h:219) */
+  uint32_t reserved[2];
 } MgsTraceParams;
 void mgs_trace_params_default(MgsTraceParams* p);
 typedef struct MgsTraceOut {

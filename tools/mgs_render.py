@@ -25,6 +25,8 @@ primary surface, lit and shadowed by the traced light pass; --lights / --materia
 shadow rays.  Not combinable with --occluder-depth or --mesh.  --raster-pipeline: 3DGS (default) or 3DGUT, of --pipeline raster and hybrid.
 --pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
 the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth, --mesh or --lighting 1.
+--trace-strategy full|pass|anyhit: MgsTraceParams::trace_strategy of an unlit traced frame (sorted passes, pass-stochastic, stochastic
+any-hit); --accumulate N renders the samples frame_sample_id = 0..N-1 with temporal accumulation and writes the last, the running mean.
 
 --compare-with: float32 [H, W, 3|4] frame made elsewhere (a reference screenshot, another build's frame), uploaded as the capture;
 prints MSE / PSNR / FLIP of the rendered frame against it, computed on the device (mgs_compare_metrics).  --compare-view writes
@@ -70,6 +72,8 @@ def main():
     ap.add_argument("--shadow-color-strength", type=float, default=0.0)
     ap.add_argument("--samples-per-pass", type=int, default=18)
     ap.add_argument("--max-passes", type=int, default=200)
+    ap.add_argument("--trace-strategy", choices=["full", "pass", "anyhit"], default="full")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="N")
     ap.add_argument("--min-transmittance", type=float, default=0.01)
     ap.add_argument("--compare-with", default=None, metavar="FRAME.npy")
     ap.add_argument("--flip-mode", type=int, choices=[0, 1, 2], default=capi.FLIP_REFERENCE)
@@ -128,11 +132,16 @@ def main():
             scene.add_mesh_instance(mgs.Mesh.load_obj(path), m)
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
+    if a.pipeline != "trace" and (a.trace_strategy != "full" or a.accumulate != 1):
+        ap.error("--trace-strategy pass / anyhit and --accumulate are for --pipeline trace (unlit)")
     if a.pipeline == "trace":
         if a.occluder_depth or a.mesh:
             ap.error("--pipeline trace renders splats alone: no --occluder-depth or --mesh")
         p.collect_timings = 0
-        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance)
+        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance,
+                                      trace_strategy=["full", "pass", "anyhit"].index(a.trace_strategy))
+        if a.lighting and (t.trace_strategy or a.accumulate != 1):
+            ap.error("--trace-strategy pass / anyhit and --accumulate are for unlit traced frames")
         if a.lighting:  # mgs_render_traced_lit: --lights / --material as for the raster pipelines, shadows by one more ray per light
             lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
                                                  particle_shadow_transmittance_threshold=a.shadow_threshold,
@@ -142,7 +151,10 @@ def main():
             print(f"light pass {lo.light_ms:.3f} ms on the GPU, {lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, "
                   f"{lo.shadow_candidate_tests / sr:.1f} candidate tests and {lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
         else:
-            o = scene.render_traced(p, t, want_stats=True)
+            for k in range(max(a.accumulate, 1)):  # the running mean of the samples is the frame after the last
+                if a.accumulate > 1:
+                    p.frame_sample_id, p.temporal_sampling = k, 1
+                o = scene.render_traced(p, t, want_stats=True)
         img = scene.download_frame(p).astype(np.float32)
         rays = W * H
         print(f"{scene.splat_count} splats, {o.leaves} leaves in {o.nodes} nodes (build {o.build_ms:.3f} ms), {o.node_visits / rays:.1f} node visits and "

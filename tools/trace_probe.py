@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--lit] [--hybrid] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
-tests per ray, and writes everything as JSON.  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
+tests per ray, and writes everything as JSON.  --trace-strategy: MgsTraceParams::trace_strategy of the unlit frames (the lit
+and hybrid ones take the sorted strategy alone).  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
 lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  --hybrid (with --lit) renders the same lit
 scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and the shadow counters beside the traced ones.  Needs an MI355X.
 """
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--samples-per-pass", type=int, default=18)
+    ap.add_argument("--trace-strategy", choices=["full", "pass", "anyhit"], default="full")
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--json", default=None)
@@ -45,7 +47,7 @@ def main():
         V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, W, H)
         p = capi.default_params(W, H)
         capi.set_camera(p, V, P, eye)
-        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+        t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, trace_strategy=["full", "pass", "anyhit"].index(a.trace_strategy))
         first = scene.render_traced(p, t, want_stats=True)
         for _ in range(a.warmup):
             scene.render_traced(p, t, want_stats=True)
@@ -54,7 +56,7 @@ def main():
             o = scene.render_traced(p, t, want_stats=True)
             ms.append(o.trace_ms)
         rays = W * H
-        r = dict(scene=name, width=W, height=H, samples_per_pass=a.samples_per_pass, splats=n, leaves=int(o.leaves), nodes=int(o.nodes),
+        r = dict(scene=name, width=W, height=H, samples_per_pass=a.samples_per_pass, trace_strategy=a.trace_strategy, splats=n, leaves=int(o.leaves), nodes=int(o.nodes),
                  build_ms=float(first.build_ms), first_trace_ms=float(first.trace_ms), trace_ms_median=float(np.median(ms)),
                  trace_ms_min=float(min(ms)), trace_ms_max=float(max(ms)), repeats=a.repeats, warmup=a.warmup,
                  node_visits_per_ray=o.node_visits / rays, candidate_tests_per_ray=o.candidate_tests / rays,
@@ -62,6 +64,7 @@ def main():
                  scene_bytes=scene.memory_usage()[0])
         if a.lit:
             p.lighting_mode = 1
+            t.trace_strategy = capi.TRACE_STRATEGY_FULL_ANYHIT
             scene.set_material(0, capi.make_material(ambient=(0.1, 0.1, 0.1), diffuse=(0.8, 0.8, 0.8), emission=(0.0, 0.0, 0.0)))
             spots = [(4.0, 6.0, 3.0), (-5.0, 5.0, 2.0), (2.0, 7.0, -5.0), (-3.0, 4.0, -4.0)]
             r["lit"] = []

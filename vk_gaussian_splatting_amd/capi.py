@@ -124,7 +124,12 @@ class MeshOut(C.Structure):
 class TraceParams(C.Structure):
     """MgsTraceParams: the knobs of the traced pipeline that MgsFrameParams has no room for"""
     _fields_ = [("samples_per_pass", C.c_int32), ("max_passes", C.c_int32), ("min_transmittance", C.c_float),
-                ("kernel_adaptive_clamping", C.c_int32), ("depth_iso_threshold", C.c_float), ("reserved", C.c_uint32 * 3)]
+                ("kernel_adaptive_clamping", C.c_int32), ("depth_iso_threshold", C.c_float), ("trace_strategy", C.c_int32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+# MgsTraceStrategy (MgsTraceParams::trace_strategy)
+TRACE_STRATEGY_FULL_ANYHIT, TRACE_STRATEGY_PASS_STOCHASTIC, TRACE_STRATEGY_STOCHASTIC_ANYHIT = 0, 1, 2
 
 
 class TraceLightParams(C.Structure):

@@ -16,6 +16,7 @@ void mgs_trace_params_default(MgsTraceParams* p)
   p->min_transmittance        = 0.01f;  // shaderio.h:272
   p->kernel_adaptive_clamping = 1;      // parameters.h:217
   p->depth_iso_threshold      = 0.7f;   // depthIsoThresholdRTX, parameters.h:226
+  p->trace_strategy           = MGS_TRACE_STRATEGY_FULL_ANYHIT;  // parameters.h:219
 }
 
 void mgs_trace_light_params_default(MgsTraceLightParams* p)
@@ -50,6 +51,8 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const
     return failTrace(MGS_ERR_INVALID_ARG, "trace: depth_iso_threshold must be in [0, 1]");
   if(t.kernel_adaptive_clamping != 0 && t.kernel_adaptive_clamping != 1)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: kernel_adaptive_clamping must be 0 or 1");
+  if(t.trace_strategy < MGS_TRACE_STRATEGY_FULL_ANYHIT || t.trace_strategy > MGS_TRACE_STRATEGY_STOCHASTIC_ANYHIT)
+    return failTrace(MGS_ERR_INVALID_ARG, "trace: trace_strategy must be MGS_TRACE_STRATEGY_FULL_ANYHIT, PASS_STOCHASTIC or STOCHASTIC_ANYHIT");
   if(p->width <= 0 || p->height <= 0 || p->width > 8192 || p->height > 8192)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: width/height must be in [1,8192]");
   if(p->target_format < MGS_TARGET_RGBA16F || p->target_format > MGS_TARGET_RGBA8)
@@ -81,6 +84,10 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const
   }
   if(lit)
   {
+    // (the reference also randomises the shadow rays under the any-hit strategy, rgen.slang:1364-1400)
+    if(t.trace_strategy != MGS_TRACE_STRATEGY_FULL_ANYHIT)
+      return failTrace(MGS_ERR_UNSUPPORTED, hybrid ? "mgs_render_hybrid: the stochastic trace strategies are mgs_render_traced's (trace_strategy must be 0)"
+                                                   : "mgs_render_traced_lit: the stochastic trace strategies are mgs_render_traced's (trace_strategy must be 0)");
     if(lit->shadows_mode < MGS_SHADOWS_DISABLED || lit->shadows_mode > MGS_SHADOWS_SOFT)
       return failTrace(MGS_ERR_INVALID_ARG, "trace: shadows_mode must be MGS_SHADOWS_DISABLED, MGS_SHADOWS_HARD or MGS_SHADOWS_SOFT");
     if(!(lit->particle_shadow_offset >= 0.0f) || !std::isfinite(lit->particle_shadow_offset))
@@ -105,7 +112,7 @@ static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const
       return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: lighting_mode != 0 is mgs_render_traced_lit's");
   }
   if(p->sort_mode == MGS_SORT_STOCHASTIC)
-    return failTrace(MGS_ERR_UNSUPPORTED, "trace: the stochastic trace strategies are out of scope");
+    return failTrace(MGS_ERR_UNSUPPORTED, "trace: sort_mode has no meaning for a traced frame (the stochastic strategies are MgsTraceParams::trace_strategy)");
   return MGS_OK;
 }
 
@@ -422,7 +429,10 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   L.outNormal         = F.surfaceOutputs ? s->surf.normal.p : nullptr;
   L.outIsoDist        = lit ? ts.isoDist.p : nullptr;
   L.outRadiance       = lit ? ts.radiance.p : nullptr;
-  launchTrace(st, L, F, d.shFormat);
+  if(t.trace_strategy == MGS_TRACE_STRATEGY_FULL_ANYHIT)
+    launchTrace(st, L, F, d.shFormat);
+  else
+    launchTraceStochastic(st, L, F, d.shFormat, t.trace_strategy);
   if(lit)
   {  // the light pass rewrites the frame's pixels from the fp32 radiance k_trace left
     HIPCHK(hipEventRecord(ts.ev[3], st));

@@ -20,66 +20,10 @@
 #include "sh_eval.h"
 #include "target_pixel.h"
 #include "trace_common.h"
+#include "trace_shade.h"
 #include "trace_traverse.h"
 
 namespace mgs {
-
-// model-space normal of an accepted hit (computeEllipsoidNormalMaxDensityPlane :358-418, computeEllipsoidNormal :423-496), to world
-// space as particleProcessHit does (:218): normalize(transpose(transformRotScaleInverse)-product), i.e. the inverse transpose
-__device__ __forceinline__ void hitNormalWorld(const TraceArgs& a, const FrameConst& F, const ParticleEval& E, float (&nw)[3])
-{
-  const float l0 = E.om[0] - E.p[0], l1 = E.om[1] - E.p[1], l2 = E.om[2] - E.p[2];
-  const bool  iso = F.normalMethod == 1;
-  const float th  = iso ? fmaxf(0.02f * fmaxf(fmaxf(E.s[0], E.s[1]), E.s[2]), F.thinParticleThreshold) : F.thinParticleThreshold;
-  const bool  t0 = E.s[0] < th, t1 = E.s[1] < th, t2 = E.s[2] < th;
-  const int   smallCount = (t0 ? 1 : 0) + (t1 ? 1 : 0) + (t2 ? 1 : 0);
-  const float* R = E.R;
-  float        n0 = -E.dmN[0], n1 = -E.dmN[1], n2 = -E.dmN[2];  // two or more degenerate axes, or no surface point: -rayDirection
-  if(smallCount == 0 && !iso)
-  {
-    const float c0 = (l0 * R[0] + l1 * R[3] + l2 * R[6]) * (1.0f / (E.s[0] * E.s[0]));
-    const float c1 = (l0 * R[1] + l1 * R[4] + l2 * R[7]) * (1.0f / (E.s[1] * E.s[1]));
-    const float c2 = (l0 * R[2] + l1 * R[5] + l2 * R[8]) * (1.0f / (E.s[2] * E.s[2]));
-    const float g0 = c0 * R[0] + c1 * R[1] + c2 * R[2], g1 = c0 * R[3] + c1 * R[4] + c2 * R[5], g2 = c0 * R[6] + c1 * R[7] + c2 * R[8];
-    const float rl = rsqrtf(g0 * g0 + g1 * g1 + g2 * g2);
-    n0 = g0 * rl; n1 = g1 * rl; n2 = g2 * rl;
-    if(n0 * l0 + n1 * l1 + n2 * l2 < 0.0f) { n0 = -n0; n1 = -n1; n2 = -n2; }
-  }
-  else if(smallCount == 0)
-  {  // raySphereIntersection(canonical origin, NORMALISED canonical direction, 3, 0, inf), written around the point of closest
-     // approach like the 3DGUT compositor (k_composite_gut.hip has the reason: the textbook discriminant cancels in fp32)
-    const float dd = E.dc[0] * E.dc[0] + E.dc[1] * E.dc[1] + E.dc[2] * E.dc[2];
-    const float tm = -(E.oc[0] * E.dc[0] + E.oc[1] * E.dc[1] + E.oc[2] * E.dc[2]) / dd;
-    const float kx = E.dc[1] * E.oc[2] - E.dc[2] * E.oc[1], ky = E.dc[2] * E.oc[0] - E.dc[0] * E.oc[2],
-                kz = E.dc[0] * E.oc[1] - E.dc[1] * E.oc[0];
-    const float rem = 9.0f - (kx * kx + ky * ky + kz * kz) / dd;
-    if(rem >= 0.0f)
-    {
-      const float half = sqrtf(rem / dd);
-      const float tq   = (tm - half >= 0.0f) ? tm - half : tm + half;
-      if(tq >= 0.0f)
-      {
-        float       h0 = E.oc[0] + tq * E.dc[0], h1 = E.oc[1] + tq * E.dc[1], h2 = E.oc[2] + tq * E.dc[2];
-        const float hl = rsqrtf(h0 * h0 + h1 * h1 + h2 * h2);
-        h0 = h0 * hl / E.s[0]; h1 = h1 * hl / E.s[1]; h2 = h2 * hl / E.s[2];
-        const float g0 = R[0] * h0 + R[1] * h1 + R[2] * h2, g1 = R[3] * h0 + R[4] * h1 + R[5] * h2, g2 = R[6] * h0 + R[7] * h1 + R[8] * h2;
-        const float rl = rsqrtf(g0 * g0 + g1 * g1 + g2 * g2);
-        n0 = g0 * rl; n1 = g1 * rl; n2 = g2 * rl;
-      }
-    }
-  }
-  else if(smallCount == 1)
-  {
-    n0 = t0 ? R[0] : (t1 ? R[1] : R[2]);  // (selects: a runtime index would put the particle into scratch memory)
-    n1 = t0 ? R[3] : (t1 ? R[4] : R[5]);
-    n2 = t0 ? R[6] : (t1 ? R[7] : R[8]);
-    if(n0 * l0 + n1 * l1 + n2 * l2 < 0.0f) { n0 = -n0; n1 = -n1; n2 = -n2; }
-  }
-  const float* Ri = a.inst->inst[E.k].rsInv;  // glm column-major: (Ri^T n)_c = sum_r Ri[3c + r] n_r
-  const float  w0 = Ri[0] * n0 + Ri[1] * n1 + Ri[2] * n2, w1 = Ri[3] * n0 + Ri[4] * n1 + Ri[5] * n2, w2 = Ri[6] * n0 + Ri[7] * n1 + Ri[8] * n2;
-  const float  wl = rsqrtf(w0 * w0 + w1 * w1 + w2 * w2);
-  nw[0] = w0 * wl; nw[1] = w1 * wl; nw[2] = w2 * wl;
-}
 
 // SHF: SH storage format; KB: K-buffer slots in registers (>= samples_per_pass)
 template <int SHF, int KB>
@@ -136,7 +80,8 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
           continue;
         ParticleEval E;
         evalParticle(a, g, ray, E);
-        // particleProcessHit, threedgrt.h.slang:166-185
+        // particleProcessHit, threedgrt.h.slang:166-185 (written out here although trace_shade.h has it as shadeHit for the stochastic
+        // strategies: calling that costs k_trace<0, 4> and k_trace<0, 18> a VGPR each and changes every instantiation's code)
         float      alpha  = fminf(F.alphaClamp, E.resp * E.density);
         const bool accept = E.density > F.alphaCull && alpha > F.alphaCull && E.resp > F.kernelMinResponse;
         if(accept)

@@ -127,6 +127,8 @@ void launchBvhGather(hipStream_t stream, const uint32_t* sortedVals, const float
 void launchBvhLevel(hipStream_t stream, const float4* below, uint32_t nBelow, float4* level, uint32_t nLevel);
 // the traversal (k_trace.hip): one ray per lane, a wave64 = an 8 x 8 pixel tile
 void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat);
+// the stochastic trace strategies (k_trace_stochastic.hip): strategy 1 = pass-stochastic, 2 = stochastic any-hit
+void launchTraceStochastic(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat, int strategy);
 void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameConst& F);  // k_trace_light.hip
 // the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);

@@ -159,6 +159,8 @@ __device__ __forceinline__ void evalParticle(const TraceArgs& a, uint32_t g, con
 // The K nearest hits of the ray inside (t0, t1), through the proxies: kd / kid come back sorted by (t, caller's id), empty slots
 // hold (inf, kTraceInvalid).  KB: K-buffer slots in registers (>= K).  A candidate exists when t0 < t < t1 and the proxy test
 // passes; it is inserted as rahit.slang:152-167, ties in t by ascending global id in the caller's order.
+// The walk below (expand, the sorting network, the step loop) has a copy in traverseProxies, further down, which says why: a fix to
+// one is a fix to both.
 // The buffer is a local of the function and comes back by value: handed in by reference it stays memory until the function is inlined,
 // and the traversal then allocates half as many registers again.
 template <int KB>
@@ -297,6 +299,95 @@ __device__ __forceinline__ NearestK<KB> collectNearest(const TraceArgs& a, Trace
   N.nodeVisits = nodeVisits;
   N.candTests  = candTests;
   return N;
+}
+
+// The same walk with the candidate step left to the caller (the stochastic any-hit of k_trace_stochastic.hip, whose step is an
+// accept-and-draw into one slot instead of the sorted insertion): candidate(g) is called for the particle of every leaf whose box
+// the ray meets inside [t0, t1] no farther than `cut`, nearest children first.  `cut` is the caller's variable and is read again
+// at every node, so a candidate may lower it; a box AT the cut is still visited (te <= cut, as above).  collectNearest keeps its own
+// copy of the walk: routed through this function k_trace<0, 4> and k_trace<0, 18> take one more VGPR each, and the sorted
+// strategy's kernels are held to their resources.
+template <class Candidate>
+__device__ __forceinline__ void traverseProxies(const TraceArgs& a, TraceLds& S, int tid, const TraceRay& ray, float t0, float t1, const float& cut,
+                                                Candidate&& candidate, unsigned long long& nodeVisits)
+{
+  const int      top     = a.nLevels - 1;
+  const uint32_t maxStep = 2u * a.totalNodes + 2u;
+  auto expand = [&](int level, uint32_t idx) {
+    const uint32_t nBelow = S.cnt[level - 1], base = S.off[level - 1];
+    uint32_t       key[8];
+#pragma unroll
+    for(int c = 0; c < 8; ++c)  // bound: 8 children
+    {
+      const uint32_t ci = idx * 8u + (uint32_t)c;
+      key[c]            = 0xFFFFFFFFu;
+      if(ci < nBelow)
+      {
+        const float4 lo = a.nodes[2 * (size_t)(base + ci)], hi = a.nodes[2 * (size_t)(base + ci) + 1];
+        float        te;
+        if(slabHit(ray, lo, hi, t0, t1, te) && te <= cut)
+          key[c] = (__float_as_uint(te) & ~7u) | (uint32_t)c;
+      }
+    }
+    MGS_CSWAP(0, 1) MGS_CSWAP(2, 3) MGS_CSWAP(4, 5) MGS_CSWAP(6, 7)
+    MGS_CSWAP(0, 2) MGS_CSWAP(1, 3) MGS_CSWAP(4, 6) MGS_CSWAP(5, 7)
+    MGS_CSWAP(1, 2) MGS_CSWAP(5, 6) MGS_CSWAP(0, 4) MGS_CSWAP(3, 7)
+    MGS_CSWAP(1, 5) MGS_CSWAP(2, 6)
+    MGS_CSWAP(1, 4) MGS_CSWAP(3, 6)
+    MGS_CSWAP(2, 4) MGS_CSWAP(3, 5)
+    MGS_CSWAP(3, 4)
+    uint32_t pend = 0, cnt = 0;
+#pragma unroll
+    for(int c = 0; c < 8; ++c)
+      if(key[c] != 0xFFFFFFFFu)
+      {
+        pend |= (key[c] & 7u) << (3 * c);
+        ++cnt;
+      }
+    S.pend[level][tid] = pend | (cnt << 24);
+  };
+
+  if(top == 0)
+  {  // a single leaf
+    const float4 lo = a.nodes[0], hi = a.nodes[1];
+    float        te;
+    ++nodeVisits;
+    if(slabHit(ray, lo, hi, t0, t1, te))
+      candidate(__float_as_uint(lo.w));
+    return;
+  }
+  int      level = top;
+  uint32_t idx   = 0;
+  expand(level, idx);
+  for(uint32_t step = 0; step < maxStep; ++step)  // bound: every node is entered once and left once
+  {
+    const uint32_t pend = S.pend[level][tid];
+    const uint32_t cnt  = pend >> 24;
+    if(cnt == 0u)
+    {
+      if(level == top)
+        break;
+      ++level;
+      idx >>= 3;
+      continue;
+    }
+    S.pend[level][tid] = ((pend & 0xFFFFFFu) >> 3) | ((cnt - 1u) << 24);
+    const uint32_t ci   = idx * 8u + (pend & 7u);
+    const uint32_t node = S.off[level - 1] + ci;
+    const float4   lo = a.nodes[2 * (size_t)node], hi = a.nodes[2 * (size_t)node + 1];
+    float          te;
+    ++nodeVisits;
+    if(!slabHit(ray, lo, hi, t0, t1, te) || !(te <= cut))
+      continue;
+    if(level == 1)
+      candidate(__float_as_uint(lo.w));
+    else
+    {
+      --level;
+      idx = ci;
+      expand(level, idx);
+    }
+  }
 }
 #undef MGS_CSWAP
 
