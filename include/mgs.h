@@ -47,12 +47,15 @@ extern "C" {
                             3DGUT record hook (MGS_HAS_PROJECTED_GUT below): one entry point, both numbers stay —
                                  mgs_frame_download_projected_gut;
                             trace strategies (MGS_HAS_TRACE_STRATEGIES below): no entry point, both numbers stay — MgsTraceParams::reserved[0] is
-                                 named trace_strategy (0 = what it was), MGS_TRACE_STRATEGY_* */
+                                 named trace_strategy (0 = what it was), MGS_TRACE_STRATEGY_*;
+                            ray queries (MGS_HAS_RAY_QUERY below): entry points only, both numbers stay — mgs_ray_query_params_default,
+                                 mgs_trace_rays, mgs_trace_rays_device, mgs_trace_generate_rays */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_STRATEGIES 1 /* feature macro: MgsTraceParams::trace_strategy and MGS_TRACE_STRATEGY_* exist (within ABI 5.1: the first reserved word
                                      of MgsTraceParams is named, 0 = what it was; no struct size or default changed) */
+#define MGS_HAS_RAY_QUERY 1     /* feature macro: mgs_trace_rays and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
@@ -543,6 +546,8 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
  * Direct lighting with hard shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
  * A rasterised primary surface under the same light pass is mgs_render_hybrid (MGS_HAS_HYBRID, below).
+ * Rays of the caller's own (other sensors, probes, picking, secondary rays shot from the caller's geometry) are mgs_trace_rays
+ * (MGS_HAS_RAY_QUERY, below): the caller cuts a ray at its own surfaces with the ray's window, as the occluder does for the raster pipelines.
  * Out of scope: meshes in the traced scene, soft shadows, indirect lighting and bounces, wireframe, visualisation modes other than final, DLSS, mgs_render_gathered for traced frames (strip rows are honoured, the exchange
  * is not wired), trace profile feedback.
  *
@@ -755,6 +760,101 @@ int mgs_trace_download_shadow_hits(MgsScene scene_or_context, uint32_t* host_dst
 int mgs_render_hybrid(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
                       const MgsTraceLightParams* light /* NULL = defaults */, MgsFrameOut* out /* may be NULL */,
                       MgsTraceLightOut* light_out /* may be NULL */);
+
+/* ---- ray queries (MGS_HAS_RAY_QUERY): the caller's rays through the scene's particle hierarchy, with the walk of mgs_render_traced's
+ * MGS_TRACE_STRATEGY_FULL_ANYHIT (traceRayParticlesInsertionSort, shaders/threedgrt_raytrace.rgen.slang:615-819; insertion
+ * rahit.slang:152-167; hit parameter rint.slang:159-172; particleProcessHit and particleIntegrate, threedgrt.h.slang:166-235).  For
+ * sensors the library has no model of (rolling shutter, distortion: every ray its own origin), lidar and depth probes, picking, and
+ * the reflection, refraction and shadow rays an integrator shoots from its OWN geometry into the splats: the library knows no
+ * geometry but the particles, the caller ends a ray at its own surface with t_max and starts the secondary ray itself.
+ *
+ * The ray and its window.  A ray is used AS GIVEN: the direction is not renormalised, and t is the parameter along the given
+ * direction (world units for a unit direction).  Nothing in the walk assumes unit length: the hit parameter is -dot(o,d)/dot(d,d)
+ * with the unnormalised canonical direction (rint.slang:166-168), the distance to the ray divides by dot(d,d), the node test runs
+ * on 1 / direction, and the two places that need a unit vector (the response's model-space direction, rgen:697-698, and the normal
+ * fallback -rayDirection) normalise it themselves.  The window of the first pass is (t_min + epsT, t_max + epsT) with the primary
+ * walk's epsT = 1e-9; a negative t_min is taken as 0 (a ray has no hits behind its origin).  From there everything is strategy 0 of
+ * mgs_render_traced: passes of samples_per_pass nearest hits, max_passes, min_transmittance, what a hit is and when it is accepted,
+ * radiance with SH, the transmittance in double, ties in t by ascending global id in the caller's order, depth_iso_threshold,
+ * normal_method / thin_particle_threshold, MGS_DEBUG_SH_ONLY and MGS_DEBUG_OPACITY_GAUSSIAN_DISABLED.
+ *
+ * Results, at the ray's index: radiance and transmittance = float(T) of the walk (the frame's alpha is 1 - this); t_iso = the ray
+ * parameter of the first accepted hit after which T is below depth_iso_threshold (0 when nothing was picked) and id = that
+ * particle's global id in the caller's order (0xFFFFFFFF when none); hit_count = accepted hits; passes = passes started; normal =
+ * the integrated normal in xyz and the sum of the weights in w.  t_iso, id and normal are filled when params->surface_outputs is 1
+ * (as the side outputs of a traced frame are: set it for picking and depth probes), else 0 / 0xFFFFFFFF / zeros.
+ *
+ * Invalid rays.  A ray with a non-finite component (t_min and t_max included), a zero-length direction or t_min > t_max never reaches
+ * the traversal: its result is radiance 0, transmittance 1, nothing picked, hit_count 0, passes 0, and it is counted in invalid_rays.
+ * Device arrays cannot be checked on the host, so this is a per-ray outcome and not an error code.
+ *
+ * Reads of MgsFrameParams: sh_degree, alpha_cull_threshold, kernel_degree, kernel_min_response (> 0), alpha_clamp, normal_method,
+ * thin_particle_threshold, surface_outputs and debug_flags (the two bits the traced frames honour).  view, proj, camera_pos, width,
+ * height, the strip rows, the lens, target_format and temporal_sampling are neither read nor range-checked.  trace_strategy != 0 (the
+ * stochastic strategies' seeds are per pixel), lighting_mode != 0 and sort_mode == MGS_SORT_STOCHASTIC: MGS_ERR_UNSUPPORTED; reorder
+ * other than 0 / 1, NULL rays or results with count > 0, misaligned device pointers: MGS_ERR_INVALID_ARG; more than 2^31 - 1 rays:
+ * MGS_ERR_UNSUPPORTED.  All of this is checked before the handle is looked at.  `trace` / `query` NULL = the defaults.
+ *
+ * count == 0 is MGS_OK without a launch.  A scene without instances (committed or not) yields transmittance 1 and nothing else for
+ * every valid ray.  The hierarchy is the scene's, built lazily under mgs_render_traced's rules and shared with the traced frames.  A
+ * bound occluder is not looked at.  A ray query writes its results only: the handle's frame, side outputs and hit counts stay as
+ * they are; it does rewrite the handle's per-frame device constants and counters, so mgs_frame_stats, mgs_frame_row_costs and
+ * mgs_frame_download_projected of an earlier frame are not meaningful afterwards (a frame context keeps the two apart).
+ * mgs_trace_rays copies the batch through staging buffers of the handle and waits; mgs_trace_rays_device takes device pointers
+ * (16-byte aligned), is ordered on the handle's stream and, with reorder = 0, waits only when `out` is non-NULL.  With reorder = 1
+ * it always blocks the host: mgs_radix_sort_u32 waits for the stream two or three times (and for the device when its scratch grows).
+ *
+ * Reorder (query->reorder = 1): the lanes of a wave walk nearly the same nodes only when their rays are alike.  A 32-bit coherence
+ * key per ray — 21 bits of Morton code of the origin's cell in the scene's box (origins outside are clamped), the direction's
+ * octant, 4 + 4 bits of |d.x| and |d.y| over the direction's 1-norm; the largest key for an invalid ray; nothing but the ray and
+ * the box enters — is sorted with the ray's index by the library's stable radix sort (mgs_radix_sort_u32), and lane i of workgroup b
+ * traces the ray at position b * 256 + i of that order.  Results are written at the ray's own index and do not depend on the
+ * order, bit for bit; the integer statistics are equal as well.  Keys and indices (8 B / ray) and the staging buffers of the host
+ * variant belong to the handle and count into working_bytes.  reorder_ms is the time between HIP events before the key kernel and
+ * behind the sort: it includes the stream standing idle during the sort's host round trips, not only the kernels.  Default 0:
+ * DESIGN.md section 3.14 has what was measured (tools/trace_probe.py --rays measures it). */
+typedef struct MgsRay {
+  float origin[3];
+  float t_min;
+  float direction[3];
+  float t_max;
+} MgsRay; /* 32 B */
+typedef struct MgsRayResult {
+  float    radiance[3];
+  float    transmittance; /* float(T) of the walk; 1 for an invalid ray */
+  float    t_iso;
+  uint32_t id;
+  uint32_t hit_count;
+  uint32_t passes;
+  float    normal[4];
+} MgsRayResult; /* 48 B */
+typedef struct MgsRayQueryParams {
+  int32_t  reorder; /* 0 / 1, default 0 */
+  uint32_t reserved[3];
+} MgsRayQueryParams;
+typedef struct MgsRayQueryOut {
+  MgsTraceOut trace;        /* as of a traced frame: the hierarchy, the batch's integer sums, the most passes any ray started, trace_ms
+                               from HIP events around the traversal */
+  float       reorder_ms;   /* HIP events around the key and sort launches, the sort's host waits included (0 without reorder) */
+  uint32_t    invalid_rays;
+  uint32_t    reserved[2];
+} MgsRayQueryOut;
+void mgs_ray_query_params_default(MgsRayQueryParams* q);
+int  mgs_trace_rays(MgsScene scene_or_context, const MgsRay* rays_host, uint64_t count, const MgsFrameParams* params,
+                    const MgsTraceParams* trace /* NULL = defaults */, const MgsRayQueryParams* query /* NULL = defaults */,
+                    MgsRayResult* results_host, MgsRayQueryOut* out /* may be NULL */);
+int  mgs_trace_rays_device(MgsScene scene_or_context, const MgsRay* rays_device, uint64_t count, const MgsFrameParams* params,
+                           const MgsTraceParams* trace /* NULL = defaults */, const MgsRayQueryParams* query /* NULL = defaults */,
+                           MgsRayResult* results_device, MgsRayQueryOut* out /* may be NULL */);
+/* The primary rays mgs_render_traced would trace for *params, written to rays_device[height][width] (device memory, 16-byte
+ * aligned, row-major; the strip rows are not looked at): pinhole, fisheye and depth of field as "Ray" above (rgen:159-196), exactly
+ * the ray the kernel of mgs_render_traced's strategy 0 traces, rounding for rounding (the light pass and the stochastic strategies
+ * compute the same ray with roundings of their own in the last bit),
+ * t_min = 0.001, t_max = 10000.  A fisheye pixel outside the image circle gets t_min = 1, t_max = 0, an invalid ray.  Reads and
+ * checks *params as mgs_render_traced does; ordered on the handle's stream, does not wait.  The seam for a caller who starts
+ * from the library's camera and perturbs it: tracing these rays gives the traced frame's radiance, 1 - alpha, hit counts, picked
+ * ids and normals bit for bit. */
+int  mgs_trace_generate_rays(MgsScene scene_or_context, const MgsFrameParams* params, MgsRay* rays_device);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

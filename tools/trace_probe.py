@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
 tests per ray, and writes everything as JSON.  --trace-strategy: MgsTraceParams::trace_strategy of the unlit frames (the lit
 and hybrid ones take the sorted strategy alone).  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
 lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  --hybrid (with --lit) renders the same lit
-scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and the shadow counters beside the traced ones.  Needs an MI355X.
+scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and the shadow counters beside the traced ones.
+--rays N adds ray queries (mgs_trace_rays_device) of about N rays, for every N given: a RANDOM batch (origins uniform in the ball of
+the camera's distance, each aimed at a random point of the inner half of that ball: neighbouring lanes share nothing) and a CAMERA
+batch (mgs_trace_generate_rays of the probe's camera at the frame size of the scene's aspect with about N pixels, row-major), each
+with reorder off and on: the median trace_ms and reorder_ms and the visits per ray; and mgs_render_traced's trace_ms of that same
+frame, whose lanes are 8 x 8 pixels where the row-major batch's are 64 x 1.  Needs an MI355X.
 """
 import argparse
 import json
@@ -22,6 +27,67 @@ import vk_gaussian_splatting_amd as mgs  # noqa: E402
 from vk_gaussian_splatting_amd import capi, synth  # noqa: E402
 
 
+def random_rays(n, radius, seed=1):
+    """n incoherent rays as a RAY_DTYPE array: origins uniform in the ball of `radius`, aimed at random points of the ball of radius / 2"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+
+    def ball(r):
+        v = rng.standard_normal((n, 3))
+        v /= np.linalg.norm(v, axis=1, keepdims=True)
+        return v * (r * rng.random((n, 1)) ** (1.0 / 3.0))
+
+    o, target = ball(radius), ball(0.5 * radius)
+    d = target - o
+    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
+    return capi.make_rays(o, d)
+
+
+def camera_frame_size(n, W, H):
+    """the frame of the aspect W : H with about n pixels"""
+    h = max(int(round((n * H / W) ** 0.5)), 1)
+    return max(n // h, 1), h
+
+
+def probe_rays(scene, p, t, n, eye, W, H, warmup, repeats):
+    """the four ray-query runs of --rays for one batch size, and the traced frame the camera batch corresponds to"""
+    import torch
+
+    def timed(rays_ptr, count, reorder):
+        res = torch.empty(count * 12, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        tms, rms = [], []
+        for k in range(warmup + repeats):
+            _, o = scene.trace_rays((rays_ptr, count), p, t, reorder=reorder, want_stats=True, results=res.data_ptr())
+            if k >= warmup:
+                tms.append(o.trace.trace_ms)
+                rms.append(o.reorder_ms)
+        return dict(reorder=int(reorder), rays=count, trace_ms_median=float(np.median(tms)), trace_ms_min=float(min(tms)), trace_ms_max=float(max(tms)),
+                    reorder_ms_median=float(np.median(rms)), reorder_ms_min=float(min(rms)), node_visits_per_ray=o.trace.node_visits / count,
+                    candidate_tests_per_ray=o.trace.candidate_tests / count, accepted_hits_per_ray=o.trace.accepted_hits / count,
+                    invalid_rays=int(o.invalid_rays))
+
+    out = dict(requested=n)
+    rnd = torch.from_numpy(random_rays(n, float(np.linalg.norm(eye))).view(np.float32).copy()).cuda()
+    out["random"] = [timed(rnd.data_ptr(), n, r) for r in (False, True)]
+    w, h = camera_frame_size(n, W, H)
+    pc = capi.default_params(w, h)
+    V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, w, h)
+    capi.set_camera(pc, V, P, eye)
+    cam = torch.empty(w * h * 8, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    scene.generate_rays(pc, cam.data_ptr())
+    scene.sync()
+    out["camera"] = [timed(cam.data_ptr(), w * h, r) for r in (False, True)]
+    fms = []
+    for k in range(warmup + repeats):
+        o = scene.render_traced(pc, t, want_stats=True)
+        if k >= warmup:
+            fms.append(o.trace_ms)
+    out["camera_frame"] = dict(width=w, height=h, trace_ms_median=float(np.median(fms)), trace_ms_min=float(min(fms)), trace_ms_max=float(max(fms)),
+                               node_visits_per_ray=o.node_visits / (w * h))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("scenes", nargs="+")
@@ -32,6 +98,7 @@ def main():
     ap.add_argument("--trace-strategy", choices=["full", "pass", "anyhit"], default="full")
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--hybrid", action="store_true")
+    ap.add_argument("--rays", type=int, nargs="+", default=[])
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -62,6 +129,10 @@ def main():
                  node_visits_per_ray=o.node_visits / rays, candidate_tests_per_ray=o.candidate_tests / rays,
                  accepted_hits_per_ray=o.accepted_hits / rays, max_passes_used=int(o.max_passes_used),
                  scene_bytes=scene.memory_usage()[0])
+        if a.rays:
+            if a.trace_strategy != "full":
+                ap.error("--rays: ray queries take --trace-strategy full only")
+            r["ray_queries"] = [probe_rays(scene, p, t, nr, eye, W, H, a.warmup, a.repeats) for nr in a.rays]
         if a.lit:
             p.lighting_mode = 1
             t.trace_strategy = capi.TRACE_STRATEGY_FULL_ANYHIT

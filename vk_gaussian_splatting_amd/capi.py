@@ -157,6 +157,44 @@ class TraceOut(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Ray(C.Structure):
+    """MgsRay: origin, t_min, direction, t_max (32 bytes; RAY_DTYPE is the same layout for numpy)"""
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("direction", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayResult(C.Structure):
+    """MgsRayResult (48 bytes; RAY_RESULT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("radiance", C.c_float * 3), ("transmittance", C.c_float), ("t_iso", C.c_float), ("id", C.c_uint32),
+                ("hit_count", C.c_uint32), ("passes", C.c_uint32), ("normal", C.c_float * 4)]
+
+
+class RayQueryParams(C.Structure):
+    """MgsRayQueryParams"""
+    _fields_ = [("reorder", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+class RayQueryOut(C.Structure):
+    """MgsRayQueryOut: MgsTraceOut of the batch, the device time of the reorder and the number of refused rays"""
+    _fields_ = [("trace", TraceOut), ("reorder_ms", C.c_float), ("invalid_rays", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return dict(self.trace.as_dict(), reorder_ms=self.reorder_ms, invalid_rays=self.invalid_rays)
+
+
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("direction", np.float32, 3), ("t_max", np.float32)])
+RAY_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("transmittance", np.float32), ("t_iso", np.float32), ("id", np.uint32),
+                             ("hit_count", np.uint32), ("passes", np.uint32), ("normal", np.float32, 4)])
+
+
+def make_rays(origin, direction, t_min=0.001, t_max=10000.0):
+    """a RAY_DTYPE array from origins [n,3], directions [n,3] and windows (scalars or [n])"""
+    o = np.asarray(origin, np.float32).reshape(-1, 3)
+    r = np.zeros(o.shape[0], RAY_DTYPE)
+    r["origin"], r["direction"] = o, np.asarray(direction, np.float32).reshape(-1, 3)
+    r["t_min"], r["t_max"] = t_min, t_max
+    return r
+
+
 class CompareParams(C.Structure):
     """MgsCompareParams"""
     _fields_ = [("flip_mode", C.c_int32), ("pixels_per_degree", C.c_float)]
@@ -259,6 +297,10 @@ def load_library():
         "mgs_trace_light_params_default": (None, [P(TraceLightParams)]),
         "mgs_render_traced_lit": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceLightParams), P(TraceOut), P(TraceLightOut)]),
         "mgs_trace_download_shadow_hits": (C.c_int, [vp, P(C.c_uint32), C.c_size_t]),
+        "mgs_ray_query_params_default": (None, [P(RayQueryParams)]),
+        "mgs_trace_rays": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(RayQueryParams), vp, P(RayQueryOut)]),
+        "mgs_trace_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(RayQueryParams), vp, P(RayQueryOut)]),
+        "mgs_trace_generate_rays": (C.c_int, [vp, P(FrameParams), vp]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -317,6 +359,7 @@ EXPORTED_SYMBOLS = [
     "mgs_mesh_instance_set_transform", "mgs_mesh_instance_set_visible", "mgs_meshes_render", "mgs_meshes_download",
     "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
     "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits", "mgs_render_hybrid",
+    "mgs_ray_query_params_default", "mgs_trace_rays", "mgs_trace_rays_device", "mgs_trace_generate_rays",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -736,6 +779,32 @@ class Scene:
         if not params.collect_timings:
             _check(self._lib.mgs_frame_stats(self._h, C.byref(out)))
         return out, lout
+
+    def trace_rays(self, rays, params, trace=None, reorder=False, want_stats=False, results=None):
+        """mgs_trace_rays / mgs_trace_rays_device: the caller's rays through the scene's hierarchy with the walk of render_traced's
+        strategy 0.  rays = a RAY_DTYPE array (make_rays) -> returns a RAY_RESULT_DTYPE array (waits); or rays = (device pointer,
+        count) with results = a device pointer to count * 48 bytes, both 16-byte aligned -> ordered on the handle's stream, returns
+        None.  want_stats waits and returns (results, RayQueryOut)."""
+        out, q = RayQueryOut(), RayQueryParams()
+        self._lib.mgs_ray_query_params_default(C.byref(q))
+        q.reorder = int(bool(reorder))
+        tr = C.byref(trace) if trace is not None else None
+        if isinstance(rays, tuple):
+            ptr, count = rays
+            _check(self._lib.mgs_trace_rays_device(self._h, C.c_void_p(ptr or None), int(count), C.byref(params), tr, C.byref(q),
+                                                   C.c_void_p(results or None), C.byref(out) if want_stats else None))
+            res = None
+        else:
+            r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+            res = np.zeros(r.shape[0], RAY_RESULT_DTYPE)
+            _check(self._lib.mgs_trace_rays(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(params), tr, C.byref(q),
+                                            res.ctypes.data_as(C.c_void_p), C.byref(out) if want_stats else None))
+        return (res, out) if want_stats else res
+
+    def generate_rays(self, params, rays_device):
+        """mgs_trace_generate_rays: the primary rays render_traced would trace for params, written row-major to the device pointer
+        rays_device (height * width * 32 bytes, 16-byte aligned); ordered on the handle's stream"""
+        _check(self._lib.mgs_trace_generate_rays(self._h, C.byref(params), C.c_void_p(rays_device or None)))
 
     def trace_shadow_hits(self, params):
         """shadow hits accepted per pixel of the last lit traced frame, summed over the lights, uint32[H,W]"""

@@ -1,0 +1,263 @@
+// api_rays.hip — ray queries, host side: mgs_trace_rays / mgs_trace_rays_device trace the caller's rays through the scene's hierarchy
+// with the walk of mgs_render_traced's strategy 0, mgs_trace_generate_rays writes out a frame's primary rays.  The range checks, the
+// hierarchy and the traversal's arguments are api_trace.hip's.
+#include <cmath>
+#include <memory>
+
+#include "scene_state.h"
+
+void mgs_ray_query_params_default(MgsRayQueryParams* q)
+{
+  if(q)
+    std::memset(q, 0, sizeof(*q));  // reorder 0: the caller's order
+}
+
+// *p with every field a ray query does not read set to a value that is in range and reads no memory: the caller's camera, frame
+// size, strip rows, lens, sample and target are neither read nor checked
+static MgsFrameParams withoutCamera(const MgsFrameParams& p)
+{
+  MgsFrameParams q = p;
+  std::memset(q.view, 0, sizeof(q.view));
+  std::memset(q.proj, 0, sizeof(q.proj));
+  std::memset(q.camera_pos, 0, sizeof(q.camera_pos));
+  q.view[0] = q.view[5] = q.view[10] = q.view[15] = 1.0f;
+  q.proj[0] = q.proj[5] = q.proj[10] = q.proj[15] = 1.0f;
+  q.width = q.height  = kTilePx;
+  q.strip_row_begin   = 0;
+  q.strip_row_end     = 0;
+  q.target_format     = MGS_TARGET_RGBA32F;
+  q.camera_model      = MGS_CAMERA_PINHOLE;
+  q.fov_rad           = 0.0f;
+  q.dof_mode          = MGS_DOF_DISABLED;
+  q.frame_sample_id   = 0;
+  q.temporal_sampling = 0;
+  return q;
+}
+
+namespace {
+struct RayBatch
+{
+  const MgsRay* rays    = nullptr;  // device
+  MgsRayResult* results = nullptr;  // device
+  uint64_t      count   = 0;
+};
+}  // namespace
+
+// the checks that need no device, in the order of the other traced entry points
+static int validateRays(const MgsFrameParams* p, const MgsTraceParams& t, const MgsRayQueryParams& q, const void* rays, const void* results,
+                        uint64_t count, bool onDevice, const char* what)
+{
+  if(!p)
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null params");
+  const MgsFrameParams v = withoutCamera(*p);
+  if(int rc = validateTrace(&v, t))
+    return rc;
+  if(t.trace_strategy != MGS_TRACE_STRATEGY_FULL_ANYHIT)
+    return failTrace(MGS_ERR_UNSUPPORTED, std::string(what) + ": the stochastic trace strategies are mgs_render_traced's, their seeds are per pixel "
+                                                              "(trace_strategy must be 0)");
+  if(q.reorder != 0 && q.reorder != 1)
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": reorder must be 0 or 1");
+  if(count > 0 && (!rays || !results))
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null rays or results with count > 0");
+  if(count > 0x7FFFFFFFull)
+    return failTrace(MGS_ERR_UNSUPPORTED, std::string(what) + ": at most 2^31 - 1 rays per call");
+  if(onDevice && (((uintptr_t)rays | (uintptr_t)results) & 15u))
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": rays and results must be 16-byte aligned");
+  return MGS_OK;
+}
+
+// the batch on the device, on the handle's stream; waits only for `out`
+static int traceRaysOnDevice(MgsScene s, const RayBatch& b, const MgsFrameParams* p, const MgsTraceParams& t, const MgsRayQueryParams& qp,
+                             MgsRayQueryOut* out, const char* what)
+{
+  if(!s)
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null scene");
+  if(out)
+    std::memset(out, 0, sizeof(*out));
+  if(b.count == 0)
+    return MGS_OK;
+  SceneData& d     = *s->d;
+  const bool empty = d.instances.empty();
+  if(!empty && !d.committed)
+    return failTrace(MGS_ERR_STATE, std::string(what) + ": call mgs_scene_commit first");
+  HIPCHK(hipSetDevice(s->device));
+  if(!empty)
+    if(int wrc = ensureWorkingSet(s))
+      return wrc;
+  // the frame's constants as mgs_render_traced builds them, without a camera
+  MgsFrameParams q      = withoutCamera(*p);
+  q.pipeline            = MGS_PIPELINE_3DGUT;
+  q.sort_mode           = MGS_SORT_GPU_RADIX;
+  q.lighting_mode       = MGS_LIGHTING_DISABLED;
+  q.depth_iso_threshold = t.depth_iso_threshold;
+  auto A  = std::make_unique<FrameArgs>();
+  int  rc = buildFrameArgs(s, &q, *A);
+  if(rc)
+    return rc;
+  TracePassState& ts = s->trace;
+  if((rc = ensureTraceEvents(ts))) return rc;
+  if((rc = ts.ctr.ensure(1))) return rc;
+  if((rc = ts.rayInvalid.ensure(1))) return rc;
+  const uint32_t n = (uint32_t)b.count;
+  if(qp.reorder)
+  {
+    if((rc = ts.rayKeys.ensure(n))) return rc;
+    if((rc = ts.rayIdx.ensure(n))) return rc;
+  }
+  if((rc = uploadFrameState(s, *A, s->stream))) return rc;
+  const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
+  float            buildMs = 0.0f;
+  uint32_t         rebuilt = 0;
+  if((rc = ensureHierarchy(s, *A, proxy, &buildMs, &rebuilt))) return rc;
+  hipStream_t st = s->stream;
+  if(qp.reorder)
+  {
+    HIPCHK(hipEventRecord(ts.ev[6], st));
+    RayKeyArgs K{};
+    K.rays  = reinterpret_cast<const float4*>(b.rays);
+    K.keys  = ts.rayKeys.p;
+    K.idx   = ts.rayIdx.p;
+    K.count = n;
+    sceneBox(d, K.sceneLo, K.sceneInvExt);
+    launchRaysKey(st, K);
+    HIPCHK(hipGetLastError());
+    // the library's own (key, value) sort: stable, so rays with equal keys keep the caller's order
+    if((rc = mgs_radix_sort_u32(s, ts.rayKeys.p, ts.rayIdx.p, n, 0, 32, nullptr))) return rc;
+    HIPCHK(hipEventRecord(ts.ev[7], st));
+  }
+  HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
+  HIPCHK(hipMemsetAsync(ts.rayInvalid.p, 0, 4, st));
+  HIPCHK(hipEventRecord(ts.ev[2], st));
+  TraceRaysArgs L{};
+  L.t       = traceArgs(s, proxy, t, 0);
+  L.t.image = nullptr;  // a ray query writes results only: the handle's frame, side outputs and hit counts stay as they are
+  L.rays    = reinterpret_cast<const float4*>(b.rays);
+  L.results = reinterpret_cast<float4*>(b.results);
+  L.perm    = qp.reorder ? ts.rayIdx.p : nullptr;
+  L.count   = n;
+  L.invalid = ts.rayInvalid.p;
+  L.surf    = p->surface_outputs != 0 ? 1 : 0;
+  launchTraceRays(st, L, d.shFormat);
+  HIPCHK(hipEventRecord(ts.ev[3], st));
+  HIPCHK(hipGetLastError());
+  if(out)
+  {
+    TraceCounters hc{};
+    uint32_t      invalid = 0;
+    HIPCHK(hipMemcpyAsync(&hc, ts.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&invalid, ts.rayInvalid.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out->trace.leaves          = empty ? 0 : d.bvh.leaves;
+    out->trace.nodes           = empty ? 0 : d.bvh.totalNodes;
+    out->trace.node_visits     = hc.nodeVisits;
+    out->trace.candidate_tests = hc.candidateTests;
+    out->trace.accepted_hits   = hc.acceptedHits;
+    out->trace.max_passes_used = hc.maxPassesUsed;
+    out->trace.bvh_rebuilt     = rebuilt;
+    out->trace.build_ms        = buildMs;
+    out->invalid_rays          = invalid;
+    HIPCHK(hipEventElapsedTime(&out->trace.trace_ms, ts.ev[2], ts.ev[3]));
+    if(qp.reorder)
+      HIPCHK(hipEventElapsedTime(&out->reorder_ms, ts.ev[6], ts.ev[7]));
+  }
+  return MGS_OK;
+}
+
+static int mgs_trace_rays_impl(MgsScene s, const void* rays, uint64_t count, const MgsFrameParams* p, const MgsTraceParams* tp,
+                               const MgsRayQueryParams* qp, void* results, MgsRayQueryOut* out, bool host)
+{
+  const char*    what = host ? "mgs_trace_rays" : "mgs_trace_rays_device";
+  MgsTraceParams t;
+  if(tp)
+    t = *tp;
+  else
+    mgs_trace_params_default(&t);
+  MgsRayQueryParams q;
+  if(qp)
+    q = *qp;
+  else
+    mgs_ray_query_params_default(&q);
+  // (before the handle is looked at; host arrays need no alignment: they are staged)
+  if(int rc = validateRays(p, t, q, rays, results, count, !host, what))
+    return rc;
+  RayBatch b;
+  b.count = count;
+  if(!host)
+  {
+    b.rays    = static_cast<const MgsRay*>(rays);
+    b.results = static_cast<MgsRayResult*>(results);
+    return traceRaysOnDevice(s, b, p, t, q, out, what);
+  }
+  if(!s)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_rays: null scene");
+  if(count == 0)
+  {
+    if(out)
+      std::memset(out, 0, sizeof(*out));
+    return MGS_OK;
+  }
+  HIPCHK(hipSetDevice(s->device));
+  TracePassState& ts = s->trace;
+  int             rc;
+  if((rc = ts.rayStage.ensure(2 * (size_t)count))) return rc;
+  if((rc = ts.resultStage.ensure(3 * (size_t)count))) return rc;
+  HIPCHK(hipMemcpyAsync(ts.rayStage.p, rays, (size_t)count * sizeof(MgsRay), hipMemcpyHostToDevice, s->stream));
+  b.rays    = reinterpret_cast<const MgsRay*>(ts.rayStage.p);
+  b.results = reinterpret_cast<MgsRayResult*>(ts.resultStage.p);
+  if((rc = traceRaysOnDevice(s, b, p, t, q, out, what)))
+  {
+    (void)hipStreamSynchronize(s->stream);  // the upload reads the caller's array
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(results, ts.resultStage.p, (size_t)count * sizeof(MgsRayResult), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return MGS_OK;
+}
+int mgs_trace_rays(MgsScene s, const MgsRay* rays, uint64_t count, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsRayQueryParams* qp,
+                   MgsRayResult* results, MgsRayQueryOut* out)
+{
+  return guarded("mgs_trace_rays", [&] { return mgs_trace_rays_impl(s, rays, count, p, tp, qp, results, out, true); });
+}
+int mgs_trace_rays_device(MgsScene s, const MgsRay* rays, uint64_t count, const MgsFrameParams* p, const MgsTraceParams* tp,
+                          const MgsRayQueryParams* qp, MgsRayResult* results, MgsRayQueryOut* out)
+{
+  return guarded("mgs_trace_rays_device", [&] { return mgs_trace_rays_impl(s, rays, count, p, tp, qp, results, out, false); });
+}
+
+static int mgs_trace_generate_rays_impl(MgsScene s, const MgsFrameParams* p, MgsRay* raysDev)
+{
+  if(!p)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: null params");
+  MgsTraceParams t;
+  mgs_trace_params_default(&t);
+  if(int rc = validateTrace(p, t))  // (before the handle is looked at)
+    return rc;
+  if(!raysDev || ((uintptr_t)raysDev & 15u))
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: rays must be a 16-byte aligned device pointer");
+  if(!s)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: null scene");
+  SceneData& d = *s->d;
+  if(!d.instances.empty() && !d.committed)
+    return failTrace(MGS_ERR_STATE, "mgs_trace_generate_rays: call mgs_scene_commit first");
+  HIPCHK(hipSetDevice(s->device));
+  if(!d.instances.empty())
+    if(int wrc = ensureWorkingSet(s))
+      return wrc;
+  MgsFrameParams q = *p;  // the constants of mgs_render_traced's frame
+  q.pipeline       = MGS_PIPELINE_3DGUT;
+  q.sort_mode      = MGS_SORT_GPU_RADIX;
+  auto A  = std::make_unique<FrameArgs>();
+  int  rc = buildFrameArgs(s, &q, *A);
+  if(rc)
+    return rc;
+  mat4InverseDouble(p->view, A->f.lightViewInv);
+  mat4InverseDouble(p->proj, A->f.lightProjInv);
+  if((rc = uploadFrameState(s, *A, s->stream))) return rc;
+  launchRaysGenerate(s->stream, s->fb.dArgs.p, reinterpret_cast<float4*>(raysDev), (uint32_t)A->f.width * (uint32_t)A->f.height);
+  HIPCHK(hipGetLastError());
+  return MGS_OK;
+}
+int mgs_trace_generate_rays(MgsScene s, const MgsFrameParams* p, MgsRay* raysDev)
+{
+  return guarded("mgs_trace_generate_rays", [&] { return mgs_trace_generate_rays_impl(s, p, raysDev); });
+}

@@ -30,7 +30,7 @@ void mgs_trace_light_params_default(MgsTraceLightParams* p)
   p->particle_shadow_color_strength          = 0.0f;                  // parameters.h:224
 }
 
-static int failTrace(int code, const std::string& msg)
+int failTrace(int code, const std::string& msg)
 {
   setError(msg);
   return code;
@@ -39,7 +39,7 @@ static int failTrace(int code, const std::string& msg)
 // what needs no device: the ranges of MgsTraceParams and of the MgsFrameParams fields the traced pipeline reads
 // (lit: the checks of mgs_render_traced_lit, whose lighting_mode rule differs; hybrid: those of mgs_render_hybrid, which has no
 // primary walk and takes its surface from one of the raster pipelines)
-static int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr, bool hybrid = false)
+int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit, bool hybrid)
 {
   if(t.samples_per_pass < 1 || t.samples_per_pass > 32)
     return failTrace(MGS_ERR_INVALID_ARG, "trace: samples_per_pass must be in [1, 32]");
@@ -132,7 +132,7 @@ static std::vector<uint8_t> bvhSignature(const SceneData& d, const TraceProxy& p
 }
 
 // the frame in which the Morton codes are quantised: the union of the instances' transformed set boxes (finite centres only)
-static void sceneBox(const SceneData& d, float lo[3], float invExt[3])
+void sceneBox(const SceneData& d, float lo[3], float invExt[3])
 {
   double wl[3] = {1e300, 1e300, 1e300}, wh[3] = {-1e300, -1e300, -1e300};
   std::vector<std::array<float, 6>> setBox(d.sets.size());
@@ -264,7 +264,7 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
 }
 
 // the scene's hierarchy for this frame's proxy: rebuilt when its signature differs (the frame's constants are on the device)
-static int ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt)
+int ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt)
 {
   SceneData& d = *s->d;
   *buildMs = 0.0f;
@@ -278,7 +278,7 @@ static int ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& pro
   return buildBvh(s, A, proxy, std::move(sig), buildMs);
 }
 
-static int ensureTraceEvents(TracePassState& ts)
+int ensureTraceEvents(TracePassState& ts)
 {
   if(!ts.ev[0])
     for(auto& e : ts.ev)
@@ -299,7 +299,7 @@ static int ensureLightScratch(MgsScene s, size_t pixels)
 }
 
 // what every kernel of the traced pipeline receives: frame, hierarchy, proxy, the rays' knobs, the image (the outputs stay null)
-static TraceArgs traceArgs(MgsScene s, const TraceProxy& proxy, const MgsTraceParams& t, int fmt)
+TraceArgs traceArgs(MgsScene s, const TraceProxy& proxy, const MgsTraceParams& t, int fmt)
 {
   SceneData& d = *s->d;
   TraceArgs  L{};

@@ -348,6 +348,28 @@ struct TraceArgs
   float*                outIsoDist;   // a lit frame's inputs of the light pass (mgs_render_traced_lit), null otherwise: the ray
   float4*               outRadiance;  // parameter of the iso-surface hit (0 = none) and the pixel in fp32 (rgb, 1 - T)
 };
+// what a ray query (k_trace_rays.hip, mgs_trace_rays) receives by value: the traversal's arguments (image, hit counts and side outputs
+// stay null) and the caller's batch.  A ray is two float4, (origin, t_min) and (direction, t_max); a result three, (radiance,
+// float(T)), (t_iso, id, hit count, passes as bits) and the integrated normal with its weight.
+struct TraceRaysArgs
+{
+  TraceArgs       t;
+  const float4*   rays;     // [2 * count]
+  float4*         results;  // [3 * count], at the ray's index in the caller's order
+  const uint32_t* perm;     // [count] lane -> ray index (a reordered batch), or null: the caller's order
+  uint32_t        count;
+  uint32_t*       invalid;  // [1] rays that were refused (non-finite, zero direction, t_min > t_max)
+  int32_t         surf;     // 1: integrate the normals (surface_outputs)
+};
+// the coherence keys of a reordered batch (k_rays_key): the scene box of the hierarchy's Morton frame (api_trace.hip: sceneBox)
+struct RayKeyArgs
+{
+  const float4* rays;
+  uint32_t*     keys;  // [count]
+  uint32_t*     idx;   // [count] iota, the sort's values
+  uint32_t      count;
+  float         sceneLo[3], sceneInvExt[3];
+};
 // the shadow rays' statistics (MgsTraceLightOut)
 struct TraceLightCounters
 {

@@ -130,6 +130,10 @@ void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, in
 // the stochastic trace strategies (k_trace_stochastic.hip): strategy 1 = pass-stochastic, 2 = stochastic any-hit
 void launchTraceStochastic(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat, int strategy);
 void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameConst& F);  // k_trace_light.hip
+// ray queries (k_trace_rays.hip): the frame's primary rays written out row-major; a batch's coherence keys; one ray per lane
+void launchRaysGenerate(hipStream_t stream, const FrameArgs* dArgs, float4* rays, uint32_t pixels);
+void launchRaysKey(hipStream_t stream, const RayKeyArgs& a);
+void launchTraceRays(hipStream_t stream, const TraceRaysArgs& a, int shFormat);
 // the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);

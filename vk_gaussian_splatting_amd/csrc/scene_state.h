@@ -483,11 +483,19 @@ struct TracePassState
   DevBuf<uint32_t>           shadowHits;
   DevBuf<TraceLightCounters> lctr;
   DevBuf<float4>             hybridNormal;  // a hybrid frame's normalised normal (mgs_render_hybrid): the raster side outputs stay as they are
+  // ray queries (mgs_trace_rays, api_rays.hip): the host variant's staging of rays and results, the refused rays' counter, and a
+  // reordered batch's coherence keys and ray indices (sorted in place: the indices become the permutation)
+  DevBuf<float4>             rayStage, resultStage;
+  DevBuf<uint32_t>           rayInvalid, rayKeys, rayIdx;
   int                   w = 0, h = 0;
   bool                  have = false, haveLit = false;
-  hipEvent_t            ev[6] = {};  // build begin / end, traversal begin / end, light pass begin / end
+  hipEvent_t            ev[8] = {};  // build begin / end, traversal begin / end, light pass begin / end, ray reorder begin / end
   template <class F>
-  void eachBuffer(F&& f) { f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); f(hybridNormal); }
+  void eachBuffer(F&& f)
+  {
+    f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); f(hybridNormal);
+    f(rayStage); f(resultStage); f(rayInvalid); f(rayKeys); f(rayIdx);
+  }
   void release()
   {
     eachBuffer([](auto& b) { b.release(); });
@@ -664,6 +672,14 @@ struct FrameTail
   virtual ~FrameTail() = default;
 };
 int  renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail* tail);  // api_frame.hip: mgs_render's frame
+// api_trace.hip, shared with the ray queries of api_rays.hip: the range checks that need no device, the Morton frame of the
+// hierarchy, its lazy build, the handle's events and what every traversal kernel receives
+int  failTrace(int code, const std::string& msg);
+int  validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr, bool hybrid = false);
+void sceneBox(const SceneData& d, float lo[3], float invExt[3]);
+int  ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt);
+int  ensureTraceEvents(TracePassState& ts);
+TraceArgs traceArgs(MgsScene s, const TraceProxy& proxy, const MgsTraceParams& t, int fmt);
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip
 int  cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking);         // api_sort.hip
