@@ -2,6 +2,8 @@
 MODE tied:  generated rays of a 40 x 24 pinhole, fisheye and depth-of-field frame traced as a batch, next to the traced frame itself,
             at samples_per_pass 4, 18 and 32
 MODE batch: the batch of ray_cases.py on the device: reorder off and on, reversed and shuffled
+MODE shared: one handle through mgs_render_traced, a ray query of that frame's rays, mgs_render_traced_lit, mgs_render_hybrid and
+            mgs_render_traced again, with the same parameters: whether each call rebuilt the hierarchy, the first and the last frame
 MODE edges: counts around the wave and workgroup sizes with a sentinel behind the results, an all-invalid batch, a scene without
             instances, the host variant, a query on a frame context next to a finished frame, the reorder buffers in working_bytes"""
 import os
@@ -95,6 +97,26 @@ elif mode == "batch":
             for k in STATS:
                 res[f"{name}_{reorder}_{k}"] = o[k]
             res[f"{name}_{reorder}_reorder_ms"] = o["reorder_ms"]
+    scene.close()
+    np.savez(out, **res)
+elif mode == "shared":
+    res = {}
+    scene = build()
+    W, H = case["W"], case["H"]
+    p, t = params(W, H), capi.default_trace_params()
+    lit = params(W, H, lighting_mode=capi.LIGHTING_DIRECT)
+    rays = torch.zeros(W * H * 8, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    o = scene.render_traced(p, t, want_stats=True)
+    res["first_rebuilt"], res["first_image"], res["first_hits"] = o.bvh_rebuilt, scene.download_frame(p), scene.trace_hit_counts(p)
+    scene.generate_rays(p, rays.data_ptr())
+    got, q = query(scene, rays, W * H, p, t)
+    res["query_rebuilt"], res["query_hits"] = q["bvh_rebuilt"], got["hit_count"].reshape(H, W)
+    o, _ = scene.render_traced_lit(lit, t, None, want_stats=True)
+    res["lit_rebuilt"] = o.bvh_rebuilt
+    scene.render_hybrid(lit, t, None, want_stats=True)
+    o = scene.render_traced(p, t, want_stats=True)
+    res["last_rebuilt"], res["last_image"], res["last_hits"] = o.bvh_rebuilt, scene.download_frame(p), scene.trace_hit_counts(p)
     scene.close()
     np.savez(out, **res)
 else:

@@ -4,7 +4,7 @@ a. Tied to the traced frames bit for bit: the rays mgs_trace_generate_rays write
    makes of the same parameters.
 b. Arbitrary rays against the float64 restatement (np_trace_rays.py) under the bars test_gpu_trace.py holds strategy 0 to.
 c. Reorder changes nothing but time.
-d. Sizes and edges.   e. The reorder buffers in working_bytes."""
+d. Sizes and edges.   e. The reorder buffers in working_bytes.   f. One hierarchy for every traced entry point of a handle."""
 import os
 import subprocess
 import sys
@@ -116,6 +116,18 @@ def test_reorder_changes_nothing_but_time(batch):
         for k in ("node_visits", "candidate_tests", "accepted_hits", "max_passes_used", "invalid_rays"):
             assert int(batch[f"{name}_{k}"]) == int(batch[f"caller_0_{k}"]), (name, k)
     assert float(batch["caller_0_reorder_ms"]) == 0.0       # no reorder, no events read (times themselves are not asserted)
+
+
+def test_entry_points_share_one_hierarchy(tmp_path):
+    """Every traced entry point derives the hierarchy's proxy from the same four parameters, so one handle that goes through
+    mgs_render_traced, mgs_trace_rays_device, mgs_render_traced_lit, mgs_render_hybrid and mgs_render_traced again builds the
+    hierarchy once, and the last frame is the first"""
+    r = run_child(tmp_path, "shared")
+    assert int(r["first_rebuilt"]) == 1
+    assert int(r["query_rebuilt"]) == 0 and int(r["lit_rebuilt"]) == 0 and int(r["last_rebuilt"]) == 0
+    assert np.array_equal(r["query_hits"], r["first_hits"]) and r["first_hits"].max() > 3
+    assert r["last_image"].tobytes() == r["first_image"].tobytes() and r["first_image"].any()
+    assert np.array_equal(r["last_hits"], r["first_hits"])
 
 
 @pytest.fixture(scope="module")

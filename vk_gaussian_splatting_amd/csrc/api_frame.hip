@@ -542,18 +542,23 @@ static int launchFrame(const FramePass& fp, bool timed)
   return issueFrame(fp, timed);
 }
 
-static void recordLastFrame(const FramePass& fp, bool timed)
+void recordLastFrameHead(LastFrame& last, const MgsFrameParams& p, const FrameConst& F, bool timed, bool listsPartial)
 {
-  MgsScene          s = fp.s;
-  const FrameConst& F = fp.A->f;
-  LastFrame&        last = s->last;
-  last.params                 = *fp.p;
+  last.params                 = p;
   last.params.strip_row_begin = F.stripRow0;
   last.params.strip_row_end   = F.stripRow1;
   last.have         = true;
   last.timed        = timed;
   last.wasSortOnly  = false;
-  last.listsPartial = false;
+  last.listsPartial = listsPartial;
+}
+
+static void recordLastFrame(const FramePass& fp, bool timed)
+{
+  MgsScene          s = fp.s;
+  const FrameConst& F = fp.A->f;
+  LastFrame&        last = s->last;
+  recordLastFrameHead(last, *fp.p, F, timed, false);
   last.rideShift = F.rideShift;
   last.codeBits  = rideCodeBits(F);
   last.binsX     = F.binsX;

@@ -76,24 +76,14 @@ static int traceRaysOnDevice(MgsScene s, const RayBatch& b, const MgsFrameParams
     std::memset(out, 0, sizeof(*out));
   if(b.count == 0)
     return MGS_OK;
-  SceneData& d     = *s->d;
-  const bool empty = d.instances.empty();
-  if(!empty && !d.committed)
-    return failTrace(MGS_ERR_STATE, std::string(what) + ": call mgs_scene_commit first");
-  HIPCHK(hipSetDevice(s->device));
-  if(!empty)
-    if(int wrc = ensureWorkingSet(s))
-      return wrc;
-  // the frame's constants as mgs_render_traced builds them, without a camera
+  // the frame's constants as mgs_render_traced builds them, without a camera (so without the rays' inverses)
   MgsFrameParams q      = withoutCamera(*p);
-  q.pipeline            = MGS_PIPELINE_3DGUT;
-  q.sort_mode           = MGS_SORT_GPU_RADIX;
   q.lighting_mode       = MGS_LIGHTING_DISABLED;
   q.depth_iso_threshold = t.depth_iso_threshold;
-  auto A  = std::make_unique<FrameArgs>();
-  int  rc = buildFrameArgs(s, &q, *A);
-  if(rc)
-    return rc;
+  std::unique_ptr<FrameArgs> A;
+  int                        rc;
+  if((rc = traceFrameArgs(s, q, what, false, A))) return rc;
+  SceneData&      d  = *s->d;
   TracePassState& ts = s->trace;
   if((rc = ensureTraceEvents(ts))) return rc;
   if((rc = ts.ctr.ensure(1))) return rc;
@@ -105,14 +95,14 @@ static int traceRaysOnDevice(MgsScene s, const RayBatch& b, const MgsFrameParams
     if((rc = ts.rayIdx.ensure(n))) return rc;
   }
   if((rc = uploadFrameState(s, *A, s->stream))) return rc;
-  const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
+  const TraceProxy proxy   = traceProxy(*p, t);
   float            buildMs = 0.0f;
   uint32_t         rebuilt = 0;
   if((rc = ensureHierarchy(s, *A, proxy, &buildMs, &rebuilt))) return rc;
   hipStream_t st = s->stream;
   if(qp.reorder)
   {
-    HIPCHK(hipEventRecord(ts.ev[6], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvReorderBegin], st));
     RayKeyArgs K{};
     K.rays  = reinterpret_cast<const float4*>(b.rays);
     K.keys  = ts.rayKeys.p;
@@ -123,11 +113,11 @@ static int traceRaysOnDevice(MgsScene s, const RayBatch& b, const MgsFrameParams
     HIPCHK(hipGetLastError());
     // the library's own (key, value) sort: stable, so rays with equal keys keep the caller's order
     if((rc = mgs_radix_sort_u32(s, ts.rayKeys.p, ts.rayIdx.p, n, 0, 32, nullptr))) return rc;
-    HIPCHK(hipEventRecord(ts.ev[7], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvReorderEnd], st));
   }
   HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
   HIPCHK(hipMemsetAsync(ts.rayInvalid.p, 0, 4, st));
-  HIPCHK(hipEventRecord(ts.ev[2], st));
+  HIPCHK(hipEventRecord(ts.ev[kEvTraverseBegin], st));
   TraceRaysArgs L{};
   L.t       = traceArgs(s, proxy, t, 0);
   L.t.image = nullptr;  // a ray query writes results only: the handle's frame, side outputs and hit counts stay as they are
@@ -138,27 +128,19 @@ static int traceRaysOnDevice(MgsScene s, const RayBatch& b, const MgsFrameParams
   L.invalid = ts.rayInvalid.p;
   L.surf    = p->surface_outputs != 0 ? 1 : 0;
   launchTraceRays(st, L, d.shFormat);
-  HIPCHK(hipEventRecord(ts.ev[3], st));
+  HIPCHK(hipEventRecord(ts.ev[kEvTraverseEnd], st));
   HIPCHK(hipGetLastError());
   if(out)
   {
-    TraceCounters hc{};
-    uint32_t      invalid = 0;
-    HIPCHK(hipMemcpyAsync(&hc, ts.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+    TraceOutRead R;
+    uint32_t     invalid = 0;
+    if((rc = R.begin(s))) return rc;
     HIPCHK(hipMemcpyAsync(&invalid, ts.rayInvalid.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    out->trace.leaves          = empty ? 0 : d.bvh.leaves;
-    out->trace.nodes           = empty ? 0 : d.bvh.totalNodes;
-    out->trace.node_visits     = hc.nodeVisits;
-    out->trace.candidate_tests = hc.candidateTests;
-    out->trace.accepted_hits   = hc.acceptedHits;
-    out->trace.max_passes_used = hc.maxPassesUsed;
-    out->trace.bvh_rebuilt     = rebuilt;
-    out->trace.build_ms        = buildMs;
-    out->invalid_rays          = invalid;
-    HIPCHK(hipEventElapsedTime(&out->trace.trace_ms, ts.ev[2], ts.ev[3]));
+    if((rc = R.finish(s, rebuilt, buildMs, &out->trace))) return rc;
+    out->invalid_rays = invalid;
     if(qp.reorder)
-      HIPCHK(hipEventElapsedTime(&out->reorder_ms, ts.ev[6], ts.ev[7]));
+      HIPCHK(hipEventElapsedTime(&out->reorder_ms, ts.ev[kEvReorderBegin], ts.ev[kEvReorderEnd]));
   }
   return MGS_OK;
 }
@@ -167,16 +149,8 @@ static int mgs_trace_rays_impl(MgsScene s, const void* rays, uint64_t count, con
                                const MgsRayQueryParams* qp, void* results, MgsRayQueryOut* out, bool host)
 {
   const char*    what = host ? "mgs_trace_rays" : "mgs_trace_rays_device";
-  MgsTraceParams t;
-  if(tp)
-    t = *tp;
-  else
-    mgs_trace_params_default(&t);
-  MgsRayQueryParams q;
-  if(qp)
-    q = *qp;
-  else
-    mgs_ray_query_params_default(&q);
+  const MgsTraceParams    t = traceParamsOr(tp);
+  const MgsRayQueryParams q = rayQueryParamsOr(qp);
   // (before the handle is looked at; host arrays need no alignment: they are staged)
   if(int rc = validateRays(p, t, q, rays, results, count, !host, what))
     return rc;
@@ -228,30 +202,16 @@ static int mgs_trace_generate_rays_impl(MgsScene s, const MgsFrameParams* p, Mgs
 {
   if(!p)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: null params");
-  MgsTraceParams t;
-  mgs_trace_params_default(&t);
-  if(int rc = validateTrace(p, t))  // (before the handle is looked at)
+  if(int rc = validateTrace(p, traceParamsOr(nullptr)))  // (before the handle is looked at)
     return rc;
   if(!raysDev || ((uintptr_t)raysDev & 15u))
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: rays must be a 16-byte aligned device pointer");
   if(!s)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_generate_rays: null scene");
-  SceneData& d = *s->d;
-  if(!d.instances.empty() && !d.committed)
-    return failTrace(MGS_ERR_STATE, "mgs_trace_generate_rays: call mgs_scene_commit first");
-  HIPCHK(hipSetDevice(s->device));
-  if(!d.instances.empty())
-    if(int wrc = ensureWorkingSet(s))
-      return wrc;
-  MgsFrameParams q = *p;  // the constants of mgs_render_traced's frame
-  q.pipeline       = MGS_PIPELINE_3DGUT;
-  q.sort_mode      = MGS_SORT_GPU_RADIX;
-  auto A  = std::make_unique<FrameArgs>();
-  int  rc = buildFrameArgs(s, &q, *A);
-  if(rc)
-    return rc;
-  mat4InverseDouble(p->view, A->f.lightViewInv);
-  mat4InverseDouble(p->proj, A->f.lightProjInv);
+  MgsFrameParams q = *p;  // the constants of mgs_render_traced's frame (the iso threshold, which no ray depends on, stays the caller's)
+  std::unique_ptr<FrameArgs> A;
+  int                        rc;
+  if((rc = traceFrameArgs(s, q, "mgs_trace_generate_rays", true, A))) return rc;
   if((rc = uploadFrameState(s, *A, s->stream))) return rc;
   launchRaysGenerate(s->stream, s->fb.dArgs.p, reinterpret_cast<float4*>(raysDev), (uint32_t)A->f.width * (uint32_t)A->f.height);
   HIPCHK(hipGetLastError());

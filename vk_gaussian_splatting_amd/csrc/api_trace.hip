@@ -5,6 +5,7 @@
 #include <memory>
 
 #include "scene_state.h"
+#include "trace_dispatch.h"
 
 void mgs_trace_params_default(MgsTraceParams* p)
 {
@@ -116,6 +117,33 @@ int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTra
   return MGS_OK;
 }
 
+// The constants of a traced entry point's frame on handle s (not null), as the raster pipelines build them: the 3DGUT fields carry
+// the ray's parameters.  q: the caller's own copy of the frame's parameters (a ray query's is without a camera), which leaves here
+// with the pipeline and sort mode the constants were built for; what: the entry point's name for the messages; rayInverses:
+// viewInverse / projInverse of the rays, host double, rounded once (a ray query has no camera to invert).
+int traceFrameArgs(MgsScene s, MgsFrameParams& q, const char* what, bool rayInverses, std::unique_ptr<FrameArgs>& A)
+{
+  SceneData& d     = *s->d;
+  const bool empty = d.instances.empty();
+  if(!empty && !d.committed)
+    return failTrace(MGS_ERR_STATE, std::string(what) + ": call mgs_scene_commit first");
+  HIPCHK(hipSetDevice(s->device));
+  if(!empty)
+    if(int wrc = ensureWorkingSet(s))
+      return wrc;
+  q.pipeline  = MGS_PIPELINE_3DGUT;
+  q.sort_mode = MGS_SORT_GPU_RADIX;
+  A           = std::make_unique<FrameArgs>();
+  if(int rc = buildFrameArgs(s, &q, *A))
+    return rc;
+  if(rayInverses)
+  {
+    mat4InverseDouble(q.view, A->f.lightViewInv);
+    mat4InverseDouble(q.proj, A->f.lightProjInv);
+  }
+  return MGS_OK;
+}
+
 // everything the hierarchy depends on, as bytes: a traced frame whose signature differs rebuilds
 static std::vector<uint8_t> bvhSignature(const SceneData& d, const TraceProxy& proxy)
 {
@@ -215,7 +243,7 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
     HIPCHK(hipMemcpyAsync(B.callerId.p, caller.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // the sources are locals
   }
-  HIPCHK(hipEventRecord(t.ev[0], st));
+  HIPCHK(hipEventRecord(t.ev[kEvBuildBegin], st));
   BvhBuildArgs L{};
   L.frame = s->fb.dArgs.p;
   L.proxy = proxy;
@@ -253,9 +281,9 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
   for(int l = 1; l < B.nLevels; ++l)  // one plain kernel per level
     launchBvhLevel(st, B.nodes.p + 2 * (size_t)B.levelOffset[l - 1], B.levelCount[l - 1], B.nodes.p + 2 * (size_t)B.levelOffset[l], B.levelCount[l]);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(t.ev[1], st));
+  HIPCHK(hipEventRecord(t.ev[kEvBuildEnd], st));
   HIPCHK(hipStreamSynchronize(st));  // other contexts may trace over it as soon as this call returns
-  HIPCHK(hipEventElapsedTime(buildMs, t.ev[0], t.ev[1]));
+  HIPCHK(hipEventElapsedTime(buildMs, t.ev[kEvBuildBegin], t.ev[kEvBuildEnd]));
   t.keys.release(), t.vals.release(), t.leafBox.release();
   B.proxy     = proxy;
   B.signature = std::move(sig);
@@ -280,7 +308,7 @@ int ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, flo
 
 int ensureTraceEvents(TracePassState& ts)
 {
-  if(!ts.ev[0])
+  if(!ts.ev[kEvBuildBegin])
     for(auto& e : ts.ev)
       HIPCHK(hipEventCreate(&e));
   return MGS_OK;
@@ -340,7 +368,7 @@ static TraceLightArgs traceLightArgs(MgsScene s, const TraceArgs& L, const MgsTr
   G.shadowHits          = ts.shadowHits.p;
   G.lctr                = ts.lctr.p;
   G.shadowsMode         = lt.shadows_mode;
-  G.shFormat            = d.shFormat == 0 ? 0 : d.shFormat == 1 ? 1 : 2;
+  G.shFormat            = shFormatIndex(d.shFormat);
   G.shadowOffset        = lt.particle_shadow_offset;
   G.shadowThreshold     = lt.particle_shadow_transmittance_threshold;
   G.shadowColorStrength = lt.particle_shadow_color_strength;
@@ -359,7 +387,37 @@ static int readLightOut(MgsScene s, MgsTraceLightOut* lout)
   lout->shadow_node_visits     = hc.nodeVisits;
   lout->shadow_candidate_tests = hc.candidateTests;
   lout->shadow_accepted_hits   = hc.acceptedHits;
-  HIPCHK(hipEventElapsedTime(&lout->light_ms, ts.ev[4], ts.ev[5]));
+  HIPCHK(hipEventElapsedTime(&lout->light_ms, ts.ev[kEvLightBegin], ts.ev[kEvLightEnd]));
+  return MGS_OK;
+}
+
+int TraceOutRead::begin(MgsScene s)
+{
+  HIPCHK(hipMemcpyAsync(&hc, s->trace.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, s->stream));
+  return MGS_OK;
+}
+
+int TraceOutRead::finish(MgsScene s, uint32_t rebuilt, float buildMs, MgsTraceOut* out) const
+{
+  const SceneData& d     = *s->d;
+  const bool       empty = d.instances.empty();
+  out->leaves          = empty ? 0 : d.bvh.leaves;
+  out->nodes           = empty ? 0 : d.bvh.totalNodes;
+  out->node_visits     = hc.nodeVisits;
+  out->candidate_tests = hc.candidateTests;
+  out->accepted_hits   = hc.acceptedHits;
+  out->max_passes_used = hc.maxPassesUsed;
+  out->bvh_rebuilt     = rebuilt;
+  out->build_ms        = buildMs;
+  HIPCHK(hipEventElapsedTime(&out->trace_ms, s->trace.ev[kEvTraverseBegin], s->trace.ev[kEvTraverseEnd]));
+  return MGS_OK;
+}
+
+// The end of trace_ms.  A lit frame records it before its light pass, which has light_ms; an unlit frame behind the temporal
+// accumulation, the last work of the frame.
+static int endTraversal(TracePassState& ts, hipStream_t st)
+{
+  HIPCHK(hipEventRecord(ts.ev[kEvTraverseEnd], st));
   return MGS_OK;
 }
 
@@ -369,16 +427,8 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
 {
   if(!p)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null params");
-  MgsTraceParams t;
-  if(tp)
-    t = *tp;
-  else
-    mgs_trace_params_default(&t);
-  MgsTraceLightParams lt;
-  if(lit && lp)
-    lt = *lp;
-  else
-    mgs_trace_light_params_default(&lt);
+  const MgsTraceParams      t  = traceParamsOr(tp);
+  const MgsTraceLightParams lt = traceLightParamsOr(lit ? lp : nullptr);
   if(int rc = validateTrace(p, t, lit ? &lt : nullptr))  // (before the handle is looked at: the ranges can be checked without a device)
     return rc;
   if(!s)
@@ -386,98 +436,68 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(s->occ.depth)
     return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: an occluder is bound (meshes in the traced scene are out of scope); unbind it with "
                                           "mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
-  SceneData&  d     = *s->d;
-  const bool  empty = d.instances.empty();
-  if(!empty && !d.committed)
-    return failTrace(MGS_ERR_STATE, "mgs_render_traced: call mgs_scene_commit first");
-  HIPCHK(hipSetDevice(s->device));
-  if(!empty)
-    if(int wrc = ensureWorkingSet(s))
-      return wrc;
-  // the frame's constants as the raster pipelines build them: the 3DGUT fields carry the ray's parameters
-  MgsFrameParams q = *p;
-  q.pipeline       = MGS_PIPELINE_3DGUT;
-  q.sort_mode      = MGS_SORT_GPU_RADIX;
+  MgsFrameParams q      = *p;
   q.depth_iso_threshold = t.depth_iso_threshold;
-  auto A  = std::make_unique<FrameArgs>();
-  int  rc = buildFrameArgs(s, &q, *A);
-  if(rc)
-    return rc;
-  FrameConst& F = A->f;
-  mat4InverseDouble(p->view, F.lightViewInv);  // viewInverse / projInverse of the rays: host double, rounded once
-  mat4InverseDouble(p->proj, F.lightProjInv);
+  std::unique_ptr<FrameArgs> A;
+  int                        rc;
+  if((rc = traceFrameArgs(s, q, "mgs_render_traced", true, A))) return rc;
+  const FrameConst& F = A->f;
   if((rc = ensureFrameImage(s, &q, F))) return rc;
   TracePassState& ts = s->trace;
   if((rc = ensureTraceEvents(ts))) return rc;
   const size_t pixels = (size_t)F.width * F.height;
   if((rc = ts.hitCount.ensure(pixels))) return rc;
   if((rc = ts.ctr.ensure(1))) return rc;
-  if(lit)
+  if(lit)  // scratch
     if((rc = ensureLightScratch(s, pixels))) return rc;
   if((rc = uploadFrameState(s, *A, s->stream))) return rc;
-  const TraceProxy proxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold};
+  const TraceProxy proxy   = traceProxy(*p, t);
   float            buildMs = 0.0f;
   uint32_t         rebuilt = 0;
   if((rc = ensureHierarchy(s, *A, proxy, &buildMs, &rebuilt))) return rc;
   hipStream_t st = s->stream;
   HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
-  HIPCHK(hipEventRecord(ts.ev[2], st));
+  HIPCHK(hipEventRecord(ts.ev[kEvTraverseBegin], st));
   TraceArgs L = traceArgs(s, proxy, t, targetLayout(p->target_format).fmt);
-  L.hitCount          = ts.hitCount.p;
-  L.outDepth          = F.surfaceOutputs ? s->surf.depth.p : nullptr;
-  L.outId             = F.surfaceOutputs ? s->surf.id.p : nullptr;
-  L.outNormal         = F.surfaceOutputs ? s->surf.normal.p : nullptr;
-  L.outIsoDist        = lit ? ts.isoDist.p : nullptr;
-  L.outRadiance       = lit ? ts.radiance.p : nullptr;
+  L.hitCount    = ts.hitCount.p;
+  L.outDepth    = F.surfaceOutputs ? s->surf.depth.p : nullptr;
+  L.outId       = F.surfaceOutputs ? s->surf.id.p : nullptr;
+  L.outNormal   = F.surfaceOutputs ? s->surf.normal.p : nullptr;
+  L.outIsoDist  = lit ? ts.isoDist.p : nullptr;  // what the light pass reads besides the side outputs
+  L.outRadiance = lit ? ts.radiance.p : nullptr;
   if(t.trace_strategy == MGS_TRACE_STRATEGY_FULL_ANYHIT)
-    launchTrace(st, L, F, d.shFormat);
+    launchTrace(st, L, F, s->d->shFormat);
   else
-    launchTraceStochastic(st, L, F, d.shFormat, t.trace_strategy);
+    launchTraceStochastic(st, L, F, s->d->shFormat, t.trace_strategy);
   if(lit)
-  {  // the light pass rewrites the frame's pixels from the fp32 radiance k_trace left
-    HIPCHK(hipEventRecord(ts.ev[3], st));
+  {  // launch: the light pass rewrites the frame's pixels from the fp32 radiance k_trace left
+    if((rc = endTraversal(ts, st))) return rc;
     HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
-    HIPCHK(hipEventRecord(ts.ev[4], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
     launchTraceLight(st, traceLightArgs(s, L, lt, s->surf.id.p, s->surf.normal.p), F);
-    HIPCHK(hipEventRecord(ts.ev[5], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
   }
   if(F.temporalSampling)
     launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.fmt);
   if(!lit)
-  {
-    HIPCHK(hipEventRecord(ts.ev[3], st));
-  }
+    if((rc = endTraversal(ts, st))) return rc;
   HIPCHK(hipGetLastError());
-  // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare)
-  LastFrame& last = s->last;
-  last.params                 = *p;
-  last.params.strip_row_begin = F.stripRow0;
-  last.params.strip_row_end   = F.stripRow1;
-  last.have         = true;
-  last.timed        = false;
-  last.wasSortOnly  = false;
-  last.listsPartial = true;  // no bin lists belong to this frame (mgs_frame_row_costs: MGS_ERR_STATE)
+  // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare); no bin lists belong to it
+  // (mgs_frame_row_costs: MGS_ERR_STATE)
+  recordLastFrameHead(s->last, *p, F, false, true);
   ts.w    = F.width;
   ts.h    = F.height;
   ts.have = true;
   ts.haveLit = lit;  // the shadow hits are those of the last traced frame only when that frame was lit
-  if(lit && lout)
+  if(lit && lout)  // read-back
     if((rc = readLightOut(s, lout))) return rc;
   if(out)
   {
     std::memset(out, 0, sizeof(*out));
-    TraceCounters hc{};
-    HIPCHK(hipMemcpyAsync(&hc, ts.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
+    TraceOutRead R;
+    if((rc = R.begin(s))) return rc;
     HIPCHK(hipStreamSynchronize(st));
-    out->leaves          = empty ? 0 : d.bvh.leaves;
-    out->nodes           = empty ? 0 : d.bvh.totalNodes;
-    out->node_visits     = hc.nodeVisits;
-    out->candidate_tests = hc.candidateTests;
-    out->accepted_hits   = hc.acceptedHits;
-    out->max_passes_used = hc.maxPassesUsed;
-    out->bvh_rebuilt     = rebuilt;
-    out->build_ms        = buildMs;
-    HIPCHK(hipEventElapsedTime(&out->trace_ms, ts.ev[2], ts.ev[3]));
+    if((rc = R.finish(s, rebuilt, buildMs, out))) return rc;
   }
   return MGS_OK;
 }
@@ -503,7 +523,7 @@ struct HybridTail : FrameTail
   float                      buildMs = 0.0f;
   uint32_t                   rebuilt = 0;
 
-  TraceProxy proxy() const { return TraceProxy{p->kernel_min_response, t.kernel_adaptive_clamping, p->kernel_degree, p->alpha_cull_threshold}; }
+  TraceProxy proxy() const { return traceProxy(*p, t); }
   int        afterUpload(const FrameArgs& A) override
   {
     TracePassState& ts = s->trace;
@@ -520,7 +540,7 @@ struct HybridTail : FrameTail
     const FrameConst& F  = A.f;
     hipStream_t       st = s->stream;
     HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
-    HIPCHK(hipEventRecord(ts.ev[4], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
     HybridSurfaceArgs H{};
     H.frame       = s->fb.dArgs.p;
     H.image       = s->fb.image.p;
@@ -532,7 +552,7 @@ struct HybridTail : FrameTail
     H.outRadiance = ts.radiance.p;
     launchHybridSurface(st, H, F, fmt);
     launchTraceLight(st, traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p), F);
-    HIPCHK(hipEventRecord(ts.ev[5], st));
+    HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
     if(F.temporalSampling)  // the lit sample is what the running mean folds in
       launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, fmt);
     HIPCHK(hipGetLastError());
@@ -547,14 +567,8 @@ static int mgs_render_hybrid_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(!p)
     return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_hybrid: null params");
   HybridTail tail;
-  if(tp)
-    tail.t = *tp;
-  else
-    mgs_trace_params_default(&tail.t);
-  if(lp)
-    tail.lt = *lp;
-  else
-    mgs_trace_light_params_default(&tail.lt);
+  tail.t  = traceParamsOr(tp);
+  tail.lt = traceLightParamsOr(lp);
   if(int rc = validateTrace(p, tail.t, &tail.lt, true))  // (before the handle is looked at)
     return rc;
   if(!s)
@@ -585,32 +599,35 @@ int mgs_render_hybrid(MgsScene s, const MgsFrameParams* p, const MgsTraceParams*
   return guarded("mgs_render_hybrid", [&] { return mgs_render_hybrid_impl(s, p, tp, lp, out, lout); });
 }
 
-int mgs_trace_download_shadow_hits(MgsScene s, uint32_t* dst, size_t count)
+// one per-pixel plane of the handle's last traced frame to the host; waits.  have: the last frame wrote the plane (noFrame is the
+// message when it did not); tooSmall: the message for a destination, or a plane, smaller than that frame
+static int downloadTracePlane(MgsScene s, uint32_t* dst, size_t count, DevBuf<uint32_t> TracePassState::*plane, bool TracePassState::*have,
+                              const char* what, const char* noFrame, const char* tooSmall)
 {
   if(!s || !dst)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_shadow_hits: null argument");
-  if(!s->trace.haveLit)
-    return failTrace(MGS_ERR_STATE, "mgs_trace_download_shadow_hits: the handle's last traced frame was not a lit one");
-  const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
-  if(count < n || s->trace.shadowHits.n < n)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_shadow_hits: destination too small, or the last traced frame was not lit at this size");
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null argument");
+  const TracePassState& ts = s->trace;
+  if(!(ts.*have))
+    return failTrace(MGS_ERR_STATE, noFrame);
+  const size_t n = (size_t)ts.w * (size_t)ts.h;
+  if(count < n || (ts.*plane).n < n)
+    return failTrace(MGS_ERR_INVALID_ARG, tooSmall);
   HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipMemcpyAsync(dst, s->trace.shadowHits.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipMemcpyAsync(dst, (ts.*plane).p, n * 4, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   return MGS_OK;
 }
 
+int mgs_trace_download_shadow_hits(MgsScene s, uint32_t* dst, size_t count)
+{
+  return downloadTracePlane(s, dst, count, &TracePassState::shadowHits, &TracePassState::haveLit, "mgs_trace_download_shadow_hits",
+                            "mgs_trace_download_shadow_hits: the handle's last traced frame was not a lit one",
+                            "mgs_trace_download_shadow_hits: destination too small, or the last traced frame was not lit at this size");
+}
+
+// (a frame that has hit counts sized their plane: only the destination can be too small)
 int mgs_trace_download_hit_counts(MgsScene s, uint32_t* dst, size_t count)
 {
-  if(!s || !dst)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_hit_counts: null argument");
-  if(!s->trace.have)
-    return failTrace(MGS_ERR_STATE, "mgs_trace_download_hit_counts: no traced frame yet");
-  const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
-  if(count < n)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_hit_counts: destination too small");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipMemcpyAsync(dst, s->trace.hitCount.p, n * 4, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return MGS_OK;
+  return downloadTracePlane(s, dst, count, &TracePassState::hitCount, &TracePassState::have, "mgs_trace_download_hit_counts",
+                            "mgs_trace_download_hit_counts: no traced frame yet", "mgs_trace_download_hit_counts: destination too small");
 }

@@ -15,6 +15,7 @@
 #include "shade_direct.h"
 #include "target_pixel.h"
 #include "trace_common.h"
+#include "trace_dispatch.h"
 #include "trace_traverse.h"
 
 namespace mgs {
@@ -24,9 +25,8 @@ template <int FMT>
 __global__ __launch_bounds__(256) void k_hybrid_surface(const HybridSurfaceArgs a)
 {
   const FrameConst& F = a.frame->f;
-  const int tid = threadIdx.x, lane = laneId(), w = tid >> 6;
-  const int tx = (int)blockIdx.x % F.tilesX, ty = F.stripRow0 + (int)blockIdx.x / F.tilesX;
-  const int px = tx * kTilePx + (w & 1) * 8 + (lane & 7), py = ty * kTilePx + (w >> 1) * 8 + (lane >> 3);
+  int px, py;
+  tilePixel(F, (int)threadIdx.x, px, py);
   if(px >= F.width || py >= F.height)
     return;
   const size_t pix = (size_t)py * F.width + px;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_hybrid_surface(const HybridSurfaceArgs 
 
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt)
 {
-  const int tiles = F.tilesX * (F.stripRow1 - F.stripRow0);
+  const int tiles = stripTiles(F);
   if(tiles <= 0)
     return;
   if(fmt == kTargetF16)

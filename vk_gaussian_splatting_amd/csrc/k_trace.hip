@@ -11,15 +11,13 @@
 // samples_per_pass); the ray, the particle evaluation and the collection of the K nearest hits are trace_traverse.h, shared with the
 // shadow rays of k_trace_light.hip.  Every loop is bounded: passes by max_passes, the walk by samples_per_pass, the traversal by
 // 2 * nodes + 2 steps, children by 8.  Nothing waits on another lane, wave or workgroup.
-#include <cstdio>
-#include <cstdlib>
-
 #include "gut_common.h"
 #include "kernels_common.h"
 #include "launchers.h"
 #include "sh_eval.h"
 #include "target_pixel.h"
 #include "trace_common.h"
+#include "trace_dispatch.h"
 #include "trace_shade.h"
 #include "trace_traverse.h"
 
@@ -32,10 +30,10 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
   __shared__ TraceLds S;
   const FrameArgs*  Ap = a.frame;
   const FrameConst& F  = Ap->f;
-  const int tid = threadIdx.x, lane = laneId(), w = tid >> 6;
+  const int tid = threadIdx.x;
   traceLdsInit(S, a, tid);
-  const int tx = (int)blockIdx.x % F.tilesX, ty = F.stripRow0 + (int)blockIdx.x / F.tilesX;
-  const int px = tx * kTilePx + (w & 1) * 8 + (lane & 7), py = ty * kTilePx + (w >> 1) * 8 + (lane >> 3);
+  int px, py;
+  tilePixel(F, tid, px, py);
   if(px >= F.width || py >= F.height)
     return;  // (no barrier below)
   const size_t pix = (size_t)py * F.width + px;
@@ -157,28 +155,14 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
   atomicMax(&a.ctr->maxPassesUsed, passesUsed);
 }
 
-[[noreturn]] static void unlistedTrace(int v)
-{
-  std::fprintf(stderr, "launchTrace: no traversal instantiation for variant %d\n", v);
-  std::abort();
-}
-
 void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat)
 {
-  const int tiles = F.tilesX * (F.stripRow1 - F.stripRow0);
+  const int tiles = stripTiles(F);
   if(tiles <= 0)
     return;
-  const int shf = shFormat == 0 ? 0 : shFormat == 1 ? 1 : 2;
-  const int kb  = a.samplesPerPass <= 4 ? 0 : a.samplesPerPass <= 18 ? 1 : 2;
-#define MGS_TRACE(SHF, KBI, KB) case(SHF) * 3 + (KBI): hipLaunchKernelGGL((k_trace<SHF, KB>), dim3(tiles), dim3(256), 0, stream, a); break;
-  switch(shf * 3 + kb)
-  {
-    MGS_TRACE(0, 0, 4) MGS_TRACE(0, 1, 18) MGS_TRACE(0, 2, 32)
-    MGS_TRACE(1, 0, 4) MGS_TRACE(1, 1, 18) MGS_TRACE(1, 2, 32)
-    MGS_TRACE(2, 0, 4) MGS_TRACE(2, 1, 18) MGS_TRACE(2, 2, 32)
-    default: unlistedTrace(shf * 3 + kb);
-  }
-#undef MGS_TRACE
+  withShFormatAndKBuffer("launchTrace", shFormat, a.samplesPerPass, [&](auto shf, auto kb) {
+    hipLaunchKernelGGL((k_trace<decltype(shf)::value, decltype(kb)::value>), dim3(tiles), dim3(256), 0, stream, a);
+  });
 }
 
 }  // namespace mgs

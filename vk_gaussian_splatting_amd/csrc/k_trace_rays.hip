@@ -10,14 +10,12 @@
 // caller's order.  The K-buffer, the collection and the particle evaluation are trace_traverse.h, as for k_trace.hip.  Every loop is
 // bounded as there: passes by max_passes, the walk by samples_per_pass, the traversal by 2 * nodes + 2 steps, children by 8.  Nothing
 // waits on another lane, wave or workgroup, and no lane returns: a tail workgroup's spare lanes and the invalid rays skip the work.
-#include <cstdio>
-#include <cstdlib>
-
 #include "gut_common.h"
 #include "kernels_common.h"
 #include "launchers.h"
 #include "sh_eval.h"
 #include "trace_common.h"
+#include "trace_dispatch.h"
 #include "trace_shade.h"
 #include "trace_traverse.h"
 
@@ -183,7 +181,10 @@ __global__ __launch_bounds__(256) void k_trace_rays(TraceRaysArgs q)
   // (the pick stays inside `if(surf)` as in k_trace.hip: taken out of it, the compiler contracts this walk's arithmetic differently
   // and the results stop being the traced frame's bit for bit; a caller who wants t_iso and id sets surface_outputs)
   // the pass loop of k_trace.hip with the ray's own window, written out again: k_trace's instantiations are held to their registers
-  // (k_trace.hip:83-84 has the same note for shadeHit), so the walk is not moved into a shared header.  A fix to one is a fix to both.
+  // (k_trace.hip's walk has the same note for shadeHit), so the walk is not moved into a shared header.  Tried as a whole too: one
+  // force-inlined template over <SHF, KB> with this statement order and the accumulators in a struct taken by reference gave all
+  // eighteen instantiations of the two kernels other code (0 to 8 VGPRs fewer, 30 to 60 instructions shorter: other roundings are
+  // possible, and test_gpu_rays.py's bit-for-bit comparison is what holds the two walks together).  A fix to one is a fix to both.
   if(rayOk && a.nLevels > 0)
     for(int pass = 0; pass < a.maxPasses; ++pass)  // bound: max_passes
     {
@@ -268,12 +269,6 @@ __global__ __launch_bounds__(256) void k_trace_rays(TraceRaysArgs q)
   }
 }
 
-[[noreturn]] static void unlistedTraceRays(int v)
-{
-  std::fprintf(stderr, "launchTraceRays: no traversal instantiation for variant %d\n", v);
-  std::abort();
-}
-
 void launchRaysGenerate(hipStream_t stream, const FrameArgs* dArgs, float4* rays, uint32_t pixels)
 {
   if(pixels)
@@ -291,17 +286,9 @@ void launchTraceRays(hipStream_t stream, const TraceRaysArgs& a, int shFormat)
   if(a.count == 0)
     return;
   const uint32_t groups = (a.count + 255u) / 256u;
-  const int      shf = shFormat == 0 ? 0 : shFormat == 1 ? 1 : 2;
-  const int      kb  = a.t.samplesPerPass <= 4 ? 0 : a.t.samplesPerPass <= 18 ? 1 : 2;
-#define MGS_TRACE_RAYS(SHF, KBI, KB) case(SHF) * 3 + (KBI): hipLaunchKernelGGL((k_trace_rays<SHF, KB>), dim3(groups), dim3(256), 0, stream, a); break;
-  switch(shf * 3 + kb)
-  {
-    MGS_TRACE_RAYS(0, 0, 4) MGS_TRACE_RAYS(0, 1, 18) MGS_TRACE_RAYS(0, 2, 32)
-    MGS_TRACE_RAYS(1, 0, 4) MGS_TRACE_RAYS(1, 1, 18) MGS_TRACE_RAYS(1, 2, 32)
-    MGS_TRACE_RAYS(2, 0, 4) MGS_TRACE_RAYS(2, 1, 18) MGS_TRACE_RAYS(2, 2, 32)
-    default: unlistedTraceRays(shf * 3 + kb);
-  }
-#undef MGS_TRACE_RAYS
+  withShFormatAndKBuffer("launchTraceRays", shFormat, a.t.samplesPerPass, [&](auto shf, auto kb) {
+    hipLaunchKernelGGL((k_trace_rays<decltype(shf)::value, decltype(kb)::value>), dim3(groups), dim3(256), 0, stream, a);
+  });
 }
 
 }  // namespace mgs

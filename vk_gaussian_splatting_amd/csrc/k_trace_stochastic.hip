@@ -20,6 +20,7 @@
 #include "sh_eval.h"
 #include "target_pixel.h"
 #include "trace_common.h"
+#include "trace_dispatch.h"
 #include "trace_shade.h"
 #include "trace_traverse.h"
 
@@ -54,10 +55,10 @@ __global__ __launch_bounds__(256) void k_trace_pass_stochastic(TraceArgs a)
   __shared__ TraceLds S;
   const FrameArgs*  Ap = a.frame;
   const FrameConst& F  = Ap->f;
-  const int tid = threadIdx.x, lane = laneId(), w = tid >> 6;
+  const int tid = threadIdx.x;
   traceLdsInit(S, a, tid);
-  const int tx = (int)blockIdx.x % F.tilesX, ty = F.stripRow0 + (int)blockIdx.x / F.tilesX;
-  const int px = tx * kTilePx + (w & 1) * 8 + (lane & 7), py = ty * kTilePx + (w >> 1) * 8 + (lane >> 3);
+  int px, py;
+  tilePixel(F, tid, px, py);
   if(px >= F.width || py >= F.height)
     return;  // (no barrier below)
   const size_t pix = (size_t)py * F.width + px;
@@ -168,10 +169,10 @@ __global__ __launch_bounds__(256) void k_trace_anyhit_stochastic(TraceArgs a)
   __shared__ TraceLds S;
   const FrameArgs*  Ap = a.frame;
   const FrameConst& F  = Ap->f;
-  const int tid = threadIdx.x, lane = laneId(), w = tid >> 6;
+  const int tid = threadIdx.x;
   traceLdsInit(S, a, tid);
-  const int tx = (int)blockIdx.x % F.tilesX, ty = F.stripRow0 + (int)blockIdx.x / F.tilesX;
-  const int px = tx * kTilePx + (w & 1) * 8 + (lane & 7), py = ty * kTilePx + (w >> 1) * 8 + (lane >> 3);
+  int px, py;
+  tilePixel(F, tid, px, py);
   if(px >= F.width || py >= F.height)
     return;  // (no barrier below)
   const size_t pix = (size_t)py * F.width + px;
@@ -228,41 +229,24 @@ __global__ __launch_bounds__(256) void k_trace_anyhit_stochastic(TraceArgs a)
                        kept ? 1.0f : 0.0f, nodeVisits, candTests, traced ? 1u : 0u);
 }
 
-[[noreturn]] static void unlistedStochastic(int strategy, int v)
-{
-  std::fprintf(stderr, "launchTraceStochastic: no instantiation for strategy %d, variant %d\n", strategy, v);
-  std::abort();
-}
-
 void launchTraceStochastic(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat, int strategy)
 {
-  const int tiles = F.tilesX * (F.stripRow1 - F.stripRow0);
+  const int tiles = stripTiles(F);
   if(tiles <= 0)
     return;
-  const int shf = shFormat == 0 ? 0 : shFormat == 1 ? 1 : 2;
   if(strategy == 2)
+    withShFormat(shFormat, [&](auto shf) {
+      hipLaunchKernelGGL((k_trace_anyhit_stochastic<decltype(shf)::value>), dim3(tiles), dim3(256), 0, stream, a);
+    });
+  else if(strategy == 1)
+    withShFormatAndKBuffer("launchTraceStochastic", shFormat, a.samplesPerPass, [&](auto shf, auto kb) {
+      hipLaunchKernelGGL((k_trace_pass_stochastic<decltype(shf)::value, decltype(kb)::value>), dim3(tiles), dim3(256), 0, stream, a);
+    });
+  else
   {
-    switch(shf)
-    {
-      case 0: hipLaunchKernelGGL((k_trace_anyhit_stochastic<0>), dim3(tiles), dim3(256), 0, stream, a); break;
-      case 1: hipLaunchKernelGGL((k_trace_anyhit_stochastic<1>), dim3(tiles), dim3(256), 0, stream, a); break;
-      default: hipLaunchKernelGGL((k_trace_anyhit_stochastic<2>), dim3(tiles), dim3(256), 0, stream, a); break;
-    }
-    return;
+    std::fprintf(stderr, "launchTraceStochastic: no instantiation for strategy %d\n", strategy);
+    std::abort();
   }
-  if(strategy != 1)
-    unlistedStochastic(strategy, shf);
-  const int kb = a.samplesPerPass <= 4 ? 0 : a.samplesPerPass <= 18 ? 1 : 2;
-#define MGS_TRACE(SHF, KBI, KB) \
-  case(SHF) * 3 + (KBI): hipLaunchKernelGGL((k_trace_pass_stochastic<SHF, KB>), dim3(tiles), dim3(256), 0, stream, a); break;
-  switch(shf * 3 + kb)
-  {
-    MGS_TRACE(0, 0, 4) MGS_TRACE(0, 1, 18) MGS_TRACE(0, 2, 32)
-    MGS_TRACE(1, 0, 4) MGS_TRACE(1, 1, 18) MGS_TRACE(1, 2, 32)
-    MGS_TRACE(2, 0, 4) MGS_TRACE(2, 1, 18) MGS_TRACE(2, 2, 32)
-    default: unlistedStochastic(strategy, shf * 3 + kb);
-  }
-#undef MGS_TRACE
 }
 
 }  // namespace mgs

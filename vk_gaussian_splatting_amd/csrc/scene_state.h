@@ -471,6 +471,10 @@ struct MeshPassState
 
 // the traced pipeline's per-handle state (mgs_render_traced): hit counts and counters of the last traced frame, the scratch of a
 // hierarchy build this handle ran (freed when the build is done), the events around build and frame
+enum TraceEvent  // TracePassState::ev: the brackets of build_ms, trace_ms, light_ms and reorder_ms
+{
+  kEvBuildBegin, kEvBuildEnd, kEvTraverseBegin, kEvTraverseEnd, kEvLightBegin, kEvLightEnd, kEvReorderBegin, kEvReorderEnd, kEvCount
+};
 struct TracePassState
 {
   DevBuf<uint32_t>      hitCount;
@@ -489,7 +493,7 @@ struct TracePassState
   DevBuf<uint32_t>           rayInvalid, rayKeys, rayIdx;
   int                   w = 0, h = 0;
   bool                  have = false, haveLit = false;
-  hipEvent_t            ev[8] = {};  // build begin / end, traversal begin / end, light pass begin / end, ray reorder begin / end
+  hipEvent_t            ev[kEvCount] = {};  // indexed by TraceEvent
   template <class F>
   void eachBuffer(F&& f)
   {
@@ -672,14 +676,45 @@ struct FrameTail
   virtual ~FrameTail() = default;
 };
 int  renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail* tail);  // api_frame.hip: mgs_render's frame
-// api_trace.hip, shared with the ray queries of api_rays.hip: the range checks that need no device, the Morton frame of the
-// hierarchy, its lazy build, the handle's events and what every traversal kernel receives
+// api_frame.hip: what every frame leaves in the handle's LastFrame (the caller's parameters with the strip rows it rendered); a
+// raster frame adds its bins and its sort, a traced frame has none
+void recordLastFrameHead(LastFrame& last, const MgsFrameParams& p, const FrameConst& F, bool timed, bool listsPartial);
+// api_trace.hip, shared with the ray queries of api_rays.hip: the range checks that need no device, the frame's constants, the
+// Morton frame of the hierarchy, its lazy build, the handle's events, what every traversal kernel receives and what it reports
 int  failTrace(int code, const std::string& msg);
 int  validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTraceLightParams* lit = nullptr, bool hybrid = false);
+// the caller's optional parameter block: *p, or what the block's mgs_*_params_default fills in for NULL
+template <class P>
+P paramsOr(const P* p, void (*defaults)(P*))
+{
+  P v;
+  if(p)
+    v = *p;
+  else
+    defaults(&v);
+  return v;
+}
+inline MgsTraceParams      traceParamsOr(const MgsTraceParams* tp) { return paramsOr(tp, mgs_trace_params_default); }
+inline MgsTraceLightParams traceLightParamsOr(const MgsTraceLightParams* lp) { return paramsOr(lp, mgs_trace_light_params_default); }
+inline MgsRayQueryParams   rayQueryParamsOr(const MgsRayQueryParams* qp) { return paramsOr(qp, mgs_ray_query_params_default); }
+int  traceFrameArgs(MgsScene s, MgsFrameParams& q, const char* what, bool rayInverses, std::unique_ptr<FrameArgs>& A);
 void sceneBox(const SceneData& d, float lo[3], float invExt[3]);
 int  ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt);
 int  ensureTraceEvents(TracePassState& ts);
 TraceArgs traceArgs(MgsScene s, const TraceProxy& proxy, const MgsTraceParams& t, int fmt);
+// the hierarchy's proxy of a frame: every traced entry point builds it here, so that alternating between them never rebuilds
+inline TraceProxy traceProxy(const MgsFrameParams& p, const MgsTraceParams& t)
+{
+  return TraceProxy{p.kernel_min_response, t.kernel_adaptive_clamping, p.kernel_degree, p.alpha_cull_threshold};
+}
+// MgsTraceOut of the walk between the traversal events: begin() enqueues the counters' copy on the handle's stream, the caller
+// waits for the stream once (behind whatever else it reads back), finish() fills *out
+struct TraceOutRead
+{
+  TraceCounters hc{};
+  int begin(MgsScene s);
+  int finish(MgsScene s, uint32_t rebuilt, float buildMs, MgsTraceOut* out) const;
+};
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip
 int  cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking);         // api_sort.hip

@@ -41,6 +41,15 @@ __device__ __forceinline__ void traceLdsInit(TraceLds& S, const TraceArgs& a, in
   __syncthreads();
 }
 
+// the lane's pixel in the traced pipeline's tiling: a workgroup = a 16 x 16 tile of the frame's strip, a wave64 = an 8 x 8 quarter of it
+__device__ __forceinline__ void tilePixel(const FrameConst& F, int tid, int& px, int& py)
+{
+  const int lane = laneId(), w = tid >> 6;
+  const int tx = (int)blockIdx.x % F.tilesX, ty = F.stripRow0 + (int)blockIdx.x / F.tilesX;
+  px = tx * kTilePx + (w & 1) * 8 + (lane & 7);
+  py = ty * kTilePx + (w >> 1) * 8 + (lane >> 3);
+}
+
 // the pixel's primary ray (rgen.slang:165-196); false: a fisheye pixel outside the image circle
 __device__ __forceinline__ bool primaryRay(const FrameConst& F, int px, int py, TraceRay& ray)
 {
