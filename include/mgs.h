@@ -49,7 +49,9 @@ extern "C" {
                             trace strategies (MGS_HAS_TRACE_STRATEGIES below): no entry point, both numbers stay — MgsTraceParams::reserved[0] is
                                  named trace_strategy (0 = what it was), MGS_TRACE_STRATEGY_*;
                             ray queries (MGS_HAS_RAY_QUERY below): entry points only, both numbers stay — mgs_ray_query_params_default,
-                                 mgs_trace_rays, mgs_trace_rays_device, mgs_trace_generate_rays */
+                                 mgs_trace_rays, mgs_trace_rays_device, mgs_trace_generate_rays;
+                            sensor models (MGS_HAS_SENSOR_MODEL below): entry points and one new struct, both numbers stay —
+                                 mgs_sensor_model_from_frame, mgs_frame_set_sensor */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
@@ -59,6 +61,8 @@ extern "C" {
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_SENSOR_MODEL 1  /* feature macro: MgsSensorModel, mgs_sensor_model_from_frame and mgs_frame_set_sensor exist (added within ABI 5.1, no
+                                  existing struct or default changed) */
 
 typedef enum MgsStatus {
   MGS_OK              = 0,
@@ -761,10 +765,80 @@ int mgs_render_hybrid(MgsScene scene_or_context, const MgsFrameParams* params, c
                       const MgsTraceLightParams* light /* NULL = defaults */, MgsFrameOut* out /* may be NULL */,
                       MgsTraceLightOut* light_out /* may be NULL */);
 
+/* ---- sensor models (MGS_HAS_SENSOR_MODEL): the 3DGUT raster pipeline through a calibrated camera.  The unscented transform pushes a
+ * particle's sigma points through a non-linear camera; the reference carries the OpenCV pinhole model (radial, tangential and
+ * thin-prism distortion) and the OpenCV fisheye polynomial in full (CameraModelParameters, shaders/threedgut_camera_models.h.slang:25-61;
+ * projectPointPinhole, projectPointFisheye, shaders/threedgut_camera_projections.h.slang:85-186) but its application only ever fills in
+ * the perfect models (initPerfectPinholeCamera / initPerfectFisheyeCamera, threedgut_camera_models.h.slang:66-138).  A bound
+ * MgsSensorModel fills in the rest.
+ *
+ * Projection of a sigma point: projectPointWithShutter with the global shutter (threedgut_camera_projections.h.slang:189-205) and
+ *   pinhole (:85-136): uv = xy / z; icD = (1 + r2 (k1 + r2 (k2 + r2 k3))) / (1 + r2 (k4 + r2 (k5 + r2 k6))); delta from tangential[2] and
+ *     thin_prism[4] (:109-112); p = (icD uv + delta) * focal_length + principal_point where icD lies in (0.8, 1.2) (:118-124), else the
+ *     point is invalid and clipped to length(resolution) / sqrt(r2) * uv + principal_point (:125-133); z <= 0: invalid, (0, 0) (:88-92);
+ *   fisheye (:149-171): theta = min(atan2(|xy|, z), max_angle) (:152-160), p = focal_length * xy * theta (1 + poly(theta^2) theta^2) / |xy|
+ *     + principal_point with evalPolyHorner4 (:51-59, :163-165); theta >= max_angle: invalid;
+ *   both: valid only withinResolution with the 0.1 margin (:78-83, GUT_IN_IMAGE_MARGIN_FACTOR).
+ * Everything downstream of the seven projected points is the frame's as before: centroid, covariance, extents, the quad's depth from
+ * `proj`, bin rectangle, canonical frame.  max_angle = 0 asks for computeMaxAngle of the viewport, the principal point and the focal
+ * length (threedgut_camera_models.h.slang:87-119).  shutter: 0 = global; any rolling type is MGS_ERR_UNSUPPORTED (the reference marks
+ * that code untested, threedgut_camera_projections.h.slang:207-210).  applyRenderingResolution (:138-147) is not applied, as in the
+ * reference (:167-168).
+ *
+ * Ray of pixel (x, y).  PARITY UNPINNED: the reference has no inverse of these models (its fragment shader generates the perfect
+ * pinhole / equidistant ray, threedgut_raster.frag.slang:101-111), so the inverse is defined by this library.  The ray is the
+ * camera-space direction whose projection is the image point (x + 0.5, y + 0.5) — the pixel centre the front end's quad placement
+ * assumes —, rotated to world space by viewInverse and normalised.  This convention is self-consistent: projecting a pixel's ray
+ * lands on the pixel's centre.  (Without a sensor the pinhole ray keeps the reference's second 0.5, and the fisheye ray its
+ * resolution - 1.)  Pinhole: Newton on the 2x2 Jacobian of the forward map uv -> icD uv + delta from (p - c) / f; fisheye: Newton on
+ * theta (1 + poly(theta^2) theta^2) = |(p - c) / f| from that radius.  Both run 8 iterations in fp32.  A pixel has NO ray where the
+ * iteration ends outside the model's validity (icD outside (0.8, 1.2); theta >= max_angle), where it misses the image point by more
+ * than 0.01 pixel (no convergence), or where the forward map is not monotone at the result (Jacobian determinant / derivative <= 0).
+ * Such a pixel is what a fisheye pixel outside the field of view is without a sensor: no fragment, transparent black (opaque black
+ * under MGS_SORT_STOCHASTIC), no side output.
+ *
+ * mgs_sensor_model_from_frame fills *out with the perfect model the frame *p uses without a sensor: `model` from camera_model, the
+ * focal length of the 3DGUT front end ((proj[0] width / 2, proj[5] height / 2); fisheye: (width, -height) / fov_rad,
+ * src/gaussian_splatting.cpp:1239-1251 — focal_length[1] follows the sign of proj[5]), the principal point at the viewport's centre,
+ * zero coefficients and max_angle = computeMaxAngle.  Callers start from it and perturb.
+ *
+ * mgs_frame_set_sensor binds a copy of *sensor to the handle (a scene or a frame context; each has its own, as the occluder), NULL
+ * unbinds.  Ranges are checked before the handle is looked at: model and shutter in range, every value finite, focal_length non-zero,
+ * max_angle >= 0, reserved words 0 (MGS_ERR_INVALID_ARG); a rolling shutter: MGS_ERR_UNSUPPORTED.  While a sensor is bound it
+ * replaces camera_model and fov_rad for the projection and the rays of
+ *   mgs_render / mgs_render_gathered with MGS_PIPELINE_3DGUT — both extent methods, every kernel degree, depth of field, surface_outputs,
+ *     occluder, MGS_SORT_STOCHASTIC, strips, frame contexts, temporal accumulation, every target format, graph replay on and off;
+ *   mgs_frame_download_projected_gut (the records of such a frame);
+ *   mgs_trace_generate_rays, which then writes the sensor's rays (origin viewInverse's translation, or the lens sample under depth of
+ *     field; a pixel without a ray gets the invalid window t_min = 1, t_max = 0): trace them with mgs_trace_rays_device.
+ * The depth key, the frustum cull and the sort keep using view / proj: a caller whose sensor sees beyond proj's dilated frustum sets
+ * frustum_culling to MGS_CULL_NONE.  The workgroup-level pre-cull of the front end is off for such a frame.
+ * MGS_ERR_UNSUPPORTED while a sensor is bound (unbind it with mgs_frame_set_sensor(handle, NULL)): mgs_render with MGS_PIPELINE_3DGS
+ * (EWA splatting has no model of distortion), lighting_mode != 0 (the deferred pass unprojects through projInverse), mgs_meshes_render,
+ * mgs_render_traced, mgs_render_traced_lit and mgs_render_hybrid.  mgs_trace_rays / mgs_trace_rays_device take the caller's rays and
+ * do not look at the binding.  With no sensor bound every entry point behaves exactly as before. */
+#define MGS_SENSOR_OPENCV_PINHOLE 0
+#define MGS_SENSOR_OPENCV_FISHEYE 1
+typedef struct MgsSensorModel {
+  int32_t  model;              /* MGS_SENSOR_* */
+  int32_t  shutter;            /* 0 = global; anything else: MGS_ERR_UNSUPPORTED */
+  float    focal_length[2];    /* pixels, in the sign convention of the frame's own focal length (y follows proj[5]) */
+  float    principal_point[2]; /* pixels */
+  float    radial[6];          /* pinhole: k1..k6 (numerator 0..2, denominator 3..5) */
+  float    tangential[2];      /* pinhole */
+  float    thin_prism[4];      /* pinhole */
+  float    fisheye_radial[4];  /* fisheye: forward polynomial in theta^2 */
+  float    max_angle;          /* fisheye; 0 = computeMaxAngle of the viewport, principal point and focal length */
+  uint32_t reserved[9];        /* must be 0 */
+} MgsSensorModel; /* 128 B */
+int mgs_sensor_model_from_frame(const MgsFrameParams* params, MgsSensorModel* out);
+int mgs_frame_set_sensor(MgsScene scene_or_context, const MgsSensorModel* sensor /* NULL unbinds */);
+
 /* ---- ray queries (MGS_HAS_RAY_QUERY): the caller's rays through the scene's particle hierarchy, with the walk of mgs_render_traced's
  * MGS_TRACE_STRATEGY_FULL_ANYHIT (traceRayParticlesInsertionSort, shaders/threedgrt_raytrace.rgen.slang:615-819; insertion
  * rahit.slang:152-167; hit parameter rint.slang:159-172; particleProcessHit and particleIntegrate, threedgrt.h.slang:166-235).  For
- * sensors the library has no model of (rolling shutter, distortion: every ray its own origin), lidar and depth probes, picking, and
+ * sensors the library has no model of (rolling shutter: every ray its own origin; the OpenCV pinhole and fisheye models with
+ * distortion are mgs_frame_set_sensor's, whose rays mgs_trace_generate_rays writes), lidar and depth probes, picking, and
  * the reflection, refraction and shadow rays an integrator shoots from its OWN geometry into the splats: the library knows no
  * geometry but the particles, the caller ends a ray at its own surface with t_max and starts the secondary ray itself.
  *

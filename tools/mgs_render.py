@@ -66,6 +66,9 @@ def main():
     ap.add_argument("--material", type=float, nargs=13, default=None)
     ap.add_argument("--pipeline", choices=["raster", "trace", "hybrid"], default="raster")  # hybrid: the raster surface lit with traced shadow rays
     ap.add_argument("--raster-pipeline", choices=["3dgs", "3dgut"], default="3dgs")  # of --pipeline raster and hybrid
+    # --sensor FILE.json with --pipeline raster --raster-pipeline 3dgut: a flat JSON of MgsSensorModel's fields (model, focal_length,
+    # principal_point, radial, tangential, thin_prism, fisheye_radial, max_angle); fields left out keep the frame's perfect camera
+    ap.add_argument("--sensor", default=None, metavar="FILE.json")
     ap.add_argument("--shadows", type=int, choices=[0, 1], default=0)  # --pipeline trace --lighting 1: hard shadow rays through the splats
     ap.add_argument("--shadow-offset", type=float, default=0.2)
     ap.add_argument("--shadow-threshold", type=float, default=0.8)
@@ -98,6 +101,12 @@ def main():
     p.collect_timings = 1
     if a.pipeline != "trace":
         p.pipeline = capi.PIPELINE_3DGUT if a.raster_pipeline == "3dgut" else capi.PIPELINE_3DGS
+    if a.sensor:
+        if a.pipeline != "raster" or a.raster_pipeline != "3dgut" or a.lighting or a.mesh:
+            ap.error("--sensor needs --pipeline raster --raster-pipeline 3dgut without --lighting and --mesh (mgs_frame_set_sensor)")
+        import json
+        with open(a.sensor) as f:
+            scene.set_sensor(capi.sensor_model_from_frame(p).update(**json.load(f)))
     if a.pipeline == "hybrid" and (a.occluder_depth or a.mesh):
         ap.error("--pipeline hybrid lights and shadows splats alone (meshes in the traced scene are out of scope): no --occluder-depth or --mesh")
     if a.pipeline == "hybrid" and not a.lighting:

@@ -181,6 +181,46 @@ class RayQueryOut(C.Structure):
         return dict(self.trace.as_dict(), reorder_ms=self.reorder_ms, invalid_rays=self.invalid_rays)
 
 
+SENSOR_OPENCV_PINHOLE, SENSOR_OPENCV_FISHEYE = 0, 1
+
+
+class SensorModel(C.Structure):
+    """MgsSensorModel (128 bytes): the OpenCV pinhole / fisheye camera of the 3DGUT pipeline with its distortion coefficients"""
+    _fields_ = [("model", C.c_int32), ("shutter", C.c_int32), ("focal_length", C.c_float * 2), ("principal_point", C.c_float * 2),
+                ("radial", C.c_float * 6), ("tangential", C.c_float * 2), ("thin_prism", C.c_float * 4), ("fisheye_radial", C.c_float * 4),
+                ("max_angle", C.c_float), ("reserved", C.c_uint32 * 9)]
+
+    FIELDS = ("model", "shutter", "focal_length", "principal_point", "radial", "tangential", "thin_prism", "fisheye_radial", "max_angle")
+
+    def as_dict(self):
+        return {k: (getattr(self, k) if k in ("model", "shutter", "max_angle") else list(getattr(self, k))) for k in self.FIELDS}
+
+    def update(self, **fields):
+        """set fields by name (scalars, or sequences of the field's length); returns self"""
+        for k, v in fields.items():
+            if k not in self.FIELDS:
+                raise KeyError(k)
+            if k in ("model", "shutter"):
+                setattr(self, k, int(v))
+            elif k == "max_angle":
+                self.max_angle = float(v)
+            else:
+                arr = getattr(self, k)
+                v = [float(x) for x in v]
+                if len(v) != len(arr):
+                    raise ValueError(f"{k}: {len(arr)} values expected")
+                for i, x in enumerate(v):
+                    arr[i] = x
+        return self
+
+
+def sensor_model_from_frame(params):
+    """mgs_sensor_model_from_frame: the perfect model the frame uses without a sensor; start from it and perturb"""
+    m = SensorModel()
+    _check(load_library().mgs_sensor_model_from_frame(C.byref(params), C.byref(m)))
+    return m
+
+
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("direction", np.float32, 3), ("t_max", np.float32)])
 RAY_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("transmittance", np.float32), ("t_iso", np.float32), ("id", np.uint32),
                              ("hit_count", np.uint32), ("passes", np.uint32), ("normal", np.float32, 4)])
@@ -307,6 +347,8 @@ def load_library():
         "mgs_scene_set_list_capacity": (C.c_int, [vp, C.c_uint64]),
         "mgs_frame_set_occluder": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
         "mgs_frame_upload_occluder": (C.c_int, [vp, P(F), P(F), C.c_int, C.c_int]),
+        "mgs_sensor_model_from_frame": (C.c_int, [P(FrameParams), P(SensorModel)]),
+        "mgs_frame_set_sensor": (C.c_int, [vp, P(SensorModel)]),
         "mgs_scene_download_set": (C.c_int, [vp, C.c_int, C.c_int, P(F), C.c_size_t]),
         "mgs_scene_storage_order": (C.c_int, [vp, C.c_int, P(C.c_uint32), C.c_size_t]),
         "mgs_frame_params_default": (None, [P(FrameParams)]),
@@ -351,7 +393,7 @@ EXPORTED_SYMBOLS = [
     "mgs_splatset_destroy", "mgs_scene_create", "mgs_scene_destroy", "mgs_scene_set_stream", "mgs_instance_add",
     "mgs_instance_set_transform", "mgs_scene_commit", "mgs_scene_splat_count", "mgs_scene_storage_order", "mgs_scene_download_set",
     "mgs_frame_context_create", "mgs_frame_context_destroy", "mgs_scene_memory_usage", "mgs_scene_set_list_capacity",
-    "mgs_frame_set_occluder", "mgs_frame_upload_occluder",
+    "mgs_frame_set_occluder", "mgs_frame_upload_occluder", "mgs_sensor_model_from_frame", "mgs_frame_set_sensor",
     "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_instance_set_material",
     "mgs_compare_capture", "mgs_compare_capture_upload", "mgs_compare_release", "mgs_compare_params_default", "mgs_compare_metrics",
     "mgs_compare_view_default", "mgs_compare_composite", "mgs_compare_download_composite",
@@ -653,6 +695,11 @@ class Scene:
 
     def clear_occluder(self):
         _check(self._lib.mgs_frame_set_occluder(self._h, None, None, 0, 0))
+
+    def set_sensor(self, model):
+        """bind a SensorModel to this handle (mgs_frame_set_sensor; copied at the call), None unbinds.  While bound it replaces
+        camera_model / fov_rad for the projection and the rays of this handle's 3DGUT frames and of generate_rays."""
+        _check(self._lib.mgs_frame_set_sensor(self._h, None if model is None else C.byref(model)))
 
     def memory_usage(self):
         """(scene_bytes, working_bytes): the committed data shared by all contexts, and this handle's working set"""

@@ -257,6 +257,9 @@ static int validateFrameParams(const MgsFrameParams* p, const FrameConst& F, con
   if(p->lighting_mode != MGS_LIGHTING_DISABLED && p->sort_mode == MGS_SORT_STOCHASTIC)
     return fail(MGS_ERR_UNSUPPORTED, "frame: lighting of MGS_SORT_STOCHASTIC frames is not supported (the reference's stochastic pipeline is not front to back: "
                                      "it yields no surface to light)");
+  if(F.sensor.bound && p->lighting_mode != MGS_LIGHTING_DISABLED)
+    return fail(MGS_ERR_UNSUPPORTED, "frame: a sensor model is bound (the deferred lighting pass unprojects through projInverse); unbind it with "
+                                     "mgs_frame_set_sensor(handle, NULL)");
   if(occ.depth)
   {
     if(occ.w != F.width || occ.h != F.height)
@@ -315,6 +318,7 @@ ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuS
   L.dArgs           = fb.dArgs.p;
   L.totalPartitions = A.f.totalPartitions;
   L.full            = full;
+  L.sensor          = A.f.sensor.bound != 0;
   L.ctr             = fb.ctr.p;
   L.slotPairs       = fb.pairB.p;
   L.slotCount       = fb.slotCount.p;
@@ -514,7 +518,8 @@ static GraphCache::Key graphKey(const FramePass& fp)
                               ((F.pipeline == 1 && F.normalMethod == 1) ? 16 : 0) |
                               (F.lightingMode << 5) |  // 0..2: the lighting pass is a launch of its own; what it gets by value is in this key or moves with the buffers
                               (fp.hybrid ? 128 : 0) |  // a hybrid frame's graph ends before the accumulation
-                              (F.rideShift << 8) | (F.rideShapes << 16) | (F.rideSplit << 24)};  // ... and everything that selects a kernel variant or a launch argument
+                              (F.rideShift << 8) | (F.rideShapes << 16) | (F.rideSplit << 24) |  // ... and everything that selects a kernel variant or a launch argument
+                              (F.sensor.bound ? (1 << 25) : 0)};  // k_project_gut<true>; the sensor's constants themselves travel with the frame's upload
   std::memcpy(key.v, kv, sizeof(kv));
   key.p[0] = fp.s->fb.image.p;
   key.p[1] = fp.s->surf.depth.p;
@@ -597,6 +602,8 @@ int renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail
   if((rc = buildFrameArgs(s, p, A))) return rc;
   const FrameConst& F = A.f;
   if((rc = validateFrameParams(p, F, s->occ))) return rc;
+  if(p->pipeline == MGS_PIPELINE_3DGS)
+    if((rc = refuseBoundSensor(s, "frame", "EWA splatting has no model of distortion: MGS_PIPELINE_3DGS cannot serve it"))) return rc;
   if(tail)
   {  // the rays of the tail's kernels: what a lit frame's constants carry (the raster kernels read none of it)
     std::memcpy(A.f.cameraPos, p->camera_pos, sizeof(A.f.cameraPos));

@@ -1,5 +1,7 @@
 // api_frameargs.hip — a frame's parameters: their defaults, and the constants the kernels read, built from them (buildFrameArgs).
 #include <cmath>
+#include <cstddef>
+#include <string>
 
 #include "scene_state.h"
 
@@ -76,6 +78,130 @@ void mat4InverseDouble(const float m[16], float out[16])
   for(int r = 0; r < 4; ++r)
     for(int c = 0; c < 4; ++c)
       out[c * 4 + r] = (float)a[r][4 + c];
+}
+
+// ---- sensor models (mgs_frame_set_sensor) -------------------------------------------------------------------------------------
+// computeMaxAngle, threedgut_camera_models.h.slang:87-119
+static float sensorMaxAngle(float w, float h, const float pp[2], const float f[2])
+{
+  const float mdx = pp[0] > 0.5f * w ? pp[0] : w - pp[0], mdy = pp[1] > 0.5f * h ? pp[1] : h - pp[1];
+  const float maxR = std::sqrt(mdx * mdx + mdy * mdy);
+  return std::max(2.0f * maxR / f[0], 2.0f * maxR / f[1]) / 2.0f;
+}
+// frameInfo.focal of the 3DGUT pipelines (gaussian_splatting.cpp:1239-1251) and the field of view it is derived from
+static void gutFocalOf(const MgsFrameParams* p, float focal[2], float* fovRad)
+{
+  *fovRad = p->fov_rad > 0.0f ? p->fov_rad : 2.0f * std::atan(1.0f / std::fabs(p->proj[5]));
+  if(p->camera_model == MGS_CAMERA_FISHEYE && p->pipeline == MGS_PIPELINE_3DGUT)
+  {
+    focal[0] = (float)p->width / *fovRad;
+    focal[1] = -(float)p->height / *fovRad;
+  }
+  else
+  {
+    focal[0] = p->proj[0] * 0.5f * (float)p->width;
+    focal[1] = p->proj[5] * 0.5f * (float)p->height;
+  }
+}
+
+int mgs_sensor_model_from_frame(const MgsFrameParams* p, MgsSensorModel* out)
+{
+  if(!p || !out)
+  {
+    setError("mgs_sensor_model_from_frame: null argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(p->width <= 0 || p->height <= 0 || p->width > 8192 || p->height > 8192 || p->camera_model < MGS_CAMERA_PINHOLE || p->camera_model > MGS_CAMERA_FISHEYE)
+  {
+    setError("mgs_sensor_model_from_frame: width/height must be in [1,8192] and camera_model one of MGS_CAMERA_*");
+    return MGS_ERR_INVALID_ARG;
+  }
+  std::memset(out, 0, sizeof(*out));
+  MgsFrameParams q = *p;
+  q.pipeline       = MGS_PIPELINE_3DGUT;  // the sensor is the 3DGUT pipeline's: a fisheye frame's focal length is the fisheye one
+  float fov;
+  gutFocalOf(&q, out->focal_length, &fov);
+  out->model              = p->camera_model == MGS_CAMERA_FISHEYE ? MGS_SENSOR_OPENCV_FISHEYE : MGS_SENSOR_OPENCV_PINHOLE;
+  out->principal_point[0] = (float)p->width * 0.5f;
+  out->principal_point[1] = (float)p->height * 0.5f;
+  out->max_angle          = sensorMaxAngle((float)p->width, (float)p->height, out->principal_point, out->focal_length);
+  return MGS_OK;
+}
+
+int mgs_frame_set_sensor(MgsScene s, const MgsSensorModel* m)
+{
+  if(m)
+  {  // (before the handle is looked at)
+    if(m->model < MGS_SENSOR_OPENCV_PINHOLE || m->model > MGS_SENSOR_OPENCV_FISHEYE)
+    {
+      setError("mgs_frame_set_sensor: model must be MGS_SENSOR_OPENCV_PINHOLE or MGS_SENSOR_OPENCV_FISHEYE");
+      return MGS_ERR_INVALID_ARG;
+    }
+    if(m->shutter < 0 || m->shutter > 4)
+    {
+      setError("mgs_frame_set_sensor: shutter out of range");
+      return MGS_ERR_INVALID_ARG;
+    }
+    const float* f = m->focal_length;  // the 21 floats from focal_length to max_angle are contiguous
+    static_assert(offsetof(MgsSensorModel, max_angle) - offsetof(MgsSensorModel, focal_length) == 20 * sizeof(float), "float block");
+    for(int i = 0; i < 21; ++i)
+      if(!std::isfinite(f[i]))
+      {
+        setError("mgs_frame_set_sensor: every value must be finite");
+        return MGS_ERR_INVALID_ARG;
+      }
+    if(m->focal_length[0] == 0.0f || m->focal_length[1] == 0.0f || m->max_angle < 0.0f)
+    {
+      setError("mgs_frame_set_sensor: focal_length must be non-zero and max_angle >= 0");
+      return MGS_ERR_INVALID_ARG;
+    }
+    for(uint32_t r : m->reserved)
+      if(r != 0u)
+      {
+        setError("mgs_frame_set_sensor: reserved words must be 0");
+        return MGS_ERR_INVALID_ARG;
+      }
+    if(m->shutter != 0)
+    {
+      setError("mgs_frame_set_sensor: rolling shutters are not supported (the reference marks that code untested); shutter must be 0");
+      return MGS_ERR_UNSUPPORTED;
+    }
+  }
+  if(!s)
+  {
+    setError("mgs_frame_set_sensor: null scene");
+    return MGS_ERR_INVALID_ARG;
+  }
+  s->sensor.bound = m != nullptr;
+  if(m)
+    s->sensor.model = *m;
+  return MGS_OK;
+}
+
+int refuseBoundSensor(MgsScene s, const char* what, const char* why)
+{
+  if(!s->sensor.bound)
+    return MGS_OK;
+  setError(std::string(what) + ": a sensor model is bound (" + why + "); unbind it with mgs_frame_set_sensor(handle, NULL)");
+  return MGS_ERR_UNSUPPORTED;
+}
+
+// the bound sensor as the 3DGUT kernels read it
+static void fillSensorConst(const MgsSensorModel& m, int width, int height, SensorConst& S)
+{
+  S.bound = 1;
+  S.model = m.model;
+  std::memcpy(S.focal, m.focal_length, sizeof(S.focal));
+  std::memcpy(S.principal, m.principal_point, sizeof(S.principal));
+  std::memcpy(S.radial, m.radial, sizeof(S.radial));
+  std::memcpy(S.tangential, m.tangential, sizeof(S.tangential));
+  std::memcpy(S.thinPrism, m.thin_prism, sizeof(S.thinPrism));
+  std::memcpy(S.fisheye, m.fisheye_radial, sizeof(S.fisheye));
+  S.maxAngle    = m.max_angle > 0.0f ? m.max_angle : sensorMaxAngle((float)width, (float)height, m.principal_point, m.focal_length);
+  S.clipRadius  = std::sqrt((float)width * (float)width + (float)height * (float)height);
+  S.rcpFocal[0] = (float)(1.0 / (double)m.focal_length[0]);
+  S.rcpFocal[1] = (float)(1.0 / (double)m.focal_length[1]);
+  S.tolNorm     = kSensorTolPx / std::max(std::fabs(m.focal_length[0]), std::fabs(m.focal_length[1]));
 }
 
 // coarse bins (the default): stable multi-split straight into the per-bin lists, no records, no pair sort; MGS_DIRECT_BIN=0
@@ -342,6 +468,12 @@ int buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A)
   F.totalSplats     = s->d->totalSplats;
   F.totalPartitions = s->d->totalParts;
   F.partitionCull   = F.cullMode == MGS_CULL_AT_DIST ? 1 : 0;
+  if(s->sensor.bound && p->pipeline == MGS_PIPELINE_3DGUT)
+  {  // the handle's sensor model replaces cameraModel / fovRad for the projection and the rays; the pre-cull of partition_cull.h
+     // bounds the two perfect models only
+    fillSensorConst(s->sensor.model, p->width, p->height, F.sensor);
+    F.partitionCull = 0;
+  }
   uint32_t offset = 0, block = 0;
   for(int k = 0; k < F.nInstances; ++k)
   {

@@ -354,6 +354,8 @@ static int mgs_meshes_render_impl(MgsScene s, const MgsFrameParams* p, MgsMeshOu
       return MGS_ERR_INVALID_ARG;
     }
   }
+  if(int rc = refuseBoundSensor(s, "mgs_meshes_render", "the mesh pass rasterises through view / proj, which has no distortion"))
+    return rc;
   SceneData& d = *s->d;
   HIPCHK(hipSetDevice(s->device));
   const size_t n = (size_t)p->width * (size_t)p->height;

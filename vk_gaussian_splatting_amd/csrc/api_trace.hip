@@ -133,6 +133,9 @@ int traceFrameArgs(MgsScene s, MgsFrameParams& q, const char* what, bool rayInve
       return wrc;
   q.pipeline  = MGS_PIPELINE_3DGUT;
   q.sort_mode = MGS_SORT_GPU_RADIX;
+  // (with a sensor bound to the handle, buildFrameArgs fills FrameConst::sensor and clears partitionCull for this 3DGUT frame too.  Of
+  // the callers only mgs_trace_generate_rays reads it: the traced frames refuse before they get here, and the ray queries, which "do
+  // not look at the binding", launch k_trace_rays, which reads neither field.)
   A           = std::make_unique<FrameArgs>();
   if(int rc = buildFrameArgs(s, &q, *A))
     return rc;
@@ -436,6 +439,9 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(s->occ.depth)
     return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: an occluder is bound (meshes in the traced scene are out of scope); unbind it with "
                                           "mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
+  if(int rc = refuseBoundSensor(s, lit ? "mgs_render_traced_lit" : "mgs_render_traced", "the traced frames generate the perfect cameras' rays; trace the sensor's "
+                                                                                         "rays with mgs_trace_generate_rays and mgs_trace_rays_device"))
+    return rc;
   MgsFrameParams q      = *p;
   q.depth_iso_threshold = t.depth_iso_threshold;
   std::unique_ptr<FrameArgs> A;
@@ -576,6 +582,8 @@ static int mgs_render_hybrid_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(s->occ.depth)
     return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: an occluder is bound (shadowing mesh pixels needs meshes in the traced scene, which are out of "
                                           "scope); unbind it with mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
+  if(int rc = refuseBoundSensor(s, "mgs_render_hybrid", "the shadow rays start from a surface unprojected through the perfect cameras"))
+    return rc;
   tail.s = s;
   tail.p = p;
   // step 1: exactly mgs_render's unlit frame with the surface outputs on (the deferred pass is off in hybrid mode, NEED_SURFACE_INFO on)

@@ -52,6 +52,28 @@ struct InstanceConst
   int32_t      shStride;       // stored elements per splat (logical 0/9/24/45 padded to a 16-byte multiple)
 };
 
+// the handle's sensor model (mgs_frame_set_sensor; CameraModelParameters, threedgut_camera_models.h.slang:25-50, global shutter) as the
+// 3DGUT kernels read it: gutProjectSensor / gutSensorRay (gut_common.h).  bound == 0: none, the frame's cameraModel / fovRad hold.
+struct SensorConst
+{
+  int32_t bound;
+  int32_t model;          // MGS_SENSOR_OPENCV_PINHOLE 0 / MGS_SENSOR_OPENCV_FISHEYE 1
+  float   focal[2];       // pixels, the sign convention of gutFocal
+  float   principal[2];
+  float   radial[6];      // pinhole: numerator k1..k3, denominator k4..k6
+  float   tangential[2];
+  float   thinPrism[4];
+  float   fisheye[4];     // forward polynomial in theta^2
+  float   maxAngle;       // fisheye; the caller's, or computeMaxAngle of the viewport, the principal point and the focal length
+  float   clipRadius;     // length(resolution): the out-of-limits fallback of projectPointPinhole (:131-132)
+  float   rcpFocal[2];    // 1 / focal (host double, rounded once): the inverse's normalised image point
+  float   tolNorm;        // the inverse's convergence bound, kSensorTolPx pixels in normalised units: kSensorTolPx / max |focal|
+  float   pad[5];
+};
+static_assert(sizeof(SensorConst) == 128, "32 words");
+constexpr int   kSensorNewtonIters = 8;      // fixed iteration count of gutSensorRay
+constexpr float kSensorTolPx       = 1e-2f;  // a pixel whose inverse misses its image point by more has no ray
+
 // frame constants (shaderio::FrameInfo, shaders/shaderio.h:238-317, reduced)
 struct FrameConst
 {
@@ -113,6 +135,9 @@ struct FrameConst
   float    cameraPos[3];           // frameInfo.cameraPosition
   float    lightViewInv[16], lightProjInv[16];  // viewInverse / projInverse computed in double and rounded once (viewInv / projInv
                                                 // above are the fp32 closed form the 3DGUT rays are pinned to)
+  // the handle's sensor model (read by k_project_gut<true>, the 3DGUT compositors' prologue and k_rays_generate; last, so that a
+  // frame without one uploads zeros behind everything the other kernels read)
+  SensorConst sensor;
 };
 
 struct FrameArgs

@@ -53,7 +53,18 @@ __device__ __forceinline__ bool gutProjectCam(const FrameConst& F, float cx, flo
   return ok && (ox > -mx) && (oy > -my) && (ox < resx + mx) && (oy < resy + my);
 }
 
+// a sigma point through the frame's camera: the perfect models above, or the handle's sensor model (gut_common.h: gutProjectSensor)
+template <bool SENSOR>
+__device__ __forceinline__ bool gutProjectPoint(const FrameConst& F, float cx, float cy, float cz, float& ox, float& oy)
+{
+  if constexpr(SENSOR)
+    return gutProjectSensor(F, cx, cy, cz, ox, oy);
+  else
+    return gutProjectCam(F, cx, cy, cz, ox, oy);
+}
+
 // the per-splat 3DGUT front end; returns false when the splat emits no quad
+template <bool SENSOR>
 __device__ __forceinline__ bool projectSplatGut(const FrameConst& F, const InstanceConst& I, uint32_t li, GutRec& out, uint32_t& rectOut)
 {
   // mesh.slang:116-122.  The colour (base + SH, :142-148) does not influence any decision of the front end: it is
@@ -81,7 +92,7 @@ __device__ __forceinline__ bool projectSplatGut(const FrameConst& F, const Insta
   const float  vcy = MV[1] * px + MV[5] * py + MV[9] * pz + MV[13];
   const float  vcz = MV[2] * px + MV[6] * py + MV[10] * pz + MV[14];
   float spx[7], spy[7];
-  int   nValid = gutProjectCam(F, vcx, vcy, -vcz, spx[0], spy[0]) ? 1 : 0;
+  int   nValid = gutProjectPoint<SENSOR>(F, vcx, vcy, -vcz, spx[0], spy[0]) ? 1 : 0;
   constexpr float kDelta = 1.73205080757f, kWI = 1.0f / 6.0f;
   float ccx = 0.0f, ccy = 0.0f;  // weight of the mean: lambda / (D + lambda) = 0
 #pragma unroll
@@ -91,10 +102,10 @@ __device__ __forceinline__ bool projectSplatGut(const FrameConst& F, const Insta
     const float dvx = MV[0] * ex + MV[4] * ey + MV[8] * ez;
     const float dvy = MV[1] * ex + MV[5] * ey + MV[9] * ez;
     const float dvz = MV[2] * ex + MV[6] * ey + MV[10] * ez;
-    nValid += gutProjectCam(F, vcx + dvx, vcy + dvy, -(vcz + dvz), spx[a + 1], spy[a + 1]) ? 1 : 0;
+    nValid += gutProjectPoint<SENSOR>(F, vcx + dvx, vcy + dvy, -(vcz + dvz), spx[a + 1], spy[a + 1]) ? 1 : 0;
     ccx += kWI * spx[a + 1];
     ccy += kWI * spy[a + 1];
-    nValid += gutProjectCam(F, vcx - dvx, vcy - dvy, -(vcz - dvz), spx[a + 4], spy[a + 4]) ? 1 : 0;
+    nValid += gutProjectPoint<SENSOR>(F, vcx - dvx, vcy - dvy, -(vcz - dvz), spx[a + 4], spy[a + 4]) ? 1 : 0;
     ccx += kWI * spx[a + 4];
     ccy += kWI * spy[a + 4];
   }
@@ -230,7 +241,10 @@ __device__ __forceinline__ bool projectSplatGut(const FrameConst& F, const Insta
 }
 
 // Phase 1 (key + frustum cull + ordered compaction) is k_project's, statement for statement: the sorted (key, id)
-// stream of a 3DGUT frame is bit-identical to the 3DGS frame's before the front-end rejections.
+// stream of a 3DGUT frame is bit-identical to the 3DGS frame's before the front-end rejections.  SENSOR: the sigma points go
+// through the handle's sensor model (mgs_frame_set_sensor) instead of the frame's perfect camera; nothing else differs, and the
+// host switches the partition pre-cull off for such a frame (partition_cull.h bounds the two perfect models only).
+template <bool SENSOR>
 __global__ __launch_bounds__(kGutThreads) void k_project_gut(const FrameArgs* __restrict__ Ap, FrameCounters* __restrict__ ctr,
                                                              uint2* __restrict__ slotPairs, uint32_t* __restrict__ slotCount,
                                                              GutRec* __restrict__ rec, uint32_t* __restrict__ rect,
@@ -326,7 +340,7 @@ __global__ __launch_bounds__(kGutThreads) void k_project_gut(const FrameArgs* __
       const uint32_t li = local0 + s_li[j];
       GutRec         r;
       uint32_t       rc;
-      if(projectSplatGut(A.f, I, li, r, rc))
+      if(projectSplatGut<SENSOR>(A.f, I, li, r, rc))
       {
         gidOk       = I.globalOffset + li;
         float4* dst = &s_grec[w][lane * 7];
@@ -378,8 +392,12 @@ void launchProjectGut(hipStream_t stream, const ProjectLaunch& L)
 {
   if(L.totalPartitions == 0)
     return;
-  hipLaunchKernelGGL(k_project_gut, dim3(L.totalPartitions), dim3(kGutThreads), 0, stream, L.dArgs, L.ctr, L.slotPairs, L.slotCount, L.recGut,
-                     L.rect, L.slotHist2, L.top16Rec, L.top16Count, L.osPlan, L.order);
+  if(L.sensor)
+    hipLaunchKernelGGL(k_project_gut<true>, dim3(L.totalPartitions), dim3(kGutThreads), 0, stream, L.dArgs, L.ctr, L.slotPairs, L.slotCount, L.recGut,
+                       L.rect, L.slotHist2, L.top16Rec, L.top16Count, L.osPlan, L.order);
+  else
+    hipLaunchKernelGGL(k_project_gut<false>, dim3(L.totalPartitions), dim3(kGutThreads), 0, stream, L.dArgs, L.ctr, L.slotPairs, L.slotCount, L.recGut,
+                       L.rect, L.slotHist2, L.top16Rec, L.top16Count, L.osPlan, L.order);
 }
 
 }  // namespace mgs

@@ -88,7 +88,21 @@ __global__ __launch_bounds__(256) void k_rays_generate(const FrameArgs* __restri
   if(i >= (uint32_t)F.width * (uint32_t)F.height)
     return;
   float      o[3], d[3];
-  const bool ok = primaryRayAsTraced(F, (int)(i % (uint32_t)F.width), (int)(i / (uint32_t)F.width), o, d);
+  const int  px = (int)(i % (uint32_t)F.width), py = (int)(i / (uint32_t)F.width);
+  bool       ok;
+  if(F.sensor.bound != 0)
+  {  // the handle's sensor model: the ray the 3DGUT compositors give this pixel (gut_common.h), lens sample included
+    ok   = gutPixelRay(F, (float)px + 0.5f, (float)py + 0.5f, d[0], d[1], d[2]);
+    o[0] = F.viewInv[12]; o[1] = F.viewInv[13]; o[2] = F.viewInv[14];
+    if(F.dofMode != 0)
+    {
+      float lx, ly, lz;
+      gutLensSample<false>(F, rngXxhash32((uint32_t)px, (uint32_t)py, (uint32_t)F.frameSampleId), lx, ly, lz, d[0], d[1], d[2]);
+      o[0] += lx; o[1] += ly; o[2] += lz;
+    }
+  }
+  else
+    ok = primaryRayAsTraced(F, px, py, o, d);
   rays[2 * (size_t)i]     = make_float4(o[0], o[1], o[2], ok ? 0.001f : 1.0f);
   rays[2 * (size_t)i + 1] = make_float4(d[0], d[1], d[2], ok ? 10000.0f : 0.0f);
 }

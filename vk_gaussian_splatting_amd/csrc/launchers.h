@@ -23,6 +23,7 @@ struct ProjectLaunch
   const FrameArgs* dArgs;            // the frame's constants on the device
   uint32_t         totalPartitions;  // the grid: FrameConst::totalPartitions
   bool             full;             // false: keys only (mgs_sort_keys); the 3DGUT kernel always runs in full
+  bool             sensor;           // launchProjectGut: FrameConst::sensor is bound (k_project_gut<true>)
   FrameCounters*   ctr;
   uint2*           slotPairs;
   uint32_t*        slotCount;

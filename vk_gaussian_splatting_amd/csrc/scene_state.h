@@ -407,6 +407,13 @@ struct OccluderBinding
   void release() { ownDepth.release(), ownColor.release(); }
 };
 
+// the handle's sensor model (mgs_frame_set_sensor): a copy of the caller's, validated; buildFrameArgs turns it into SensorConst
+struct SensorBinding
+{
+  bool           bound = false;
+  MgsSensorModel model{};
+};
+
 // FTB side outputs of the last frame rendered with surface_outputs (mgs_render, mgs_frame_download_surface)
 struct SurfaceOutputs
 {
@@ -641,6 +648,7 @@ struct MgsScene_t
   UploadRing      up;
   GraphCache      graphs;
   OccluderBinding occ;
+  SensorBinding   sensor;
   SurfaceOutputs  surf;
   CompareState    cmp;
   MeshPassState   mesh;
@@ -662,6 +670,8 @@ int  buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A);       //
 bool directBinning(const FrameConst& F);                                      // api_frameargs.hip
 bool binPolicyEligible(const MgsFrameParams* p);                              // api_frameargs.hip
 int  ensureFrameState(MgsScene s);                                            // api_frame.hip
+// api_frameargs.hip: MGS_ERR_UNSUPPORTED with the message every entry point without a sensor model gives while one is bound
+int  refuseBoundSensor(MgsScene s, const char* what, const char* why);
 // api_frame.hip: image, side outputs, accumulator; a frame of the graph also sizes its range table and names its occluder depth
 int  ensureFrameImage(MgsScene s, const MgsFrameParams* p, const FrameConst& F, uint32_t rangeEntries = 0, const float* occDepth = nullptr);
 void mat4InverseDouble(const float m[16], float out[16]);                     // api_frameargs.hip
