@@ -51,13 +51,17 @@ extern "C" {
                             ray queries (MGS_HAS_RAY_QUERY below): entry points only, both numbers stay — mgs_ray_query_params_default,
                                  mgs_trace_rays, mgs_trace_rays_device, mgs_trace_generate_rays;
                             sensor models (MGS_HAS_SENSOR_MODEL below): entry points and one new struct, both numbers stay —
-                                 mgs_sensor_model_from_frame, mgs_frame_set_sensor */
+                                 mgs_sensor_model_from_frame, mgs_frame_set_sensor;
+                            shadow and light queries (MGS_HAS_SHADOW_QUERY below): entry points and new structs, both numbers stay —
+                                 mgs_trace_shadow_rays, mgs_trace_shadow_rays_device, mgs_shade_points, mgs_shade_points_device */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_STRATEGIES 1 /* feature macro: MgsTraceParams::trace_strategy and MGS_TRACE_STRATEGY_* exist (within ABI 5.1: the first reserved word
                                      of MgsTraceParams is named, 0 = what it was; no struct size or default changed) */
 #define MGS_HAS_RAY_QUERY 1     /* feature macro: mgs_trace_rays and its companions exist (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_SHADOW_QUERY 1  /* feature macro: mgs_trace_shadow_rays, mgs_shade_points and their _device variants exist (added within ABI 5.1, no
+                                  existing struct or default changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
@@ -929,6 +933,101 @@ int  mgs_trace_rays_device(MgsScene scene_or_context, const MgsRay* rays_device,
  * from the library's camera and perturbs it: tracing these rays gives the traced frame's radiance, 1 - alpha, hit counts, picked
  * ids and normals bit for bit. */
 int  mgs_trace_generate_rays(MgsScene scene_or_context, const MgsFrameParams* params, MgsRay* rays_device);
+
+/* ---- shadow and light queries (MGS_HAS_SHADOW_QUERY): the splats' shadows on the caller's own surfaces.  A caller who rasterises
+ * meshes with mgs_meshes_render, or brings a G-buffer of its own, hands over shadow rays, or whole surface points, and gets back what
+ * the light pass of mgs_render_traced_lit computes for a splat-surface pixel: traceShadowRayParticle
+ * (shaders/threedgrt_raytrace.rgen.slang:1344-1464) per ray, evaluateLightingAndShadingParticles (:1082-1144) per point.  The library
+ * still knows no geometry but the particles, and no existing entry point changes: a bound occluder or sensor is refused by the traced
+ * and hybrid frames as before.  The ray queries above return the PRIMARY walk's radiance and transmittance, which is not a light
+ * pass's shadow: that is one collection, a window that ends 0.001 before the light, the threshold cut, the ramp and the tint.
+ *
+ * Shadow rays (mgs_trace_shadow_rays, mgs_trace_shadow_rays_device).  The ray is an MgsRay, used AS GIVEN: the direction is not
+ * renormalised, and t is the parameter along the given direction (world units for a unit direction).  Nothing in the walk assumes
+ * unit length: the hit parameter is -dot(o,d)/dot(d,d) with the unnormalised canonical direction (rint.slang:166-168), the distance
+ * to the ray divides by dot(d,d), the node test runs on 1 / direction, and the response's model-space direction (rgen:697-698)
+ * normalises itself.  t_max plays lightDist: the collection window is (max(t_min, 0), t_max - 0.001) with the subtraction in fp32
+ * and no epsT; ONE collection of the samples_per_pass nearest hits, no second pass (occluders beyond the samples_per_pass-th are not
+ * seen); the slots are walked in order, a slot with t >= t_max is skipped; particleProcessHit / particleIntegrate with the
+ * transmittance in double; after each slot a transmittance below particle_shadow_transmittance_threshold becomes 0 and ends the
+ * walk; then T = saturate(T), scaledT = saturate((T - threshold) / (1 - threshold)), normalizedColor = shadowRadiance / max
+ * component (1 where that is <= 0.001), transmittance = saturate(scaledT * lerp(1, normalizedColor,
+ * particle_shadow_color_strength * (1 - scaledT))).  With t_min = 0 and t_max = lightDist this is the light pass's shadow ray,
+ * operation for operation (one device function serves both).  MGS_DEBUG_SH_ONLY and MGS_DEBUG_OPACITY_GAUSSIAN_DISABLED are honoured
+ * as they are there.  Of MgsTraceLightParams the call reads particle_shadow_transmittance_threshold and
+ * particle_shadow_color_strength; particle_shadow_offset is NOT READ (the caller has placed the origin), not even range-checked.
+ * shadows_mode must be MGS_SHADOWS_HARD: MGS_SHADOWS_SOFT is MGS_ERR_UNSUPPORTED, any other value MGS_ERR_INVALID_ARG; `light` NULL =
+ * the defaults with shadows_mode MGS_SHADOWS_HARD.  Of MgsTraceParams it reads samples_per_pass and kernel_adaptive_clamping.
+ * An invalid ray (a non-finite component, a zero-length direction or t_min > t_max) never reaches the traversal: transmittance
+ * (1,1,1), 0 hits, counted in invalid_rays; a per-ray outcome, not an error code.  Reads of MgsFrameParams, the range checks before
+ * the handle is looked at, count == 0, the lazily built shared hierarchy, the staging of the host variant, the alignment and stream
+ * order of the device variant and `query->reorder` (the ray queries' coherence key and sort) are those of the ray queries, above;
+ * trace_strategy must be 0.  A scene without instances yields (1,1,1) and 0 hits.  MgsRayQueryOut is filled as for a ray query:
+ * accepted_hits is the sum of `hits`, max_passes_used is 1 where any valid ray was traced.
+ *
+ * Light queries (mgs_shade_points, mgs_shade_points_device).  A surface point is position, normal, view direction (the direction the
+ * viewer's ray TRAVELS, rayDirection, as given), the surface's own colour `radiance` (what the light pass multiplies the material
+ * by) and an index into the call's material array (host memory, 1 to 256 entries; uploaded to a table of the handle's).  Per point
+ * the result is step 3 of the hybrid frames' documentation at the caller's position: needShading as updateMaterialNeedsShading
+ * derives it; radiance * emission alone when it is 0; each light of the scene's table (mgs_scene_set_lights) through
+ * computeLightToSurfaceVector, a point or spot light out of range SKIPPED without an ambient term; with shadows_mode =
+ * MGS_SHADOWS_HARD one shadow ray per light as above, from position + lightDir * particle_shadow_offset (read here) with t_min 0
+ * and t_max lightDist; shading with the shadowed light colour, inShadow (max component < 0.001) returning after the ambient term;
+ * with no lights a headlight at params->camera_pos (the one camera field that is read; it must be finite), never shadowed.  The
+ * normal is normalised; a normal of length <= 0.2 is replaced by -view_dir, the light pass's fallback.  With shadows_mode =
+ * MGS_SHADOWS_DISABLED the call is pure shading and builds no hierarchy.  lighting_mode is not read.
+ * An invalid point (a non-finite position, normal, view direction or radiance, or a material index at or above the count) gets colour
+ * 0 and 0 hits and is counted in *invalid_points.  The host variant checks the indices itself: one out of range is
+ * MGS_ERR_INVALID_ARG, as is a material count outside [1, 256].  Statistics go out through MgsTraceLightOut (shadow_rays = points
+ * with a shaded material x lights in range, 0 with shadows off; light_ms = HIP events around the kernel).  Reorder sorts on the
+ * position's Morton cell alone (the key kernel's second entry).  Everything else as for shadow rays: the materials are converted into a
+ * host table of the handle's and uploaded on its stream, so the device variant does not wait for them (the caller's array may be
+ * reused when the call returns).
+ *
+ * Both write their results and the handle's per-frame device constants and counters only: the handle's frame, side outputs, hit
+ * counts and shadow hits stay as they are, but mgs_frame_stats, mgs_frame_row_costs and mgs_frame_download_projected of an earlier
+ * frame are not meaningful afterwards (a frame context keeps the two apart).  A bound occluder or sensor is not looked at.  Staging
+ * buffers, keys and the material table belong to the handle and count into working_bytes.
+ * PARITY UNPINNED: the reference shades a MESH hit with its own mesh function (barycentric normals, the mesh's material, mesh
+ * shadow rays through both acceleration structures); this shades a caller's point with the PARTICLES' function and shadows it by
+ * particles only, so a hybrid picture made this way agrees with the reference's in the splats' shadows on the mesh, not in the mesh's
+ * own shading model or in mesh-on-mesh shadows.  The window's lower bound t_min and non-unit directions have no counterpart in the
+ * reference (its shadow rays start at TMin 0 with a unit direction).  The headlight sits at camera_pos, which for a caller's point
+ * need not be where view_dir starts. */
+typedef struct MgsShadowResult {
+  float    transmittance[3]; /* what the light's colour is multiplied by; (1,1,1) for an invalid ray */
+  uint32_t hits;             /* hits the walk accepted */
+} MgsShadowResult; /* 16 B */
+typedef struct MgsSurfacePoint {
+  float    position[3];
+  uint32_t material; /* index into the call's material array */
+  float    normal[3];
+  float    _pad0;
+  float    view_dir[3]; /* the direction the viewer's ray travels (rayDirection), as given */
+  float    _pad1;
+  float    radiance[3]; /* the surface's own colour: what the light pass multiplies the material by */
+  float    _pad2;
+} MgsSurfacePoint; /* 64 B */
+typedef struct MgsShadeResult {
+  float    color[3];
+  uint32_t shadow_hits; /* accepted shadow hits, summed over the lights */
+} MgsShadeResult; /* 16 B */
+int mgs_trace_shadow_rays(MgsScene scene_or_context, const MgsRay* rays_host, uint64_t count, const MgsFrameParams* params,
+                          const MgsTraceParams* trace /* NULL = defaults */, const MgsTraceLightParams* light /* NULL = defaults, hard shadows */,
+                          const MgsRayQueryParams* query /* NULL = defaults */, MgsShadowResult* results_host, MgsRayQueryOut* out /* may be NULL */);
+int mgs_trace_shadow_rays_device(MgsScene scene_or_context, const MgsRay* rays_device, uint64_t count, const MgsFrameParams* params,
+                                 const MgsTraceParams* trace /* NULL = defaults */, const MgsTraceLightParams* light /* NULL = defaults, hard shadows */,
+                                 const MgsRayQueryParams* query /* NULL = defaults */, MgsShadowResult* results_device,
+                                 MgsRayQueryOut* out /* may be NULL */);
+int mgs_shade_points(MgsScene scene_or_context, const MgsSurfacePoint* points_host, uint64_t count, const MgsMaterial* materials_host,
+                     uint32_t material_count, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
+                     const MgsTraceLightParams* light /* NULL = defaults */, const MgsRayQueryParams* query /* NULL = defaults */,
+                     MgsShadeResult* results_host, MgsTraceLightOut* light_out /* may be NULL */, uint32_t* invalid_points /* may be NULL */);
+int mgs_shade_points_device(MgsScene scene_or_context, const MgsSurfacePoint* points_device, uint64_t count, const MgsMaterial* materials_host,
+                            uint32_t material_count, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
+                            const MgsTraceLightParams* light /* NULL = defaults */, const MgsRayQueryParams* query /* NULL = defaults */,
+                            MgsShadeResult* results_device, MgsTraceLightOut* light_out /* may be NULL */,
+                            uint32_t* invalid_points /* may be NULL */);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

@@ -4,7 +4,7 @@
   python tools/mgs_render.py scene.ply|scene.spz|scene.splat|syn:<n> out.png [--size W H] [--eye x y z]
                              [--center x y z] [--fov deg] [--flip-y] [--sh-format 0|1|2] [--rgba-format 0|1|2]
                              [--occluder-depth FILE.npy [--background FILE.npy]]
-                             [--mesh FILE.obj [--mesh-transform 16 floats]]...
+                             [--mesh FILE.obj [--mesh-transform 16 floats]]... [--lighting 1 --mesh-shadows 1]
                              [--lighting 0|1 [--lights FILE.json] [--material a a a d d d s s s e e e shininess]]
                              [--pipeline raster|trace|hybrid [--samples-per-pass N --max-passes N --min-transmittance X]
                               [--lighting 1 [--shadows 1] [--shadow-offset X --shadow-threshold X --shadow-color-strength X]]]
@@ -18,6 +18,11 @@ depth-tested against it (z <= depth).  --background: float32 [H, W, 4] linear co
 with the field names of MgsLight (type, color, intensity, position, range, direction, inner_cone_deg, outer_cone_deg,
 attenuation_mode; absent fields keep the reference's defaults); without it the headlight at the camera lights the scene.
 --material: ambient, diffuse, specular, emission (rgb each) and shininess of the single instance (default: fully emissive).
+
+--mesh ... --lighting 1 --mesh-shadows 1 (raster pipelines): after the mesh pass every mesh pixel is lit with the scene's lights and
+shadowed by the splats (mgs_shade_points_device: position from the mesh depth, flat normal and material of the pixel's primitive,
+--shadow-* and --samples-per-pass as for the traced frames), the result replaces the occluder's colour image, and the splats are
+rendered over it: a mesh floor under a splat object shows the object's shadow.  Needs torch for the device images.
 
 --pipeline trace --lighting 1 [--shadows 1]: a lit traced frame (mgs_render_traced_lit), --lights / --material as for the raster pipelines.
 --pipeline hybrid --lighting 1 [--shadows 1]: a hybrid frame (mgs_render_hybrid): the rasterised frame of --raster-pipeline as the
@@ -46,6 +51,61 @@ import vk_gaussian_splatting_amd as mgs  # noqa: E402
 from vk_gaussian_splatting_amd import capi, synth  # noqa: E402
 
 
+def shade_mesh_pixels(scene, meshes, p, V, P, a):
+    """--mesh-shadows 1: light the mesh pixels of the last mesh pass with the scene's light table and shadow them by the splats
+    (mgs_shade_points_device), then bind the mesh depth and the new colours as the occluder (mgs_frame_set_occluder).  Positions are
+    rebuilt from the mesh depth through the inverse of proj * view; the mesh pass exposes no normals, so they are flat: the face
+    normal of the pixel's primitive from the mesh arrays, turned toward the viewer (the pass draws both windings).  The material is
+    the primitive's, radiance is 1 (a mesh's colour is its material).  Returns the device images: the caller keeps them alive."""
+    import torch
+    W, H = p.width, p.height
+    depth, _, prim = scene.download_meshes()
+    rows, cols = np.nonzero(prim != capi.MESH_NONE)
+    face_n, face_m, mats = [], [], []
+    for mesh, M in meshes:  # primitive ids are global: the instances' triangles concatenated in creation order
+        v = mesh.view()
+        M = np.eye(4) if M is None else np.asarray(M, np.float64)
+        tri = (v["positions"].astype(np.float64) @ M[:3, :3].T + M[:3, 3])[v["indices"]]
+        face_n.append(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]))
+        own = v["materials"] or [dict(ambient=(0.1,) * 3, diffuse=(0.7,) * 3, specular=(1.0,) * 3, emission=(0.0,) * 3, shininess=32.0)]  # the loader's default
+        face_m.append(len(mats) + np.minimum(v["material_ids"], len(own) - 1))
+        mats += own
+    if len(mats) > 256:
+        raise SystemExit("--mesh-shadows: the meshes hold more than 256 materials (mgs_shade_points takes 1 to 256)")
+    face_n, face_m = np.concatenate(face_n), np.concatenate(face_m)
+    depth_dev = torch.from_numpy(depth).cuda()
+    color_dev = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
+    if len(rows):
+        ndc = np.stack([(cols + 0.5) / W * 2 - 1, (rows + 0.5) / H * 2 - 1, depth[rows, cols].astype(np.float64), np.ones(len(rows))], 1)  # row 0 = NDC y -1
+        world = ndc @ np.linalg.inv(np.asarray(P, np.float64) @ np.asarray(V, np.float64)).T
+        pos = world[:, :3] / world[:, 3:4]
+        view = pos - np.asarray(a.eye, np.float64)[None]
+        view /= np.linalg.norm(view, axis=1, keepdims=True)
+        nrm = face_n[prim[rows, cols]]
+        nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-300)
+        nrm[(nrm * view).sum(1) > 0] *= -1.0
+        pts = capi.make_surface_points(pos, nrm, view, np.ones_like(pos), face_m[prim[rows, cols]])
+        pts_dev = torch.from_numpy(pts.view(np.float32).reshape(-1)).cuda()
+        res_dev = torch.zeros(len(rows) * 4, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # the query runs on the handle's stream
+        q = capi.default_params(W, H)
+        capi.set_camera(q, V, P, a.eye)
+        lp = capi.default_trace_light_params(shadows_mode=1, particle_shadow_offset=a.shadow_offset,
+                                             particle_shadow_transmittance_threshold=a.shadow_threshold,
+                                             particle_shadow_color_strength=a.shadow_color_strength)
+        lo, bad = scene.shade_points_device(pts_dev.data_ptr(), len(rows), mats, q, res_dev.data_ptr(),
+                                            capi.default_trace_params(samples_per_pass=a.samples_per_pass), lp, reorder=True, want_stats=True)
+        sr = max(int(lo.shadow_rays), 1)
+        print(f"{len(rows)} mesh pixels shaded ({bad} invalid), light query {lo.light_ms:.3f} ms on the GPU, {lo.shadow_rays} shadow rays, "
+              f"{lo.shadow_node_visits / sr:.1f} node visits and {lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
+        at = (torch.from_numpy(rows).cuda(), torch.from_numpy(cols).cuda())
+        color_dev[at[0], at[1], :3] = res_dev.view(-1, 4)[:, :3]
+        color_dev[at[0], at[1], 3] = 1.0
+        torch.cuda.synchronize()
+    scene.set_occluder(depth_dev.data_ptr(), color_dev.data_ptr(), W, H)
+    return depth_dev, color_dev
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("scene")
@@ -61,6 +121,7 @@ def main():
     ap.add_argument("--background", default=None, metavar="FILE.npy")
     ap.add_argument("--mesh", action="append", default=[], metavar="FILE.obj")
     ap.add_argument("--mesh-transform", action="append", type=float, nargs=16, default=[], metavar="M")
+    ap.add_argument("--mesh-shadows", type=int, choices=[0, 1], default=0)  # --mesh --lighting 1: the splats' shadows on the meshes
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
@@ -111,6 +172,8 @@ def main():
         ap.error("--pipeline hybrid lights and shadows splats alone (meshes in the traced scene are out of scope): no --occluder-depth or --mesh")
     if a.pipeline == "hybrid" and not a.lighting:
         ap.error("--pipeline hybrid needs --lighting 1 (without lighting it is --pipeline raster)")
+    if a.mesh_shadows and not (a.mesh and a.lighting and a.pipeline == "raster"):
+        ap.error("--mesh-shadows 1 needs --mesh, --lighting 1 and --pipeline raster")
     if a.background and not a.occluder_depth:
         ap.error("--background needs --occluder-depth")
     if a.occluder_depth:
@@ -136,11 +199,15 @@ def main():
             ap.error("--mesh makes the occluder images itself: do not combine it with --occluder-depth")
         if len(a.mesh_transform) > len(a.mesh):
             ap.error("more --mesh-transform than --mesh")
+        meshes = []
         for k, path in enumerate(a.mesh):
             m = np.array(a.mesh_transform[k], np.float32).reshape(4, 4) if k < len(a.mesh_transform) else None
-            scene.add_mesh_instance(mgs.Mesh.load_obj(path), m)
+            meshes.append((mgs.Mesh.load_obj(path), m))
+            scene.add_mesh_instance(*meshes[-1])
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
+        if a.mesh_shadows:
+            held = shade_mesh_pixels(scene, meshes, p, V, P, a)  # the occluder's images: keep them until the frame is downloaded
     if a.pipeline != "trace" and (a.trace_strategy != "full" or a.accumulate != 1):
         ap.error("--trace-strategy pass / anyhit and --accumulate are for --pipeline trace (unlit)")
     if a.pipeline == "trace":

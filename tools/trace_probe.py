@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
@@ -13,7 +13,11 @@ scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and 
 the camera's distance, each aimed at a random point of the inner half of that ball: neighbouring lanes share nothing) and a CAMERA
 batch (mgs_trace_generate_rays of the probe's camera at the frame size of the scene's aspect with about N pixels, row-major), each
 with reorder off and on: the median trace_ms and reorder_ms and the visits per ray; and mgs_render_traced's trace_ms of that same
-frame, whose lanes are 8 x 8 pixels where the row-major batch's are 64 x 1.  Needs an MI355X.
+frame, whose lanes are 8 x 8 pixels where the row-major batch's are 64 x 1.
+--shadow-rays N adds shadow queries (mgs_trace_shadow_rays_device) of N rays toward one point light above the scene, for every N
+given: a RANDOM batch (origins uniform in the ball of the camera's distance) and a COHERENT one (origins on a regular grid of the
+plane below the scene, row-major), each with reorder off and on: the median trace_ms and reorder_ms and the rays per second.
+Needs an MI355X.
 """
 import argparse
 import json
@@ -88,6 +92,42 @@ def probe_rays(scene, p, t, n, eye, W, H, warmup, repeats):
     return out
 
 
+def probe_shadow_rays(scene, p, t, n, eye, warmup, repeats):
+    """the four shadow-query runs of --shadow-rays for one batch size: unit directions toward a point light, t_max = its distance"""
+    import torch
+    radius = float(np.linalg.norm(eye))
+    light = np.array((0.3 * radius, 1.2 * radius, 0.2 * radius))
+    rng = np.random.Generator(np.random.PCG64(2))
+    v = rng.standard_normal((n, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    side = max(int(np.ceil(n ** 0.5)), 1)
+    g = np.linspace(-radius, radius, side)
+    gx, gz = np.meshgrid(g, g)
+    batches = dict(random=v * (radius * rng.random((n, 1)) ** (1.0 / 3.0)),
+                   coherent=np.stack([gx.ravel(), np.full(side * side, -0.5 * radius), gz.ravel()], 1)[:n])
+    lp = capi.default_trace_light_params(shadows_mode=1)
+    out = dict(requested=n)
+    for name, o in batches.items():
+        d = light[None] - o
+        dist = np.linalg.norm(d, axis=1)
+        dev = torch.from_numpy(capi.make_rays(o, d / dist[:, None], 0.0, dist).view(np.float32).copy()).cuda()
+        res = torch.empty(n * 4, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        out[name] = []
+        for reorder in (False, True):
+            tms, rms = [], []
+            for k in range(warmup + repeats):
+                q = scene.trace_shadow_rays_device(dev.data_ptr(), n, p, res.data_ptr(), t, lp, reorder=reorder, want_stats=True)
+                if k >= warmup:
+                    tms.append(q.trace.trace_ms)
+                    rms.append(q.reorder_ms)
+            med = float(np.median(tms))
+            out[name].append(dict(reorder=int(reorder), rays=n, trace_ms_median=med, trace_ms_min=float(min(tms)), reorder_ms_median=float(np.median(rms)),
+                                  rays_per_second=n / (med * 1e-3) if med > 0 else 0.0, node_visits_per_ray=q.trace.node_visits / n,
+                                  accepted_hits_per_ray=q.trace.accepted_hits / n))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("scenes", nargs="+")
@@ -99,6 +139,7 @@ def main():
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--rays", type=int, nargs="+", default=[])
+    ap.add_argument("--shadow-rays", type=int, nargs="+", default=[])
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -133,6 +174,9 @@ def main():
             if a.trace_strategy != "full":
                 ap.error("--rays: ray queries take --trace-strategy full only")
             r["ray_queries"] = [probe_rays(scene, p, t, nr, eye, W, H, a.warmup, a.repeats) for nr in a.rays]
+        if a.shadow_rays:
+            tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+            r["shadow_queries"] = [probe_shadow_rays(scene, p, tq, nr, eye, a.warmup, a.repeats) for nr in a.shadow_rays]
         if a.lit:
             p.lighting_mode = 1
             t.trace_strategy = capi.TRACE_STRATEGY_FULL_ANYHIT

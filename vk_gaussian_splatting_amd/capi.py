@@ -181,6 +181,22 @@ class RayQueryOut(C.Structure):
         return dict(self.trace.as_dict(), reorder_ms=self.reorder_ms, invalid_rays=self.invalid_rays)
 
 
+class ShadowResult(C.Structure):
+    """MgsShadowResult (16 bytes; SHADOW_RESULT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("transmittance", C.c_float * 3), ("hits", C.c_uint32)]
+
+
+class SurfacePoint(C.Structure):
+    """MgsSurfacePoint (64 bytes; SURFACE_POINT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("position", C.c_float * 3), ("material", C.c_uint32), ("normal", C.c_float * 3), ("_pad0", C.c_float),
+                ("view_dir", C.c_float * 3), ("_pad1", C.c_float), ("radiance", C.c_float * 3), ("_pad2", C.c_float)]
+
+
+class ShadeResult(C.Structure):
+    """MgsShadeResult (16 bytes; SHADE_RESULT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("color", C.c_float * 3), ("shadow_hits", C.c_uint32)]
+
+
 SENSOR_OPENCV_PINHOLE, SENSOR_OPENCV_FISHEYE = 0, 1
 
 
@@ -224,6 +240,22 @@ def sensor_model_from_frame(params):
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("direction", np.float32, 3), ("t_max", np.float32)])
 RAY_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("transmittance", np.float32), ("t_iso", np.float32), ("id", np.uint32),
                              ("hit_count", np.uint32), ("passes", np.uint32), ("normal", np.float32, 4)])
+
+
+SHADOW_RESULT_DTYPE = np.dtype([("transmittance", np.float32, 3), ("hits", np.uint32)])
+SURFACE_POINT_DTYPE = np.dtype([("position", np.float32, 3), ("material", np.uint32), ("normal", np.float32, 3), ("_pad0", np.float32),
+                                ("view_dir", np.float32, 3), ("_pad1", np.float32), ("radiance", np.float32, 3), ("_pad2", np.float32)])
+SHADE_RESULT_DTYPE = np.dtype([("color", np.float32, 3), ("shadow_hits", np.uint32)])
+
+
+def make_surface_points(position, normal, view_dir, radiance, material=0):
+    """a SURFACE_POINT_DTYPE array from positions, normals, view directions and radiances [n,3] and material indices (scalar or [n])"""
+    o = np.asarray(position, np.float32).reshape(-1, 3)
+    r = np.zeros(o.shape[0], SURFACE_POINT_DTYPE)
+    r["position"], r["normal"] = o, np.asarray(normal, np.float32).reshape(-1, 3)
+    r["view_dir"], r["radiance"] = np.asarray(view_dir, np.float32).reshape(-1, 3), np.asarray(radiance, np.float32).reshape(-1, 3)
+    r["material"] = material
+    return r
 
 
 def make_rays(origin, direction, t_min=0.001, t_max=10000.0):
@@ -341,6 +373,13 @@ def load_library():
         "mgs_trace_rays": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(RayQueryParams), vp, P(RayQueryOut)]),
         "mgs_trace_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(RayQueryParams), vp, P(RayQueryOut)]),
         "mgs_trace_generate_rays": (C.c_int, [vp, P(FrameParams), vp]),
+        "mgs_trace_shadow_rays": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(TraceLightParams), P(RayQueryParams), vp, P(RayQueryOut)]),
+        "mgs_trace_shadow_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(FrameParams), P(TraceParams), P(TraceLightParams), P(RayQueryParams), vp,
+                                                   P(RayQueryOut)]),
+        "mgs_shade_points": (C.c_int, [vp, vp, C.c_uint64, P(Material), C.c_uint32, P(FrameParams), P(TraceParams), P(TraceLightParams),
+                                       P(RayQueryParams), vp, P(TraceLightOut), P(C.c_uint32)]),
+        "mgs_shade_points_device": (C.c_int, [vp, vp, C.c_uint64, P(Material), C.c_uint32, P(FrameParams), P(TraceParams), P(TraceLightParams),
+                                              P(RayQueryParams), vp, P(TraceLightOut), P(C.c_uint32)]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -402,6 +441,7 @@ EXPORTED_SYMBOLS = [
     "mgs_trace_params_default", "mgs_render_traced", "mgs_trace_download_hit_counts",
     "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits", "mgs_render_hybrid",
     "mgs_ray_query_params_default", "mgs_trace_rays", "mgs_trace_rays_device", "mgs_trace_generate_rays",
+    "mgs_trace_shadow_rays", "mgs_trace_shadow_rays_device", "mgs_shade_points", "mgs_shade_points_device",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -847,6 +887,65 @@ class Scene:
             _check(self._lib.mgs_trace_rays(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(params), tr, C.byref(q),
                                             res.ctypes.data_as(C.c_void_p), C.byref(out) if want_stats else None))
         return (res, out) if want_stats else res
+
+    def _query_params(self, reorder):
+        q = RayQueryParams()
+        self._lib.mgs_ray_query_params_default(C.byref(q))
+        q.reorder = int(bool(reorder))
+        return q
+
+    def trace_shadow_rays(self, rays, params, trace=None, light=None, reorder=False, want_stats=False):
+        """mgs_trace_shadow_rays: the caller's shadow rays (a RAY_DTYPE array; t_max is the light's ray parameter) as the light pass of a
+        lit frame traces its own -> a SHADOW_RESULT_DTYPE array (waits).  light = a TraceLightParams (shadows_mode must be
+        MGS_SHADOWS_HARD = 1) or None for the defaults with hard shadows.  want_stats returns (results, RayQueryOut)."""
+        out, q = RayQueryOut(), self._query_params(reorder)
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        res = np.zeros(r.shape[0], SHADOW_RESULT_DTYPE)
+        _check(self._lib.mgs_trace_shadow_rays(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(params),
+                                               C.byref(trace) if trace is not None else None, C.byref(light) if light is not None else None,
+                                               C.byref(q), res.ctypes.data_as(C.c_void_p), C.byref(out) if want_stats else None))
+        return (res, out) if want_stats else res
+
+    def trace_shadow_rays_device(self, rays_device, count, params, results_device, trace=None, light=None, reorder=False, want_stats=False):
+        """mgs_trace_shadow_rays_device: count rays at the device pointer rays_device, results (count * 16 bytes) to results_device, both
+        16-byte aligned; ordered on the handle's stream.  want_stats waits and returns a RayQueryOut."""
+        out, q = RayQueryOut(), self._query_params(reorder)
+        _check(self._lib.mgs_trace_shadow_rays_device(self._h, C.c_void_p(rays_device or None), int(count), C.byref(params),
+                                                      C.byref(trace) if trace is not None else None, C.byref(light) if light is not None else None,
+                                                      C.byref(q), C.c_void_p(results_device or None), C.byref(out) if want_stats else None))
+        return out if want_stats else None
+
+    @staticmethod
+    def _material_array(materials):
+        mats = [m if isinstance(m, Material) else make_material(**m) for m in materials]
+        return (Material * max(len(mats), 1))(*mats), len(mats)
+
+    def shade_points(self, points, materials, params, trace=None, light=None, reorder=False, want_stats=False):
+        """mgs_shade_points: the caller's surface points (a SURFACE_POINT_DTYPE array, make_surface_points) under the scene's lights,
+        each light shadowed by one ray through the splats when light.shadows_mode is MGS_SHADOWS_HARD = 1; materials = a list of Material or
+        of make_material keyword dicts (1 to 256) -> a SHADE_RESULT_DTYPE array (waits).  want_stats returns (results, TraceLightOut,
+        invalid points)."""
+        lout, bad, q = TraceLightOut(), C.c_uint32(0), self._query_params(reorder)
+        pts = np.ascontiguousarray(points, dtype=SURFACE_POINT_DTYPE).reshape(-1)
+        res = np.zeros(pts.shape[0], SHADE_RESULT_DTYPE)
+        arr, n = self._material_array(materials)
+        _check(self._lib.mgs_shade_points(self._h, pts.ctypes.data_as(C.c_void_p), pts.shape[0], arr, n, C.byref(params),
+                                          C.byref(trace) if trace is not None else None, C.byref(light) if light is not None else None,
+                                          C.byref(q), res.ctypes.data_as(C.c_void_p), C.byref(lout) if want_stats else None,
+                                          C.byref(bad) if want_stats else None))
+        return (res, lout, int(bad.value)) if want_stats else res
+
+    def shade_points_device(self, points_device, count, materials, params, results_device, trace=None, light=None, reorder=False,
+                            want_stats=False):
+        """mgs_shade_points_device: count points at the device pointer points_device, results (count * 16 bytes) to results_device, both
+        16-byte aligned; ordered on the handle's stream.  want_stats waits and returns (TraceLightOut, invalid points)."""
+        lout, bad, q = TraceLightOut(), C.c_uint32(0), self._query_params(reorder)
+        arr, n = self._material_array(materials)
+        _check(self._lib.mgs_shade_points_device(self._h, C.c_void_p(points_device or None), int(count), arr, n, C.byref(params),
+                                                 C.byref(trace) if trace is not None else None, C.byref(light) if light is not None else None,
+                                                 C.byref(q), C.c_void_p(results_device or None), C.byref(lout) if want_stats else None,
+                                                 C.byref(bad) if want_stats else None))
+        return (lout, int(bad.value)) if want_stats else None
 
     def generate_rays(self, params, rays_device):
         """mgs_trace_generate_rays: the primary rays render_traced would trace for params, written row-major to the device pointer

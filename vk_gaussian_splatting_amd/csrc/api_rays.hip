@@ -14,7 +14,7 @@ void mgs_ray_query_params_default(MgsRayQueryParams* q)
 
 // *p with every field a ray query does not read set to a value that is in range and reads no memory: the caller's camera, frame
 // size, strip rows, lens, sample and target are neither read nor checked
-static MgsFrameParams withoutCamera(const MgsFrameParams& p)
+MgsFrameParams withoutCamera(const MgsFrameParams& p)
 {
   MgsFrameParams q = p;
   std::memset(q.view, 0, sizeof(q.view));
@@ -44,9 +44,10 @@ struct RayBatch
 }  // namespace
 
 // the checks that need no device, in the order of the other traced entry points
-static int validateRays(const MgsFrameParams* p, const MgsTraceParams& t, const MgsRayQueryParams& q, const void* rays, const void* results,
-                        uint64_t count, bool onDevice, const char* what)
+int validateRays(const MgsFrameParams* p, const MgsTraceParams& t, const MgsRayQueryParams& q, const void* rays, const void* results, uint64_t count,
+                 bool onDevice, const char* what, const char* items)
 {
+  const std::string w = std::string(what) + ": ", n(items);
   if(!p)
     return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null params");
   const MgsFrameParams v = withoutCamera(*p);
@@ -58,11 +59,11 @@ static int validateRays(const MgsFrameParams* p, const MgsTraceParams& t, const 
   if(q.reorder != 0 && q.reorder != 1)
     return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": reorder must be 0 or 1");
   if(count > 0 && (!rays || !results))
-    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": null rays or results with count > 0");
+    return failTrace(MGS_ERR_INVALID_ARG, w + "null " + n + " or results with count > 0");
   if(count > 0x7FFFFFFFull)
-    return failTrace(MGS_ERR_UNSUPPORTED, std::string(what) + ": at most 2^31 - 1 rays per call");
+    return failTrace(MGS_ERR_UNSUPPORTED, w + "at most 2^31 - 1 " + n + " per call");
   if(onDevice && (((uintptr_t)rays | (uintptr_t)results) & 15u))
-    return failTrace(MGS_ERR_INVALID_ARG, std::string(what) + ": rays and results must be 16-byte aligned");
+    return failTrace(MGS_ERR_INVALID_ARG, w + n + " and results must be 16-byte aligned");
   return MGS_OK;
 }
 

@@ -9,7 +9,7 @@ static void materialDefault(MgsMaterial& m)
   std::memset(&m, 0, sizeof(m));
   m.emission[0] = m.emission[1] = m.emission[2] = 1.0f;
 }
-static MaterialDev materialToDevice(const MgsMaterial& m)
+MaterialDev materialToDevice(const MgsMaterial& m)
 {
   MaterialDev d{};
   std::memcpy(d.ambient, m.ambient, 12);

@@ -417,6 +417,37 @@ struct TraceLightArgs
   float               shadowOffset, shadowThreshold, shadowColorStrength;
 };
 
+// what a shadow or light query (k_shadow_query.hip; mgs_trace_shadow_rays, mgs_shade_points) receives by value: the traversal's
+// arguments (image, hit counts and side outputs stay null) and the caller's batch.  A shadow ray is a ray query's two float4; a
+// surface point four, (position, material index as bits), (normal, -), (view direction, -), (radiance, -).  A result is one float4:
+// (transmittance, hits as bits) of a shadow ray, (colour, shadow hits as bits) of a point.
+struct ShadowQueryArgs
+{
+  TraceArgs           t;
+  const float4*       items;     // [2 * count] rays or [4 * count] points
+  float4*             results;   // [count], at the item's index in the caller's order
+  const uint32_t*     perm;      // [count] lane -> item index (a reordered batch), or null: the caller's order
+  uint32_t            count;
+  uint32_t*           invalid;   // [1] items that were refused
+  TraceLightCounters* lctr;      // points: the shadow rays' sums (the rays' own go to t.ctr)
+  const LightTable*   table;     // points: the scene's lights
+  const MaterialDev*  mats;      // points: the call's materials
+  uint32_t            matCount;
+  int32_t             shadowsMode;  // points: MGS_SHADOWS_*
+  int32_t             shFormat;     // storage format of the SH records (read when shadowColorStrength != 0)
+  float               shadowOffset, shadowThreshold, shadowColorStrength;
+  float               cameraPos[3];  // points: the headlight's position
+};
+// the coherence keys of a reordered batch of points (k_points_key): the Morton cell of the position alone
+struct PointKeyArgs
+{
+  const float4* points;  // [4 * count]
+  uint32_t*     keys;
+  uint32_t*     idx;
+  uint32_t      count;
+  float         sceneLo[3], sceneInvExt[3];
+};
+
 // what the hand-over of a hybrid frame (k_hybrid.hip, mgs_render_hybrid) receives by value: the raster pass's pixel and side outputs
 // in, the light pass's per-pixel inputs (TraceLightArgs) out
 struct HybridSurfaceArgs

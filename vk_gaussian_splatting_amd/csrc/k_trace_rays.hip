@@ -107,21 +107,23 @@ __global__ __launch_bounds__(256) void k_rays_generate(const FrameArgs* __restri
   rays[2 * (size_t)i + 1] = make_float4(d[0], d[1], d[2], ok ? 10000.0f : 0.0f);
 }
 
-// what mgs.h calls an invalid ray; written so that a NaN anywhere fails it
-__device__ __forceinline__ bool rayValid(const float4& o, const float4& d)
-{
-  const float big = 3.4028234664e38f;
-  const bool  fin = fabsf(o.x) <= big && fabsf(o.y) <= big && fabsf(o.z) <= big && fabsf(o.w) <= big && fabsf(d.x) <= big && fabsf(d.y) <= big
-                   && fabsf(d.z) <= big && fabsf(d.w) <= big;
-  return fin && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f) && o.w <= d.w;
-}
-
 __device__ __forceinline__ uint32_t raySpread7(uint32_t v)
 {  // 7 bits to every third bit
   v = (v | (v << 8)) & 0x0000700Fu;
   v = (v | (v << 4)) & 0x000430C3u;
   v = (v | (v << 2)) & 0x00049249u;
   return v;
+}
+
+// 21 bits of Morton code of a position's cell in the scene box, 128 cells per axis (positions outside are clamped)
+__device__ __forceinline__ uint32_t mortonCell21(const float4& o, const float (&lo)[3], const float (&invExt)[3])
+{
+  const float oc[3] = {o.x, o.y, o.z};
+  uint32_t    q[3];
+#pragma unroll
+  for(int c = 0; c < 3; ++c)
+    q[c] = (uint32_t)fminf(fmaxf((oc[c] - lo[c]) * invExt[c], 0.0f) * 128.0f, 127.0f);
+  return raySpread7(q[0]) | (raySpread7(q[1]) << 1) | (raySpread7(q[2]) << 2);
 }
 
 // coherence key of a ray: 21 bits of Morton code of the origin's cell in the scene box (origins outside are clamped), the direction's
@@ -136,19 +138,30 @@ __global__ __launch_bounds__(256) void k_rays_key(RayKeyArgs a)
   uint32_t     key = 0xFFFFFFFFu;
   if(rayValid(o, d))
   {
-    const float oc[3] = {o.x, o.y, o.z};
-    uint32_t    q[3];
-#pragma unroll
-    for(int c = 0; c < 3; ++c)
-      q[c] = (uint32_t)fminf(fmaxf((oc[c] - a.sceneLo[c]) * a.sceneInvExt[c], 0.0f) * 128.0f, 127.0f);
     const float    ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
     const float    m  = fmaxf(fmaxf(ax, ay), az);  // (scaled by the largest component first: the 1-norm of a huge direction would overflow)
     const float    sx = ax / m, sy = ay / m, sz = az / m, n1 = sx + sy + sz;
     const uint32_t qx = (uint32_t)fminf(sx / n1 * 16.0f, 15.0f), qy = (uint32_t)fminf(sy / n1 * 16.0f, 15.0f);
     const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-    const uint32_t mort = raySpread7(q[0]) | (raySpread7(q[1]) << 1) | (raySpread7(q[2]) << 2);
+    const uint32_t mort = mortonCell21(o, a.sceneLo, a.sceneInvExt);
     key = min((mort << 11) | (oct << 8) | (qx << 4) | qy, 0xFFFFFFFEu);
   }
+  a.keys[i] = key;
+  a.idx[i]  = i;
+}
+
+// the key kernel's second entry, for a batch of surface points (mgs_shade_points): the position's Morton cell alone, in the bits the
+// rays' keys keep it in; a point with a non-finite position gets the largest key (the shading kernel decides what is invalid)
+__global__ __launch_bounds__(256) void k_points_key(PointKeyArgs a)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if(i >= a.count)
+    return;
+  const float4 o   = a.points[4 * (size_t)i];
+  const float  big = 3.4028234664e38f;
+  uint32_t     key = 0xFFFFFFFFu;
+  if(fabsf(o.x) <= big && fabsf(o.y) <= big && fabsf(o.z) <= big)
+    key = mortonCell21(o, a.sceneLo, a.sceneInvExt) << 11;
   a.keys[i] = key;
   a.idx[i]  = i;
 }
@@ -293,6 +306,12 @@ void launchRaysKey(hipStream_t stream, const RayKeyArgs& a)
 {
   if(a.count)
     hipLaunchKernelGGL(k_rays_key, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, a);
+}
+
+void launchPointsKey(hipStream_t stream, const PointKeyArgs& a)
+{
+  if(a.count)
+    hipLaunchKernelGGL(k_points_key, dim3((a.count + 255u) / 256u), dim3(256), 0, stream, a);
 }
 
 void launchTraceRays(hipStream_t stream, const TraceRaysArgs& a, int shFormat)

@@ -135,6 +135,10 @@ void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameCo
 void launchRaysGenerate(hipStream_t stream, const FrameArgs* dArgs, float4* rays, uint32_t pixels);
 void launchRaysKey(hipStream_t stream, const RayKeyArgs& a);
 void launchTraceRays(hipStream_t stream, const TraceRaysArgs& a, int shFormat);
+void launchPointsKey(hipStream_t stream, const PointKeyArgs& a);  // a batch of surface points: the position's Morton cell
+// shadow and light queries (k_shadow_query.hip): one shadow ray, or one surface point under the scene's lights, per lane
+void launchShadowRays(hipStream_t stream, const ShadowQueryArgs& a);
+void launchShadePoints(hipStream_t stream, const ShadowQueryArgs& a);
 // the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);

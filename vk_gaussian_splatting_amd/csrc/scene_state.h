@@ -478,9 +478,9 @@ struct MeshPassState
 
 // the traced pipeline's per-handle state (mgs_render_traced): hit counts and counters of the last traced frame, the scratch of a
 // hierarchy build this handle ran (freed when the build is done), the events around build and frame
-enum TraceEvent  // TracePassState::ev: the brackets of build_ms, trace_ms, light_ms and reorder_ms
+enum TraceEvent  // TracePassState::ev: the brackets of build_ms, trace_ms, light_ms and reorder_ms; the upload of queryMatsHost
 {
-  kEvBuildBegin, kEvBuildEnd, kEvTraverseBegin, kEvTraverseEnd, kEvLightBegin, kEvLightEnd, kEvReorderBegin, kEvReorderEnd, kEvCount
+  kEvBuildBegin, kEvBuildEnd, kEvTraverseBegin, kEvTraverseEnd, kEvLightBegin, kEvLightEnd, kEvReorderBegin, kEvReorderEnd, kEvMatsUploaded, kEvCount
 };
 struct TracePassState
 {
@@ -498,6 +498,8 @@ struct TracePassState
   // reordered batch's coherence keys and ray indices (sorted in place: the indices become the permutation)
   DevBuf<float4>             rayStage, resultStage;
   DevBuf<uint32_t>           rayInvalid, rayKeys, rayIdx;
+  DevBuf<MaterialDev>        queryMats;  // a light query's materials (mgs_shade_points, api_shadow_query.hip): the call's array, uploaded
+  std::vector<MaterialDev>   queryMatsHost;  // ... converted: the source of that upload, rewritten only after kEvMatsUploaded
   int                   w = 0, h = 0;
   bool                  have = false, haveLit = false;
   hipEvent_t            ev[kEvCount] = {};  // indexed by TraceEvent
@@ -505,7 +507,7 @@ struct TracePassState
   void eachBuffer(F&& f)
   {
     f(hitCount); f(ctr); f(keys); f(vals); f(leafCount); f(leafBox); f(isoDist); f(radiance); f(shadowHits); f(lctr); f(hybridNormal);
-    f(rayStage); f(resultStage); f(rayInvalid); f(rayKeys); f(rayIdx);
+    f(rayStage); f(resultStage); f(rayInvalid); f(rayKeys); f(rayIdx); f(queryMats);
   }
   void release()
   {
@@ -664,6 +666,7 @@ struct MgsScene_t
 // ---- helpers more than one unit calls ---------------------------------------------------------------------------------------
 int  sizeWorkingSet(MgsScene s);                                              // api_scene.hip
 int  ensureLightTable(SceneData& d);                                          // api_scene.hip
+MaterialDev materialToDevice(const MgsMaterial& m);                           // api_scene.hip: with needShading derived
 void mapIdsToCaller(MgsScene s, uint32_t* ids, size_t n);                     // api_scene.hip: storage global id -> caller's
 void mapIdsToStorage(MgsScene s, uint32_t* ids, size_t n);                    // ... and back
 int  buildFrameArgs(MgsScene s, const MgsFrameParams* p, FrameArgs& A);       // api_frameargs.hip
@@ -707,6 +710,11 @@ P paramsOr(const P* p, void (*defaults)(P*))
 inline MgsTraceParams      traceParamsOr(const MgsTraceParams* tp) { return paramsOr(tp, mgs_trace_params_default); }
 inline MgsTraceLightParams traceLightParamsOr(const MgsTraceLightParams* lp) { return paramsOr(lp, mgs_trace_light_params_default); }
 inline MgsRayQueryParams   rayQueryParamsOr(const MgsRayQueryParams* qp) { return paramsOr(qp, mgs_ray_query_params_default); }
+// api_rays.hip, shared with the shadow and light queries of api_shadow_query.hip: *p without the fields a query does not read, and
+// the checks of a batch that need no device (`items`: what the batch holds, "rays" or "points", for the messages)
+MgsFrameParams withoutCamera(const MgsFrameParams& p);
+int  validateRays(const MgsFrameParams* p, const MgsTraceParams& t, const MgsRayQueryParams& q, const void* rays, const void* results,
+                  uint64_t count, bool onDevice, const char* what, const char* items = "rays");
 int  traceFrameArgs(MgsScene s, MgsFrameParams& q, const char* what, bool rayInverses, std::unique_ptr<FrameArgs>& A);
 void sceneBox(const SceneData& d, float lo[3], float invExt[3]);
 int  ensureHierarchy(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, float* buildMs, uint32_t* rebuilt);

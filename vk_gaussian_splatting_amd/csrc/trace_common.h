@@ -1,6 +1,6 @@
 // trace_common.h — what the hierarchy build (k_bvh.hip) and the traversal (k_trace.hip) must compute alike: the particle as the
 // 3DGRT shaders fetch it and the proxy ellipsoid's threshold and radius (the generalised-Gaussian response itself: kernelResponse,
-// gut_common.h, shared with the 3DGUT compositor).
+// gut_common.h, shared with the 3DGUT compositor); and what the ray and shadow queries must refuse alike (rayValid).
 #pragma once
 #include "gut_common.h"
 #include "kernels_common.h"
@@ -41,6 +41,15 @@ __device__ __forceinline__ float proxyRadius(const TraceProxy& P, float thr)
   const float n = (float)P.kernelDegree;
   const float s = -4.5f / powf(3.0f, n);
   return powf(logf(thr) / s, 1.0f / n);
+}
+
+// what mgs.h calls an invalid ray; written so that a NaN anywhere fails it
+__device__ __forceinline__ bool rayValid(const float4& o, const float4& d)
+{
+  const float big = 3.4028234664e38f;
+  const bool  fin = fabsf(o.x) <= big && fabsf(o.y) <= big && fabsf(o.z) <= big && fabsf(o.w) <= big && fabsf(d.x) <= big && fabsf(d.y) <= big
+                   && fabsf(d.z) <= big && fabsf(d.w) <= big;
+  return fin && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f) && o.w <= d.w;
 }
 
 }  // namespace mgs
