@@ -53,7 +53,9 @@ extern "C" {
                             sensor models (MGS_HAS_SENSOR_MODEL below): entry points and one new struct, both numbers stay —
                                  mgs_sensor_model_from_frame, mgs_frame_set_sensor;
                             shadow and light queries (MGS_HAS_SHADOW_QUERY below): entry points and new structs, both numbers stay —
-                                 mgs_trace_shadow_rays, mgs_trace_shadow_rays_device, mgs_shade_points, mgs_shade_points_device */
+                                 mgs_trace_shadow_rays, mgs_trace_shadow_rays_device, mgs_shade_points, mgs_shade_points_device;
+                            mesh ray queries (MGS_HAS_MESH_RAY_QUERY below): entry points and new structs, both numbers stay —
+                                 mgs_mesh_ray_params_default, mgs_trace_mesh_rays, mgs_trace_mesh_rays_device */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
@@ -62,6 +64,8 @@ extern "C" {
 #define MGS_HAS_RAY_QUERY 1     /* feature macro: mgs_trace_rays and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_SHADOW_QUERY 1  /* feature macro: mgs_trace_shadow_rays, mgs_shade_points and their _device variants exist (added within ABI 5.1, no
                                   existing struct or default changed) */
+#define MGS_HAS_MESH_RAY_QUERY 1 /* feature macro: mgs_trace_mesh_rays and its companions exist (added within ABI 5.1, no existing struct or default
+                                   changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
@@ -1028,6 +1032,119 @@ int mgs_shade_points_device(MgsScene scene_or_context, const MgsSurfacePoint* po
                             const MgsTraceLightParams* light /* NULL = defaults */, const MgsRayQueryParams* query /* NULL = defaults */,
                             MgsShadeResult* results_device, MgsTraceLightOut* light_out /* may be NULL */,
                             uint32_t* invalid_points /* may be NULL */);
+
+/* ---- mesh ray queries (MGS_HAS_MESH_RAY_QUERY): the caller's rays against the scene's triangle meshes.  Replaces, for rays the
+ * caller supplies, the mesh TLAS with traceBounceRayMeshes (shaders/threedgrt_raytrace.rgen.slang:495-553), the closest-hit shader
+ * (shaders/threedgrt_raytrace.rchit.slang:31-67) and traceShadowRayMesh (rgen:1295-1341).  For picking on meshes, reflection and
+ * refraction rays shot from or at meshes, mesh-on-mesh shadow rays (multiply the result with mgs_trace_shadow_rays' splat shadow), and
+ * as a second, independent implementation next to the mesh rasteriser.  Everything here is additive: no frame kernel and no other
+ * entry point looks at the triangle hierarchy yet.
+ *
+ * The hierarchy.  One leaf per triangle of every mesh instance, in world space: world vertices are M p in fp32, the products in the
+ * order of the mesh pass's vertex stage (mgs_meshes_render: ((x m0 + y m4) + z m8) + m12), here with each operation rounded once.
+ * The rasteriser's kernel writes the same expression but leaves the compiler free to fuse a product into the following sum, so
+ * the two triangles are the same up to that contraction: a vertex may differ in its last bit.  A triangle with a non-finite world vertex or with zero area in float (the cross
+ * product of its edge vectors is exactly 0) gets no leaf.  The leaf's box is the min / max of the three vertices inflated by 4 ulps
+ * of its extent plus 2 ulps of its magnitude per axis.  The tree is the splat hierarchy's implicit complete 8-ary tree: leaves sorted
+ * (the library's stable radix sort) by the 30-bit Morton code of the leaf centroid in the meshes' world box, which the host computes
+ * in double from the meshes' local boxes and the instances' transforms; a node bounds eight consecutive nodes of the level below.  No
+ * pointers, no atomics: the build is bit-reproducible.  Triangle records (world vertices, global primitive id, instance id, material
+ * id; 48 B) are stored in leaf order.  The hierarchy belongs to the SCENE and is shared by its frame contexts; it is rebuilt lazily
+ * by the next mesh query after mgs_mesh_instance_add or mgs_mesh_instance_set_transform, and a rebuild first waits for the work in
+ * flight on all contexts (the rule of the splat hierarchy).  Mesh queries on different contexts of one scene may run from different
+ * threads: the check, a rebuild and the query's launches are serialised by a mutex of the hierarchy.  The editing calls
+ * (mgs_mesh_instance_*) are not part of that: do not edit the scene while another thread queries it.  Its bytes count into scene_bytes of mgs_scene_memory_usage; staging,
+ * keys and counters belong to the handle and count into working_bytes.  mgs_mesh_instance_set_visible does NOT rebuild: visibility
+ * is read per candidate triangle at query time from the device mesh table.  No mesh instance, or no valid triangle: every ray
+ * misses and nothing is launched for the build.
+ *
+ * The ray and its window.  The ray is an MgsRay, used AS GIVEN: the direction is not renormalised and t is the parameter along the
+ * given direction, as in mgs_trace_rays.  A hit needs t_min' < t < t_max with t_min' = max(t_min, 0): both ends are OPEN and there is
+ * no epsT; the caller adds 0.001 where it wants the reference's TMin.  What the reference's hardware does with a hit exactly at an
+ * end of the window is PARITY UNPINNED.  An invalid ray (a non-finite component, t_min and t_max included, a zero-length direction or
+ * t_min > t_max) never reaches the traversal: it is a miss and is counted in invalid_rays (a per-ray outcome, not an error code).
+ *
+ * Intersection.  Watertight, both facings: the reference sets VK_GEOMETRY_INSTANCE_TRIANGLE_FACING_CULL_DISABLE_BIT_KHR on every
+ * mesh instance (src/mesh_manager_vk.cpp:446), so the RAY_FLAG_CULL_BACK_FACING_TRIANGLES of its mesh rays has no effect and back
+ * faces are hit.  The test is the shear-to-ray-space formulation of Woop, Benthin and Wald (JCGT 2013): the vertices are moved to
+ * the ray's origin and sheared so that the ray runs along the axis of its largest direction component; the three edge functions are
+ * taken from the sheared x and y, each product and difference rounded once (never contracted into a fused multiply-add), so an edge
+ * shared by two triangles gives both the same magnitude with the opposite sign; edges are inclusive (all three >= 0 or all three
+ * <= 0); when any edge function is exactly 0 the three are recomputed in double; t = (U z0 + V z1 + W z2) / (U + V + W) with the
+ * sheared z.  The fixed-function test of the reference's device is not specified beyond watertightness: which of two triangles a ray
+ * exactly on their shared edge reports, and the last bits of t and of the barycentrics, are PARITY UNPINNED.
+ * Ties.  Two hits with bit-identical t resolve to the LOWER global primitive id, whatever the order of traversal.
+ *
+ * MGS_MESH_RAYS_CLOSEST reports the nearest hit: t; instance_id (creation order); primitive_id, the GLOBAL primitive id, exactly the
+ * id mgs_meshes_download(which = 2) reports (instances concatenated in creation order, visible or not); material_id (the
+ * triangle's index into its mesh's materials); the barycentrics b1, b2 of vertices 1 and 2 (rchit.slang:50-51; vertex 0 has
+ * 1 - b1 - b2); position = the instance transform of the interpolated LOCAL positions (rchit.slang:54-55); normal =
+ * normalize(transpose(transformRotScaleInverse) n) of the interpolated vertex normals (rchit.slang:58-59), with the
+ * transformRotScaleInverse the mesh pass uses, NOT flipped towards the ray; hit = 1.  A miss is t = +inf, all three ids 0xFFFFFFFF,
+ * position, normal and barycentrics 0, hit = 0.
+ * MGS_MESH_RAYS_OCCLUSION reports only whether ANYTHING is hit in the window (traceShadowRayMesh with
+ * RAY_FLAG_ACCEPT_FIRST_HIT_AND_END_SEARCH): hit = 1 or 0, every other field as for a miss; the traversal stops at the first hit it
+ * finds.  Meshes carry no transmittance here (MgsMaterial has no such field and the OBJ subset reads no Tf), so every mesh is
+ * opaque and the shadow is transmittance 1 - hit; a boolean keeps "first hit" deterministic.  Coloured mesh shadows are later work.
+ *
+ * Independence from the splats.  A scene without splats may be queried (mesh instances do not need mgs_scene_commit); the splat
+ * hierarchy is neither built nor read; a bound occluder or sensor is not looked at; the handle's frame, side outputs, hit counts and
+ * mesh-pass images stay untouched.  A hierarchy build and a reorder run mgs_radix_sort_u32 on the handle, which rewrites the handle's
+ * per-frame device counters: mgs_frame_stats and mgs_frame_row_costs of an earlier frame are not meaningful afterwards (a frame
+ * context keeps the two apart).
+ * Reorder (params->reorder = 1): the ray queries' coherence key and sort (see there) with the meshes' world box in place of the
+ * scene's.  Hits and integer statistics are identical with and without it, bit for bit.
+ *
+ * Arguments, checked before the handle is looked at: mode not one of the two, reorder not 0 / 1, a non-zero reserved word, NULL rays
+ * or hits with count > 0, misaligned device pointers: MGS_ERR_INVALID_ARG; more than 2^31 - 1 rays: MGS_ERR_UNSUPPORTED.  `params`
+ * NULL = the defaults (closest, no reorder).  count == 0 is MGS_OK without a launch.  mgs_trace_mesh_rays copies the batch through
+ * staging buffers of the handle and waits; mgs_trace_mesh_rays_device takes device pointers (16-byte aligned), is ordered on the
+ * handle's stream and, with reorder = 0 and no rebuild due, waits only when `out` is non-NULL.
+ *
+ * Out of scope here, and what the hierarchy is meant to serve next: mesh hits inside mgs_render_traced, mgs_render_traced_lit and
+ * mgs_render_hybrid (the frame follow-up: the same traversal and triangle test called from the frame kernels), and mesh occlusion
+ * inside mgs_trace_shadow_rays and mgs_shade_points (the occlusion mode's walk).  Not planned on it: mesh material transmittance,
+ * ior, reflection and refraction bounces, light proxies, ray masks, refitting instead of rebuilding, mgs_render_gathered. */
+typedef enum MgsMeshRayMode {
+  MGS_MESH_RAYS_CLOSEST   = 0,
+  MGS_MESH_RAYS_OCCLUSION = 1
+} MgsMeshRayMode;
+typedef struct MgsMeshHit {     /* 64 B = four 16-byte vectors; arrays of it on the device must be 16-byte aligned */
+  float    t;                   /* offset  0: ray parameter of the hit; +inf = miss (and always in occlusion mode) */
+  uint32_t instance_id;         /*         4: mesh instance, creation order; 0xFFFFFFFF = none */
+  uint32_t primitive_id;        /*         8: global primitive id as mgs_meshes_download(which = 2); 0xFFFFFFFF = none */
+  uint32_t material_id;         /*        12: index into the mesh's materials; 0xFFFFFFFF = none */
+  float    position[3];         /*        16: world position */
+  float    b1;                  /*        28: barycentric weight of vertex 1 */
+  float    normal[3];           /*        32: world normal, unit length, not flipped towards the ray */
+  float    b2;                  /*        44: barycentric weight of vertex 2 */
+  uint32_t hit;                 /*        48: 1 = something is hit in the window, 0 = nothing */
+  uint32_t reserved[3];         /*        52: written as 0 */
+} MgsMeshHit;
+typedef struct MgsMeshRayParams {
+  int32_t  mode;    /* MgsMeshRayMode, default MGS_MESH_RAYS_CLOSEST */
+  int32_t  reorder; /* 0 / 1, default 0 */
+  uint32_t reserved[2]; /* must be 0 */
+} MgsMeshRayParams;
+typedef struct MgsMeshRayOut {
+  uint64_t triangles;      /* triangles of all mesh instances, visible or not */
+  uint64_t leaves;         /* ... that got a leaf */
+  uint64_t nodes;          /* nodes of all levels, the leaves included */
+  uint64_t node_visits;    /* integer sums over the valid rays of the batch */
+  uint64_t triangle_tests; /* ray/triangle tests (triangles of invisible instances are skipped before the test) */
+  uint64_t hits;           /* rays with hit = 1 */
+  uint32_t invalid_rays;
+  uint32_t bvh_rebuilt;    /* 1: this call rebuilt the hierarchy */
+  float    build_ms;       /* HIP events around the build's launches (0 when nothing was built) */
+  float    trace_ms;       /* HIP events around the ray/triangle kernel */
+  float    reorder_ms;     /* HIP events around the key and sort launches, the sort's host waits included (0 without reorder) */
+  uint32_t reserved;
+} MgsMeshRayOut;
+void mgs_mesh_ray_params_default(MgsMeshRayParams* params);
+int  mgs_trace_mesh_rays(MgsScene scene_or_context, const MgsRay* rays_host, uint64_t count, const MgsMeshRayParams* params /* NULL = defaults */,
+                         MgsMeshHit* hits_host, MgsMeshRayOut* out /* may be NULL */);
+int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_device, uint64_t count,
+                                const MgsMeshRayParams* params /* NULL = defaults */, MgsMeshHit* hits_device, MgsMeshRayOut* out /* may be NULL */);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

@@ -121,6 +121,7 @@ def main():
     ap.add_argument("--background", default=None, metavar="FILE.npy")
     ap.add_argument("--mesh", action="append", default=[], metavar="FILE.obj")
     ap.add_argument("--mesh-transform", action="append", type=float, nargs=16, default=[], metavar="M")
+    ap.add_argument("--mesh-pick-image", default=None, metavar="OUT.npy")  # --mesh: closest-hit global primitive ids of the primary rays (mgs_trace_mesh_rays_device)
     ap.add_argument("--mesh-shadows", type=int, choices=[0, 1], default=0)  # --mesh --lighting 1: the splats' shadows on the meshes
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
@@ -206,6 +207,17 @@ def main():
             scene.add_mesh_instance(*meshes[-1])
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
+        if a.mesh_pick_image:
+            # the frame's primary rays (mgs_trace_generate_rays) against the meshes: uint32 [H, W], 0xFFFFFFFF = nothing hit
+            import torch
+            rays = torch.empty(p.width * p.height * 8, dtype=torch.float32, device="cuda")
+            hits = torch.empty(p.width * p.height * 16, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            scene.generate_rays(p, rays.data_ptr())
+            ro = scene.trace_mesh_rays_device(rays.data_ptr(), p.width * p.height, hits.data_ptr(), want_stats=True)
+            pick = hits.cpu().numpy().view(capi.MESH_HIT_DTYPE)["primitive_id"].reshape(p.height, p.width)
+            np.save(a.mesh_pick_image, pick)
+            print(f"mesh pick image: {ro.hits} of {p.width * p.height} rays hit, {ro.leaves} leaves, build {ro.build_ms:.3f} ms, trace {ro.trace_ms:.3f} ms")
         if a.mesh_shadows:
             held = shade_mesh_pixels(scene, meshes, p, V, P, a)  # the occluder's images: keep them until the frame is downloaded
     if a.pipeline != "trace" and (a.trace_strategy != "full" or a.accumulate != 1):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
@@ -17,6 +17,9 @@ frame, whose lanes are 8 x 8 pixels where the row-major batch's are 64 x 1.
 --shadow-rays N adds shadow queries (mgs_trace_shadow_rays_device) of N rays toward one point light above the scene, for every N
 given: a RANDOM batch (origins uniform in the ball of the camera's distance) and a COHERENT one (origins on a regular grid of the
 plane below the scene, row-major), each with reorder off and on: the median trace_ms and reorder_ms and the rays per second.
+--mesh-rays N [--mesh file.obj] needs no syn: scene: mesh ray queries (mgs_trace_mesh_rays_device) of about N rays against the mesh
+(default: tests/golden/meshes/fixture.obj) instanced on a 3 x 3 grid: a CAMERA batch (mgs_trace_generate_rays) and a RANDOM batch,
+closest and occlusion mode, reorder off and on: MgsMeshRayOut with the median trace_ms and reorder_ms, and the build time.
 Needs an MI355X.
 """
 import argparse
@@ -44,6 +47,52 @@ def random_rays(n, radius, seed=1):
     d = target - o
     d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
     return capi.make_rays(o, d)
+
+
+def probe_mesh_rays(path, n, W, H, warmup, repeats):
+    """the eight mesh-ray runs of --mesh-rays for one batch size: (camera, random) x (closest, occlusion) x (reorder off, on)"""
+    import torch
+    scene = mgs.Scene(0)
+    mesh = capi.Mesh.load_obj(path)
+    pos = mesh.view()["positions"]
+    ext = float(np.abs(pos).max()) * 2.5
+    for i in range(9):
+        M = np.eye(4, dtype=np.float32)
+        M[0, 3], M[2, 3] = (i % 3 - 1) * ext, (i // 3 - 1) * ext
+        scene.add_mesh_instance(mesh, M)
+    eye = np.float32([2.0 * ext, 1.5 * ext, 2.5 * ext])
+    w, h = camera_frame_size(n, W, H)
+    pc = capi.default_params(w, h)
+    V, P = mgs.camera_lookat_perspective(eye, [0, 0, 0], [0, 1, 0], 60.0, 0.1, 2000.0, w, h)
+    capi.set_camera(pc, V, P, eye)
+    cam = torch.empty(w * h * 8, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    scene.generate_rays(pc, cam.data_ptr())
+    scene.sync()
+    rnd = torch.from_numpy(random_rays(n, float(np.linalg.norm(eye))).view(np.float32).copy()).cuda()
+    out = dict(requested=n, mesh=os.path.basename(path), instances=9, runs=[])
+    for batch, dev, count in (("camera", cam, w * h), ("random", rnd, n)):
+        hits = torch.empty(count * 16, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        for mode, tag in ((capi.MESH_RAYS_CLOSEST, "closest"), (capi.MESH_RAYS_OCCLUSION, "occlusion")):
+            for reorder in (False, True):
+                tms, rms = [], []
+                for k in range(warmup + repeats):
+                    o = scene.trace_mesh_rays_device(dev.data_ptr(), count, hits.data_ptr(), mode=mode, reorder=reorder, want_stats=True)
+                    if o.bvh_rebuilt:
+                        out["build_ms"] = float(o.build_ms)
+                    if k >= warmup:
+                        tms.append(o.trace_ms)
+                        rms.append(o.reorder_ms)
+                d = {k: v for k, v in o.as_dict().items() if not k.endswith("_ms")}
+                d.update(batch=batch, mode=tag, reorder=int(reorder), rays=count, trace_ms_median=float(np.median(tms)), trace_ms_min=float(min(tms)),
+                         trace_ms_max=float(max(tms)), reorder_ms_median=float(np.median(rms)), node_visits_per_ray=o.node_visits / count,
+                         triangle_tests_per_ray=o.triangle_tests / count)
+                out["runs"].append(d)
+    out["scene_bytes"] = scene.memory_usage()[0]
+    scene.close()
+    mesh.close()
+    return out
 
 
 def camera_frame_size(n, W, H):
@@ -130,7 +179,7 @@ def probe_shadow_rays(scene, p, t, n, eye, warmup, repeats):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("scenes", nargs="+")
+    ap.add_argument("scenes", nargs="*")
     ap.add_argument("--size", type=int, nargs=2, default=[1920, 1080])
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
@@ -140,10 +189,18 @@ def main():
     ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--rays", type=int, nargs="+", default=[])
     ap.add_argument("--shadow-rays", type=int, nargs="+", default=[])
+    ap.add_argument("--mesh-rays", type=int, nargs="+", default=[])
+    ap.add_argument("--mesh", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "meshes", "fixture.obj"))
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
+    if not a.scenes and not a.mesh_rays:
+        ap.error("give at least one syn:<n> scene, or --mesh-rays N")
     results = []
+    for nr in a.mesh_rays:
+        r = dict(mesh_ray_queries=probe_mesh_rays(a.mesh, nr, W, H, a.warmup, a.repeats), repeats=a.repeats, warmup=a.warmup)
+        print(json.dumps(r))
+        results.append(r)
     for name in a.scenes:
         if not name.startswith("syn:"):
             ap.error("scenes are syn:<n>")

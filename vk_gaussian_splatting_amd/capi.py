@@ -197,6 +197,37 @@ class ShadeResult(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("shadow_hits", C.c_uint32)]
 
 
+# MgsMeshRayMode (MgsMeshRayParams::mode)
+MESH_RAYS_CLOSEST, MESH_RAYS_OCCLUSION = 0, 1
+
+
+class MeshHit(C.Structure):
+    """MgsMeshHit (64 bytes; MESH_HIT_DTYPE is the same layout for numpy)"""
+    _fields_ = [("t", C.c_float), ("instance_id", C.c_uint32), ("primitive_id", C.c_uint32), ("material_id", C.c_uint32),
+                ("position", C.c_float * 3), ("b1", C.c_float), ("normal", C.c_float * 3), ("b2", C.c_float),
+                ("hit", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class MeshRayParams(C.Structure):
+    """MgsMeshRayParams"""
+    _fields_ = [("mode", C.c_int32), ("reorder", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class MeshRayOut(C.Structure):
+    """MgsMeshRayOut: the triangle hierarchy's size, the batch's integer sums and the device times of one mesh ray query"""
+    _fields_ = [("triangles", C.c_uint64), ("leaves", C.c_uint64), ("nodes", C.c_uint64), ("node_visits", C.c_uint64),
+                ("triangle_tests", C.c_uint64), ("hits", C.c_uint64), ("invalid_rays", C.c_uint32), ("bvh_rebuilt", C.c_uint32),
+                ("build_ms", C.c_float), ("trace_ms", C.c_float), ("reorder_ms", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+MESH_HIT_DTYPE = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("primitive_id", np.uint32), ("material_id", np.uint32),
+                           ("position", np.float32, 3), ("b1", np.float32), ("normal", np.float32, 3), ("b2", np.float32),
+                           ("hit", np.uint32), ("reserved", np.uint32, 3)])
+
+
 SENSOR_OPENCV_PINHOLE, SENSOR_OPENCV_FISHEYE = 0, 1
 
 
@@ -380,6 +411,9 @@ def load_library():
                                        P(RayQueryParams), vp, P(TraceLightOut), P(C.c_uint32)]),
         "mgs_shade_points_device": (C.c_int, [vp, vp, C.c_uint64, P(Material), C.c_uint32, P(FrameParams), P(TraceParams), P(TraceLightParams),
                                               P(RayQueryParams), vp, P(TraceLightOut), P(C.c_uint32)]),
+        "mgs_mesh_ray_params_default": (None, [P(MeshRayParams)]),
+        "mgs_trace_mesh_rays": (C.c_int, [vp, vp, C.c_uint64, P(MeshRayParams), vp, P(MeshRayOut)]),
+        "mgs_trace_mesh_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(MeshRayParams), vp, P(MeshRayOut)]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -442,6 +476,7 @@ EXPORTED_SYMBOLS = [
     "mgs_trace_light_params_default", "mgs_render_traced_lit", "mgs_trace_download_shadow_hits", "mgs_render_hybrid",
     "mgs_ray_query_params_default", "mgs_trace_rays", "mgs_trace_rays_device", "mgs_trace_generate_rays",
     "mgs_trace_shadow_rays", "mgs_trace_shadow_rays_device", "mgs_shade_points", "mgs_shade_points_device",
+    "mgs_mesh_ray_params_default", "mgs_trace_mesh_rays", "mgs_trace_mesh_rays_device",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -946,6 +981,31 @@ class Scene:
                                                  C.byref(q), C.c_void_p(results_device or None), C.byref(lout) if want_stats else None,
                                                  C.byref(bad) if want_stats else None))
         return (lout, int(bad.value)) if want_stats else None
+
+    def mesh_ray_params(self, mode=MESH_RAYS_CLOSEST, reorder=False):
+        q = MeshRayParams()
+        self._lib.mgs_mesh_ray_params_default(C.byref(q))
+        q.mode, q.reorder = int(mode), int(bool(reorder))
+        return q
+
+    def trace_mesh_rays(self, rays, mode=MESH_RAYS_CLOSEST, reorder=False, want_stats=False, params=None):
+        """mgs_trace_mesh_rays: the caller's rays (a RAY_DTYPE array, make_rays) against the scene's triangle meshes -> a MESH_HIT_DTYPE
+        array (waits).  mode = MESH_RAYS_CLOSEST (nearest hit with ids, barycentrics, position, normal) or MESH_RAYS_OCCLUSION (the hit
+        flag alone).  params = a MeshRayParams replaces mode / reorder.  want_stats returns (hits, MeshRayOut)."""
+        out, q = MeshRayOut(), (params if params is not None else self.mesh_ray_params(mode, reorder))
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
+        res = np.zeros(r.shape[0], MESH_HIT_DTYPE)
+        _check(self._lib.mgs_trace_mesh_rays(self._h, r.ctypes.data_as(C.c_void_p), r.shape[0], C.byref(q), res.ctypes.data_as(C.c_void_p),
+                                             C.byref(out) if want_stats else None))
+        return (res, out) if want_stats else res
+
+    def trace_mesh_rays_device(self, rays_device, count, hits_device, mode=MESH_RAYS_CLOSEST, reorder=False, want_stats=False, params=None):
+        """mgs_trace_mesh_rays_device: count rays at the device pointer rays_device, hits (count * 64 bytes) to hits_device, both 16-byte
+        aligned (torch allocations are); ordered on the handle's stream.  want_stats waits and returns a MeshRayOut."""
+        out, q = MeshRayOut(), (params if params is not None else self.mesh_ray_params(mode, reorder))
+        _check(self._lib.mgs_trace_mesh_rays_device(self._h, C.c_void_p(rays_device or None), int(count), C.byref(q),
+                                                    C.c_void_p(hits_device or None), C.byref(out) if want_stats else None))
+        return out if want_stats else None
 
     def generate_rays(self, params, rays_device):
         """mgs_trace_generate_rays: the primary rays render_traced would trace for params, written row-major to the device pointer

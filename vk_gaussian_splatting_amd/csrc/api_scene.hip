@@ -96,6 +96,7 @@ SceneData::~SceneData()
     m.release();
   meshTab.release();
   bvh.release();
+  meshBvh.release();
 }
 
 void mgs_scene_destroy(MgsScene s)
@@ -121,6 +122,7 @@ void mgs_scene_destroy(MgsScene s)
   s->cmp.release();
   s->mesh.release();
   s->trace.release();
+  s->meshRays.release();
   s->rs.release();
   s->cpu.release();
   s->binPolicy.release();
@@ -193,7 +195,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   }
   if(sceneBytes)
   {
-    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes() + s->d->bvh.bytes();
+    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes() + s->d->bvh.bytes() + s->d->meshBvh.bytes();
     for(const auto& m : s->d->meshes)
       b += m.bytes();
     for(const auto& d : s->d->sets)
@@ -204,7 +206,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   {
     uint64_t b   = s->cpu.distDev.bytes();
     auto     add = [&](auto& buf) { b += buf.bytes(); };
-    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add); s->trace.eachBuffer(add);
+    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add); s->trace.eachBuffer(add); s->meshRays.eachBuffer(add);
     *workingBytes = b;
   }
   return MGS_OK;

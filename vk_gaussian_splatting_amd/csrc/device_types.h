@@ -463,6 +463,48 @@ struct HybridSurfaceArgs
   float4*          outRadiance;  // the stored pixel in fp32: rgb and alpha
 };
 
+// ---- mesh ray queries (k_mesh_bvh.hip, k_mesh_rays.hip, api_mesh_rays.hip) ----
+// The triangle hierarchy has the splat hierarchy's layout (above): level 0 holds one leaf per valid triangle of every mesh instance,
+// sorted by the 30-bit Morton code of the leaf centroid, and a leaf's lo.w holds the LEAF's own index as bits, which is also the index
+// of its triangle record.  A record is three float4 in leaf order: (world v0, global primitive id), (world v1, instance id),
+// (world v2, material id), the ids as bits.
+struct MeshBvhBuildArgs
+{
+  const MeshTable* table;
+  float            boxLo[3], boxInvExt[3];  // Morton quantisation frame (host: the instances' transformed local boxes)
+  uint32_t         totalTris;
+  uint32_t*        keys;     // [totalTris] Morton code, kTraceInvalid = no leaf
+  uint32_t*        vals;     // [totalTris] global primitive id
+  float4*          leafBox;  // [2 * totalTris]
+};
+struct MeshBvhRecordArgs
+{
+  const MeshTable* table;
+  const uint32_t*  sortedVals;  // [leaves] global primitive id of leaf i
+  float4*          level0;      // [2 * leaves] the gathered leaves: lo.w becomes i
+  float4*          tris;        // [3 * leaves]
+  uint32_t         leaves;
+};
+struct MeshRayCounters
+{
+  unsigned long long nodeVisits, triangleTests, hits;
+  uint32_t           invalidRays, pad;
+};
+// what the ray/triangle kernel receives by value.  `t` carries the hierarchy for the traversal of trace_traverse.h (nodes, levels,
+// node count); nothing else of it is read and its frame pointer stays null.  A hit is four float4: (t, instance, primitive,
+// material), (world position, b1), (world normal, b2), (hit flag, 0, 0, 0).
+struct MeshRayArgs
+{
+  TraceArgs        t;
+  const float4*    tris;
+  const MeshTable* table;
+  const float4*    rays;  // [2 * count]
+  float4*          hits;  // [4 * count], at the ray's index in the caller's order
+  const uint32_t*  perm;  // [count] lane -> ray index (a reordered batch), or null: the caller's order
+  uint32_t         count;
+  MeshRayCounters* ctr;
+};
+
 // the caller's geometry as the compositors' launchers receive it
 struct Occluder
 {

@@ -139,6 +139,11 @@ void launchPointsKey(hipStream_t stream, const PointKeyArgs& a);  // a batch of 
 // shadow and light queries (k_shadow_query.hip): one shadow ray, or one surface point under the scene's lights, per lane
 void launchShadowRays(hipStream_t stream, const ShadowQueryArgs& a);
 void launchShadePoints(hipStream_t stream, const ShadowQueryArgs& a);
+// mesh ray queries: the triangle hierarchy's leaves and records (k_mesh_bvh.hip; count, gather and levels are k_bvh.hip's), and the
+// ray/triangle kernel (k_mesh_rays.hip; mode 0 = closest hit, 1 = occlusion)
+void launchMeshBvhLeaves(hipStream_t stream, const MeshBvhBuildArgs& a);
+void launchMeshBvhRecords(hipStream_t stream, const MeshBvhRecordArgs& a);
+void launchMeshRays(hipStream_t stream, const MeshRayArgs& a, int mode);
 // the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);

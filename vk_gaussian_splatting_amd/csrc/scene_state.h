@@ -241,6 +241,24 @@ struct TraceBvhState
   void     release() { nodes.release(), callerId.release(), inst.release(); built = false; }
 };
 
+// The triangle hierarchy of the mesh ray queries (mgs_trace_mesh_rays; api_mesh_rays.hip, k_mesh_bvh.hip): every mesh instance's
+// triangles in world space.  It belongs to the SCENE and is shared by its frame contexts; rebuilt lazily by the next mesh query whose
+// inputs (`signature`: the mesh instances and their transforms; visibility is not part of it) differ from what it was built for.
+struct MeshBvhState
+{
+  DevBuf<float4>       nodes;  // all levels, two float4 per node
+  DevBuf<float4>       tris;   // three float4 per leaf, in leaf order (device_types.h)
+  uint32_t             levelOffset[kBvhMaxLevels] = {}, levelCount[kBvhMaxLevels] = {};
+  int                  nLevels = 0;
+  uint32_t             totalNodes = 0, leaves = 0, triangles = 0;
+  float                boxLo[3] = {}, boxInvExt[3] = {};  // the meshes' world box: the Morton frame, and the reorder keys'
+  std::vector<uint8_t> signature;
+  bool                 built = false;
+  std::mutex           mtx;  // held by a mesh query from its signature check to its last launch (api_mesh_rays.hip)
+  uint64_t bytes() const { return nodes.bytes() + tris.bytes(); }
+  void     release() { nodes.release(), tris.release(); built = false; }
+};
+
 // What a commit produces: the resident splat buffers and the instance list.  ONE copy per scene, shared read-only by the scene
 // handle and every frame context created from it — the reference likewise keeps one copy of the splat buffers however many
 // frames are in flight, which is why processUpdateRequests waits for the device before it touches them
@@ -266,7 +284,8 @@ struct SceneData
   std::unique_ptr<MeshTable> meshHost;
   DevBuf<MeshTable>      meshTab;
   TraceBvhState          bvh;            // mgs_render_traced
-  uint64_t               epoch = 0;      // bumped by every commit: a context re-sizes its working set when it lags
+  MeshBvhState           meshBvh;        // mgs_trace_mesh_rays
+  uint64_t               epoch = 0;     // bumped by every commit: a context re-sizes its working set when it lags
   std::mutex             mtx;            // guards `handles`
   std::vector<MgsScene_t*> handles;      // the owning scene and its live frame contexts
   ~SceneData();
@@ -520,6 +539,28 @@ struct TracePassState
   }
 };
 
+// the mesh ray queries' per-handle state (mgs_trace_mesh_rays, api_mesh_rays.hip): the host variant's staging of rays and hits, the
+// batch's counters, a reordered batch's coherence keys and ray indices, the scratch of a hierarchy build this handle ran (freed when
+// the build is done), the events around build, reorder and traversal
+struct MeshRayState
+{
+  DevBuf<float4>          rayStage, hitStage, leafBox;
+  DevBuf<uint32_t>        keys, vals, leafCount, rayKeys, rayIdx;
+  DevBuf<MeshRayCounters> ctr;
+  hipEvent_t              ev[6] = {};  // build, reorder, traversal: begin and end
+  template <class F>
+  void eachBuffer(F&& f) { f(rayStage); f(hitStage); f(leafBox); f(keys); f(vals); f(leafCount); f(rayKeys); f(rayIdx); f(ctr); }
+  void release()
+  {
+    eachBuffer([](auto& b) { b.release(); });
+    for(auto& e : ev)
+    {
+      if(e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 // scratch of the stand-alone sort (mgs_radix_sort_u32): owned by the handle (its device, its stream)
 struct SortScratch
 {
@@ -655,6 +696,7 @@ struct MgsScene_t
   CompareState    cmp;
   MeshPassState   mesh;
   TracePassState  trace;
+  MeshRayState    meshRays;
   SortScratch     rs;
   CommState       comm;
   CpuSortState    cpu;
