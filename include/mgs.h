@@ -1101,9 +1101,9 @@ int mgs_shade_points_device(MgsScene scene_or_context, const MgsSurfacePoint* po
  * staging buffers of the handle and waits; mgs_trace_mesh_rays_device takes device pointers (16-byte aligned), is ordered on the
  * handle's stream and, with reorder = 0 and no rebuild due, waits only when `out` is non-NULL.
  *
- * Out of scope here, and what the hierarchy is meant to serve next: mesh hits inside mgs_render_traced, mgs_render_traced_lit and
- * mgs_render_hybrid (the frame follow-up: the same traversal and triangle test called from the frame kernels), and mesh occlusion
- * inside mgs_trace_shadow_rays and mgs_shade_points (the occlusion mode's walk).  Not planned on it: mesh material transmittance,
+ * Mesh hits inside mgs_render_traced and mgs_render_traced_lit are the next section's (MGS_HAS_TRACE_MESHES: the same traversal and
+ * triangle test called from the frame kernels).  Out of scope here, and what the hierarchy is meant to serve next: mesh hits inside
+ * mgs_render_hybrid, and mesh occlusion inside mgs_trace_shadow_rays and mgs_shade_points (the occlusion mode's walk).  Not planned on it: mesh material transmittance,
  * ior, reflection and refraction bounces, light proxies, ray masks, refitting instead of rebuilding, mgs_render_gathered. */
 typedef enum MgsMeshRayMode {
   MGS_MESH_RAYS_CLOSEST   = 0,
@@ -1145,6 +1145,76 @@ int  mgs_trace_mesh_rays(MgsScene scene_or_context, const MgsRay* rays_host, uin
                          MgsMeshHit* hits_host, MgsMeshRayOut* out /* may be NULL */);
 int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_device, uint64_t count,
                                 const MgsMeshRayParams* params /* NULL = defaults */, MgsMeshHit* hits_device, MgsMeshRayOut* out /* may be NULL */);
+
+/* ---- mesh hits in the traced frames (MGS_HAS_TRACE_MESHES): the scene's triangle meshes take part in mgs_render_traced (unlit) and
+ * mgs_render_traced_lit, at bounce 0.  Restates, of shaders/threedgrt_raytrace.rgen.slang, traceBounceRayMeshes at bounce 0
+ * (:495-553), the mesh parts of evaluateLightingAndShadingForBounce (:1037-1077), evaluateLightingAndShadingMeshes in its direct
+ * mode (:1222-1255), traceShadowRayForLight with traceShadowRayMesh (:1262-1341) and the depth rule of writeToGBuffers (:1490-1502).
+ * Added within ABI 5.1: entry points and one new struct; MgsTraceParams (32 B) and MgsTraceOut (56 B) do not change.
+ *
+ * The setting.  mgs_frame_set_trace_meshes belongs to the handle, scene or frame context, as mgs_frame_set_occluder and
+ * mgs_frame_set_sensor do.  Off is the default (NULL = off), and with it off every entry point does exactly what it did before,
+ * bit for bit, whether or not the scene holds mesh instances.  enabled not 0 / 1, a threshold outside [0, 1] (NaN included) or a
+ * non-zero reserved word: MGS_ERR_INVALID_ARG, checked before the handle is looked at.  With the setting on, mgs_render_traced with
+ * trace_strategy 0 and mgs_render_traced_lit include the scene's visible mesh instances; mgs_render_traced with strategy 1 or 2 and
+ * mgs_render_hybrid (whose mesh depth pre-pass is later work) return MGS_ERR_UNSUPPORTED; mgs_render, mgs_meshes_render and the ray,
+ * shadow and mesh-ray queries do not read it.  A scene without splats but with meshes renders the meshes alone.  A scene with no
+ * visible mesh instance renders the frame it renders with the setting off, bit for bit (the frame's kernels are then the same ones;
+ * only the all-miss hit records are written besides).  mgs_render_gathered is not wired.
+ *
+ * Primary mesh ray (:495-553).  The hit of a pixel with a valid ray is exactly what mgs_trace_mesh_rays in closest mode reports for
+ * the ray mgs_trace_generate_rays makes for that pixel, depth of field and fisheye included, with the window t_min = 0.001,
+ * t_max = 10000 (in fp32 the reference's epsT = 1e-9 vanishes), byte for byte; a fisheye pixel outside the image circle is a miss
+ * counted in invalid_rays.  The query's rules apply unchanged: open window, both facings, the watertight test, ties to the lower
+ * primitive id, invisible instances skipped.  A hit sets the upper end of the pixel's particle walk: its passes collect in
+ * (tMin + epsT, t_mesh + epsT).
+ * Unlit composite (:1064-1075).  Where a mesh is hit and T > min_mesh_composite_transmittance (compared in double against the walk's
+ * transmittance), rgb += float(T) * (emission + ambient + diffuse) of the hit triangle's material.
+ * Lit frame.  The primary walk and surfaceFinalFiltering are as in a frame without meshes; a discarded splat surface leaves radiance 0
+ * and T = 1.  The splat surface is shaded when t_iso > 0 && t_iso < t_mesh and the pick is valid (:1047-1049): the shading of
+ * mgs_render_traced_lit with one change, every shadow ray first asks the meshes.  The mesh occlusion ray (:1295-1341) starts at the
+ * UN-offset shadow origin and runs along lightDir with the window (0.001, lightDist - 0.001); meshes are opaque, so an occluded
+ * light has shadow transmittance 0 and the particle shadow ray is not traced for it (:1285); otherwise the particle shadow ray runs
+ * as before and the two transmittances multiply.  Mesh shading (:1148-1165, :1222-1255) has the condition of the unlit composite:
+ * rgb += emission, unweighted, as written at :1159; that is all when the material's needShading is 0 (MgsMaterial's rule); otherwise
+ * every light in range at meshHitWorldPos, or the never-shadowed headlight when the scene has no lights, is shaded with
+ * wavefrontComputeShadingDirectOnly(light x shadow, meshHitWorldPos, meshHitWorldNrm, material, rayDirection, inShadow, T, rgb),
+ * where meshHitWorldPos and meshHitWorldNrm are the closest hit's position and normal as MgsMeshHit reports them (the normal is not
+ * flipped towards the ray), and the shadow comes from traceShadowRayForLight at meshHitWorldPos: the meshes first, then the
+ * particles with particle_shadow_offset.  This is what puts the splats' shadow on a mesh floor.  With shadows_mode
+ * MGS_SHADOWS_DISABLED neither ray is traced.
+ * Outputs.  Alpha is 1 where a mesh was composited (the mesh is opaque); elsewhere it stays this library's 1 - T (the reference
+ * writes 1.0 everywhere).  Surface output 0 is the ndc z of the iso pick where there is one, else of origin + t_mesh * direction
+ * where a mesh is hit (:547-551), else 0; id and normal stay the splats'.  The shadow hit counts of a pixel include the particle
+ * shadow rays of its mesh point, and MgsTraceLightOut's sums include them.  Temporal accumulation, target formats, strip rows and
+ * frame contexts work as after any traced frame.
+ *
+ * mgs_trace_download_mesh_hits copies the last traced frame's per-pixel hit records ([height][width] MgsMeshHit; a miss as the
+ * query writes it); MGS_ERR_STATE unless the handle's last traced frame ran with the setting on; rows outside a strip frame's
+ * rows are stale.  mgs_trace_mesh_stats waits and reports the integer sums of that frame's primary mesh rays in `primary`
+ * (triangles, leaves, nodes, node_visits, triangle_tests, hits, invalid_rays, bvh_rebuilt, build_ms, trace_ms: HIP events around
+ * the primary mesh kernel) and of the mesh occlusion rays of a lit frame in `shadow` (hits = rays occluded; trace_ms: HIP events
+ * around the mesh composite kernel, which traces those of the mesh points; those of the splat surface run inside the light pass and
+ * are in light_ms); `shadow` is all zero after an unlit frame.  Either may be NULL.
+ *
+ * The frame's set-up runs the lazy build of the mesh ray queries' triangle hierarchy as it stands and holds the hierarchy's mutex
+ * from the signature check to the frame's last launch; a rebuild waits for all contexts' streams.  Per-pixel buffers belong to the
+ * handle and count into working_bytes: the hit record (64 B), its t (4 B) and the walk's transmittance rounded once to fp32 (4 B);
+ * an unlit frame with a visible mesh also keeps the lit frames' fp32 pixel and ray parameter (16 B + 4 B).
+ * PARITY UNPINNED: what the mesh ray queries list, and the reference's RAY_FLAG_CULL_BACK_FACING_TRIANGLES, which has no effect there.
+ * Out of scope: hybrid frames with meshes, mesh occlusion inside mgs_trace_shadow_rays / mgs_shade_points, the stochastic
+ * strategies with meshes, mesh transmittance / ior / reflection / refraction bounces, indirect lighting, soft shadows, light
+ * proxies, ray masks, mgs_render_gathered. */
+#define MGS_HAS_TRACE_MESHES 1
+typedef struct MgsTraceMeshParams {
+  int32_t  enabled;                          /* 0 / 1, default 0 */
+  float    min_mesh_composite_transmittance; /* frameInfo.minMeshCompositeTransmittance, default 0.0 (shaderio.h:285); [0, 1] */
+  uint32_t reserved[2];                      /* must be 0 */
+} MgsTraceMeshParams;
+void mgs_trace_mesh_params_default(MgsTraceMeshParams* params);
+int  mgs_frame_set_trace_meshes(MgsScene scene_or_context, const MgsTraceMeshParams* params /* NULL = off */);
+int  mgs_trace_download_mesh_hits(MgsScene scene_or_context, MgsMeshHit* host_dst, size_t count); /* [height][width] */
+int  mgs_trace_mesh_stats(MgsScene scene_or_context, MgsMeshRayOut* primary, MgsMeshRayOut* shadow); /* either may be NULL; waits */
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

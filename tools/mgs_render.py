@@ -29,7 +29,10 @@ rendered over it: a mesh floor under a splat object shows the object's shadow.  
 primary surface, lit and shadowed by the traced light pass; --lights / --material / --shadow-* as above, --samples-per-pass of the
 shadow rays.  Not combinable with --occluder-depth or --mesh.  --raster-pipeline: 3DGS (default) or 3DGUT, of --pipeline raster and hybrid.
 --pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
-the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth, --mesh or --lighting 1.
+the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth.
+--pipeline trace --mesh FILE.obj [--lighting 1 --shadows 1]: the meshes take part in the traced frame (mgs_frame_set_trace_meshes): mesh
+hits cut the particle walk, meshes are shaded and throw and receive shadows; prints both MgsMeshRayOut blocks.  --trace-meshes 0 leaves
+the setting off (the frame of the splats alone); --mesh-composite-threshold X is min_mesh_composite_transmittance.
 --trace-strategy full|pass|anyhit: MgsTraceParams::trace_strategy of an unlit traced frame (sorted passes, pass-stochastic, stochastic
 any-hit); --accumulate N renders the samples frame_sample_id = 0..N-1 with temporal accumulation and writes the last, the running mean.
 
@@ -123,6 +126,8 @@ def main():
     ap.add_argument("--mesh-transform", action="append", type=float, nargs=16, default=[], metavar="M")
     ap.add_argument("--mesh-pick-image", default=None, metavar="OUT.npy")  # --mesh: closest-hit global primitive ids of the primary rays (mgs_trace_mesh_rays_device)
     ap.add_argument("--mesh-shadows", type=int, choices=[0, 1], default=0)  # --mesh --lighting 1: the splats' shadows on the meshes
+    ap.add_argument("--trace-meshes", type=int, choices=[0, 1], default=1)  # --pipeline trace --mesh: mgs_frame_set_trace_meshes
+    ap.add_argument("--mesh-composite-threshold", type=float, default=0.0)
     ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
@@ -205,6 +210,12 @@ def main():
             m = np.array(a.mesh_transform[k], np.float32).reshape(4, 4) if k < len(a.mesh_transform) else None
             meshes.append((mgs.Mesh.load_obj(path), m))
             scene.add_mesh_instance(*meshes[-1])
+    if a.mesh and a.pipeline == "trace":
+        # the meshes are traced with the splats: no mesh pass, no occluder (a traced frame refuses a bound one)
+        if a.mesh_pick_image:
+            ap.error("--mesh-pick-image is for the raster pipelines (a traced frame's hits are mgs_trace_download_mesh_hits)")
+        scene.set_trace_meshes(bool(a.trace_meshes), a.mesh_composite_threshold)
+    elif a.mesh:
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
         if a.mesh_pick_image:
@@ -223,8 +234,10 @@ def main():
     if a.pipeline != "trace" and (a.trace_strategy != "full" or a.accumulate != 1):
         ap.error("--trace-strategy pass / anyhit and --accumulate are for --pipeline trace (unlit)")
     if a.pipeline == "trace":
-        if a.occluder_depth or a.mesh:
-            ap.error("--pipeline trace renders splats alone: no --occluder-depth or --mesh")
+        if a.occluder_depth:
+            ap.error("--pipeline trace takes no --occluder-depth (meshes: --mesh)")
+        if a.mesh and a.trace_meshes and a.trace_strategy != "full":
+            ap.error("--pipeline trace --mesh needs --trace-strategy full (or --trace-meshes 0)")
         p.collect_timings = 0
         t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance,
                                       trace_strategy=["full", "pass", "anyhit"].index(a.trace_strategy))
@@ -244,6 +257,11 @@ def main():
                     p.frame_sample_id, p.temporal_sampling = k, 1
                 o = scene.render_traced(p, t, want_stats=True)
         img = scene.download_frame(p).astype(np.float32)
+        if a.mesh and a.trace_meshes:
+            pm, sm = scene.trace_mesh_stats()
+            print(f"meshes: {pm.triangles} triangles, {pm.leaves} leaves (build {pm.build_ms:.3f} ms); primary rays: {pm.hits} hits, "
+                  f"{pm.triangle_tests} triangle tests, {pm.trace_ms:.3f} ms; occlusion rays: {sm.hits} occluded, {sm.triangle_tests} triangle tests, "
+                  f"mesh composite {sm.trace_ms:.3f} ms")
         rays = W * H
         print(f"{scene.splat_count} splats, {o.leaves} leaves in {o.nodes} nodes (build {o.build_ms:.3f} ms), {o.node_visits / rays:.1f} node visits and "
               f"{o.candidate_tests / rays:.1f} candidate tests per ray, {o.accepted_hits / rays:.1f} hits per ray, at most {o.max_passes_used} passes, "

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--trace-meshes] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
@@ -20,6 +20,10 @@ plane below the scene, row-major), each with reorder off and on: the median trac
 --mesh-rays N [--mesh file.obj] needs no syn: scene: mesh ray queries (mgs_trace_mesh_rays_device) of about N rays against the mesh
 (default: tests/golden/meshes/fixture.obj) instanced on a 3 x 3 grid: a CAMERA batch (mgs_trace_generate_rays) and a RANDOM batch,
 closest and occlusion mode, reorder off and on: MgsMeshRayOut with the median trace_ms and reorder_ms, and the build time.
+--trace-meshes (with a syn: scene) adds the mesh (--mesh, default the fixture) on a 3 x 3 grid to the scene and measures unlit frames
+and lit frames (one point light, hard shadows) with mgs_frame_set_trace_meshes off and on: trace_ms, light_ms and both MgsMeshRayOut
+blocks of mgs_trace_mesh_stats.  shadow.trace_ms is the mesh composite kernel's time, which traces the occlusion rays of the mesh
+points; the occlusion rays of the splat surface run inside light_ms, while shadow.hits counts the occluded rays of both.
 Needs an MI355X.
 """
 import argparse
@@ -92,6 +96,43 @@ def probe_mesh_rays(path, n, W, H, warmup, repeats):
     out["scene_bytes"] = scene.memory_usage()[0]
     scene.close()
     mesh.close()
+    return out
+
+
+def probe_trace_meshes(scene, p, t, path, eye, warmup, repeats):
+    """--trace-meshes: unlit and lit frames of the scene plus the mesh on a 3 x 3 grid, the setting off and on"""
+    mesh = capi.Mesh.load_obj(path)
+    ext = float(np.abs(mesh.view()["positions"]).max()) * 2.5
+    for i in range(9):
+        M = np.eye(4, dtype=np.float32)
+        M[0, 3], M[2, 3] = (i % 3 - 1) * ext, (i // 3 - 1) * ext
+        scene.add_mesh_instance(mesh, M)
+    scene.set_material(0, capi.make_material(ambient=(0.1, 0.1, 0.1), diffuse=(0.8, 0.8, 0.8), emission=(0.0, 0.0, 0.0)))
+    scene.set_lights([capi.make_light(position=(4.0, 6.0, 3.0), range=1000.0, attenuation_mode=0)])
+    lp = capi.default_trace_light_params(shadows_mode=1)
+    out = dict(mesh=os.path.basename(path), instances=9, runs=[])
+    for on in (0, 1):
+        scene.set_trace_meshes(bool(on))
+        for lit in (0, 1):
+            p.lighting_mode = lit
+            tms, lms = [], []
+            for k in range(warmup + repeats):
+                if lit:
+                    o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
+                else:
+                    o, lo = scene.render_traced(p, t, want_stats=True), None
+                if k >= warmup:
+                    tms.append(o.trace_ms)
+                    lms.append(lo.light_ms if lit else 0.0)
+            d = dict(trace_meshes=on, lit=lit, trace_ms_median=float(np.median(tms)), trace_ms_min=float(min(tms)), trace_ms_max=float(max(tms)),
+                     light_ms_median=float(np.median(lms)), light_ms_min=float(min(lms)), shadow_rays=int(lo.shadow_rays) if lit else 0)
+            if on:
+                primary, shadow = scene.trace_mesh_stats()
+                d["primary"], d["shadow"] = primary.as_dict(), shadow.as_dict()
+                d["note"] = "shadow.trace_ms: the mesh composite kernel; the splat surface's mesh occlusion rays are inside light_ms"
+            out["runs"].append(d)
+    p.lighting_mode = 0
+    scene.set_trace_meshes(False)
     return out
 
 
@@ -191,6 +232,7 @@ def main():
     ap.add_argument("--shadow-rays", type=int, nargs="+", default=[])
     ap.add_argument("--mesh-rays", type=int, nargs="+", default=[])
     ap.add_argument("--mesh", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "meshes", "fixture.obj"))
+    ap.add_argument("--trace-meshes", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -270,6 +312,9 @@ def main():
                                                       candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
                                                       accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr)
             p.lighting_mode = 0
+        if a.trace_meshes:
+            tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+            r["trace_meshes"] = probe_trace_meshes(scene, p, tq, a.mesh, eye, a.warmup, a.repeats)
         print(json.dumps(r))
         results.append(r)
         scene.close()

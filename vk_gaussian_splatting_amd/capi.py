@@ -228,6 +228,11 @@ MESH_HIT_DTYPE = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("prim
                            ("hit", np.uint32), ("reserved", np.uint32, 3)])
 
 
+class TraceMeshParams(C.Structure):
+    """MgsTraceMeshParams (16 bytes): mesh hits in the traced frames (mgs_frame_set_trace_meshes)"""
+    _fields_ = [("enabled", C.c_int32), ("min_mesh_composite_transmittance", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 SENSOR_OPENCV_PINHOLE, SENSOR_OPENCV_FISHEYE = 0, 1
 
 
@@ -414,6 +419,10 @@ def load_library():
         "mgs_mesh_ray_params_default": (None, [P(MeshRayParams)]),
         "mgs_trace_mesh_rays": (C.c_int, [vp, vp, C.c_uint64, P(MeshRayParams), vp, P(MeshRayOut)]),
         "mgs_trace_mesh_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(MeshRayParams), vp, P(MeshRayOut)]),
+        "mgs_trace_mesh_params_default": (None, [P(TraceMeshParams)]),
+        "mgs_frame_set_trace_meshes": (C.c_int, [vp, P(TraceMeshParams)]),
+        "mgs_trace_download_mesh_hits": (C.c_int, [vp, vp, C.c_size_t]),
+        "mgs_trace_mesh_stats": (C.c_int, [vp, P(MeshRayOut), P(MeshRayOut)]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -477,6 +486,7 @@ EXPORTED_SYMBOLS = [
     "mgs_ray_query_params_default", "mgs_trace_rays", "mgs_trace_rays_device", "mgs_trace_generate_rays",
     "mgs_trace_shadow_rays", "mgs_trace_shadow_rays_device", "mgs_shade_points", "mgs_shade_points_device",
     "mgs_mesh_ray_params_default", "mgs_trace_mesh_rays", "mgs_trace_mesh_rays_device",
+    "mgs_trace_mesh_params_default", "mgs_frame_set_trace_meshes", "mgs_trace_download_mesh_hits", "mgs_trace_mesh_stats",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -1006,6 +1016,28 @@ class Scene:
         _check(self._lib.mgs_trace_mesh_rays_device(self._h, C.c_void_p(rays_device or None), int(count), C.byref(q),
                                                     C.c_void_p(hits_device or None), C.byref(out) if want_stats else None))
         return out if want_stats else None
+
+    def set_trace_meshes(self, enabled=True, min_transmittance=0.0, params=None):
+        """mgs_frame_set_trace_meshes: the scene's triangle meshes take part in this handle's render_traced (strategy 0) and
+        render_traced_lit frames; min_transmittance = min_mesh_composite_transmittance.  params = a TraceMeshParams replaces both;
+        enabled=False turns the setting off."""
+        if params is None:
+            params = TraceMeshParams()
+            self._lib.mgs_trace_mesh_params_default(C.byref(params))
+            params.enabled, params.min_mesh_composite_transmittance = int(bool(enabled)), float(min_transmittance)
+        _check(self._lib.mgs_frame_set_trace_meshes(self._h, C.byref(params)))
+
+    def trace_mesh_hits(self, params):
+        """the per-pixel closest mesh hits of the last traced frame (setting on), a MESH_HIT_DTYPE array [H,W]"""
+        out = np.zeros((params.height, params.width), MESH_HIT_DTYPE)
+        _check(self._lib.mgs_trace_download_mesh_hits(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def trace_mesh_stats(self):
+        """mgs_trace_mesh_stats of the last traced frame (setting on): (primary, shadow), two MeshRayOut; waits"""
+        primary, shadow = MeshRayOut(), MeshRayOut()
+        _check(self._lib.mgs_trace_mesh_stats(self._h, C.byref(primary), C.byref(shadow)))
+        return primary, shadow
 
     def generate_rays(self, params, rays_device):
         """mgs_trace_generate_rays: the primary rays render_traced would trace for params, written row-major to the device pointer

@@ -339,6 +339,13 @@ int traceMeshRaysImpl(MgsScene s, const void* rays, uint64_t count, const MgsMes
 }
 }  // namespace
 
+int ensureMeshHierarchyLocked(MgsScene s, float* buildMs, uint32_t* rebuilt)
+{
+  if(int rc = ensureMeshRayEvents(s->meshRays))
+    return rc;
+  return ensureMeshHierarchy(s, buildMs, rebuilt);
+}
+
 int mgs_trace_mesh_rays(MgsScene s, const MgsRay* rays, uint64_t count, const MgsMeshRayParams* qp, MgsMeshHit* hits, MgsMeshRayOut* out)
 {
   return guarded("mgs_trace_mesh_rays", [&] { return traceMeshRaysImpl(s, rays, count, qp, hits, out, true); });

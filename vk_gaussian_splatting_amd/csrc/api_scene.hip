@@ -123,6 +123,7 @@ void mgs_scene_destroy(MgsScene s)
   s->mesh.release();
   s->trace.release();
   s->meshRays.release();
+  s->traceMesh.release();
   s->rs.release();
   s->cpu.release();
   s->binPolicy.release();
@@ -206,7 +207,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   {
     uint64_t b   = s->cpu.distDev.bytes();
     auto     add = [&](auto& buf) { b += buf.bytes(); };
-    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add); s->trace.eachBuffer(add); s->meshRays.eachBuffer(add);
+    s->fb.eachBuffer(add); s->surf.eachBuffer(add); s->rs.eachBuffer(add); s->cmp.eachBuffer(add); s->mesh.eachBuffer(add); s->trace.eachBuffer(add); s->meshRays.eachBuffer(add); s->traceMesh.eachBuffer(add);
     *workingBytes = b;
   }
   return MGS_OK;

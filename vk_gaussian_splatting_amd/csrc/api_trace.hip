@@ -3,6 +3,7 @@
 #include <array>
 #include <cmath>
 #include <memory>
+#include <mutex>
 
 #include "scene_state.h"
 #include "trace_dispatch.h"
@@ -29,6 +30,13 @@ void mgs_trace_light_params_default(MgsTraceLightParams* p)
   p->particle_shadow_offset                  = 0.2f;                  // parameters.h:222
   p->particle_shadow_transmittance_threshold = 0.8f;                  // parameters.h:223
   p->particle_shadow_color_strength          = 0.0f;                  // parameters.h:224
+}
+
+void mgs_trace_mesh_params_default(MgsTraceMeshParams* p)
+{
+  if(!p)
+    return;
+  std::memset(p, 0, sizeof(*p));  // off; frameInfo.minMeshCompositeTransmittance = 0.0, shaderio.h:285
 }
 
 int failTrace(int code, const std::string& msg)
@@ -416,6 +424,56 @@ int TraceOutRead::finish(MgsScene s, uint32_t rebuilt, float buildMs, MgsTraceOu
   return MGS_OK;
 }
 
+// The mesh step of a traced frame's set-up on a handle whose setting is on: the per-pixel buffers, the lazy build of the triangle
+// hierarchy exactly as a mesh query runs it, and what the frame's kernels receive of it.  `hierarchy` comes back locked: the caller
+// holds it to the frame's last launch, so that a rebuild on another context (which waits for every stream) never frees nodes a
+// launched kernel still reads.  active: a visible instance has a leaf; without one the frame's kernels are the ones of a frame with
+// the setting off, and only the (all-miss) hit records are written.
+static int traceMeshSetUp(MgsScene s, size_t pixels, bool lit, std::unique_lock<std::mutex>& hierarchy, TraceMeshArgs& M, bool& active)
+{
+  SceneData&      d  = *s->d;
+  TraceMeshState& tm = s->traceMesh;
+  TracePassState& ts = s->trace;
+  int             rc;
+  if(!tm.ev[0])
+    for(auto& e : tm.ev)
+      HIPCHK(hipEventCreate(&e));
+  if((rc = tm.hits.ensure(4 * pixels))) return rc;
+  if((rc = tm.meshT.ensure(pixels))) return rc;
+  if((rc = tm.walkT.ensure(pixels))) return rc;
+  if((rc = tm.ctr.ensure(2))) return rc;
+  hierarchy = std::unique_lock<std::mutex>(d.meshBvh.mtx);
+  if((rc = ensureMeshHierarchyLocked(s, &tm.buildMs, &tm.rebuilt))) return rc;
+  const MeshBvhState& B = d.meshBvh;
+  tm.triangles = B.triangles, tm.leaves = B.leaves, tm.nodes = B.totalNodes;
+  active = false;
+  if(d.meshHost && B.nLevels > 0)
+    for(uint32_t k = 0; k < d.meshHost->count; ++k)
+      active = active || (d.meshHost->inst[k].visible != 0u && d.meshHost->inst[k].triCount > 0u);
+  if(active && !lit)  // the composite adds to the fp32 pixel, which an unlit frame otherwise does not keep
+  {
+    if((rc = ts.isoDist.ensure(pixels))) return rc;
+    if((rc = ts.radiance.ensure(pixels))) return rc;
+  }
+  M = TraceMeshArgs{};
+  if(active)
+  {  // (an inactive frame's primary kernel walks nothing: nLevels stays 0 and every record is a miss)
+    M.h.nodes      = B.nodes.p;
+    M.h.nLevels    = B.nLevels;
+    M.h.totalNodes = B.totalNodes;
+    std::memcpy(M.h.levelOffset, B.levelOffset, sizeof(M.h.levelOffset));
+    std::memcpy(M.h.levelCount, B.levelCount, sizeof(M.h.levelCount));
+    M.tris  = B.tris.p;
+    M.table = d.meshTab.p;
+  }
+  M.hits  = tm.hits.p;
+  M.meshT = tm.meshT.p;
+  M.walkT = tm.walkT.p;
+  M.ctr   = tm.ctr.p;
+  M.minT  = tm.minT;
+  return MGS_OK;
+}
+
 // The end of trace_ms.  A lit frame records it before its light pass, which has light_ms; an unlit frame behind the temporal
 // accumulation, the last work of the frame.
 static int endTraversal(TracePassState& ts, hipStream_t st)
@@ -442,6 +500,10 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(int rc = refuseBoundSensor(s, lit ? "mgs_render_traced_lit" : "mgs_render_traced", "the traced frames generate the perfect cameras' rays; trace the sensor's "
                                                                                          "rays with mgs_trace_generate_rays and mgs_trace_rays_device"))
     return rc;
+  const bool meshOn = s->traceMesh.enabled;
+  if(meshOn && t.trace_strategy != MGS_TRACE_STRATEGY_FULL_ANYHIT)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: the stochastic trace strategies have no mesh hits; turn the setting off with "
+                                          "mgs_frame_set_trace_meshes(handle, NULL) or use trace_strategy 0");
   MgsFrameParams q      = *p;
   q.depth_iso_threshold = t.depth_iso_threshold;
   std::unique_ptr<FrameArgs> A;
@@ -462,6 +524,18 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   uint32_t         rebuilt = 0;
   if((rc = ensureHierarchy(s, *A, proxy, &buildMs, &rebuilt))) return rc;
   hipStream_t st = s->stream;
+  TraceMeshState&              tm = s->traceMesh;
+  std::unique_lock<std::mutex> meshHierarchy;  // held from the mesh step's signature check to the frame's last launch
+  TraceMeshArgs                M{};
+  bool                         meshActive = false;
+  if(meshOn)
+  {  // launch order: mesh primary, k_trace, the light pass, the mesh composite
+    if((rc = traceMeshSetUp(s, pixels, lit, meshHierarchy, M, meshActive))) return rc;
+    HIPCHK(hipMemsetAsync(tm.ctr.p, 0, 2 * sizeof(MeshRayCounters), st));
+    HIPCHK(hipEventRecord(tm.ev[kTmevPrimaryBegin], st));
+    launchTraceMeshPrimary(st, M, s->fb.dArgs.p, F);
+    HIPCHK(hipEventRecord(tm.ev[kTmevPrimaryEnd], st));
+  }
   HIPCHK(hipMemsetAsync(ts.ctr.p, 0, sizeof(TraceCounters), st));
   HIPCHK(hipEventRecord(ts.ev[kEvTraverseBegin], st));
   TraceArgs L = traceArgs(s, proxy, t, targetLayout(p->target_format).fmt);
@@ -471,7 +545,25 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   L.outNormal   = F.surfaceOutputs ? s->surf.normal.p : nullptr;
   L.outIsoDist  = lit ? ts.isoDist.p : nullptr;  // what the light pass reads besides the side outputs
   L.outRadiance = lit ? ts.radiance.p : nullptr;
-  if(t.trace_strategy == MGS_TRACE_STRATEGY_FULL_ANYHIT)
+  if(meshActive)
+  {  // the composite adds to the fp32 pixel
+    L.outIsoDist  = ts.isoDist.p;
+    L.outRadiance = ts.radiance.p;
+  }
+  TraceLightMeshArgs G{};  // (read only when meshActive, except G.l: the light pass's arguments of every lit frame)
+  G.l      = traceLightArgs(s, L, lt, s->surf.id.p, s->surf.normal.p);
+  G.m      = M;
+  G.litOut = ts.radiance.p;
+  if(meshActive)
+  {  // k_trace only learns its per-pixel upper end, and leaves float(T) for the composite
+    TraceWalkMeshArgs Wm{};
+    Wm.t        = L;
+    Wm.meshT    = tm.meshT.p;
+    Wm.outWalkT = tm.walkT.p;
+    Wm.meshMinT = tm.minT;
+    launchTraceWithMeshes(st, Wm, F, s->d->shFormat);
+  }
+  else if(t.trace_strategy == MGS_TRACE_STRATEGY_FULL_ANYHIT)
     launchTrace(st, L, F, s->d->shFormat);
   else
     launchTraceStochastic(st, L, F, s->d->shFormat, t.trace_strategy);
@@ -480,14 +572,28 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
     if((rc = endTraversal(ts, st))) return rc;
     HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
     HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
-    launchTraceLight(st, traceLightArgs(s, L, lt, s->surf.id.p, s->surf.normal.p), F);
+    if(meshActive)
+      launchTraceLightWithMeshes(st, G, F);
+    else
+      launchTraceLight(st, G.l, F);
     HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
+  }
+  if(meshActive)
+  {
+    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeBegin], st));
+    launchTraceMeshComposite(st, G, F, lit);
+    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeEnd], st));
   }
   if(F.temporalSampling)
     launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.fmt);
   if(!lit)
     if((rc = endTraversal(ts, st))) return rc;
   HIPCHK(hipGetLastError());
+  if(meshHierarchy.owns_lock())
+    meshHierarchy.unlock();
+  tm.have       = meshOn;
+  tm.composited = meshActive;
+  tm.lit        = lit;
   // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare); no bin lists belong to it
   // (mgs_frame_row_costs: MGS_ERR_STATE)
   recordLastFrameHead(s->last, *p, F, false, true);
@@ -584,6 +690,9 @@ static int mgs_render_hybrid_impl(MgsScene s, const MgsFrameParams* p, const Mgs
                                           "scope); unbind it with mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
   if(int rc = refuseBoundSensor(s, "mgs_render_hybrid", "the shadow rays start from a surface unprojected through the perfect cameras"))
     return rc;
+  if(s->traceMesh.enabled)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: mesh hits are mgs_render_traced's and mgs_render_traced_lit's (the hybrid frame's mesh depth "
+                                          "pre-pass is later work); turn the setting off with mgs_frame_set_trace_meshes(handle, NULL)");
   tail.s = s;
   tail.p = p;
   // step 1: exactly mgs_render's unlit frame with the surface outputs on (the deferred pass is off in hybrid mode, NEED_SURFACE_INFO on)
@@ -638,4 +747,83 @@ int mgs_trace_download_hit_counts(MgsScene s, uint32_t* dst, size_t count)
 {
   return downloadTracePlane(s, dst, count, &TracePassState::hitCount, &TracePassState::have, "mgs_trace_download_hit_counts",
                             "mgs_trace_download_hit_counts: no traced frame yet", "mgs_trace_download_hit_counts: destination too small");
+}
+
+// ---- mesh hits in the traced frames: the handle's setting, the last frame's hit records and its mesh rays' statistics ----
+int mgs_frame_set_trace_meshes(MgsScene s, const MgsTraceMeshParams* p)
+{
+  return guarded("mgs_frame_set_trace_meshes", [&]() -> int {
+    if(p)
+    {  // (before the handle is looked at: the ranges can be checked without a device)
+      if(p->enabled != 0 && p->enabled != 1)
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: enabled must be 0 or 1");
+      if(!(p->min_mesh_composite_transmittance >= 0.0f && p->min_mesh_composite_transmittance <= 1.0f))
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: min_mesh_composite_transmittance must be in [0, 1]");
+      if(p->reserved[0] != 0 || p->reserved[1] != 0)
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: the reserved words of MgsTraceMeshParams must be 0");
+    }
+    if(!s)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: null scene");
+    s->traceMesh.enabled = p != nullptr && p->enabled == 1;
+    s->traceMesh.minT    = p ? p->min_mesh_composite_transmittance : 0.0f;
+    return (int)MGS_OK;
+  });
+}
+
+int mgs_trace_download_mesh_hits(MgsScene s, MgsMeshHit* dst, size_t count)
+{
+  return guarded("mgs_trace_download_mesh_hits", [&]() -> int {
+    if(!s || !dst)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_mesh_hits: null argument");
+    const TraceMeshState& tm = s->traceMesh;
+    if(!tm.have || !s->trace.have)
+      return failTrace(MGS_ERR_STATE, "mgs_trace_download_mesh_hits: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on");
+    const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
+    if(count < n || tm.hits.n < 4 * n)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_mesh_hits: destination too small");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpyAsync(dst, tm.hits.p, n * sizeof(MgsMeshHit), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return (int)MGS_OK;
+  });
+}
+
+int mgs_trace_mesh_stats(MgsScene s, MgsMeshRayOut* primary, MgsMeshRayOut* shadow)
+{
+  return guarded("mgs_trace_mesh_stats", [&]() -> int {
+    if(!s)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_mesh_stats: null scene");
+    const TraceMeshState& tm = s->traceMesh;
+    if(!tm.have || !s->trace.have)
+      return failTrace(MGS_ERR_STATE, "mgs_trace_mesh_stats: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on");
+    HIPCHK(hipSetDevice(s->device));
+    MeshRayCounters c[2] = {};
+    HIPCHK(hipMemcpyAsync(c, tm.ctr.p, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    auto fill = [&](MgsMeshRayOut* o, const MeshRayCounters& k, int evBegin, int evEnd) -> int {
+      std::memset(o, 0, sizeof(*o));
+      o->triangles      = tm.triangles;
+      o->leaves         = tm.leaves;
+      o->nodes          = tm.nodes;
+      o->node_visits    = k.nodeVisits;
+      o->triangle_tests = k.triangleTests;
+      o->hits           = k.hits;
+      o->invalid_rays   = k.invalidRays;
+      o->bvh_rebuilt    = tm.rebuilt;
+      o->build_ms       = tm.buildMs;
+      HIPCHK(hipEventElapsedTime(&o->trace_ms, tm.ev[evBegin], tm.ev[evEnd]));
+      return (int)MGS_OK;
+    };
+    if(primary)
+      if(int rc = fill(primary, c[0], kTmevPrimaryBegin, kTmevPrimaryEnd))
+        return rc;
+    if(shadow)
+    {
+      std::memset(shadow, 0, sizeof(*shadow));  // all zero after an unlit frame
+      if(tm.lit && tm.composited)
+        if(int rc = fill(shadow, c[1], kTmevCompositeBegin, kTmevCompositeEnd))
+          return rc;
+    }
+    return (int)MGS_OK;
+  });
 }

@@ -373,6 +373,28 @@ struct TraceArgs
   float*                outIsoDist;   // a lit frame's inputs of the light pass (mgs_render_traced_lit), null otherwise: the ray
   float4*               outRadiance;  // parameter of the iso-surface hit (0 = none) and the pixel in fp32 (rgb, 1 - T)
 };
+// what k_trace<., ., true> receives by value, the traversal of a frame with mesh hits (mgs_frame_set_trace_meshes): TraceArgs, which
+// every other kernel keeps as it is, plus the upper end of the pixel's particle walk and what the mesh composite weights the mesh with
+struct TraceWalkMeshArgs
+{
+  TraceArgs    t;
+  const float* meshT;     // [height][width] t of the pixel's closest mesh hit, +inf = none
+  float*       outWalkT;  // [height][width] float(T) of the walk; -1 when T > meshMinT fails in double
+  float        meshMinT;  // min_mesh_composite_transmittance
+};
+// the triangle hierarchy and the per-pixel mesh buffers of a traced frame with mesh hits (k_trace_mesh.hip, k_trace_light.hip)
+struct MeshRayCounters;  // (below, with the mesh ray queries)
+struct TraceMeshArgs
+{
+  TraceArgs        h;        // the triangle hierarchy for the traversal (nodes, levels, node count; nothing else of it is read)
+  const float4*    tris;
+  const MeshTable* table;
+  float4*          hits;     // [height][width][4] the pixel's hit record, as a mesh ray query writes it
+  float*           meshT;    // [height][width] its t, +inf = none
+  const float*     walkT;    // [height][width] what k_trace left in TraceArgs::outWalkT
+  MeshRayCounters* ctr;      // [2] the primary mesh rays' sums, the mesh occlusion rays' sums
+  float            minT;     // min_mesh_composite_transmittance
+};
 // what a ray query (k_trace_rays.hip, mgs_trace_rays) receives by value: the traversal's arguments (image, hit counts and side outputs
 // stay null) and the caller's batch.  A ray is two float4, (origin, t_min) and (direction, t_max); a result three, (radiance,
 // float(T)), (t_iso, id, hit count, passes as bits) and the integrated normal with its weight.
@@ -484,6 +506,14 @@ struct MeshBvhRecordArgs
   float4*          level0;      // [2 * leaves] the gathered leaves: lo.w becomes i
   float4*          tris;        // [3 * leaves]
   uint32_t         leaves;
+};
+// what k_trace_light<., true> and k_trace_mesh_composite receive by value in a frame with mesh hits: the light pass's arguments as
+// every other launch has them, the triangle hierarchy with the per-pixel mesh buffers, and the lit splat surface in fp32
+struct TraceLightMeshArgs
+{
+  TraceLightArgs l;
+  TraceMeshArgs  m;
+  float4*        litOut;  // [height][width] for the mesh composite behind the light pass
 };
 struct MeshRayCounters
 {

@@ -23,10 +23,18 @@
 
 namespace mgs {
 
-// SHF: SH storage format; KB: K-buffer slots in registers (>= samples_per_pass)
-template <int SHF, int KB>
-__global__ __launch_bounds__(256) void k_trace(TraceArgs a)
+// SHF: SH storage format; KB: K-buffer slots in registers (>= samples_per_pass); MESH: a frame with mesh hits
+// (mgs_frame_set_trace_meshes): the pixel's closest mesh hit, which k_trace_mesh_primary left, is the upper end of its walk
+// (rgen.slang:539), and the walk's transmittance is left for the mesh composite.  The triangle walk itself is not in here.
+template <int SHF, int KB, bool MESH>
+__global__ __launch_bounds__(256) void k_trace(std::conditional_t<MESH, TraceWalkMeshArgs, TraceArgs> args)
 {
+  const TraceArgs& a = [&]() -> const TraceArgs& {
+    if constexpr(MESH)
+      return args.t;
+    else
+      return args;
+  }();
   __shared__ TraceLds S;
   const FrameArgs*  Ap = a.frame;
   const FrameConst& F  = Ap->f;
@@ -51,7 +59,10 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
   uint32_t hitCount = 0, pickId = kTraceInvalid, passesUsed = 0;
   unsigned long long nodeVisits = 0, candTests = 0;
   float    tMin = 0.001f;
-  const float tMax = 10000.0f;
+  float       tMaxPixel = 10000.0f;
+  if constexpr(MESH)
+    tMaxPixel = fminf(args.meshT[pix], 10000.0f);  // a hit lies inside (0.001, 10000); +inf = none
+  const float tMax = MESH ? tMaxPixel : 10000.0f;
 
   if(rayOk && a.nLevels > 0)
     for(int pass = 0; pass < a.maxPasses; ++pass)  // bound: max_passes
@@ -126,6 +137,8 @@ __global__ __launch_bounds__(256) void k_trace(TraceArgs a)
   if(!rayOk)
     alphaOut = 1.0f;  // rgen.slang:185
   a.hitCount[pix] = hitCount;
+  if constexpr(MESH)  // rgen.slang:1058-1059, :1065-1066: the comparison in double; the weight is float(T)
+    args.outWalkT[pix] = T > (double)args.meshMinT ? (float)T : -1.0f;
   if(surf)
   {
     float z = 0.0f;  // "none" is 0 in this library (the reference clears to 1.0)
@@ -161,7 +174,17 @@ void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, in
   if(tiles <= 0)
     return;
   withShFormatAndKBuffer("launchTrace", shFormat, a.samplesPerPass, [&](auto shf, auto kb) {
-    hipLaunchKernelGGL((k_trace<decltype(shf)::value, decltype(kb)::value>), dim3(tiles), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((k_trace<decltype(shf)::value, decltype(kb)::value, false>), dim3(tiles), dim3(256), 0, stream, a);
+  });
+}
+
+void launchTraceWithMeshes(hipStream_t stream, const TraceWalkMeshArgs& a, const FrameConst& F, int shFormat)
+{
+  const int tiles = stripTiles(F);
+  if(tiles <= 0)
+    return;
+  withShFormatAndKBuffer("launchTraceWithMeshes", shFormat, a.t.samplesPerPass, [&](auto shf, auto kb) {
+    hipLaunchKernelGGL((k_trace<decltype(shf)::value, decltype(kb)::value, true>), dim3(tiles), dim3(256), 0, stream, a);
   });
 }
 

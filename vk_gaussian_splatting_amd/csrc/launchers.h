@@ -128,9 +128,15 @@ void launchBvhGather(hipStream_t stream, const uint32_t* sortedVals, const float
 void launchBvhLevel(hipStream_t stream, const float4* below, uint32_t nBelow, float4* level, uint32_t nLevel);
 // the traversal (k_trace.hip): one ray per lane, a wave64 = an 8 x 8 pixel tile
 void launchTrace(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat);
+void launchTraceWithMeshes(hipStream_t stream, const TraceWalkMeshArgs& a, const FrameConst& F, int shFormat);  // k_trace<., ., true>
 // the stochastic trace strategies (k_trace_stochastic.hip): strategy 1 = pass-stochastic, 2 = stochastic any-hit
 void launchTraceStochastic(hipStream_t stream, const TraceArgs& a, const FrameConst& F, int shFormat, int strategy);
 void launchTraceLight(hipStream_t stream, const TraceLightArgs& L, const FrameConst& F);  // k_trace_light.hip
+void launchTraceLightWithMeshes(hipStream_t stream, const TraceLightMeshArgs& L, const FrameConst& F);  // k_trace_light<., true>
+// mesh hits of a traced frame (k_trace_mesh.hip), in k_trace's tiling: every pixel's closest mesh hit in front of k_trace; the unlit
+// composite or the lit mesh shading behind k_trace and the light pass
+void launchTraceMeshPrimary(hipStream_t stream, const TraceMeshArgs& m, const FrameArgs* frame, const FrameConst& F);
+void launchTraceMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, const FrameConst& F, bool lit);
 // ray queries (k_trace_rays.hip): the frame's primary rays written out row-major; a batch's coherence keys; one ray per lane
 void launchRaysGenerate(hipStream_t stream, const FrameArgs* dArgs, float4* rays, uint32_t pixels);
 void launchRaysKey(hipStream_t stream, const RayKeyArgs& a);

@@ -561,6 +561,36 @@ struct MeshRayState
   }
 };
 
+// mesh hits in the traced frames (mgs_frame_set_trace_meshes; api_trace.hip, k_trace_mesh.hip): the handle's setting, the per-pixel
+// buffers of its last such frame (hit record, its t, the walk's transmittance as a float), the two counter blocks (primary mesh
+// rays, mesh occlusion rays), what mgs_trace_mesh_stats reports besides them, and the events around the two new launches
+enum TraceMeshEvent { kTmevPrimaryBegin, kTmevPrimaryEnd, kTmevCompositeBegin, kTmevCompositeEnd, kTmevCount };
+struct TraceMeshState
+{
+  bool                    enabled = false;  // mgs_frame_set_trace_meshes
+  float                   minT    = 0.0f;
+  DevBuf<float4>          hits;
+  DevBuf<float>           meshT, walkT;
+  DevBuf<MeshRayCounters> ctr;
+  bool                    have = false;       // the handle's last traced frame ran with the setting on
+  bool                    composited = false, lit = false;  // ... with a visible mesh instance (the composite ran); as a lit frame
+  uint32_t                rebuilt = 0;
+  float                   buildMs = 0.0f;
+  uint64_t                triangles = 0, leaves = 0, nodes = 0;
+  hipEvent_t              ev[kTmevCount] = {};
+  template <class F>
+  void eachBuffer(F&& f) { f(hits); f(meshT); f(walkT); f(ctr); }
+  void release()
+  {
+    eachBuffer([](auto& b) { b.release(); });
+    for(auto& e : ev)
+    {
+      if(e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 // scratch of the stand-alone sort (mgs_radix_sort_u32): owned by the handle (its device, its stream)
 struct SortScratch
 {
@@ -697,6 +727,7 @@ struct MgsScene_t
   MeshPassState   mesh;
   TracePassState  trace;
   MeshRayState    meshRays;
+  TraceMeshState  traceMesh;
   SortScratch     rs;
   CommState       comm;
   CpuSortState    cpu;
@@ -775,6 +806,9 @@ struct TraceOutRead
   int begin(MgsScene s);
   int finish(MgsScene s, uint32_t rebuilt, float buildMs, MgsTraceOut* out) const;
 };
+// api_mesh_rays.hip: the lazy build of the triangle hierarchy on handle s, as a mesh query runs it; the caller holds
+// SceneData::meshBvh.mtx from this call to its last launch that reads the hierarchy
+int  ensureMeshHierarchyLocked(MgsScene s, float* buildMs, uint32_t* rebuilt);
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip
 int  cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking);         // api_sort.hip
