@@ -718,7 +718,7 @@ typedef struct MgsTraceLightOut {
   uint32_t reserved;
 } MgsTraceLightOut;
 /* One lit traced frame into the handle's frame buffer.  Reads everything mgs_render_traced reads, plus lighting_mode, which must be
- * MGS_LIGHTING_DIRECT: MGS_LIGHTING_INDIRECT needs bounces and returns MGS_ERR_UNSUPPORTED, MGS_LIGHTING_DISABLED or any other value
+ * MGS_LIGHTING_DIRECT: MGS_LIGHTING_INDIRECT needs bounces (mgs_render_traced_indirect) and returns MGS_ERR_UNSUPPORTED here, MGS_LIGHTING_DISABLED or any other value
  * MGS_ERR_INVALID_ARG.  The ranges of the three structs are checked before the handle is looked at.  `trace` / `light` NULL = the
  * defaults; `out` or `light_out` non-NULL waits for the frame.  Afterwards mgs_frame_download, mgs_frame_copy_strip,
  * mgs_frame_download_surface (always: lighting turns the surface outputs on), mgs_trace_download_hit_counts, the image-compare entry
@@ -1203,8 +1203,8 @@ int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_de
  * an unlit frame with a visible mesh also keeps the lit frames' fp32 pixel and ray parameter (16 B + 4 B).
  * PARITY UNPINNED: what the mesh ray queries list, and the reference's RAY_FLAG_CULL_BACK_FACING_TRIANGLES, which has no effect there.
  * Out of scope: hybrid frames with meshes, mesh occlusion inside mgs_trace_shadow_rays / mgs_shade_points, the stochastic
- * strategies with meshes, mesh transmittance / ior / reflection / refraction bounces, indirect lighting, soft shadows, light
- * proxies, ray masks, mgs_render_gathered. */
+ * strategies with meshes, soft shadows, light proxies, ray masks, mgs_render_gathered.  Mesh transmittance / ior / reflection /
+ * refraction bounces and indirect lighting are mgs_render_traced_indirect's (MGS_HAS_TRACE_BOUNCES, below). */
 #define MGS_HAS_TRACE_MESHES 1
 typedef struct MgsTraceMeshParams {
   int32_t  enabled;                          /* 0 / 1, default 0 */
@@ -1215,6 +1215,94 @@ void mgs_trace_mesh_params_default(MgsTraceMeshParams* params);
 int  mgs_frame_set_trace_meshes(MgsScene scene_or_context, const MgsTraceMeshParams* params /* NULL = off */);
 int  mgs_trace_download_mesh_hits(MgsScene scene_or_context, MgsMeshHit* host_dst, size_t count); /* [height][width] */
 int  mgs_trace_mesh_stats(MgsScene scene_or_context, MgsMeshRayOut* primary, MgsMeshRayOut* shadow); /* either may be NULL; waits */
+
+/* ---- reflection and refraction bounces (MGS_HAS_TRACE_BOUNCES): the indirect traced frame, the reference's LIGHTING_INDIRECT
+ * (shaderio.h:133) for trace strategy 0: the bounce loop of shaders/threedgrt_raytrace.rgen.slang:230-337 off mesh materials that
+ * say "mirror" or "glass".  mgs_render_traced_lit, mgs_render_hybrid and mgs_render keep answering MGS_LIGHTING_INDIRECT as before.
+ *
+ * Bounce 0 is the frame mgs_render_traced_lit makes with the handle's trace-mesh setting on, except that the mesh is shaded in the
+ * indirect mode of evaluateLightingAndShadingMeshes (:1169-1219) through wavefrontComputeShading (wavefront.h.slang:282-376), and the
+ * transmittance is a double3 from the first material multiplication on.  The light term is the direct function's (:233-280).  After
+ * it the material's illum selects: <= 0: T = 0; == 1: T *= specular, new ray = (meshHitWorldPos, reflect(rayDir, worldNrm));
+ * >= 2: T *= transmittance, new ray from meshHitWorldPos along refract(rayDir, N, eta) with eta = 1 / ior, and N = -worldNrm,
+ * eta = ior when dot(rayDir, worldNrm) > 0; the result is normalised; when length(refracted) > 0 fails, reflect(rayDir, N) (total
+ * internal reflection).  Both set done = 0.  The light loop's state rule (:1186-1197): a light out of range is skipped before
+ * anything happens; T, ray and done are restored before every light but the first; what survives is what the last light shaded
+ * left; radiance accumulates over all lights with the restored T; with every light out of range nothing is called, done stays 1
+ * and the pixel ends; with no lights the never-shadowed headlight at camera_pos applies.  A material whose needShading is 0 adds its
+ * emission and never bounces (:1159-1165).
+ *
+ * Bounce b >= 1, for pixels with done == 0, b up to max_bounces inclusive (:328-330): tMin = 0.001, tMax = 10000; the closest mesh
+ * hit of the bounce ray under the rules of mgs_trace_mesh_rays (:505-552); isoSurfDepth and integratedNormal reset (:568-573); the
+ * pass walk of strategy 0 in (tMin + epsT, t_mesh + epsT) with the CARRIED radiance, double3 transmittance and hit count
+ * (:615-763): loop and slot conditions are maxComponent(T) > min_transmittance, the iso pick is taken when isoSurfDepth == 0 and
+ * T.x < depth_iso_threshold (the x channel, as written).  surfaceFinalFiltering does not run (:581): the integrated normal is the
+ * raw weighted sum and a walk without a pick keeps its unshaded radiance.  Then evaluateLightingAndShadingForBounce (:1037-1062):
+ * the splat surface is shaded when t_iso > 0, t_iso < t_mesh and there is a pick, on radiance - radianceBeforeParticles (added back
+ * afterwards), at origin + t_iso * dir, with the lit frame's shadow origin and both shadow walks; then the mesh as at bounce 0 when
+ * hit and maxComponent(T) > min_mesh_composite_transmittance (in double).
+ *
+ * Outputs.  The image is the final radiance; alpha, surface depth, picked id and normal are bounce 0's, as the lit mesh frame
+ * defines them.  mgs_trace_download_hit_counts and mgs_trace_download_shadow_hits sum over all bounces; MgsTraceOut::accepted_hits
+ * and MgsTraceLightOut's sums include the bounces' rays; mgs_trace_download_mesh_hits stays the primary hit.  Temporal accumulation,
+ * target formats, strip rows and frame contexts work as after any traced frame.
+ *
+ * Bounce materials are the three fields of ObjMaterial (wavefront.h:37-50) MgsMaterial leaves out; illum is the reference's DERIVED
+ * model (0, 1, >= 2), not the MTL statement's number.  mgs_bounce_material_from_mtl restates src/obj_loader.cpp:50-59 as written: it
+ * tests transmittance.x twice and never .z, so Tf = (0, 0, 1) is not refractive.  mgs_mesh_instance_set_bounce_materials is indexed by
+ * the triangle's material id; ids >= count and an instance never set are illum 0; count = 0 clears.  It belongs to the scene and
+ * follows the ordering rule of mgs_scene_set_lights (waits for all contexts, rewrites the device table, MGS_ERR_STATE on a context
+ * handle); it does not invalidate the triangle hierarchy.  A non-finite field, illum >= 2 with ior not finite or <= 0, or a non-zero
+ * reserved word is MGS_ERR_INVALID_ARG.
+ *
+ * mgs_render_traced_indirect follows mgs_render_traced_lit's conventions (NULL = defaults, a non-NULL out waits, ranges are checked
+ * before the handle is looked at).  lighting_mode must be MGS_LIGHTING_INDIRECT (anything else: MGS_ERR_INVALID_ARG);
+ * trace_strategy != 0 and MGS_SHADOWS_SOFT are MGS_ERR_UNSUPPORTED; max_bounces outside [1, 16] is MGS_ERR_INVALID_ARG; the
+ * handle's trace-mesh setting off is MGS_ERR_STATE (nothing to bounce off; min_mesh_composite_transmittance is read from that
+ * setting).  A bound sensor model and a bound occluder are refused as the lit frame refuses them.  MgsTraceBounceOut: index b - 1
+ * holds the live pixels and the mesh hits of bounce b, particle_hits the hits accepted at b >= 1, bounce_ms HIP events around
+ * everything after bounce 0.  The host enqueues max_bounces rounds unconditionally; counts never leave the device in between.
+ *
+ * Bounce 0 runs the lit mesh frame's launches as they are; a hand-over kernel behind them shades the pixels whose material bounces a
+ * second time, in fp32 for the carried radiance (their shadow rays are traced twice and counted once).  With every bounce material
+ * illum 0, or every mesh instance invisible, the frame is mgs_render_traced_lit's byte for byte.
+ * Per-pixel bounce state belongs to the handle and counts into working_bytes: 64 B a pixel — a live word (4 B), ray origin and
+ * direction (24 B), the fp32 radiance (12 B) and the double3 transmittance (24 B) — plus a 264-byte counter block, besides the lit
+ * mesh frame's 92 B.  The closest mesh walks of the bounce rays are not part of mgs_trace_mesh_stats' `primary`; the bounces' mesh
+ * occlusion rays are in `shadow`.
+ * Out of scope: the stochastic strategies' bounces, soft shadows, hybrid frames, light proxies, ray masks, textures, multi-GPU
+ * (mgs_render_gathered).
+ * mgs_mesh_load_obj additionally reads Tf / Kt, Ni and illum from the material library (initial values 0, 1, 0; tinyobj is not in
+ * the reference tree, so these defaults are build-defined, PARITY UNPINNED as the loader's subset is); MgsMeshView and everything
+ * the loader returned before are unchanged.  mgs_mesh_bounce_materials returns them through mgs_bounce_material_from_mtl, one per
+ * material of the mesh (`count` receives that number; capacity 0 only asks for it; a smaller capacity is MGS_ERR_INVALID_ARG); a
+ * mesh from arrays returns defaults. */
+#define MGS_HAS_TRACE_BOUNCES 1
+typedef struct MgsBounceMaterial {
+  float    transmittance[3]; /* ObjMaterial::transmittance (Tf), default 0 */
+  float    ior;              /* ObjMaterial::ior (Ni), default 1 */
+  int32_t  illum;            /* the derived model: <= 0 none, 1 reflective, >= 2 refractive; default 0 */
+  uint32_t reserved[3];      /* must be 0 */
+} MgsBounceMaterial;
+typedef struct MgsTraceBounceParams {
+  int32_t  max_bounces;      /* frameInfo.rtxMaxBounces, default 3 (shaderio.h:273); [1, 16] */
+  uint32_t reserved[3];      /* must be 0 */
+} MgsTraceBounceParams;
+typedef struct MgsTraceBounceOut {
+  uint64_t rays[16];         /* [b - 1]: pixels live at bounce b */
+  uint64_t mesh_hits[16];    /* [b - 1]: of them, bounce rays that hit a mesh */
+  uint64_t particle_hits;    /* particle hits accepted at b >= 1 */
+  float    bounce_ms;        /* HIP events around everything after bounce 0 */
+  uint32_t reserved;
+} MgsTraceBounceOut;
+void mgs_bounce_material_default(MgsBounceMaterial* m);
+void mgs_bounce_material_from_mtl(const float tf[3], float ni, int mtl_illum, MgsBounceMaterial* out);
+int  mgs_mesh_bounce_materials(MgsMesh mesh, MgsBounceMaterial* out, uint32_t capacity, uint32_t* count);
+int  mgs_mesh_instance_set_bounce_materials(MgsScene scene, int mesh_instance_id, const MgsBounceMaterial* m, uint32_t count);
+void mgs_trace_bounce_params_default(MgsTraceBounceParams* params);
+int  mgs_render_traced_indirect(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace,
+                                const MgsTraceLightParams* light, const MgsTraceBounceParams* bounce, MgsTraceOut* out,
+                                MgsTraceLightOut* light_out, MgsTraceBounceOut* bounce_out);
 
 /* ---- runtime image comparison: replaces ImageCompare (src/image_compare.{h,cpp}) with its two compute shaders
  * (shaders/image_compare_metric.comp.slang, shaders/image_compare_composite.comp.slang, colour helpers shaders/color.h.slang).

@@ -128,7 +128,10 @@ def main():
     ap.add_argument("--mesh-shadows", type=int, choices=[0, 1], default=0)  # --mesh --lighting 1: the splats' shadows on the meshes
     ap.add_argument("--trace-meshes", type=int, choices=[0, 1], default=1)  # --pipeline trace --mesh: mgs_frame_set_trace_meshes
     ap.add_argument("--mesh-composite-threshold", type=float, default=0.0)
-    ap.add_argument("--lighting", type=int, choices=[0, 1], default=0)
+    ap.add_argument("--lighting", type=int, choices=[0, 1, 2], default=0)  # 2: --pipeline trace --mesh, mgs_render_traced_indirect
+    ap.add_argument("--max-bounces", type=int, default=3)  # --lighting 2
+    # --lighting 2: illum ior tf tf tf for every material of the k-th --mesh (illum: the derived model 0 / 1 / 2) in place of what its MTL says
+    ap.add_argument("--mesh-bounce", action="append", type=float, nargs=5, default=[], metavar="B")
     ap.add_argument("--lights", default=None, metavar="FILE.json")
     ap.add_argument("--material", type=float, nargs=13, default=None)
     ap.add_argument("--pipeline", choices=["raster", "trace", "hybrid"], default="raster")  # hybrid: the raster surface lit with traced shadow rays
@@ -190,8 +193,10 @@ def main():
         scene.upload_occluder(depth, back)
     if (a.lights or a.material) and not a.lighting:
         ap.error("--lights / --material need --lighting 1")
+    if a.lighting == 2 and not (a.pipeline == "trace" and a.mesh and a.trace_meshes):
+        ap.error("--lighting 2 needs --pipeline trace and --mesh (bounces off mesh materials, mgs_render_traced_indirect)")
     if a.lighting:
-        p.lighting_mode = capi.LIGHTING_DIRECT
+        p.lighting_mode = capi.LIGHTING_DIRECT if a.lighting == 1 else 2  # MGS_LIGHTING_INDIRECT
         if a.lights:
             import json
             with open(a.lights) as f:
@@ -209,7 +214,13 @@ def main():
         for k, path in enumerate(a.mesh):
             m = np.array(a.mesh_transform[k], np.float32).reshape(4, 4) if k < len(a.mesh_transform) else None
             meshes.append((mgs.Mesh.load_obj(path), m))
-            scene.add_mesh_instance(*meshes[-1])
+            inst = scene.add_mesh_instance(*meshes[-1])
+            if a.lighting == 2:  # bounce materials: the OBJ's MTL (Tf / Ni / illum), or --mesh-bounce for all of this mesh's materials
+                bm = meshes[-1][0].bounce_materials()
+                if k < len(a.mesh_bounce):
+                    b = a.mesh_bounce[k]
+                    bm = [capi.bounce_material(b[2:5], b[1], int(b[0])) for _ in bm]
+                scene.set_mesh_bounce_materials(inst, bm)
     if a.mesh and a.pipeline == "trace":
         # the meshes are traced with the splats: no mesh pass, no occluder (a traced frame refuses a bound one)
         if a.mesh_pick_image:
@@ -247,7 +258,12 @@ def main():
             lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
                                                  particle_shadow_transmittance_threshold=a.shadow_threshold,
                                                  particle_shadow_color_strength=a.shadow_color_strength)
-            o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
+            if a.lighting == 2:
+                o, lo, bo = scene.render_traced_indirect(p, t, lp, a.max_bounces, want_stats=True)
+                print(f"bounces {bo.bounce_ms:.3f} ms on the GPU, live pixels per bounce {list(bo.rays)[:a.max_bounces]}, mesh hits "
+                      f"{list(bo.mesh_hits)[:a.max_bounces]}, {bo.particle_hits} particle hits")
+            else:
+                o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
             sr = max(int(lo.shadow_rays), 1)
             print(f"light pass {lo.light_ms:.3f} ms on the GPU, {lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, "
                   f"{lo.shadow_candidate_tests / sr:.1f} candidate tests and {lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")

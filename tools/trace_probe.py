@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--trace-meshes] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--trace-meshes [--indirect]] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
@@ -24,6 +24,9 @@ closest and occlusion mode, reorder off and on: MgsMeshRayOut with the median tr
 and lit frames (one point light, hard shadows) with mgs_frame_set_trace_meshes off and on: trace_ms, light_ms and both MgsMeshRayOut
 blocks of mgs_trace_mesh_stats.  shadow.trace_ms is the mesh composite kernel's time, which traces the occlusion rays of the mesh
 points; the occlusion rays of the splat surface run inside light_ms, while shadow.hits counts the occluded rays of both.
+--indirect (with --trace-meshes) adds mgs_render_traced_indirect: on that scene with every bounce material illum 0 (max_bounces 3 and
+16: what the rounds without a live pixel cost next to the lit frame), then with a mirror floor under the grid (max_bounces 1 and 3):
+MgsTraceBounceOut with the median bounce_ms, the live pixels per bounce and their share of the frame.
 Needs an MI355X.
 """
 import argparse
@@ -99,7 +102,7 @@ def probe_mesh_rays(path, n, W, H, warmup, repeats):
     return out
 
 
-def probe_trace_meshes(scene, p, t, path, eye, warmup, repeats):
+def probe_trace_meshes(scene, p, t, path, eye, warmup, repeats, indirect=False):
     """--trace-meshes: unlit and lit frames of the scene plus the mesh on a 3 x 3 grid, the setting off and on"""
     mesh = capi.Mesh.load_obj(path)
     ext = float(np.abs(mesh.view()["positions"]).max()) * 2.5
@@ -131,8 +134,41 @@ def probe_trace_meshes(scene, p, t, path, eye, warmup, repeats):
                 d["primary"], d["shadow"] = primary.as_dict(), shadow.as_dict()
                 d["note"] = "shadow.trace_ms: the mesh composite kernel; the splat surface's mesh occlusion rays are inside light_ms"
             out["runs"].append(d)
+    if indirect:
+        out["indirect"] = probe_indirect(scene, p, t, lp, ext, warmup, repeats)
     p.lighting_mode = 0
     scene.set_trace_meshes(False)
+    return out
+
+
+def probe_indirect(scene, p, t, lp, ext, warmup, repeats):
+    """--indirect (with --trace-meshes, the setting on): mgs_render_traced_indirect.  First on the scene as it is, every bounce
+    material illum 0: against the lit frame above, the price of max_bounces rounds without a live pixel.  Then with a mirror floor
+    under the grid, max_bounces 1 and 3: bounce_ms, the live pixels per bounce and their share of the frame."""
+    pixels = p.width * p.height
+    p.lighting_mode = 2
+
+    def run(nb):
+        tms, lms, cms, bms = [], [], [], []
+        for k in range(warmup + repeats):
+            o, lo, bo = scene.render_traced_indirect(p, t, lp, nb, want_stats=True)
+            _, shadow = scene.trace_mesh_stats()
+            if k >= warmup:
+                tms.append(o.trace_ms), lms.append(lo.light_ms), cms.append(shadow.trace_ms), bms.append(bo.bounce_ms)
+        rays = list(bo.rays)[:nb]
+        return dict(max_bounces=nb, trace_ms_median=float(np.median(tms)), light_ms_median=float(np.median(lms)),
+                    composite_ms_median=float(np.median(cms)), bounce_ms_median=float(np.median(bms)), bounce_ms_min=float(min(bms)),
+                    bounce_ms_max=float(max(bms)), rays=rays, mesh_hits=list(bo.mesh_hits)[:nb], live_fraction=[r / pixels for r in rays],
+                    particle_hits=int(bo.particle_hits), shadow_rays=int(lo.shadow_rays))
+    out = dict(empty=[run(3), run(16)])
+    s = 2.0 * ext
+    y = -0.6 * ext
+    floor = capi.Mesh.from_arrays(np.float32([[-s, y, s], [s, y, s], [s, y, -s], [-s, y, -s]]), [[0, 1, 2], [0, 2, 3]], np.float32([[0, 1, 0]] * 4), [0, 0],
+                                  [capi.make_material(ambient=(0.02, 0.02, 0.02), diffuse=(0.1, 0.1, 0.1), specular=(0.8, 0.8, 0.8), shininess=32.0)])
+    inst = scene.add_mesh_instance(floor, None)
+    scene.set_mesh_bounce_materials(inst, [capi.bounce_material(illum=1)])
+    out["mirror_floor"] = [run(1), run(3)]
+    out["note"] = "bounce_ms: the hand-over of bounce 0 (which shades the bouncing pixels again) and max_bounces rounds"
     return out
 
 
@@ -233,6 +269,7 @@ def main():
     ap.add_argument("--mesh-rays", type=int, nargs="+", default=[])
     ap.add_argument("--mesh", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "meshes", "fixture.obj"))
     ap.add_argument("--trace-meshes", action="store_true")
+    ap.add_argument("--indirect", action="store_true")  # with --trace-meshes: MgsTraceBounceOut of mgs_render_traced_indirect
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     W, H = a.size
@@ -314,7 +351,7 @@ def main():
             p.lighting_mode = 0
         if a.trace_meshes:
             tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
-            r["trace_meshes"] = probe_trace_meshes(scene, p, tq, a.mesh, eye, a.warmup, a.repeats)
+            r["trace_meshes"] = probe_trace_meshes(scene, p, tq, a.mesh, eye, a.warmup, a.repeats, a.indirect)
         print(json.dumps(r))
         results.append(r)
         scene.close()

@@ -233,6 +233,41 @@ class TraceMeshParams(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("min_mesh_composite_transmittance", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class BounceMaterial(C.Structure):
+    """MgsBounceMaterial (32 bytes): what a mesh material says about bounces (mgs_mesh_instance_set_bounce_materials)"""
+    _fields_ = [("transmittance", C.c_float * 3), ("ior", C.c_float), ("illum", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+class TraceBounceParams(C.Structure):
+    """MgsTraceBounceParams (16 bytes): the bounces of an indirect traced frame (mgs_render_traced_indirect)"""
+    _fields_ = [("max_bounces", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+class TraceBounceOut(C.Structure):
+    """MgsTraceBounceOut: per bounce the live pixels and their mesh hits, the particle hits of all bounces, the bounces' device time"""
+    _fields_ = [("rays", C.c_uint64 * 16), ("mesh_hits", C.c_uint64 * 16), ("particle_hits", C.c_uint64), ("bounce_ms", C.c_float),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(rays=list(self.rays), mesh_hits=list(self.mesh_hits), particle_hits=self.particle_hits, bounce_ms=self.bounce_ms)
+
+
+def bounce_material(transmittance=(0.0, 0.0, 0.0), ior=1.0, illum=0):
+    """a BounceMaterial from its three fields (illum: the derived model 0 / 1 / >= 2)"""
+    m = BounceMaterial()
+    load_library().mgs_bounce_material_default(C.byref(m))
+    m.transmittance[:] = [float(v) for v in transmittance]
+    m.ior, m.illum = float(ior), int(illum)
+    return m
+
+
+def bounce_material_from_mtl(tf, ni, mtl_illum):
+    """mgs_bounce_material_from_mtl: the loader's rule (src/obj_loader.cpp:50-59) for a material's Tf, Ni and illum statements"""
+    m = BounceMaterial()
+    load_library().mgs_bounce_material_from_mtl((C.c_float * 3)(*[float(v) for v in tf]), float(ni), int(mtl_illum), C.byref(m))
+    return m
+
+
 SENSOR_OPENCV_PINHOLE, SENSOR_OPENCV_FISHEYE = 0, 1
 
 
@@ -423,6 +458,13 @@ def load_library():
         "mgs_frame_set_trace_meshes": (C.c_int, [vp, P(TraceMeshParams)]),
         "mgs_trace_download_mesh_hits": (C.c_int, [vp, vp, C.c_size_t]),
         "mgs_trace_mesh_stats": (C.c_int, [vp, P(MeshRayOut), P(MeshRayOut)]),
+        "mgs_bounce_material_default": (None, [P(BounceMaterial)]),
+        "mgs_bounce_material_from_mtl": (None, [P(F), F, C.c_int, P(BounceMaterial)]),
+        "mgs_mesh_bounce_materials": (C.c_int, [vp, P(BounceMaterial), C.c_uint32, P(C.c_uint32)]),
+        "mgs_mesh_instance_set_bounce_materials": (C.c_int, [vp, C.c_int, P(BounceMaterial), C.c_uint32]),
+        "mgs_trace_bounce_params_default": (None, [P(TraceBounceParams)]),
+        "mgs_render_traced_indirect": (C.c_int, [vp, P(FrameParams), P(TraceParams), P(TraceLightParams), P(TraceBounceParams), P(TraceOut),
+                                                 P(TraceLightOut), P(TraceBounceOut)]),
         "mgs_frame_context_create": (C.c_int, [vp, P(vp)]),
         "mgs_frame_context_destroy": (None, [vp]),
         "mgs_scene_memory_usage": (C.c_int, [vp, P(C.c_uint64), P(C.c_uint64)]),
@@ -487,6 +529,8 @@ EXPORTED_SYMBOLS = [
     "mgs_trace_shadow_rays", "mgs_trace_shadow_rays_device", "mgs_shade_points", "mgs_shade_points_device",
     "mgs_mesh_ray_params_default", "mgs_trace_mesh_rays", "mgs_trace_mesh_rays_device",
     "mgs_trace_mesh_params_default", "mgs_frame_set_trace_meshes", "mgs_trace_download_mesh_hits", "mgs_trace_mesh_stats",
+    "mgs_bounce_material_default", "mgs_bounce_material_from_mtl", "mgs_mesh_bounce_materials", "mgs_mesh_instance_set_bounce_materials",
+    "mgs_trace_bounce_params_default", "mgs_render_traced_indirect",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
     "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
@@ -616,6 +660,20 @@ class Mesh:
                 for i in range(v.material_count)]
         return dict(positions=cp(v.positions, 3 * nv).reshape(-1, 3), normals=cp(v.normals, 3 * nv).reshape(-1, 3),
                     indices=cp(v.indices, ni).reshape(-1, 3), material_ids=cp(v.material_ids, ni // 3), materials=mats)
+
+    def bounce_materials(self):
+        """mgs_mesh_bounce_materials: one BounceMaterial per material of the mesh, from the MTL's Tf / Ni / illum through the loader's
+        rule (a mesh from arrays: defaults); pass the list to Scene.set_mesh_bounce_materials"""
+        n = C.c_uint32()
+        _check(load_library().mgs_mesh_bounce_materials(self._h, None, 0, C.byref(n)))
+        arr = (BounceMaterial * max(n.value, 1))()
+        _check(load_library().mgs_mesh_bounce_materials(self._h, arr, n.value, C.byref(n)))
+        out = []
+        for i in range(n.value):   # copies: the array's elements would keep it alive and alias it
+            m = BounceMaterial()
+            C.memmove(C.byref(m), C.byref(arr[i]), C.sizeof(BounceMaterial))
+            out.append(m)
+        return out
 
     def close(self):
         if self._h:
@@ -894,6 +952,32 @@ class Scene:
                                                C.byref(light) if light is not None else None,
                                                C.byref(out) if want_stats else None, C.byref(lout) if want_stats else None))
         return (out, lout) if want_stats else None
+
+    def render_traced_indirect(self, params, trace=None, light=None, bounce=None, want_stats=False):
+        """mgs_render_traced_indirect: the lit traced frame with mesh hits (set_trace_meshes on) whose mirror and glass materials
+        (set_mesh_bounce_materials) send bounce rays (params.lighting_mode must be MGS_LIGHTING_INDIRECT); trace / light / bounce = a
+        TraceParams / TraceLightParams / TraceBounceParams, or an int max_bounces, or None for the defaults; want_stats waits and
+        returns (TraceOut, TraceLightOut, TraceBounceOut)"""
+        out, lout, bout = TraceOut(), TraceLightOut(), TraceBounceOut()
+        if isinstance(bounce, int):
+            b = TraceBounceParams()
+            self._lib.mgs_trace_bounce_params_default(C.byref(b))
+            b.max_bounces = bounce
+            bounce = b
+        self._sort_only = False
+        self._frame_wh = (params.width, params.height)
+        _check(self._lib.mgs_render_traced_indirect(self._h, C.byref(params), C.byref(trace) if trace is not None else None,
+                                                    C.byref(light) if light is not None else None,
+                                                    C.byref(bounce) if bounce is not None else None,
+                                                    C.byref(out) if want_stats else None, C.byref(lout) if want_stats else None,
+                                                    C.byref(bout) if want_stats else None))
+        return (out, lout, bout) if want_stats else None
+
+    def set_mesh_bounce_materials(self, mesh_instance, materials):
+        """mgs_mesh_instance_set_bounce_materials: materials = BounceMaterial objects (bounce_material(...)) indexed by the triangles'
+        material id; an empty list clears"""
+        arr = (BounceMaterial * max(len(materials), 1))(*materials)
+        _check(self._lib.mgs_mesh_instance_set_bounce_materials(self._h, int(mesh_instance), arr if materials else None, len(materials)))
 
     def render_hybrid(self, params, trace=None, light=None, want_stats=False):
         """mgs_render_hybrid: the rasterised frame of params.pipeline (3DGS or 3DGUT) as the primary surface, lit by the scene's

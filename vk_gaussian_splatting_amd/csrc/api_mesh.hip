@@ -290,6 +290,138 @@ int mgs_mesh_instance_set_visible(MgsScene s, int id, int visible)
   });
 }
 
+// ---- bounce materials (mgs_render_traced_indirect) -------------------------------------------------------------------------------
+static_assert(sizeof(BounceMatDev) == sizeof(MgsBounceMaterial) && sizeof(MgsBounceMaterial) == 32, "the kernels read MgsBounceMaterial as it is");
+static_assert(sizeof(MgsTraceBounceParams) == 16 && sizeof(MgsTraceBounceOut) == 272, "documented sizes");
+
+void mgs_bounce_material_default(MgsBounceMaterial* m)
+{
+  if(!m)
+    return;
+  std::memset(m, 0, sizeof(*m));
+  m->ior = 1.0f;
+}
+
+// src/obj_loader.cpp:50-59 as written: transmittance.x is tested twice and .z never
+void mgs_bounce_material_from_mtl(const float tf[3], float ni, int mtl_illum, MgsBounceMaterial* out)
+{
+  if(!out)
+    return;
+  mgs_bounce_material_default(out);
+  if(tf)
+    std::memcpy(out->transmittance, tf, 12);
+  out->ior = ni;
+  if(out->transmittance[0] != 0.0f || out->transmittance[1] != 0.0f || out->transmittance[0] != 0.0f)
+    out->illum = 2;  // refractive
+  else if(mtl_illum > 1)
+    out->illum = 1;  // reflective
+  else
+    out->illum = 0;
+}
+
+// what the mesh's material library says, through the loader's rule; a mesh from arrays has no library: defaults
+int mgs_mesh_bounce_materials(MgsMesh mesh, MgsBounceMaterial* out, uint32_t capacity, uint32_t* count)
+{
+  if(!mesh || !count || (capacity > 0 && !out))
+  {
+    setError("mgs_mesh_bounce_materials: null argument");
+    return MGS_ERR_INVALID_ARG;
+  }
+  const HostMesh& m = *mesh->data;
+  const uint32_t  n = (uint32_t)m.materials.size();
+  *count = n;
+  if(capacity < n)
+  {
+    if(capacity == 0)
+      return MGS_OK;  // the size query
+    setError("mgs_mesh_bounce_materials: the mesh has " + std::to_string(n) + " materials, the destination holds " + std::to_string(capacity));
+    return MGS_ERR_INVALID_ARG;
+  }
+  for(uint32_t k = 0; k < n; ++k)
+  {
+    if(k < m.mtlBounce.size())
+      mgs_bounce_material_from_mtl(m.mtlBounce[k].tf, m.mtlBounce[k].ni, m.mtlBounce[k].illum, &out[k]);
+    else
+      mgs_bounce_material_default(&out[k]);
+  }
+  return MGS_OK;
+}
+
+// rebuilds the flat array and the per-instance slices and rewrites the device copies, after the frames in flight on every handle of
+// the scene are done (the rule of mgs_scene_set_lights).  The triangle hierarchy does not depend on them.
+static int rewriteBounceTable(SceneData& d)
+{
+  HIPCHK(hipSetDevice(d.device));
+  auto                      T = std::make_unique<BounceTable>();
+  std::vector<BounceMatDev> flat;
+  std::memset(T.get(), 0, sizeof(BounceTable));
+  for(size_t k = 0; k < d.bounceMats.size() && k < (size_t)kMaxMeshInstances; ++k)
+  {
+    T->offset[k] = (uint32_t)flat.size();
+    T->count[k]  = (uint32_t)d.bounceMats[k].size();
+    flat.insert(flat.end(), d.bounceMats[k].begin(), d.bounceMats[k].end());
+  }
+  {
+    std::lock_guard<std::mutex> lk(d.mtx);
+    for(MgsScene_t* h : d.handles)
+      HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if(int rc = d.bounceTab.ensure(1))
+    return rc;
+  if(int rc = d.bounceMatsDev.ensure(std::max<size_t>(flat.size(), 1)))
+    return rc;
+  if(!flat.empty())
+    HIPCHK(hipMemcpy(d.bounceMatsDev.p, flat.data(), flat.size() * sizeof(BounceMatDev), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d.bounceTab.p, T.get(), sizeof(BounceTable), hipMemcpyHostToDevice));
+  return MGS_OK;
+}
+
+// The caller holds d.meshBvh.mtx (an indirect frame's set-up does, from traceMeshSetUp to its last launch): two contexts' first
+// indirect frames, or a frame and mgs_mesh_instance_set_bounce_materials, never create or rewrite the copies at the same time.
+int ensureBounceTable(SceneData& d)
+{
+  return d.bounceTab.p ? (int)MGS_OK : rewriteBounceTable(d);
+}
+
+int mgs_mesh_instance_set_bounce_materials(MgsScene s, int id, const MgsBounceMaterial* m, uint32_t count)
+{
+  return guarded("mgs_mesh_instance_set_bounce_materials", [&]() -> int {
+    // (before the handle is looked at: the values can be checked without a device)
+    if(count > 0 && !m)
+    {
+      setError("mgs_mesh_instance_set_bounce_materials: null materials with a count");
+      return (int)MGS_ERR_INVALID_ARG;
+    }
+    for(uint32_t k = 0; k < count; ++k)
+    {
+      const MgsBounceMaterial& b = m[k];
+      const bool finite = std::isfinite(b.transmittance[0]) && std::isfinite(b.transmittance[1]) && std::isfinite(b.transmittance[2]) && std::isfinite(b.ior);
+      if(!finite || (b.illum >= 2 && !(b.ior > 0.0f)) || b.reserved[0] != 0 || b.reserved[1] != 0 || b.reserved[2] != 0)
+      {
+        setError("mgs_mesh_instance_set_bounce_materials: material " + std::to_string(k)
+                 + ": the fields must be finite, ior > 0 for illum >= 2, and the reserved words 0");
+        return (int)MGS_ERR_INVALID_ARG;
+      }
+    }
+    if(int rc = editable(s, "mgs_mesh_instance_set_bounce_materials"))
+      return rc;
+    SceneData& d = *s->d;
+    if(id < 0 || id >= (int)d.meshInstances.size())
+    {
+      setError("mgs_mesh_instance_set_bounce_materials: no such mesh instance");
+      return (int)MGS_ERR_INVALID_ARG;
+    }
+    if(d.bounceMats.size() < d.meshInstances.size())
+      d.bounceMats.resize(d.meshInstances.size());
+    std::vector<BounceMatDev> v(count);
+    if(count)
+      std::memcpy(v.data(), m, (size_t)count * sizeof(BounceMatDev));
+    std::lock_guard<std::mutex> tables(d.meshBvh.mtx);  // (an indirect frame's set-up on any context holds it while it looks at the copies)
+    d.bounceMats[id] = std::move(v);
+    return rewriteBounceTable(d);
+  });
+}
+
 // ---- the pass -------------------------------------------------------------------------------------------------------------------
 // translation of inverse(view), in double, rounded once: for a view matrix [R t; 0 1] the general inverse is taken, as the lighting
 // pass does for viewInverse

@@ -95,6 +95,8 @@ SceneData::~SceneData()
   for(auto& m : meshes)
     m.release();
   meshTab.release();
+  bounceMatsDev.release();
+  bounceTab.release();
   bvh.release();
   meshBvh.release();
 }
@@ -196,7 +198,7 @@ int mgs_scene_memory_usage(MgsScene s, uint64_t* sceneBytes, uint64_t* workingBy
   }
   if(sceneBytes)
   {
-    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes() + s->d->bvh.bytes() + s->d->meshBvh.bytes();
+    uint64_t b = s->d->compInst.bytes() + s->d->lightTab.bytes() + s->d->meshTab.bytes() + s->d->bounceMatsDev.bytes() + s->d->bounceTab.bytes() + s->d->bvh.bytes() + s->d->meshBvh.bytes();
     for(const auto& m : s->d->meshes)
       b += m.bytes();
     for(const auto& d : s->d->sets)

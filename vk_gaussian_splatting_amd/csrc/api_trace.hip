@@ -483,32 +483,46 @@ static int endTraversal(TracePassState& ts, hipStream_t st)
 }
 
 // lit: the frame of mgs_render_traced_lit (lp NULL = the defaults); otherwise lp and lout are not looked at
+// bounce: the frame of mgs_render_traced_indirect (a lit frame whose mesh composite is the indirect one, followed by max_bounces
+// bounce launches); bout is then not looked at otherwise
 static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out, bool lit = false,
-                                  const MgsTraceLightParams* lp = nullptr, MgsTraceLightOut* lout = nullptr)
+                                  const MgsTraceLightParams* lp = nullptr, MgsTraceLightOut* lout = nullptr,
+                                  const MgsTraceBounceParams* bounce = nullptr, MgsTraceBounceOut* bout = nullptr)
 {
+  const bool indirect = bounce != nullptr;
+  // the entry point's name for the messages that are raised in here (the other frames keep theirs as they were)
+  const std::string who = indirect ? "mgs_render_traced_indirect" : "mgs_render_traced";
   if(!p)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null params");
+    return failTrace(MGS_ERR_INVALID_ARG, who + ": null params");
   const MgsTraceParams      t  = traceParamsOr(tp);
   const MgsTraceLightParams lt = traceLightParamsOr(lit ? lp : nullptr);
-  if(int rc = validateTrace(p, t, lit ? &lt : nullptr))  // (before the handle is looked at: the ranges can be checked without a device)
+  // An indirect frame's bounce 0 IS the lit mesh frame: the lit frame's checks and the frame's constants are those of
+  // MGS_LIGHTING_DIRECT (`lp0`, and `q` below); the caller's own parameters, lighting_mode included, are what the handle records.
+  MgsFrameParams lp0 = *p;
+  if(indirect)
+    lp0.lighting_mode = MGS_LIGHTING_DIRECT;
+  if(int rc = validateTrace(&lp0, t, lit ? &lt : nullptr))  // (before the handle is looked at: the ranges can be checked without a device)
     return rc;
   if(!s)
-    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced: null scene");
+    return failTrace(MGS_ERR_INVALID_ARG, who + ": null scene");
   if(s->occ.depth)
-    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: an occluder is bound (meshes in the traced scene are out of scope); unbind it with "
+    return failTrace(MGS_ERR_UNSUPPORTED, who + ": an occluder is bound (meshes in the traced scene are out of scope); unbind it with "
                                           "mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
-  if(int rc = refuseBoundSensor(s, lit ? "mgs_render_traced_lit" : "mgs_render_traced", "the traced frames generate the perfect cameras' rays; trace the sensor's "
+  if(int rc = refuseBoundSensor(s, indirect ? "mgs_render_traced_indirect" : lit ? "mgs_render_traced_lit" : "mgs_render_traced", "the traced frames generate the perfect cameras' rays; trace the sensor's "
                                                                                          "rays with mgs_trace_generate_rays and mgs_trace_rays_device"))
     return rc;
   const bool meshOn = s->traceMesh.enabled;
+  if(indirect && !meshOn)
+    return failTrace(MGS_ERR_STATE, "mgs_render_traced_indirect: the handle's trace-mesh setting is off (an indirect frame bounces off mesh materials); turn "
+                                    "it on with mgs_frame_set_trace_meshes");
   if(meshOn && t.trace_strategy != MGS_TRACE_STRATEGY_FULL_ANYHIT)
-    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced: the stochastic trace strategies have no mesh hits; turn the setting off with "
+    return failTrace(MGS_ERR_UNSUPPORTED, who + ": the stochastic trace strategies have no mesh hits; turn the setting off with "
                                           "mgs_frame_set_trace_meshes(handle, NULL) or use trace_strategy 0");
-  MgsFrameParams q      = *p;
+  MgsFrameParams q      = lp0;
   q.depth_iso_threshold = t.depth_iso_threshold;
   std::unique_ptr<FrameArgs> A;
   int                        rc;
-  if((rc = traceFrameArgs(s, q, "mgs_render_traced", true, A))) return rc;
+  if((rc = traceFrameArgs(s, q, who.c_str(), true, A))) return rc;
   const FrameConst& F = A->f;
   if((rc = ensureFrameImage(s, &q, F))) return rc;
   TracePassState& ts = s->trace;
@@ -531,6 +545,17 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(meshOn)
   {  // launch order: mesh primary, k_trace, the light pass, the mesh composite
     if((rc = traceMeshSetUp(s, pixels, lit, meshHierarchy, M, meshActive))) return rc;
+    if(indirect && meshActive)
+    {  // the per-pixel bounce state (64 B a pixel), the counters, the scene's bounce materials
+      if(!tm.bounceEv[0])
+        for(auto& e : tm.bounceEv)
+          HIPCHK(hipEventCreate(&e));
+      if((rc = tm.bounceLive.ensure(pixels))) return rc;
+      if((rc = tm.bounceRay.ensure(9 * pixels))) return rc;
+      if((rc = tm.bounceT.ensure(3 * pixels))) return rc;
+      if((rc = tm.bounceCtr.ensure(1))) return rc;
+      if((rc = ensureBounceTable(*s->d))) return rc;
+    }
     HIPCHK(hipMemsetAsync(tm.ctr.p, 0, 2 * sizeof(MeshRayCounters), st));
     HIPCHK(hipEventRecord(tm.ev[kTmevPrimaryBegin], st));
     launchTraceMeshPrimary(st, M, s->fb.dArgs.p, F);
@@ -581,8 +606,32 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   if(meshActive)
   {
     HIPCHK(hipEventRecord(tm.ev[kTmevCompositeBegin], st));
+    TraceBounceArgs B{};
+    if(indirect)
+    {
+      B.g      = G;
+      B.btab   = s->d->bounceTab.p;
+      B.bmats  = s->d->bounceMatsDev.p;
+      B.live   = tm.bounceLive.p;
+      B.ray    = tm.bounceRay.p;
+      B.T      = tm.bounceT.p;
+      B.bctr   = tm.bounceCtr.p;
+      B.pixels = pixels;
+      HIPCHK(hipMemsetAsync(tm.bounceCtr.p, 0, sizeof(BounceCounters), st));
+    }
     launchTraceMeshComposite(st, G, F, lit);
     HIPCHK(hipEventRecord(tm.ev[kTmevCompositeEnd], st));
+    if(indirect)
+    {  // the hand-over of bounce 0, then max_bounces rounds, unconditionally: a round without a live pixel reads the live words and no more
+      HIPCHK(hipEventRecord(tm.bounceEv[0], st));
+      launchTraceBouncePrimary(st, B, F);
+      for(int b = 1; b <= bounce->max_bounces && b <= kMaxBounces; ++b)  // bound: kMaxBounces
+      {
+        B.bounce = b;
+        launchTraceBounce(st, B, F, s->d->shFormat);
+      }
+      HIPCHK(hipEventRecord(tm.bounceEv[1], st));
+    }
   }
   if(F.temporalSampling)
     launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, L.fmt);
@@ -611,8 +660,65 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
     HIPCHK(hipStreamSynchronize(st));
     if((rc = R.finish(s, rebuilt, buildMs, out))) return rc;
   }
+  if(indirect && bout)
+  {  // all zero when no visible mesh instance has a leaf: nothing bounced
+    std::memset(bout, 0, sizeof(*bout));
+    if(meshActive)
+    {
+      BounceCounters bc{};
+      HIPCHK(hipMemcpyAsync(&bc, tm.bounceCtr.p, sizeof(bc), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for(int b = 0; b < kMaxBounces; ++b)
+      {
+        bout->rays[b]      = bc.rays[b];
+        bout->mesh_hits[b] = bc.meshHits[b];
+      }
+      bout->particle_hits = bc.particleHits;
+      HIPCHK(hipEventElapsedTime(&bout->bounce_ms, tm.bounceEv[0], tm.bounceEv[1]));
+    }
+  }
   return MGS_OK;
 }
+
+void mgs_trace_bounce_params_default(MgsTraceBounceParams* p)
+{
+  if(!p)
+    return;
+  std::memset(p, 0, sizeof(*p));
+  p->max_bounces = 3;  // rtxMaxBounces, shaderio.h:273
+}
+
+static int mgs_render_traced_indirect_impl(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsTraceLightParams* lp,
+                                           const MgsTraceBounceParams* bp, MgsTraceOut* out, MgsTraceLightOut* lout, MgsTraceBounceOut* bout)
+{
+  if(!p)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_indirect: null params");
+  MgsTraceBounceParams b;
+  mgs_trace_bounce_params_default(&b);
+  if(bp)
+    b = *bp;
+  // (before the handle is looked at: the ranges can be checked without a device)
+  if(p->lighting_mode != MGS_LIGHTING_INDIRECT)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_indirect: lighting_mode must be MGS_LIGHTING_INDIRECT (direct lighting is mgs_render_traced_lit's)");
+  if(b.max_bounces < 1 || b.max_bounces > kMaxBounces)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_indirect: max_bounces must be in [1, 16]");
+  if(b.reserved[0] != 0 || b.reserved[1] != 0 || b.reserved[2] != 0)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_render_traced_indirect: the reserved words of MgsTraceBounceParams must be 0");
+  const MgsTraceParams      t  = traceParamsOr(tp);
+  const MgsTraceLightParams lt = traceLightParamsOr(lp);
+  if(t.trace_strategy == MGS_TRACE_STRATEGY_PASS_STOCHASTIC || t.trace_strategy == MGS_TRACE_STRATEGY_STOCHASTIC_ANYHIT)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced_indirect: the stochastic strategies' bounces are out of scope (trace_strategy must be 0)");
+  if(lt.shadows_mode == MGS_SHADOWS_SOFT)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced_indirect: soft shadows are out of scope (hard shadows only)");
+  // bounce 0 is the lit mesh frame: its checks, its set-up and its launches, with the composite and the rounds behind it exchanged
+  return mgs_render_traced_impl(s, p, &t, out, true, &lt, lout, &b, bout);
+}
+int mgs_render_traced_indirect(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, const MgsTraceLightParams* lp, const MgsTraceBounceParams* bp,
+                               MgsTraceOut* out, MgsTraceLightOut* lout, MgsTraceBounceOut* bout)
+{
+  return guarded("mgs_render_traced_indirect", [&] { return mgs_render_traced_indirect_impl(s, p, tp, lp, bp, out, lout, bout); });
+}
+
 int mgs_render_traced(MgsScene s, const MgsFrameParams* p, const MgsTraceParams* tp, MgsTraceOut* out)
 {
   return guarded("mgs_render_traced", [&] { return mgs_render_traced_impl(s, p, tp, out); });

@@ -535,6 +535,41 @@ struct MeshRayArgs
   MeshRayCounters* ctr;
 };
 
+// ---- reflection and refraction bounces (k_trace_bounce.hip, api_trace.hip: mgs_render_traced_indirect) ----
+constexpr int kMaxBounces = 16;  // the range of MgsTraceBounceParams::max_bounces
+// MgsBounceMaterial as the kernels read it (two 16-byte loads)
+struct alignas(16) BounceMatDev
+{
+  float    transmittance[3];
+  float    ior;
+  int32_t  illum;
+  uint32_t pad[3];
+};
+// per mesh instance its slice of the scene's flat bounce-material array; count 0 = never set (every material id is illum 0)
+struct BounceTable
+{
+  uint32_t offset[kMaxMeshInstances], count[kMaxMeshInstances];
+};
+struct BounceCounters
+{
+  unsigned long long rays[kMaxBounces], meshHits[kMaxBounces], particleHits;
+};
+// What the kernels of an indirect frame receive by value: the lit mesh frame's arguments as its composite has them, the bounce
+// materials, and the per-pixel bounce state (64 B a pixel): a live word, nine fp32 planes (ray origin, ray direction, radiance) and
+// three fp64 planes (the transmittance, carried between the kernels in double)
+struct TraceBounceArgs
+{
+  TraceLightMeshArgs  g;
+  const BounceTable*  btab;
+  const BounceMatDev* bmats;
+  uint32_t*           live;    // [pixels] 1: the pixel traces the next bounce
+  float*              ray;     // [9][pixels]
+  double*             T;       // [3][pixels]
+  BounceCounters*     bctr;
+  size_t              pixels;  // the planes' stride
+  int32_t             bounce;  // 1 .. max_bounces: the bounce this launch traces (k_trace_bounce)
+};
+
 // the caller's geometry as the compositors' launchers receive it
 struct Occluder
 {

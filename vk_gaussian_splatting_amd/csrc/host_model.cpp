@@ -1182,7 +1182,7 @@ bool parseCorner(const std::string& tok, size_t nPos, size_t nNrm, ObjCorner& ou
   return true;
 }
 
-void loadMtl(const std::string& path, std::vector<HostMeshMaterial>& mats, std::vector<std::string>& names)
+void loadMtl(const std::string& path, std::vector<HostMeshMaterial>& mats, std::vector<HostMtlBounce>& bounce, std::vector<std::string>& names)
 {
   std::ifstream f(path);
   if(!f)
@@ -1201,6 +1201,7 @@ void loadMtl(const std::string& path, std::vector<HostMeshMaterial>& mats, std::
       HostMeshMaterial m{};  // the parser's initial material: colours 0, shininess 1
       m.shininess = 1.0f;
       mats.push_back(m);
+      bounce.push_back(HostMtlBounce());
       names.push_back(name);
     }
     else if(!mats.empty())
@@ -1216,6 +1217,12 @@ void loadMtl(const std::string& path, std::vector<HostMeshMaterial>& mats, std::
         std::memcpy(mats.back().emission, v, 12);
       else if(key == "Ns" && parseFloats(ss, v, 1))
         mats.back().shininess = v[0];
+      else if((key == "Tf" || key == "Kt") && parseFloats(ss, v, 3))
+        std::memcpy(bounce.back().tf, v, 12);
+      else if(key == "Ni" && parseFloats(ss, v, 1))
+        bounce.back().ni = v[0];
+      else if(key == "illum" && parseFloats(ss, v, 1))
+        bounce.back().illum = (int)v[0];
     }
   }
 }
@@ -1310,12 +1317,15 @@ int loadObj(const std::string& path, HostMesh& out)
     {
       std::string name;
       while(ss >> name)
-        loadMtl(dir + name, out.materials, matNames);
+        loadMtl(dir + name, out.materials, out.mtlBounce, matNames);
     }
     // everything else is skipped
   }
   if(out.materials.empty())
+  {
     out.materials.push_back(defaultMeshMaterial());
+    out.mtlBounce.assign(1, HostMtlBounce());
+  }
   std::vector<float>   genNormals;
   std::vector<uint8_t> visited;
   std::vector<uint32_t> shapeIdx;

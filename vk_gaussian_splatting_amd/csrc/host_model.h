@@ -29,12 +29,20 @@ struct HostMeshMaterial
   float ambient[3], diffuse[3], specular[3], emission[3];
   float shininess;
 };
+// what a material library says about bounces (mgs_mesh_bounce_materials): tinyobj's initial values are Tf 0, Ni 1, illum 0
+struct HostMtlBounce
+{
+  float tf[3] = {0.0f, 0.0f, 0.0f};
+  float ni    = 1.0f;
+  int   illum = 0;
+};
 struct HostMesh
 {
   std::vector<float>            positions, normals;  // 3 per vertex
   std::vector<uint32_t>         indices;             // 3 per triangle
   std::vector<uint32_t>         materialIds;         // 1 per triangle, < materials.size()
   std::vector<HostMeshMaterial> materials;           // never empty
+  std::vector<HostMtlBounce>    mtlBounce;           // per material the MTL's Tf / Kt, Ni and illum statements; empty for a mesh from arrays
   std::string                   path;
 };
 HostMeshMaterial defaultMeshMaterial();  // the loader's default, src/obj_loader.cpp:72-81

@@ -137,6 +137,9 @@ void launchTraceLightWithMeshes(hipStream_t stream, const TraceLightMeshArgs& L,
 // composite or the lit mesh shading behind k_trace and the light pass
 void launchTraceMeshPrimary(hipStream_t stream, const TraceMeshArgs& m, const FrameArgs* frame, const FrameConst& F);
 void launchTraceMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, const FrameConst& F, bool lit);
+// bounces of an indirect frame (k_trace_bounce.hip): bounce 0's mesh shading in place of the lit composite; one bounce b >= 1
+void launchTraceBouncePrimary(hipStream_t stream, const TraceBounceArgs& B, const FrameConst& F);
+void launchTraceBounce(hipStream_t stream, const TraceBounceArgs& B, const FrameConst& F, int shFormat);
 // ray queries (k_trace_rays.hip): the frame's primary rays written out row-major; a batch's coherence keys; one ray per lane
 void launchRaysGenerate(hipStream_t stream, const FrameArgs* dArgs, float4* rays, uint32_t pixels);
 void launchRaysKey(hipStream_t stream, const RayKeyArgs& a);

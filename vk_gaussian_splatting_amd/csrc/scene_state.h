@@ -283,6 +283,11 @@ struct SceneData
   std::vector<MeshInstance> meshInstances;
   std::unique_ptr<MeshTable> meshHost;
   DevBuf<MeshTable>      meshTab;
+  // bounce materials of the mesh instances (mgs_mesh_instance_set_bounce_materials): per instance the caller's array, and the device
+  // copies an indirect frame reads (the flat array and each instance's slice of it), rewritten under the rule of mgs_scene_set_lights
+  std::vector<std::vector<BounceMatDev>> bounceMats;
+  DevBuf<BounceMatDev>   bounceMatsDev;
+  DevBuf<BounceTable>    bounceTab;
   TraceBvhState          bvh;            // mgs_render_traced
   MeshBvhState           meshBvh;        // mgs_trace_mesh_rays
   uint64_t               epoch = 0;     // bumped by every commit: a context re-sizes its working set when it lags
@@ -572,6 +577,12 @@ struct TraceMeshState
   DevBuf<float4>          hits;
   DevBuf<float>           meshT, walkT;
   DevBuf<MeshRayCounters> ctr;
+  // an indirect frame's per-pixel bounce state (mgs_render_traced_indirect, 64 B a pixel) and its counters
+  DevBuf<uint32_t>        bounceLive;
+  DevBuf<float>           bounceRay;   // [9][pixels]
+  DevBuf<double>          bounceT;     // [3][pixels]
+  DevBuf<BounceCounters>  bounceCtr;
+  hipEvent_t              bounceEv[2] = {};
   bool                    have = false;       // the handle's last traced frame ran with the setting on
   bool                    composited = false, lit = false;  // ... with a visible mesh instance (the composite ran); as a lit frame
   uint32_t                rebuilt = 0;
@@ -579,11 +590,16 @@ struct TraceMeshState
   uint64_t                triangles = 0, leaves = 0, nodes = 0;
   hipEvent_t              ev[kTmevCount] = {};
   template <class F>
-  void eachBuffer(F&& f) { f(hits); f(meshT); f(walkT); f(ctr); }
+  void eachBuffer(F&& f) { f(hits); f(meshT); f(walkT); f(ctr); f(bounceLive); f(bounceRay); f(bounceT); f(bounceCtr); }
   void release()
   {
     eachBuffer([](auto& b) { b.release(); });
     for(auto& e : ev)
+    {
+      if(e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+    for(auto& e : bounceEv)
     {
       if(e) (void)hipEventDestroy(e);
       e = nullptr;
@@ -739,6 +755,7 @@ struct MgsScene_t
 // ---- helpers more than one unit calls ---------------------------------------------------------------------------------------
 int  sizeWorkingSet(MgsScene s);                                              // api_scene.hip
 int  ensureLightTable(SceneData& d);                                          // api_scene.hip
+int  ensureBounceTable(SceneData& d);                                         // api_mesh.hip: the bounce materials' device copies exist
 MaterialDev materialToDevice(const MgsMaterial& m);                           // api_scene.hip: with needShading derived
 void mapIdsToCaller(MgsScene s, uint32_t* ids, size_t n);                     // api_scene.hip: storage global id -> caller's
 void mapIdsToStorage(MgsScene s, uint32_t* ids, size_t n);                    // ... and back
