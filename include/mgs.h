@@ -55,7 +55,9 @@ extern "C" {
                             shadow and light queries (MGS_HAS_SHADOW_QUERY below): entry points and new structs, both numbers stay —
                                  mgs_trace_shadow_rays, mgs_trace_shadow_rays_device, mgs_shade_points, mgs_shade_points_device;
                             mesh ray queries (MGS_HAS_MESH_RAY_QUERY below): entry points and new structs, both numbers stay —
-                                 mgs_mesh_ray_params_default, mgs_trace_mesh_rays, mgs_trace_mesh_rays_device */
+                                 mgs_mesh_ray_params_default, mgs_trace_mesh_rays, mgs_trace_mesh_rays_device;
+                            hierarchy hook (MGS_HAS_DEBUG_HIERARCHY below): one entry point and one new struct, both numbers stay —
+                                 mgs_debug_download_hierarchy */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
@@ -69,6 +71,8 @@ extern "C" {
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_DEBUG_HIERARCHY 1 /* feature macro: MgsHierarchyInfo and mgs_debug_download_hierarchy exist (added within ABI 5.1, no existing struct
+                                   or default changed) */
 #define MGS_HAS_SENSOR_MODEL 1  /* feature macro: MgsSensorModel, mgs_sensor_model_from_frame and mgs_frame_set_sensor exist (added within ABI 5.1, no
                                   existing struct or default changed) */
 
@@ -660,8 +664,9 @@ typedef struct MgsTraceOut {
  * space, belongs to the scene and is shared by its frame contexts.  It is rebuilt lazily by the next traced frame after
  * mgs_scene_commit, mgs_instance_add, mgs_instance_set_transform, or a change of kernel_degree, kernel_min_response,
  * kernel_adaptive_clamping or alpha_cull_threshold; a rebuild first waits for the frames in flight on all contexts (the rule of
- * mgs_scene_set_lights).  Its bytes are part of scene_bytes of mgs_scene_memory_usage.  A leaf bound is the exact box of the affine
- * image of the proxy ellipsoid, inflated by 8 ulps of the half extent plus 2 ulps of the centre; particles with density <=
+ * mgs_scene_set_lights).  Its bytes are part of scene_bytes of mgs_scene_memory_usage.  A leaf bound contains the exact box of the affine
+ * image of the proxy ellipsoid and exceeds it by no more than 2^-19 of (half extent + the sum of the absolute terms of the centre's
+ * transform) per face (mgs_debug_download_hierarchy shows it); particles with density <=
  * alpha_cull_threshold or a non-finite bound get no leaf and are never hit.  A scene without instances (committed or not) yields the
  * frame (0,0,0) with alpha 0. */
 int mgs_render_traced(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
@@ -1045,7 +1050,7 @@ int mgs_shade_points_device(MgsScene scene_or_context, const MgsSurfacePoint* po
  * The rasteriser's kernel writes the same expression but leaves the compiler free to fuse a product into the following sum, so
  * the two triangles are the same up to that contraction: a vertex may differ in its last bit.  A triangle with a non-finite world vertex or with zero area in float (the cross
  * product of its edge vectors is exactly 0) gets no leaf.  The leaf's box is the min / max of the three vertices inflated by 4 ulps
- * of its extent plus 2 ulps of its magnitude per axis.  The tree is the splat hierarchy's implicit complete 8-ary tree: leaves sorted
+ * of its extent plus 2 ulps of its magnitude plus 1e-37 per axis: it strictly contains the triangle.  The tree is the splat hierarchy's implicit complete 8-ary tree: leaves sorted
  * (the library's stable radix sort) by the 30-bit Morton code of the leaf centroid in the meshes' world box, which the host computes
  * in double from the meshes' local boxes and the instances' transforms; a node bounds eight consecutive nodes of the level below.  No
  * pointers, no atomics: the build is bit-reproducible.  Triangle records (world vertices, global primitive id, instance id, material
@@ -1396,6 +1401,27 @@ int mgs_frame_download_projected(MgsScene scene, const uint32_t* global_ids, siz
  * the camera), r, g, b (0: the compositors shade), opacity (after MS antialiasing) }; rect_out as above.  Valid after a full
  * 3DGUT frame only (MGS_ERR_STATE otherwise); meaningful only for ids that frame sorted. */
 int mgs_frame_download_projected_gut(MgsScene scene, const uint32_t* global_ids, size_t count, float* out24, uint32_t* rect_out);
+/* test/debug hook (MGS_HAS_DEBUG_HIERARCHY; no reference counterpart: the reference's acceleration structures are opaque): the
+ * scene's device-built hierarchy as the last build left it.  which 0: the splat hierarchy of the traced entry points (k_bvh.hip),
+ * which 1: the triangle hierarchy of the mesh ray queries and of traced frames with meshes (k_mesh_bvh.hip).  An implicit complete
+ * 8-ary tree: level 0 holds the leaves in Morton order, level l + 1 has ceil(level_count[l] / 8) nodes, node i of it is the union of
+ * the nodes [8i, 8i + 8) below; the levels lie one after the other from level_offset[l], the last one is the root.
+ * nodes8[i] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w } as raw bits.  lo.w of a leaf (read as uint32): which 0 the splat's
+ * global storage id (instances concatenated in creation order, the index inside a set in storage order: mgs_scene_storage_order),
+ * which 1 the leaf's own index; every other .w is 0.  tris12[i] (which 1 only) = the record of leaf i: vertex 0 xyz, global primitive
+ * id, vertex 1 xyz, mesh instance, vertex 2 xyz, material id (the ids read as uint32).  primitives = the splats / triangles the
+ * build looked at; box_lo, box_inv_ext = the frame in which the leaves' Morton codes were quantised.
+ * Waits for the handle's stream; starts no build, changes nothing the next frame or query sees and allocates no device memory.
+ * MGS_ERR_STATE when no such hierarchy has been built yet; which outside 0 / 1, NULL info: MGS_ERR_INVALID_ARG.  nodes8 / tris12
+ * NULL: not copied (info alone, to size the buffers); not NULL with node_capacity < total_nodes / tri_capacity < leaves (counted in
+ * nodes and records): MGS_ERR_INVALID_ARG, nothing written. */
+typedef struct MgsHierarchyInfo {
+  uint32_t levels, total_nodes, leaves, primitives;
+  uint32_t level_offset[11], level_count[11];
+  float    box_lo[3], box_inv_ext[3];
+} MgsHierarchyInfo;
+int mgs_debug_download_hierarchy(MgsScene scene_or_context, int which, MgsHierarchyInfo* info, float* nodes8, size_t node_capacity,
+                                 float* tris12, size_t tri_capacity);
 int mgs_sync(MgsScene scene);
 
 /* ---- sort only (metric hook): vrdxCmdSortKeyValueIndirect (3rdparty/vrdx/include/vk_radix_sort.h:73-78)

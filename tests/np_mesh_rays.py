@@ -241,11 +241,13 @@ def _trace_f32(meshes, O, D, tmin, tmax):
 
 
 def leaf_boxes(tri):
-    """k_mesh_bvh_leaves' box of world triangles [N,3,3] f32: min / max inflated by 4 ulps of the extent plus 2 ulps of the magnitude"""
-    f, ulp = np.float32, np.float32(1.1920929e-7)
+    """the box k_mesh_bvh_leaves gives world triangles [N,3,3] f32, for leaf_ok's slab test.  A restatement of the device formula: it
+    cannot disagree with what it copies.  The device's boxes themselves are checked directly, against the records' vertices, by
+    tests/test_gpu_hierarchy.py on the downloaded hierarchy."""
+    f, ulp, tiny = np.float32, np.float32(1.1920929e-7), np.float32(1e-37)
     l, u = tri.min(1), tri.max(1)
     ext = u - l
-    return l - (ext * (f(4) * ulp) + np.abs(l) * (f(2) * ulp)), u + (ext * (f(4) * ulp) + np.abs(u) * (f(2) * ulp))
+    return l - (ext * (f(4) * ulp) + np.abs(l) * (f(2) * ulp) + tiny), u + (ext * (f(4) * ulp) + np.abs(u) * (f(2) * ulp) + tiny)
 
 
 def slab_hit(O, D, lo, hi, t0, t1, cut):

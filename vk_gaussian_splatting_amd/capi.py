@@ -228,6 +228,17 @@ MESH_HIT_DTYPE = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("prim
                            ("hit", np.uint32), ("reserved", np.uint32, 3)])
 
 
+class HierarchyInfo(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("total_nodes", C.c_uint32), ("leaves", C.c_uint32), ("primitives", C.c_uint32),
+                ("level_offset", C.c_uint32 * 11), ("level_count", C.c_uint32 * 11), ("box_lo", C.c_float * 3), ("box_inv_ext", C.c_float * 3)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("levels", "total_nodes", "leaves", "primitives")}
+        d.update(level_offset=np.array(self.level_offset, np.uint32), level_count=np.array(self.level_count, np.uint32),
+                 box_lo=np.array(self.box_lo, np.float32), box_inv_ext=np.array(self.box_inv_ext, np.float32))
+        return d
+
+
 class TraceMeshParams(C.Structure):
     """MgsTraceMeshParams (16 bytes): mesh hits in the traced frames (mgs_frame_set_trace_meshes)"""
     _fields_ = [("enabled", C.c_int32), ("min_mesh_composite_transmittance", C.c_float), ("reserved", C.c_uint32 * 2)]
@@ -486,6 +497,7 @@ def load_library():
         "mgs_sync": (C.c_int, [vp]),
         "mgs_frame_download_projected": (C.c_int, [vp, P(C.c_uint32), C.c_size_t, P(F), P(C.c_uint32)]),
         "mgs_frame_download_projected_gut": (C.c_int, [vp, P(C.c_uint32), C.c_size_t, P(F), P(C.c_uint32)]),
+        "mgs_debug_download_hierarchy": (C.c_int, [vp, C.c_int, P(HierarchyInfo), P(F), C.c_size_t, P(F), C.c_size_t]),
         "mgs_loader_create": (C.c_int, [P(vp)]),
         "mgs_loader_destroy": (None, [vp]),
         "mgs_loader_push": (C.c_int, [vp, C.c_char_p]),
@@ -532,7 +544,7 @@ EXPORTED_SYMBOLS = [
     "mgs_bounce_material_default", "mgs_bounce_material_from_mtl", "mgs_mesh_bounce_materials", "mgs_mesh_instance_set_bounce_materials",
     "mgs_trace_bounce_params_default", "mgs_render_traced_indirect",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
-    "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
+    "mgs_frame_download_projected", "mgs_frame_download_projected_gut", "mgs_debug_download_hierarchy", "mgs_sync", "mgs_comm_unique_id", "mgs_scene_comm_init", "mgs_scene_comm_destroy",
     "mgs_scene_set_strip_rows", "mgs_render_gathered", "mgs_frame_row_costs",
     "mgs_loader_create", "mgs_loader_destroy", "mgs_loader_push", "mgs_loader_status", "mgs_loader_take", "mgs_sort_keys", "mgs_sort_download", "mgs_radix_sort_u32", "mgs_radix_sort_host",
     "mgs_camera_lookat_perspective", "mgs_compute_transform"]
@@ -1276,6 +1288,21 @@ class Scene:
         _check(self._lib.mgs_frame_download_projected_gut(self._h, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size,
                                                           _fp(out), rect.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out, rect
+
+    def download_hierarchy(self, which, info_only=False, node_capacity=None, tri_capacity=None):
+        """mgs_debug_download_hierarchy: (info dict, nodes uint32[total_nodes, 8] raw bits, tris uint32[leaves, 12] raw bits or None)
+        of the splat (which 0) or triangle (which 1) hierarchy as the last build left it; the capacities override the buffers' sizes"""
+        info = HierarchyInfo()
+        _check(self._lib.mgs_debug_download_hierarchy(self._h, int(which), C.byref(info), None, 0, None, 0))
+        d = info.as_dict()
+        if info_only:
+            return d, None, None
+        nn = d["total_nodes"] if node_capacity is None else int(node_capacity)
+        nt = d["leaves"] if tri_capacity is None else int(tri_capacity)
+        nodes = np.zeros((max(nn, 1), 8), np.float32)
+        tris = np.zeros((max(nt, 1), 12), np.float32) if which == 1 else None
+        _check(self._lib.mgs_debug_download_hierarchy(self._h, int(which), C.byref(info), _fp(nodes), nn, None if tris is None else _fp(tris), nt))
+        return d, nodes[:nn].view(np.uint32), None if tris is None else tris[:nt].view(np.uint32)
 
     def sort_keys(self, params):
         out = SortOut()

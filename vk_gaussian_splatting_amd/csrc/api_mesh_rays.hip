@@ -346,6 +346,34 @@ int ensureMeshHierarchyLocked(MgsScene s, float* buildMs, uint32_t* rebuilt)
   return ensureMeshHierarchy(s, buildMs, rebuilt);
 }
 
+int downloadMeshHierarchy(MgsScene s, MgsHierarchyInfo* info, float* nodes8, size_t nodeCapacity, float* tris12, size_t triCapacity)
+{
+  SceneData& d = *s->d;
+  std::lock_guard<std::mutex> hierarchy(d.meshBvh.mtx);  // no rebuild on another context while this reads
+  const MeshBvhState& B = d.meshBvh;
+  if(!B.built)
+    return failTrace(MGS_ERR_STATE, "mgs_debug_download_hierarchy: no triangle hierarchy has been built yet (a mesh query or a traced frame with meshes builds it)");
+  if((nodes8 && nodeCapacity < B.totalNodes) || (tris12 && triCapacity < B.leaves))
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_debug_download_hierarchy: node_capacity is below total_nodes or tri_capacity below leaves");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  std::memset(info, 0, sizeof(*info));
+  info->levels      = (uint32_t)B.nLevels;
+  info->total_nodes = B.totalNodes;
+  info->leaves      = B.leaves;
+  info->primitives  = B.triangles;
+  static_assert(sizeof(info->level_offset) == sizeof(B.levelOffset) && sizeof(info->level_count) == sizeof(B.levelCount), "MgsHierarchyInfo: kBvhMaxLevels levels");
+  std::memcpy(info->level_offset, B.levelOffset, sizeof(info->level_offset));
+  std::memcpy(info->level_count, B.levelCount, sizeof(info->level_count));
+  std::memcpy(info->box_lo, B.boxLo, sizeof(info->box_lo));
+  std::memcpy(info->box_inv_ext, B.boxInvExt, sizeof(info->box_inv_ext));
+  if(nodes8 && B.totalNodes)
+    HIPCHK(hipMemcpy(nodes8, B.nodes.p, (size_t)B.totalNodes * 32, hipMemcpyDeviceToHost));
+  if(tris12 && B.leaves)
+    HIPCHK(hipMemcpy(tris12, B.tris.p, (size_t)B.leaves * 48, hipMemcpyDeviceToHost));
+  return MGS_OK;
+}
+
 int mgs_trace_mesh_rays(MgsScene s, const MgsRay* rays, uint64_t count, const MgsMeshRayParams* qp, MgsMeshHit* hits, MgsMeshRayOut* out)
 {
   return guarded("mgs_trace_mesh_rays", [&] { return traceMeshRaysImpl(s, rays, count, qp, hits, out, true); });

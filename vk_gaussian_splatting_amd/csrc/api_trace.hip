@@ -259,6 +259,9 @@ static int buildBvh(MgsScene s, const FrameArgs& A, const TraceProxy& proxy, std
   L.frame = s->fb.dArgs.p;
   L.proxy = proxy;
   sceneBox(d, L.sceneLo, L.sceneInvExt);
+  std::memcpy(B.sceneLo, L.sceneLo, sizeof(B.sceneLo));
+  std::memcpy(B.sceneInvExt, L.sceneInvExt, sizeof(B.sceneInvExt));
+  B.splats      = n;
   L.totalSplats = n;
   L.keys        = t.keys.p;
   L.vals        = t.vals.p;
@@ -931,5 +934,39 @@ int mgs_trace_mesh_stats(MgsScene s, MgsMeshRayOut* primary, MgsMeshRayOut* shad
           return rc;
     }
     return (int)MGS_OK;
+  });
+}
+
+// mgs_debug_download_hierarchy(which = 0): the splat hierarchy as the last build left it, through host memory alone
+static int downloadSplatHierarchy(MgsScene s, MgsHierarchyInfo* info, float* nodes8, size_t nodeCapacity)
+{
+  const TraceBvhState& B = s->d->bvh;
+  if(!B.built)
+    return failTrace(MGS_ERR_STATE, "mgs_debug_download_hierarchy: no splat hierarchy has been built yet (a traced frame or query builds it)");
+  if(nodes8 && nodeCapacity < B.totalNodes)
+    return failTrace(MGS_ERR_INVALID_ARG, "mgs_debug_download_hierarchy: node_capacity is below total_nodes");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  std::memset(info, 0, sizeof(*info));
+  info->levels      = (uint32_t)B.nLevels;
+  info->total_nodes = B.totalNodes;
+  info->leaves      = B.leaves;
+  info->primitives  = B.splats;
+  static_assert(sizeof(info->level_offset) == sizeof(B.levelOffset) && sizeof(info->level_count) == sizeof(B.levelCount), "MgsHierarchyInfo: kBvhMaxLevels levels");
+  std::memcpy(info->level_offset, B.levelOffset, sizeof(info->level_offset));
+  std::memcpy(info->level_count, B.levelCount, sizeof(info->level_count));
+  std::memcpy(info->box_lo, B.sceneLo, sizeof(info->box_lo));
+  std::memcpy(info->box_inv_ext, B.sceneInvExt, sizeof(info->box_inv_ext));
+  if(nodes8 && B.totalNodes)
+    HIPCHK(hipMemcpy(nodes8, B.nodes.p, (size_t)B.totalNodes * 32, hipMemcpyDeviceToHost));
+  return MGS_OK;
+}
+
+int mgs_debug_download_hierarchy(MgsScene s, int which, MgsHierarchyInfo* info, float* nodes8, size_t nodeCapacity, float* tris12, size_t triCapacity)
+{
+  return guarded("mgs_debug_download_hierarchy", [&]() -> int {
+    if(!s || !info || (which != 0 && which != 1))
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_debug_download_hierarchy: null scene or info, or which is neither 0 (splats) nor 1 (triangles)");
+    return which == 0 ? downloadSplatHierarchy(s, info, nodes8, nodeCapacity) : downloadMeshHierarchy(s, info, nodes8, nodeCapacity, tris12, triCapacity);
   });
 }

@@ -22,12 +22,75 @@ __device__ __forceinline__ uint32_t mortonSpread10(uint32_t v)
   return v;
 }
 
-// One thread per global (storage) splat: the exact AABB of the affine image of the proxy ellipsoid.  With A = mat3(transform) R
-// diag(r exp(scale)) the half extent on axis a is sqrt(sum_j A_aj^2); r is the canonical radius at which the response reaches the
-// proxy threshold (trace_common.h: proxyThreshold / proxyRadius).  Inflated by 8 ulps of the half extent plus 2 ulps of the centre's
-// magnitude, which covers the rounding of the nine products, the sum, the square root and the centre's transform (each below 1 ulp
-// relative to the quantity it rounds).  No leaf: density <= alphaCullThreshold (particleProcessHit rejects every hit,
-// threedgrt.h.slang:166-170), a non-finite bound.
+// The leaf's bound in double: centre c = M p, half extent h_a = sqrt(sum_j A_aj^2) with A = mat3(M) R(q / |q|) diag(r exp(scale)), r the
+// canonical radius at which the response reaches min(kernelMinResponse [/ density], 0.97f), and T_a = sum of the absolute terms of
+// (M p)_a.  Every step is the fp32 inputs' exact formula evaluated in double: its error is a few 2^-53 of the terms it rounds.
+__device__ __forceinline__ void leafBoundDouble(const InstanceConst& I, uint32_t li, const TraceProxy& P, float density, double (&c)[3],
+                                                double (&h)[3], double (&T)[3])
+{
+  const float4 rq = *reinterpret_cast<const float4*>(I.rotations + 4 * (size_t)li);  // (w,x,y,z)
+  const double qw = rq.x, qx = rq.y, qy = rq.z, qz = rq.w;
+  const double ql = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+  const double w = qw / ql, x = qx / ql, y = qy / ql, z = qz / ql;
+  const double R[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                       2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                       2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+  const double thr = fmin(P.adaptiveClamping ? (double)P.kernelMinResponse / (double)density : (double)P.kernelMinResponse, (double)0.97f);
+  double       r;
+  if(P.kernelDegree == 0)
+    r = (1.0 - thr) / 0.329630334487;
+  else
+  {
+    const double n = (double)P.kernelDegree;
+    r = pow(log(thr) / (-4.5 / pow(3.0, n)), 1.0 / n);
+  }
+  double rs[3], p[3];
+#pragma unroll
+  for(int j = 0; j < 3; ++j)
+  {
+    rs[j] = r * exp((double)I.scales[3 * (size_t)li + j]);
+    p[j]  = (double)I.centers[3 * (size_t)li + j];
+  }
+  const float* M = I.model;
+#pragma unroll
+  for(int ax = 0; ax < 3; ++ax)
+  {
+    double sum = 0.0;
+#pragma unroll
+    for(int j = 0; j < 3; ++j)
+    {
+      const double e = ((double)M[ax] * R[j] + (double)M[4 + ax] * R[3 + j] + (double)M[8 + ax] * R[6 + j]) * rs[j];
+      sum += e * e;
+    }
+    h[ax] = sqrt(sum);
+    const double t0 = (double)M[ax] * p[0], t1 = (double)M[4 + ax] * p[1], t2 = (double)M[8 + ax] * p[2], t3 = (double)M[12 + ax];
+    c[ax] = t0 + t1 + t2 + t3;
+    T[ax] = fabs(t0) + fabs(t1) + fabs(t2) + fabs(t3);
+  }
+}
+
+// One thread per global (storage) splat: a box that contains the exact AABB of the affine image of the proxy ellipsoid.  With A =
+// mat3(transform) R diag(r exp(scale)) the half extent on axis a is sqrt(sum_j A_aj^2); r is the canonical radius at which the response
+// reaches the proxy threshold (trace_common.h: proxyThreshold, which the traversal tests a hit's response against).
+// The box is that evaluation in double (leafBoundDouble), with h widened by 8 fp32 ulps of itself plus 2 fp32 ulps of T (the cushion
+// the leaves have always had around the proxy, now around the exact one: the traversal accepts a hit on its own fp32 evaluation of
+// the response, which may lie an ulp or so outside the exact ellipsoid) plus 64 * 2^-53 * (h + T), and then rounded outward to fp32:
+// it contains the exact box and exceeds it by less than 8 ulps of h + 2 ulps of T + an ulp of the face's magnitude, inside the
+// tests' tightness bound of 32 * 2^-24 * (h + T).  What the 64 covers: about a dozen roundings of terms no larger than h and T, and
+// the one amplified error: kernelMinResponse / density rounds by 2^-53 relative, which just below the 0.97 clamp the inverse response
+// amplifies by 1 / (n |ln 0.97|) = 33 / n in the radius (degree 0: 1 / (1 - 0.97) = 33), hence in h.  tests/test_hierarchy_cpu.py
+// holds a float64 restatement of this path, in this order of operations, to an extended-precision reference.
+// Why not fp32, as this kernel first had it (inflated by 8 ulps of h + 2 ulps of |c|): that box does not hold the exact one, and no
+// count of ulps of h and T makes it.  The centre M p rounds at the magnitude of its TERMS, not of its result (x -> R (x - T0) with
+// |T0| ~ 1e3 and centres near T0: |c| ~ 1, error up to 9e-5, and a half extent of 1e-5 leaves the box beside its own splat); the
+// rotation matrix's entries carry an absolute error of an ulp of 1, which on an axis almost orthogonal to a long axis of a splat with
+// 1e4 between its scales is more than 1e3 ulps of that axis' half extent, in either direction (too small for containment or too
+// large for the tightness bound; both were seen on the device); kernelMinResponse / density just below the clamp rounds by a
+// quarter ulp of 1, amplified as above to 8 / n ulps of the radius; and the squares of its terms overflow for half extents above
+// about 1.8e19.  The build runs once per change of the scene, one thread per splat: double costs it little.
+// The Morton key is still taken from the fp32 centre: the order of the leaves is what it was.
+// No leaf: density <= alphaCullThreshold (particleProcessHit rejects every hit, threedgrt.h.slang:166-170), or a bound that is not
+// finite in fp32 (a NaN anywhere, |c| + h above FLT_MAX).
 __global__ __launch_bounds__(256) void k_bvh_leaves(BvhBuildArgs a)
 {
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -41,40 +104,29 @@ __global__ __launch_bounds__(256) void k_bvh_leaves(BvhBuildArgs a)
   const InstanceConst& I  = Ap->inst[k];
   const uint32_t       li = g - I.globalOffset;
   const float          density = I.alpha[li];
-  float                R[9], s[3], p[3];
-  loadParticle(I, li, R, s, p);
-  const float  r = proxyRadius(a.proxy, proxyThreshold(a.proxy, density));
-  const float* M = I.model;
-  float        h[3];
-#pragma unroll
-  for(int ax = 0; ax < 3; ++ax)
-  {
-    float sum = 0.0f;
-#pragma unroll
-    for(int j = 0; j < 3; ++j)
-    {  // (mat3(M) R)_{ax, j} * r * s_j
-      const float mr = M[ax] * R[j] + M[4 + ax] * R[3 + j] + M[8 + ax] * R[6 + j];
-      const float e  = mr * (r * s[j]);
-      sum += e * e;
-    }
-    h[ax] = sqrtf(sum);
-  }
-  float c[3];
-#pragma unroll
-  for(int ax = 0; ax < 3; ++ax)
-    c[ax] = M[ax] * p[0] + M[4 + ax] * p[1] + M[8 + ax] * p[2] + M[12 + ax];
+  const float*         M = I.model;
+  const float          p[3] = {I.centers[3 * (size_t)li], I.centers[3 * (size_t)li + 1], I.centers[3 * (size_t)li + 2]};
+  double               cd[3], hd[3], Td[3];
+  leafBoundDouble(I, li, a.proxy, density, cd, hd, Td);
   bool   ok = density > a.proxy.alphaCull;
   float4 lo, hi;
   float  q[3];
 #pragma unroll
   for(int ax = 0; ax < 3; ++ax)
   {
-    const float hh = h[ax] * (1.0f + 8.0f * 1.1920929e-7f) + fabsf(c[ax]) * (2.0f * 1.1920929e-7f);
-    const float l = c[ax] - hh, u = c[ax] + hh;
-    ok = ok && isfinite(l) && isfinite(u) && hh >= 0.0f;
+    const double ulp = 1.1920928955078125e-7;  // 2^-23
+    const double hh = hd[ax] * (1.0 + 8.0 * ulp) + Td[ax] * (2.0 * ulp) + 64.0 * 1.1102230246251565e-16 * (hd[ax] + Td[ax]);
+    const double xl = cd[ax] - hh, xu = cd[ax] + hh;
+    float        l = (float)xl, u = (float)xu;
+    if((double)l > xl)
+      l = nextafterf(l, -INFINITY);
+    if((double)u < xu)
+      u = nextafterf(u, INFINITY);
+    ok = ok && isfinite(l) && isfinite(u) && hd[ax] >= 0.0;
     (&lo.x)[ax] = l;
     (&hi.x)[ax] = u;
-    q[ax]       = fminf(fmaxf((c[ax] - a.sceneLo[ax]) * a.sceneInvExt[ax], 0.0f), 1.0f) * 1023.0f;
+    const float c = M[ax] * p[0] + M[4 + ax] * p[1] + M[8 + ax] * p[2] + M[12 + ax];
+    q[ax]         = fminf(fmaxf((c - a.sceneLo[ax]) * a.sceneInvExt[ax], 0.0f), 1.0f) * 1023.0f;
   }
   lo.w = __uint_as_float(g);
   hi.w = 0.0f;

@@ -72,14 +72,16 @@ __device__ __forceinline__ WorldTri worldTriangle(const MeshTable* __restrict__ 
 
 // One thread per global primitive (instances concatenated in creation order, visible or not: the id mgs_meshes_download(which = 2)
 // reports).  The leaf box is the min / max of the three world vertices, inflated on every axis by 4 ulps of the box's extent plus
-// 2 ulps of the bound's magnitude.  What the inflation is for, and what it is not:
+// 2 ulps of the bound's magnitude plus 1e-37.  What the inflation is for, and what it is not:
 //  - The box without inflation already holds the triangle exactly (the records carry the same vertex bits), so in real arithmetic
 //    the ray's parameter at a hit point lies between the box's entry and exit on every axis.  slabHit computes each slab value as
 //    (bound - o) * (1 / d): three roundings, a relative error below 1.5 ulps of the value, and it widens entry and exit by 4 ulps, so
 //    rounding in the node test alone never refuses the leaf of a true hit.
 //  - An axis-parallel triangle has a box of zero thickness, and a ray whose origin lies in that plane gets (bound - o) = 0 against an
 //    infinite 1 / d there: 0 * inf, which slabHit drops as NaN.  The magnitude term keeps the two bounds apart, so the slab stays an
-//    interval of two signed infinities; the extent term adds slack in proportion to the triangle's size.
+//    interval of two signed infinities; the extent term adds slack in proportion to the triangle's size.  In a coordinate plane
+//    through 0 the magnitude is 0 too: a third, absolute term of 1e-37 (a normal float, lost in the sum wherever another term is not
+//    0) keeps the box strictly around its triangle there as well (tests/test_gpu_hierarchy.py asserts the strict containment).
 //  - It is NOT a bound on the triangle test's own t.  t = T / det loses accuracy as det goes to 0 (a ray grazing the triangle's
 //    plane), by more than any fixed number of ulps, and the walk compares the leaf's entry with the window and with the cut.  A
 //    grazing hit whose computed t falls inside the window while the box's entry does not is refused by the leaf: a miss in place of
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void k_mesh_bvh_leaves(MeshBvhBuildArgs a)
   bool           ok = true;
   float4         lo, hi;
   float          q[3], e1[3], e2[3];
-  constexpr float ulp = 1.1920929e-7f;
+  constexpr float ulp = 1.1920929e-7f, tiny = 1e-37f;
 #pragma unroll
   for(int ax = 0; ax < 3; ++ax)
   {
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void k_mesh_bvh_leaves(MeshBvhBuildArgs a)
     ok = ok && isfinite(x0) && isfinite(x1) && isfinite(x2);
     const float l = fminf(fminf(x0, x1), x2), u = fmaxf(fmaxf(x0, x1), x2);
     const float ext = u - l;
-    const float li = l - (ext * (4.0f * ulp) + fabsf(l) * (2.0f * ulp)), ui = u + (ext * (4.0f * ulp) + fabsf(u) * (2.0f * ulp));
+    const float li = l - (ext * (4.0f * ulp) + fabsf(l) * (2.0f * ulp) + tiny), ui = u + (ext * (4.0f * ulp) + fabsf(u) * (2.0f * ulp) + tiny);
     ok = ok && isfinite(li) && isfinite(ui);
     (&lo.x)[ax] = li;
     (&hi.x)[ax] = ui;

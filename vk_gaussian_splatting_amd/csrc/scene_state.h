@@ -233,7 +233,8 @@ struct TraceBvhState
   DevBuf<TraceInstTable> inst;
   uint32_t               levelOffset[kBvhMaxLevels] = {}, levelCount[kBvhMaxLevels] = {};
   int                    nLevels = 0;
-  uint32_t               totalNodes = 0, leaves = 0;
+  uint32_t               totalNodes = 0, leaves = 0, splats = 0;
+  float                  sceneLo[3] = {}, sceneInvExt[3] = {};  // the Morton frame of the last build (sceneBox)
   TraceProxy             proxy{};
   std::vector<uint8_t>   signature;
   bool                   built = false;
@@ -826,6 +827,8 @@ struct TraceOutRead
 // api_mesh_rays.hip: the lazy build of the triangle hierarchy on handle s, as a mesh query runs it; the caller holds
 // SceneData::meshBvh.mtx from this call to its last launch that reads the hierarchy
 int  ensureMeshHierarchyLocked(MgsScene s, float* buildMs, uint32_t* rebuilt);
+// api_mesh_rays.hip: mgs_debug_download_hierarchy(which = 1), the triangle hierarchy's half of the hook (api_trace.hip)
+int  downloadMeshHierarchy(MgsScene s, MgsHierarchyInfo* info, float* nodes8, size_t nodeCapacity, float* tris12, size_t triCapacity);
 ProjectLaunch projectLaunch(MgsScene s, const FrameArgs& A, bool full, bool gpuSort);  // api_frame.hip
 void keySort(MgsScene s, hipStream_t st, bool wantKeys, const FrameConst* ride = nullptr);  // api_sort.hip
 int  cpuSortStep(MgsScene s, const MgsFrameParams* p, bool blocking);         // api_sort.hip

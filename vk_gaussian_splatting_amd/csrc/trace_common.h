@@ -1,5 +1,5 @@
 // trace_common.h — what the hierarchy build (k_bvh.hip) and the traversal (k_trace.hip) must compute alike: the particle as the
-// 3DGRT shaders fetch it and the proxy ellipsoid's threshold and radius (the generalised-Gaussian response itself: kernelResponse,
+// 3DGRT shaders fetch it and the proxy ellipsoid's threshold (its radius is the build's alone, in double: k_bvh.hip; the response itself: kernelResponse,
 // gut_common.h, shared with the 3DGUT compositor); and what the ray and shadow queries must refuse alike (rayValid).
 #pragma once
 #include "gut_common.h"
@@ -30,17 +30,6 @@ __device__ __forceinline__ void loadParticle(const InstanceConst& I, uint32_t li
 __device__ __forceinline__ float proxyThreshold(const TraceProxy& P, float density)
 {
   return fminf(P.adaptiveClamping ? P.kernelMinResponse / density : P.kernelMinResponse, 0.97f);
-}
-
-// the canonical radius at which the response falls to `thr`: the inverse of kernelResponse in the distance (degree n >= 1:
-// exp(s d^n) with s = -4.5 / 3^n; degree 0: 1 + s0 d)
-__device__ __forceinline__ float proxyRadius(const TraceProxy& P, float thr)
-{
-  if(P.kernelDegree == 0)
-    return (1.0f - thr) / 0.329630334487f;
-  const float n = (float)P.kernelDegree;
-  const float s = -4.5f / powf(3.0f, n);
-  return powf(logf(thr) / s, 1.0f / n);
 }
 
 // what mgs.h calls an invalid ray; written so that a NaN anywhere fails it
