@@ -69,6 +69,9 @@ extern "C" {
 #define MGS_HAS_MESH_RAY_QUERY 1 /* feature macro: mgs_trace_mesh_rays and its companions exist (added within ABI 5.1, no existing struct or default
                                    changed) */
 #define MGS_HAS_HYBRID 1        /* feature macro: mgs_render_hybrid exists (added within ABI 5.1, no struct or default changed) */
+#define MGS_HAS_SOFT_SHADOWS 1  /* feature macro: mgs_scene_set_light_radii exists, and mgs_render_traced_lit and mgs_render_hybrid accept MGS_SHADOWS_SOFT
+                                   in a process started with MGS_SOFT_SHADOWS=1 (added within ABI 5.1, no struct, default or outcome of an
+                                   existing call changed: without the switch MGS_SHADOWS_SOFT stays MGS_ERR_UNSUPPORTED) */
 #define MGS_HAS_MESHES 1        /* feature macro: the mgs_mesh_* / mgs_meshes_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_PROJECTED_GUT 1 /* feature macro: mgs_frame_download_projected_gut exists (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_DEBUG_HIERARCHY 1 /* feature macro: MgsHierarchyInfo and mgs_debug_download_hierarchy exist (added within ABI 5.1, no existing struct
@@ -188,8 +191,8 @@ int  mgs_instance_set_transform(MgsScene scene, int instance_id, const float tra
  * Idempotent; call again after changing formats (the reference's --updateData). */
 int  mgs_scene_commit(MgsScene scene, int sh_format, int rgba_format);
 /* ---- lights and materials of the deferred lighting pass (MgsFrameParams::lighting_mode).
- * MgsLight: the fields of shaderio::LightSource (shaders/wavefront.h:81-93) minus `radius` (soft shadows are ray traced: out of
- * scope).  direction is the direction the light shines in (the reference derives it from the light instance's rotation applied
+ * MgsLight: the fields of shaderio::LightSource (shaders/wavefront.h:81-93) minus `radius`, which only the ray-traced soft shadows
+ * read and which has its own setter (mgs_scene_set_light_radii, below).  direction is the direction the light shines in (the reference derives it from the light instance's rotation applied
  * to (0,0,-1), light_manager_vk.cpp:470-471); cone angles in degrees; attenuation_mode 0 none, 1 linear, 2 quadratic, 3 physical. */
 typedef struct MgsLight {
   int32_t type;             /* MGS_LIGHT_*, default MGS_LIGHT_POINT */
@@ -208,6 +211,13 @@ void mgs_light_default(MgsLight* light); /* fills the defaults above (wavefront.
  * MGS_ERR_INVALID_ARG.  Takes effect on every context's next frame without a re-commit: the call waits for the frames in
  * flight on all contexts, then rewrites the device table the lighting pass reads (captured frames are not re-captured). */
 int  mgs_scene_set_lights(MgsScene scene, const MgsLight* lights, int count);
+/* The radius of each entry of the light table (MGS_HAS_SOFT_SHADOWS): LightSource::radius (wavefront.h:92), which the reference
+ * fills from the light's proxyScale (light_manager_vk.cpp:480, :533; default 1.0, :104).  Read by MGS_SHADOWS_SOFT only: a point or
+ * spot light is sampled on a disk of HALF this radius (wavefront.h.slang:54), 0 makes the light a hard one.  `count` must equal the
+ * current light count; anything else, or a radius that is negative or not finite: MGS_ERR_INVALID_ARG.  NULL with count 0 restores
+ * the default 1.0 for every light, and so does every mgs_scene_set_lights.  A context handle: MGS_ERR_STATE.  Ordering as
+ * mgs_scene_set_lights: waits for the frames in flight on all contexts, rewrites the device table, rebuilds no hierarchy. */
+int  mgs_scene_set_light_radii(MgsScene scene, const float* radii, int count);
 /* An instance's material: splatMaterial of the splat set instance (shaderio::ObjMaterial, wavefront.h:37-50, reduced to what the
  * deferred pass reads).  needShading is derived inside as updateMaterialNeedsShading does (wavefront.h:55-59: the length of
  * diffuse, ambient or specular above 0.001). */
@@ -560,7 +570,7 @@ int  mgs_meshes_download(MgsScene scene_or_context, int which, void* host_dst, s
  * hardware.  Replaces GaussianSplatting::raytrace with shaders/threedgrt_raytrace.{rgen,rahit,rint}.slang (primary rays), the
  * particle proxies of particle_as_build.comp.slang and the acceleration-structure managers: a hierarchy over the particles built on
  * the device, and a per-ray traversal that collects the samples_per_pass nearest hits per pass as the any-hit shader does.
- * Direct lighting with hard shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
+ * Direct lighting with hard or soft shadow rays through the particles is mgs_render_traced_lit (MGS_HAS_TRACE_LIGHTING, below).
  * A rasterised primary surface under the same light pass is mgs_render_hybrid (MGS_HAS_HYBRID, below).
  * Rays of the caller's own (other sensors, probes, picking, secondary rays shot from the caller's geometry) are mgs_trace_rays
  * (MGS_HAS_RAY_QUERY, below): the caller cuts a ray at its own surfaces with the ray's window, as the occluder does for the raster pipelines.
@@ -701,11 +711,41 @@ int mgs_trace_download_hit_counts(MgsScene scene_or_context, uint32_t* host_dst,
  * transmittance = saturate(scaledT * lerp(1, normalizedColor, particle_shadow_color_strength * (1 - scaledT))).  light.color is
  * multiplied by it; inShadow = its max component < 0.001 (:1126-1127) returns from the shading after the ambient term.
  * Alpha stays 1 - T of the primary walk (the reference writes 1.0).
- * Soft shadows (MGS_SHADOWS_SOFT) are MGS_ERR_UNSUPPORTED: sampleDisk draws from nvshaders/random.h.slang, which is not part of the
- * reference tree, and MgsLight has no radius: PARITY UNPINNED. */
+ * Soft shadows (MGS_SHADOWS_SOFT, MGS_HAS_SOFT_SHADOWS; SHADOWS_MODE == SHADOWS_SOFT, shaderio.h:141-143) are opt-in per process: the
+ * environment switch MGS_SOFT_SHADOWS=1, read once when the library first looks at its switches.  The switch is TEMPORARY: it exists because callers of ABI 5.1 were promised
+ * MGS_ERR_UNSUPPORTED for this mode; the next ABI minor drops it and accepts the mode unconditionally.  Without it MGS_SHADOWS_SOFT is
+ * MGS_ERR_UNSUPPORTED at the range checks, the answer every earlier build of ABI 5.1 gave.  With it: computeLightToSurfaceVector
+ * with buildOrthonormalBasis and sampleDisk (shaders/wavefront.h.slang:33-102).  ONE sample per light and frame; a soft frame
+ * converges over frame_sample_ids by temporal accumulation, as depth of field does (the reference turns it on for soft shadows,
+ * gaussian_splatting.cpp:313).
+ *   Seed: one uint32 state per pixel, seedRayPass = xxhash32(px, py, frame_sample_id) (rgen.slang:228) with the ABSOLUTE pixel
+ *   coordinates, so a strip frame draws what the full frame draws.  The depth-of-field lens seeds its own copy (:193) and does not
+ *   advance this state; trace strategy 0 draws nothing from it before the lighting.  xxhash32 / pcg / rand are the restated ones
+ *   of the stochastic strategies (PARITY UNPINNED as they are: nvshaders/random.h.slang is not in the reference tree).
+ *   Per light, in table order, BEFORE the range test: a point or spot light with radius > 0 (mgs_scene_set_light_radii) draws two
+ *   numbers.  n = normalize(light.position - position); tangent, bitangent = Frisvad's basis of n (:78-92: for n.z < -0.9999999
+ *   (0,-1,0) and (-1,0,0), else a = 1 / (1 + n.z), b = -n.x n.y a, (1 - n.x n.x a, b, -n.x), (b, 1 - n.y n.y a, -n.y));
+ *   r = (radius * 0.5) * sqrt(rand(seed)) FIRST, then theta = 2 * 3.14159265 * rand(seed) (:97-101);
+ *   samplePos = light.position + r * (cos(theta) * tangent + sin(theta) * bitangent); lightDist = |samplePos - position|; the
+ *   light is SKIPPED when lightDist > range (the sample's distance decides, not the centre's; the two numbers are consumed anyway);
+ *   lightDir = normalize(samplePos - position).  A directional light, or a radius <= 0, draws nothing and is exactly the hard path.
+ *   Shadow rays: both take the sample's lightDir and lightDist — the mesh occlusion ray of a frame with trace meshes from the
+ *   un-offset position over (0.001, lightDist - 0.001), the particle ray from position + lightDir * particle_shadow_offset with
+ *   TMax = lightDist - 0.001.  Shading is unchanged: computePointLight and computeSpotLight read light.position, not the sample;
+ *   the light's colour is multiplied by the sample's transmittance.  The headlight is never shadowed and draws nothing.
+ *   A lit frame with trace meshes can run the loop over the lights twice on one pixel, for the splat surface and then for the mesh
+ *   hit (:1054, :1061, the same inout seed): the mesh shading's draws continue where the splat surface's ended, and start from the
+ *   fresh seed where that loop did not run (no pick, the splat surface behind the mesh, or the picked instance's needShading 0:
+ *   :1091-1095 returns before the loop).  No per-pixel word is carried for this: the first loop draws two numbers per light with a
+ *   disk whether the light is culled or not, so the mesh composite recomputes its end state from the light table and the light
+ *   pass's own conditions.  A hybrid frame has the same seed (:228) and one loop per pixel.
+ *   MgsTraceLightOut keeps its meaning: shadow_rays counts the rays traced.  Hard shadows, shadows off and every other entry point
+ *   keep their frames bit for bit.  Not built: several samples per light in one frame; soft shadows in mgs_render_traced_indirect
+ *   (the state would have to be carried across the bounce launches) and in mgs_trace_shadow_rays / mgs_shade_points (a query point
+ *   has no pixel to seed from), which return MGS_ERR_UNSUPPORTED. */
 #define MGS_SHADOWS_DISABLED 0 /* default (parameters.h:167) */
 #define MGS_SHADOWS_HARD 1
-#define MGS_SHADOWS_SOFT 2     /* MGS_ERR_UNSUPPORTED */
+#define MGS_SHADOWS_SOFT 2     /* mgs_render_traced_lit and mgs_render_hybrid under MGS_SOFT_SHADOWS=1; otherwise and elsewhere MGS_ERR_UNSUPPORTED */
 typedef struct MgsTraceLightParams {
   int32_t  shadows_mode;                            /* MGS_SHADOWS_*, default MGS_SHADOWS_DISABLED */
   float    particle_shadow_offset;                  /* default 0.2 (parameters.h:222); finite, >= 0 */
@@ -772,7 +812,9 @@ int mgs_trace_download_shadow_hits(MgsScene scene_or_context, uint32_t* host_dst
  * a 16 B / pixel scratch of the handle and counts into working_bytes.
  * The ranges of the three structs are checked before the handle is looked at.  lighting_mode == MGS_LIGHTING_INDIRECT:
  * MGS_ERR_UNSUPPORTED; 0 or any other value: MGS_ERR_INVALID_ARG (a hybrid frame without lighting is mgs_render's);
- * MGS_SHADOWS_SOFT, MGS_SORT_STOCHASTIC and a bound occluder (shadowing mesh pixels needs meshes in the traced scene): MGS_ERR_UNSUPPORTED.
+ * MGS_SORT_STOCHASTIC and a bound occluder (shadowing mesh pixels needs meshes in the traced scene): MGS_ERR_UNSUPPORTED.
+ * MGS_SHADOWS_SOFT is the lit traced frame's, with the same seed (rgen.slang:228 runs in hybrid too) and one loop per pixel at the
+ * handed-over position.
  * `trace` / `light` NULL = the defaults; `light_out` non-NULL waits for the frame. */
 int mgs_render_hybrid(MgsScene scene_or_context, const MgsFrameParams* params, const MgsTraceParams* trace /* NULL = defaults */,
                       const MgsTraceLightParams* light /* NULL = defaults */, MgsFrameOut* out /* may be NULL */,
@@ -965,7 +1007,7 @@ int  mgs_trace_generate_rays(MgsScene scene_or_context, const MgsFrameParams* pa
  * operation for operation (one device function serves both).  MGS_DEBUG_SH_ONLY and MGS_DEBUG_OPACITY_GAUSSIAN_DISABLED are honoured
  * as they are there.  Of MgsTraceLightParams the call reads particle_shadow_transmittance_threshold and
  * particle_shadow_color_strength; particle_shadow_offset is NOT READ (the caller has placed the origin), not even range-checked.
- * shadows_mode must be MGS_SHADOWS_HARD: MGS_SHADOWS_SOFT is MGS_ERR_UNSUPPORTED, any other value MGS_ERR_INVALID_ARG; `light` NULL =
+ * shadows_mode must be MGS_SHADOWS_HARD: MGS_SHADOWS_SOFT is MGS_ERR_UNSUPPORTED (a query point has no pixel to seed a light's disk sample from), any other value MGS_ERR_INVALID_ARG; `light` NULL =
  * the defaults with shadows_mode MGS_SHADOWS_HARD.  Of MgsTraceParams it reads samples_per_pass and kernel_adaptive_clamping.
  * An invalid ray (a non-finite component, a zero-length direction or t_min > t_max) never reaches the traversal: transmittance
  * (1,1,1), 0 hits, counted in invalid_rays; a per-ray outcome, not an error code.  Reads of MgsFrameParams, the range checks before
@@ -1208,7 +1250,7 @@ int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_de
  * an unlit frame with a visible mesh also keeps the lit frames' fp32 pixel and ray parameter (16 B + 4 B).
  * PARITY UNPINNED: what the mesh ray queries list, and the reference's RAY_FLAG_CULL_BACK_FACING_TRIANGLES, which has no effect there.
  * Out of scope: hybrid frames with meshes, mesh occlusion inside mgs_trace_shadow_rays / mgs_shade_points, the stochastic
- * strategies with meshes, soft shadows, light proxies, ray masks, mgs_render_gathered.  Mesh transmittance / ior / reflection /
+ * strategies with meshes, light proxies, ray masks, mgs_render_gathered.  Mesh transmittance / ior / reflection /
  * refraction bounces and indirect lighting are mgs_render_traced_indirect's (MGS_HAS_TRACE_BOUNCES, below). */
 #define MGS_HAS_TRACE_MESHES 1
 typedef struct MgsTraceMeshParams {
@@ -1262,7 +1304,7 @@ int  mgs_trace_mesh_stats(MgsScene scene_or_context, MgsMeshRayOut* primary, Mgs
  *
  * mgs_render_traced_indirect follows mgs_render_traced_lit's conventions (NULL = defaults, a non-NULL out waits, ranges are checked
  * before the handle is looked at).  lighting_mode must be MGS_LIGHTING_INDIRECT (anything else: MGS_ERR_INVALID_ARG);
- * trace_strategy != 0 and MGS_SHADOWS_SOFT are MGS_ERR_UNSUPPORTED; max_bounces outside [1, 16] is MGS_ERR_INVALID_ARG; the
+ * trace_strategy != 0 and MGS_SHADOWS_SOFT (its random state would have to be carried across the bounce launches: later work) are MGS_ERR_UNSUPPORTED; max_bounces outside [1, 16] is MGS_ERR_INVALID_ARG; the
  * handle's trace-mesh setting off is MGS_ERR_STATE (nothing to bounce off; min_mesh_composite_transmittance is read from that
  * setting).  A bound sensor model and a bound occluder are refused as the lit frame refuses them.  MgsTraceBounceOut: index b - 1
  * holds the live pixels and the mesh hits of bounce b, particle_hits the hits accepted at b >= 1, bounce_ms HIP events around

@@ -139,7 +139,11 @@ def main():
     # --sensor FILE.json with --pipeline raster --raster-pipeline 3dgut: a flat JSON of MgsSensorModel's fields (model, focal_length,
     # principal_point, radial, tangential, thin_prism, fisheye_radial, max_angle); fields left out keep the frame's perfect camera
     ap.add_argument("--sensor", default=None, metavar="FILE.json")
-    ap.add_argument("--shadows", type=int, choices=[0, 1], default=0)  # --pipeline trace --lighting 1: hard shadow rays through the splats
+    # --pipeline trace / hybrid --lighting 1: 1 = hard shadow rays through the splats, 2 = soft (one disk sample per light and frame:
+    # converge with --accumulate N)
+    ap.add_argument("--shadows", type=int, choices=[0, 1, 2], default=0)
+    # --shadows 2 with --lights: one radius for every light, in place of the file's "radius" keys (without it: those keys, else 1.0)
+    ap.add_argument("--light-radius", type=float, default=None, metavar="R")
     ap.add_argument("--shadow-offset", type=float, default=0.2)
     ap.add_argument("--shadow-threshold", type=float, default=0.8)
     ap.add_argument("--shadow-color-strength", type=float, default=0.0)
@@ -200,7 +204,13 @@ def main():
         if a.lights:
             import json
             with open(a.lights) as f:
-                scene.set_lights([capi.make_light(**l) for l in json.load(f)])
+                lights = json.load(f)  # MgsLight's fields, and "radius" for the soft shadows' disk
+            scene.set_lights([capi.make_light(**l) for l in lights])
+            if a.light_radius is not None:  # --light-radius wins over the file's "radius" keys
+                print(f"--light-radius {a.light_radius}: replaces the radius of all {len(lights)} lights of {a.lights}")
+                scene.set_light_radii([a.light_radius] * len(lights))
+        elif a.light_radius is not None:
+            ap.error("--light-radius needs --lights (without lights the frame has the headlight, which is never shadowed)")
         if a.material:
             m = a.material
             scene.set_material(0, capi.make_material(ambient=m[0:3], diffuse=m[3:6], specular=m[6:9], emission=m[9:12], shininess=m[12]))
@@ -242,8 +252,13 @@ def main():
             print(f"mesh pick image: {ro.hits} of {p.width * p.height} rays hit, {ro.leaves} leaves, build {ro.build_ms:.3f} ms, trace {ro.trace_ms:.3f} ms")
         if a.mesh_shadows:
             held = shade_mesh_pixels(scene, meshes, p, V, P, a)  # the occluder's images: keep them until the frame is downloaded
-    if a.pipeline != "trace" and (a.trace_strategy != "full" or a.accumulate != 1):
-        ap.error("--trace-strategy pass / anyhit and --accumulate are for --pipeline trace (unlit)")
+    soft = a.lighting == 1 and a.shadows == 2 and a.pipeline in ("trace", "hybrid")
+    if a.shadows == 2 and not soft:
+        ap.error("--shadows 2 needs --lighting 1 with --pipeline trace or hybrid")
+    if soft and os.environ.get("MGS_SOFT_SHADOWS", "0") in ("", "0"):
+        ap.error("--shadows 2: soft shadows are opt-in per process, run with MGS_SOFT_SHADOWS=1")
+    if (a.pipeline != "trace" and a.trace_strategy != "full") or (a.accumulate != 1 and not (a.pipeline == "trace" and not a.lighting) and not soft):
+        ap.error("--trace-strategy pass / anyhit are for --pipeline trace (unlit); --accumulate for that and for --shadows 2")
     if a.pipeline == "trace":
         if a.occluder_depth:
             ap.error("--pipeline trace takes no --occluder-depth (meshes: --mesh)")
@@ -252,8 +267,8 @@ def main():
         p.collect_timings = 0
         t = capi.default_trace_params(samples_per_pass=a.samples_per_pass, max_passes=a.max_passes, min_transmittance=a.min_transmittance,
                                       trace_strategy=["full", "pass", "anyhit"].index(a.trace_strategy))
-        if a.lighting and (t.trace_strategy or a.accumulate != 1):
-            ap.error("--trace-strategy pass / anyhit and --accumulate are for unlit traced frames")
+        if a.lighting and t.trace_strategy:
+            ap.error("--trace-strategy pass / anyhit are for unlit traced frames")
         if a.lighting:  # mgs_render_traced_lit: --lights / --material as for the raster pipelines, shadows by one more ray per light
             lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
                                                  particle_shadow_transmittance_threshold=a.shadow_threshold,
@@ -263,7 +278,10 @@ def main():
                 print(f"bounces {bo.bounce_ms:.3f} ms on the GPU, live pixels per bounce {list(bo.rays)[:a.max_bounces]}, mesh hits "
                       f"{list(bo.mesh_hits)[:a.max_bounces]}, {bo.particle_hits} particle hits")
             else:
-                o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
+                for k in range(max(a.accumulate, 1)):  # soft shadows: the running mean of the samples is the frame after the last
+                    if a.accumulate > 1:
+                        p.frame_sample_id, p.temporal_sampling = k, 1
+                    o, lo = scene.render_traced_lit(p, t, lp, want_stats=True)
             sr = max(int(lo.shadow_rays), 1)
             print(f"light pass {lo.light_ms:.3f} ms on the GPU, {lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, "
                   f"{lo.shadow_candidate_tests / sr:.1f} candidate tests and {lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
@@ -287,7 +305,10 @@ def main():
         lp = capi.default_trace_light_params(shadows_mode=a.shadows, particle_shadow_offset=a.shadow_offset,
                                              particle_shadow_transmittance_threshold=a.shadow_threshold,
                                              particle_shadow_color_strength=a.shadow_color_strength)
-        o, lo = scene.render_hybrid(p, t, lp, want_stats=True)
+        for k in range(max(a.accumulate, 1)):
+            if a.accumulate > 1:
+                p.frame_sample_id, p.temporal_sampling = k, 1
+            o, lo = scene.render_hybrid(p, t, lp, want_stats=True)
         img = scene.download_frame(p).astype(np.float32)
         sr = max(int(lo.shadow_rays), 1)
         print(f"{scene.splat_count} splats, {o.sorted_count} sorted, raster frame {o.stage_ms[5]:.3f} ms and light pass {lo.light_ms:.3f} ms on the GPU, "

@@ -7,7 +7,8 @@ Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup 
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
 tests per ray, and writes everything as JSON.  --trace-strategy: MgsTraceParams::trace_strategy of the unlit frames (the lit
 and hybrid ones take the sorted strategy alone).  --lit adds lit frames (mgs_render_traced_lit, a diffuse material) with 0 / 1 / 4 point
-lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray.  --hybrid (with --lit) renders the same lit
+lights and shadows off / on: the median light_ms and MgsTraceLightOut per shadow ray; in a process started with MGS_SOFT_SHADOWS=1 also a
+"soft" row per light count: hard and soft light_ms on the same scene, pose and lights, alternated frame by frame.  --hybrid (with --lit) renders the same lit
 scenes through mgs_render_hybrid as well: the raster frame's time, light_ms and the shadow counters beside the traced ones.
 --rays N adds ray queries (mgs_trace_rays_device) of about N rays, for every N given: a RANDOM batch (origins uniform in the ball of
 the camera's distance, each aimed at a random point of the inner half of that ball: neighbouring lanes share nothing) and a CAMERA
@@ -348,6 +349,29 @@ def main():
                                                       node_visits_per_shadow_ray=lo.shadow_node_visits / sr,
                                                       candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
                                                       accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr)
+            if os.environ.get("MGS_SOFT_SHADOWS", "0") not in ("", "0"):
+                # soft against hard (MGS_SHADOWS_SOFT, every light's radius 1.0: a disk of 0.5): the same scene, pose and lights,
+                # alternated frame by frame in this process; the sample id advances with the frame as an accumulating caller's does
+                r["soft"] = []
+                for nl in (1, 4):
+                    scene.set_lights([capi.make_light(position=q, range=1000.0, attenuation_mode=0) for q in spots[:nl]])
+                    ms, last = {1: [], 2: []}, {}
+                    for k in range(a.warmup + a.repeats):
+                        p.frame_sample_id = k
+                        for mode in (1, 2):
+                            _, lo = scene.render_traced_lit(p, t, capi.default_trace_light_params(shadows_mode=mode), want_stats=True)
+                            last[mode] = lo
+                            if k >= a.warmup:
+                                ms[mode].append(lo.light_ms)
+                    p.frame_sample_id = 0
+                    row = dict(lights=nl, radius=1.0)
+                    for mode, tag in ((1, "hard"), (2, "soft")):
+                        lo, sr = last[mode], max(int(last[mode].shadow_rays), 1)
+                        row[tag] = dict(light_ms_median=float(np.median(ms[mode])), light_ms_min=float(min(ms[mode])), light_ms_max=float(max(ms[mode])),
+                                        shadow_rays=int(lo.shadow_rays), node_visits_per_shadow_ray=lo.shadow_node_visits / sr,
+                                        candidate_tests_per_shadow_ray=lo.shadow_candidate_tests / sr,
+                                        accepted_hits_per_shadow_ray=lo.shadow_accepted_hits / sr)
+                    r["soft"].append(row)
             p.lighting_mode = 0
         if a.trace_meshes:
             tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)

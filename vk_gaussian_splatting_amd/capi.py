@@ -65,7 +65,8 @@ class FrameParams(C.Structure):
 
 
 class Light(C.Structure):
-    """MgsLight: shaderio::LightSource minus the soft-shadow radius; angles in degrees"""
+    """MgsLight: shaderio::LightSource; angles in degrees.  The soft-shadow radius is not a field of the C struct: make_light(radius=R)
+    keeps it as a Python attribute, which Scene.set_lights hands to mgs_scene_set_light_radii"""
     _fields_ = [("type", C.c_int32), ("color", C.c_float * 3), ("intensity", C.c_float), ("position", C.c_float * 3),
                 ("range", C.c_float), ("direction", C.c_float * 3), ("inner_cone_deg", C.c_float), ("outer_cone_deg", C.c_float),
                 ("attenuation_mode", C.c_int32)]
@@ -78,10 +79,14 @@ class Material(C.Structure):
 
 
 def make_light(**kw):
-    """an MgsLight with the reference's defaults (mgs_light_default), fields overridden by keyword"""
+    """an MgsLight with the reference's defaults (mgs_light_default), fields overridden by keyword; radius = the soft-shadow radius
+    (LightSource::radius, default 1.0), carried beside the struct for Scene.set_lights"""
     l = Light()
     load_library().mgs_light_default(C.byref(l))
     for k, v in kw.items():
+        if k == "radius":
+            l.radius = float(v)
+            continue
         if k not in dict(Light._fields_):
             raise TypeError(f"make_light: unknown field {k}")
         if k in ("color", "position", "direction"):
@@ -426,6 +431,7 @@ def load_library():
         "mgs_light_default": (None, [P(Light)]),
         "mgs_material_default": (None, [P(Material)]),
         "mgs_scene_set_lights": (C.c_int, [vp, P(Light), C.c_int]),
+        "mgs_scene_set_light_radii": (C.c_int, [vp, P(C.c_float), C.c_int]),
         "mgs_instance_set_material": (C.c_int, [vp, C.c_int, P(Material)]),
         "mgs_scene_splat_count": (C.c_uint64, [vp]),
         "mgs_compare_capture": (C.c_int, [vp]),
@@ -530,7 +536,7 @@ EXPORTED_SYMBOLS = [
     "mgs_instance_set_transform", "mgs_scene_commit", "mgs_scene_splat_count", "mgs_scene_storage_order", "mgs_scene_download_set",
     "mgs_frame_context_create", "mgs_frame_context_destroy", "mgs_scene_memory_usage", "mgs_scene_set_list_capacity",
     "mgs_frame_set_occluder", "mgs_frame_upload_occluder", "mgs_sensor_model_from_frame", "mgs_frame_set_sensor",
-    "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_instance_set_material",
+    "mgs_light_default", "mgs_material_default", "mgs_scene_set_lights", "mgs_scene_set_light_radii", "mgs_instance_set_material",
     "mgs_compare_capture", "mgs_compare_capture_upload", "mgs_compare_release", "mgs_compare_params_default", "mgs_compare_metrics",
     "mgs_compare_view_default", "mgs_compare_composite", "mgs_compare_download_composite",
     "mgs_mesh_from_arrays", "mgs_mesh_load_obj", "mgs_mesh_view", "mgs_mesh_destroy", "mgs_mesh_instance_add",
@@ -878,10 +884,22 @@ class Scene:
 
     # ---- deferred lighting (FrameParams.lighting_mode): the scene's light table and the instances' materials ----
     def set_lights(self, lights):
-        """replace the scene's lights (mgs_scene_set_lights): a sequence of Light (make_light); empty = the headlight"""
+        """replace the scene's lights (mgs_scene_set_lights): a sequence of Light (make_light); empty = the headlight.  Every radius
+        restarts at 1.0; where a light carries one (make_light(radius=R)) the radii are set too (mgs_scene_set_light_radii)"""
         lights = list(lights)
         arr = (Light * max(len(lights), 1))(*lights)
         _check(self._lib.mgs_scene_set_lights(self._h, arr if lights else None, len(lights)))
+        if any(hasattr(l, "radius") for l in lights):
+            self.set_light_radii([getattr(l, "radius", 1.0) for l in lights])
+
+    def set_light_radii(self, radii=None):
+        """the soft-shadow radius of each light of the table, in its order (mgs_scene_set_light_radii); None = the default 1.0 for all"""
+        if radii is None:
+            _check(self._lib.mgs_scene_set_light_radii(self._h, None, 0))
+            return
+        r = [float(x) for x in radii]
+        arr = (C.c_float * max(len(r), 1))(*r)
+        _check(self._lib.mgs_scene_set_light_radii(self._h, arr, len(r)))
 
     def set_material(self, instance, material):
         _check(self._lib.mgs_instance_set_material(self._h, int(instance), C.byref(material)))

@@ -381,8 +381,47 @@ static int mgs_scene_set_lights_impl(MgsScene s, const MgsLight* lights, int cou
       D.dirN[c] = L.direction[c] * inv;
     D.innerCos = std::cos(L.inner_cone_deg * (3.14159265358979323846f / 180.0f));
     D.outerCos = std::cos(L.outer_cone_deg * (3.14159265358979323846f / 180.0f));
+    D.radius   = 1.0f;  // LightSource::radius' default (light_manager_vk.cpp:104); mgs_scene_set_light_radii changes it
   }
   return rewriteLightTable(*s->d, &T, offsetof(LightTable, lights) + (size_t)count * sizeof(LightDev));
+}
+static int mgs_scene_set_light_radii_impl(MgsScene s, const float* radii, int count)
+{
+  if(!s)
+  {
+    setError("mgs_scene_set_light_radii: null handle");
+    return MGS_ERR_INVALID_ARG;
+  }
+  if(s->isContext)
+  {
+    setError("mgs_scene_set_light_radii: a frame context is read-only; the lights belong to the scene it was created from");
+    return MGS_ERR_STATE;
+  }
+  const int  lights   = s->d->lightHost ? s->d->lightHost->count : 0;
+  const bool defaults = !radii && count == 0;
+  if(!defaults && (!radii || count != lights))
+  {
+    setError("mgs_scene_set_light_radii: count must equal the number of lights of mgs_scene_set_lights (" + std::to_string(lights) + "); NULL with 0 restores the defaults");
+    return MGS_ERR_INVALID_ARG;
+  }
+  for(int i = 0; i < count; ++i)
+    if(!std::isfinite(radii[i]) || radii[i] < 0.0f)
+    {
+      setError("mgs_scene_set_light_radii: radius " + std::to_string(i) + " must be finite and >= 0");
+      return MGS_ERR_INVALID_ARG;
+    }
+  if(lights == 0)
+    return MGS_OK;
+  if(int rc = ensureLightTable(*s->d))
+    return rc;
+  LightTable& T = *s->d->lightHost;
+  for(int i = 0; i < lights; ++i)
+    T.lights[i].radius = defaults ? 1.0f : radii[i];
+  return rewriteLightTable(*s->d, T.lights, (size_t)lights * sizeof(LightDev));
+}
+int mgs_scene_set_light_radii(MgsScene s, const float* radii, int count)
+{
+  return guarded("mgs_scene_set_light_radii", [&] { return mgs_scene_set_light_radii_impl(s, radii, count); });
 }
 int mgs_scene_set_lights(MgsScene s, const MgsLight* lights, int count)
 {

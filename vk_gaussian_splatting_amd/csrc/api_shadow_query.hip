@@ -28,7 +28,7 @@ static int validateShadowKnobs(const MgsTraceLightParams& lt, bool points, const
 {
   const std::string w(what);
   if(lt.shadows_mode == MGS_SHADOWS_SOFT)
-    return failTrace(MGS_ERR_UNSUPPORTED, w + ": soft shadows are out of scope (hard shadows only)");
+    return failTrace(MGS_ERR_UNSUPPORTED, w + ": soft shadows are a frame's (a query point has no pixel to seed the light's disk sample from)");
   if(points ? (lt.shadows_mode != MGS_SHADOWS_DISABLED && lt.shadows_mode != MGS_SHADOWS_HARD) : lt.shadows_mode != MGS_SHADOWS_HARD)
     return failTrace(MGS_ERR_INVALID_ARG, w + (points ? ": shadows_mode must be MGS_SHADOWS_DISABLED or MGS_SHADOWS_HARD" : ": shadows_mode must be MGS_SHADOWS_HARD"));
   if(points && (!(lt.particle_shadow_offset >= 0.0f) || !std::isfinite(lt.particle_shadow_offset)))

@@ -110,8 +110,9 @@ int validateTrace(const MgsFrameParams* p, const MgsTraceParams& t, const MgsTra
     if(p->lighting_mode != MGS_LIGHTING_DIRECT)
       return failTrace(MGS_ERR_INVALID_ARG, hybrid ? "mgs_render_hybrid: lighting_mode must be MGS_LIGHTING_DIRECT (a hybrid frame without lighting is mgs_render's)"
                                                    : "mgs_render_traced_lit: lighting_mode must be MGS_LIGHTING_DIRECT");
-    if(lit->shadows_mode == MGS_SHADOWS_SOFT)
-      return failTrace(MGS_ERR_UNSUPPORTED, "trace: soft shadows are out of scope (hard shadows only)");
+    // within ABI 5.1 a caller that probes MGS_SHADOWS_SOFT keeps the answer it always got unless the process opts in
+    if(lit->shadows_mode == MGS_SHADOWS_SOFT && !tuning().softShadows)
+      return failTrace(MGS_ERR_UNSUPPORTED, "trace: soft shadows are off in this process; start it with MGS_SOFT_SHADOWS=1 (MGS_HAS_SOFT_SHADOWS)");
   }
   else
   {
@@ -712,7 +713,7 @@ static int mgs_render_traced_indirect_impl(MgsScene s, const MgsFrameParams* p, 
   if(t.trace_strategy == MGS_TRACE_STRATEGY_PASS_STOCHASTIC || t.trace_strategy == MGS_TRACE_STRATEGY_STOCHASTIC_ANYHIT)
     return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced_indirect: the stochastic strategies' bounces are out of scope (trace_strategy must be 0)");
   if(lt.shadows_mode == MGS_SHADOWS_SOFT)
-    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced_indirect: soft shadows are out of scope (hard shadows only)");
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_traced_indirect: soft shadows need the pixel's random state carried across the bounce launches, which is not built (MGS_SHADOWS_HARD or off)");
   // bounce 0 is the lit mesh frame: its checks, its set-up and its launches, with the composite and the rounds behind it exchanged
   return mgs_render_traced_impl(s, p, &t, out, true, &lt, lout, &b, bout);
 }

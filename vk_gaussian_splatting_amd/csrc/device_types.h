@@ -198,7 +198,7 @@ struct LightDev
   float   pos[3], range;
   float   dirN[3];             // normalize(direction)
   float   innerCos, outerCos;  // cos(radians(angle))
-  float   pad;
+  float   radius;              // LightSource::radius (mgs_scene_set_light_radii): read by soft shadows only
 };
 // one instance's material (shaderio::ObjMaterial reduced) + needShading as updateMaterialNeedsShading derives it.  64 B.
 struct alignas(16) MaterialDev

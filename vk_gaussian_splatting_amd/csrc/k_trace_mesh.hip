@@ -75,8 +75,12 @@ __global__ __launch_bounds__(256) void k_trace_mesh_primary(TraceMeshArgs m, con
 }
 
 // KB: K-buffer slots in registers of the particle shadow rays (>= samples_per_pass; 4 in an unlit frame, which traces none);
-// LIT: the mesh shading of mgs_render_traced_lit, otherwise the unlit composite of mgs_render_traced
-template <int KB, bool LIT>
+// LIT: the mesh shading of mgs_render_traced_lit, otherwise the unlit composite of mgs_render_traced; SOFT (LIT only):
+// MGS_SHADOWS_SOFT, the lights with a radius are sampled on their disk (lightToSurfaceSoft).  The pixel's random state is ONE for
+// both light loops of a pixel (rgen.slang:1054, :1061, the same inout seed): the mesh loop continues where the splat surface's loop
+// in k_trace_light ended.  That loop draws two numbers per point or spot light with a radius, culled or not, so its end state is
+// recomputed here from the light table and the light pass's own conditions for running its loop; no per-pixel word is carried
+template <int KB, bool LIT, bool SOFT>
 __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs args)
 {
   const TraceLightArgs& L = args.l;
@@ -117,7 +121,8 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
     a.outDepth[pix] = cz / cw;
   }
 
-  V3 color = {base.x, base.y, base.z};
+  V3   color = {base.x, base.y, base.z};
+  bool splatShaded = false;  // SOFT: the light pass reached its loop over the lights on this pixel
   if constexpr(LIT)
   {  // surfaceFinalFiltering and splatIsClosest as the light pass decided them: a discarded splat surface is radiance 0, T = 1
     const float isoDist = L.isoDist[pix];
@@ -125,6 +130,14 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
     {
       color = {0.0f, 0.0f, 0.0f};
       walkT = (double)1.0f > (double)args.m.minT ? 1.0f : -1.0f;
+    }
+    else if constexpr(SOFT)
+    {  // the picked instance's needShading, as k_trace_light reads it (rgen.slang:1091-1095 returns before the loop)
+      int inst = 0;
+      for(int i = 1; i < F.nInstances; ++i)  // bound: kMaxInstances
+        if(pickId >= Ap->inst[i].globalOffset)
+          inst = i;
+      splatShaded = L.table->mats[inst].needShading != 0;
     }
   }
   if(walkT < 0.0f)
@@ -156,12 +169,21 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
       const V3 worldPos = {h1.x, h1.y, h1.z}, normal = {h2.x, h2.y, h2.z};  // meshHitWorldPos, meshHitWorldNrm: the closest hit's
       const int         count = L.table->count;
       const ShadowKnobs knobs = {L.shFormat, L.shadowThreshold, L.shadowColorStrength};
+      uint32_t          seedRayPass = SOFT ? rngXxhash32((uint32_t)px, (uint32_t)py, (uint32_t)F.frameSampleId) : 0u;  // :228
+      if constexpr(SOFT)
+        if(splatShaded)
+          for(int l = 0; l < count; ++l)  // bound: kMaxLights.  The splat surface's loop: two draws per light with a disk
+            if(L.table->lights[l].type != MGS_LIGHT_DIRECTIONAL && L.table->lights[l].radius > 0.0f)
+            {
+              (void)rngPcg(seedRayPass);
+              (void)rngPcg(seedRayPass);
+            }
       for(int l = 0; l < count; ++l)  // bound: kMaxLights
       {
         const LightDev& light = L.table->lights[l];
         V3    lightDir;
         float lightDist;
-        if(!lightToSurface(light, worldPos, lightDir, lightDist))
+        if(!(SOFT ? lightToSurfaceSoft(light, worldPos, seedRayPass, lightDir, lightDist) : lightToSurface(light, worldPos, lightDir, lightDist)))
           continue;  // culled (:1230-1231)
         V3   shadowT  = {1.0f, 1.0f, 1.0f};
         bool inShadow = false;
@@ -239,11 +261,15 @@ void launchTraceMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, c
     return;
   if(!lit)
   {
-    hipLaunchKernelGGL((k_trace_mesh_composite<4, false>), dim3(tiles), dim3(256), 0, stream, L);
+    hipLaunchKernelGGL((k_trace_mesh_composite<4, false, false>), dim3(tiles), dim3(256), 0, stream, L);
     return;
   }
-  withKBuffer("launchTraceMeshComposite", L.l.t.samplesPerPass,
-              [&](auto kb) { hipLaunchKernelGGL((k_trace_mesh_composite<decltype(kb)::value, true>), dim3(tiles), dim3(256), 0, stream, L); });
+  withKBuffer("launchTraceMeshComposite", L.l.t.samplesPerPass, [&](auto kb) {
+    if(L.l.shadowsMode == MGS_SHADOWS_SOFT)
+      hipLaunchKernelGGL((k_trace_mesh_composite<decltype(kb)::value, true, true>), dim3(tiles), dim3(256), 0, stream, L);
+    else
+      hipLaunchKernelGGL((k_trace_mesh_composite<decltype(kb)::value, true, false>), dim3(tiles), dim3(256), 0, stream, L);
+  });
 }
 
 }  // namespace mgs

@@ -8,6 +8,7 @@
 
 #include "../../include/mgs.h"
 #include "device_types.h"
+#include "kernels_common.h"
 
 namespace mgs {
 
@@ -59,6 +60,49 @@ __device__ __forceinline__ bool lightToSurface(const LightDev& light, V3 worldPo
     return true;
   }
   const V3 toLight = load3(light.pos) - worldPos;
+  lightDist        = sqrtf(dot3(toLight, toLight));
+  if(lightDist > light.range)
+    return false;
+  lightDir = toLight * (1.0f / lightDist);
+  return true;
+}
+
+// computeLightToSurfaceVector under SHADOWS_MODE == SHADOWS_SOFT (wavefront.h.slang:33-102): a point or spot light with a radius is
+// sampled on a disk of half that radius around its position, perpendicular to the direction from the surface to the light
+// (buildOrthonormalBasis: Frisvad's basis with its n.z < -0.9999999 branch; sampleDisk: the radius is drawn first, then the angle).
+// The two numbers come from the pixel's state `seed` (rgen.slang:228) and are drawn BEFORE the range test, which is decided by the
+// sample's distance: a culled light has consumed them.  A directional light, or a radius <= 0, draws nothing and is lightToSurface
+// operation for operation.  sqrtf, sinf and cosf are the accurate ones: the float64 restatement's margin rests on their bounds.
+__device__ __forceinline__ bool lightToSurfaceSoft(const LightDev& light, V3 worldPos, uint32_t& seed, V3& lightDir, float& lightDist)
+{
+  if(light.type == MGS_LIGHT_DIRECTIONAL)
+  {
+    lightDir  = -load3(light.dirN);
+    lightDist = 1e10f;
+    return true;
+  }
+  V3 samplePos = load3(light.pos);
+  if(light.radius > 0.0f)
+  {
+    const V3 n = normalize3(load3(light.pos) - worldPos);
+    V3       tangent, bitangent;
+    if(n.z < -0.9999999f)
+    {
+      tangent   = {0.0f, -1.0f, 0.0f};
+      bitangent = {-1.0f, 0.0f, 0.0f};
+    }
+    else
+    {
+      const float a = 1.0f / (1.0f + n.z);
+      const float b = -n.x * n.y * a;
+      tangent       = {1.0f - n.x * n.x * a, b, -n.x};
+      bitangent     = {b, 1.0f - n.y * n.y * a, -n.y};
+    }
+    const float r     = (light.radius * 0.5f) * sqrtf(rngRand(seed));
+    const float theta = 2.0f * 3.14159265f * rngRand(seed);
+    samplePos         = samplePos + (tangent * cosf(theta) + bitangent * sinf(theta)) * r;
+  }
+  const V3 toLight = samplePos - worldPos;
   lightDist        = sqrtf(dot3(toLight, toLight));
   if(lightDist > light.range)
     return false;

@@ -28,6 +28,10 @@ struct Tuning
                                      // (a multiple of 256 in [1024, kOsPart]; kOsPart = fixed partitions)
   // mesh pass
   uint32_t meshWorkItems = 1u << 20;  // MGS_MESH_WORK_ITEMS=n: capacity of the large-triangle work list, 1 .. 2^26 chunks of 16 tiles
+  // traced light pass
+  bool softShadows = false;  // MGS_SOFT_SHADOWS=1: mgs_render_traced_lit and mgs_render_hybrid accept MGS_SHADOWS_SOFT; unset, they
+                             // answer it with MGS_ERR_UNSUPPORTED as every build before did (ABI 5.1: same behaviour by default).
+                             // TEMPORARY: goes with the next ABI minor, which accepts the mode unconditionally
   // frame submission
   bool useGraph = true;  // MGS_GRAPH=0: plain kernel launches instead of replaying the captured frame graph
   // multi-GPU

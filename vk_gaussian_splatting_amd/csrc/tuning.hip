@@ -21,6 +21,7 @@ static Tuning readTuning()
   t.exactShortcuts = flag("MGS_EXACT_SHORTCUTS", true);
   t.sortRemap      = flag("MGS_SORT_REMAP", true);
   t.useGraph       = flag("MGS_GRAPH", true);
+  t.softShadows    = flag("MGS_SOFT_SHADOWS", false);
   if(const char* e = std::getenv("MGS_RIDE_SPLIT"))
     t.rideSplitAlways = std::atoi(e) == 2;
   if(const char* e = std::getenv("MGS_DB_TRANSPOSE"))

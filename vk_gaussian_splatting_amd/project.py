@@ -196,10 +196,10 @@ def _lights_from(section, version):
     """loadLights (vkgs_project_reader.cpp:616-770) -> dicts with the field names of MgsLight"""
     def asset_fields(a, v4):
         L = {"type": int(a.get("type", 1)), "color": [float(x) for x in a.get("color", (1.0, 1.0, 1.0))], "intensity": float(a.get("intensity", 1.0)),
-             "range": 10.0, "inner_cone_deg": 30.0, "outer_cone_deg": 45.0, "attenuation_mode": 2}
-        if v4:
+             "range": 10.0, "inner_cone_deg": 30.0, "outer_cone_deg": 45.0, "attenuation_mode": 2, "radius": 1.0}
+        if v4:  # "radius" of the result is LightSource::radius = proxyScale (light_manager_vk.cpp:480), the soft shadows' disk
             for src, dst, conv in (("range", "range", float), ("innerConeAngle", "inner_cone_deg", float), ("outerConeAngle", "outer_cone_deg", float),
-                                   ("attenuationMode", "attenuation_mode", int)):
+                                   ("attenuationMode", "attenuation_mode", int), ("proxyScale", "radius", float)):
                 if src in a:
                     L[dst] = conv(a[src])
         elif "radius" in a:  # the old "radius" is the new "range"
@@ -217,6 +217,8 @@ def _lights_from(section, version):
             else:
                 L["position"] = [float(x) for x in inst.get("position", (0.0, 2.0, 0.0))]
                 L["direction"] = [0.0, 0.0, -1.0]
+                if "scale" in assets[int(inst["assetId"])]:  # the old "scale" is the new "proxyScale" (:675-679)
+                    L["radius"] = float(assets[int(inst["assetId"])]["scale"])
             out.append(L)
         return out
     items = section["items"] if isinstance(section, dict) and "items" in section else section
