@@ -57,7 +57,9 @@ extern "C" {
                             mesh ray queries (MGS_HAS_MESH_RAY_QUERY below): entry points and new structs, both numbers stay —
                                  mgs_mesh_ray_params_default, mgs_trace_mesh_rays, mgs_trace_mesh_rays_device;
                             hierarchy hook (MGS_HAS_DEBUG_HIERARCHY below): one entry point and one new struct, both numbers stay —
-                                 mgs_debug_download_hierarchy */
+                                 mgs_debug_download_hierarchy;
+                            meshes in the hybrid frames (MGS_HAS_HYBRID_MESHES below): two entry points, both numbers stay —
+                                 mgs_frame_set_hybrid_meshes, mgs_debug_download_hybrid_depth */
 #define MGS_HAS_IMAGE_COMPARE 1 /* feature macro: the mgs_compare_* entry points exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE 1         /* feature macro: mgs_render_traced and its companions exist (added within ABI 5.1, no struct or default changed) */
 #define MGS_HAS_TRACE_LIGHTING 1 /* feature macro: mgs_render_traced_lit and its companions exist (added within ABI 5.1, no struct or default changed) */
@@ -1204,7 +1206,7 @@ int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_de
  * bit for bit, whether or not the scene holds mesh instances.  enabled not 0 / 1, a threshold outside [0, 1] (NaN included) or a
  * non-zero reserved word: MGS_ERR_INVALID_ARG, checked before the handle is looked at.  With the setting on, mgs_render_traced with
  * trace_strategy 0 and mgs_render_traced_lit include the scene's visible mesh instances; mgs_render_traced with strategy 1 or 2 and
- * mgs_render_hybrid (whose mesh depth pre-pass is later work) return MGS_ERR_UNSUPPORTED; mgs_render, mgs_meshes_render and the ray,
+ * mgs_render_hybrid (whose meshes are mgs_frame_set_hybrid_meshes', MGS_HAS_HYBRID_MESHES) return MGS_ERR_UNSUPPORTED; mgs_render, mgs_meshes_render and the ray,
  * shadow and mesh-ray queries do not read it.  A scene without splats but with meshes renders the meshes alone.  A scene with no
  * visible mesh instance renders the frame it renders with the setting off, bit for bit (the frame's kernels are then the same ones;
  * only the all-miss hit records are written besides).  mgs_render_gathered is not wired.
@@ -1249,7 +1251,7 @@ int  mgs_trace_mesh_rays_device(MgsScene scene_or_context, const MgsRay* rays_de
  * handle and count into working_bytes: the hit record (64 B), its t (4 B) and the walk's transmittance rounded once to fp32 (4 B);
  * an unlit frame with a visible mesh also keeps the lit frames' fp32 pixel and ray parameter (16 B + 4 B).
  * PARITY UNPINNED: what the mesh ray queries list, and the reference's RAY_FLAG_CULL_BACK_FACING_TRIANGLES, which has no effect there.
- * Out of scope: hybrid frames with meshes, mesh occlusion inside mgs_trace_shadow_rays / mgs_shade_points, the stochastic
+ * Out of scope: mesh occlusion inside mgs_trace_shadow_rays / mgs_shade_points, the stochastic
  * strategies with meshes, light proxies, ray masks, mgs_render_gathered.  Mesh transmittance / ior / reflection /
  * refraction bounces and indirect lighting are mgs_render_traced_indirect's (MGS_HAS_TRACE_BOUNCES, below). */
 #define MGS_HAS_TRACE_MESHES 1
@@ -1262,6 +1264,52 @@ void mgs_trace_mesh_params_default(MgsTraceMeshParams* params);
 int  mgs_frame_set_trace_meshes(MgsScene scene_or_context, const MgsTraceMeshParams* params /* NULL = off */);
 int  mgs_trace_download_mesh_hits(MgsScene scene_or_context, MgsMeshHit* host_dst, size_t count); /* [height][width] */
 int  mgs_trace_mesh_stats(MgsScene scene_or_context, MgsMeshRayOut* primary, MgsMeshRayOut* shadow); /* either may be NULL; waits */
+
+/* ---- meshes in the hybrid frames (MGS_HAS_HYBRID_MESHES): the scene's triangle meshes take part in mgs_render_hybrid, the reference's
+ * PIPELINE_HYBRID and PIPELINE_HYBRID_3DGUT for composed scenes (doc/hybrid_rendering_3d_gaussians.md;
+ * shaders/threedgrt_raytrace.rgen.slang:252-281, :346-460, :1037-1077): the splats are rasterised against a traced mesh depth pre-pass,
+ * then splats and meshes are shaded together, each shadowing the other.  Added within ABI 5.1: entry points only, no struct or default
+ * changes.
+ *
+ * The setting belongs to the handle, scene or frame context, and is off by default (NULL = off).  It reuses MgsTraceMeshParams with
+ * mgs_frame_set_trace_meshes' checks (enabled 0 / 1, the threshold in [0, 1] with NaN refused, reserved words 0: MGS_ERR_INVALID_ARG
+ * before the handle is looked at).  It is deliberately a setting of its own: with it off, mgs_render_hybrid does exactly what it did
+ * before, bit for bit, including MGS_ERR_UNSUPPORTED while mgs_frame_set_trace_meshes is on or an occluder is bound.  With it on,
+ * mgs_render_hybrid does not read the trace-mesh setting; a caller-bound occluder is still MGS_ERR_UNSUPPORTED (the frame binds its own
+ * depth plane), and so is MGS_SHADOWS_SOFT (the mesh composite continues the light pass's random state, whose conditions differ in a
+ * hybrid frame: later work).  MGS_SORT_STOCHASTIC, a bound sensor, MGS_LIGHTING_INDIRECT and mgs_render_gathered behave as without
+ * the setting.  With the setting on but no visible mesh instance that has a leaf, the frame is the setting-off frame, bit for bit
+ * (only the all-miss hit records are written besides).  No other entry point reads the setting.
+ *
+ * The frame, on the handle's stream:
+ * 1. Mesh depth pre-pass (meshDepthOnly, :252-281).  The primary mesh ray of "mesh hits in the traced frames" on the pixel's ray (the
+ *    hand-over's ray; lens and fisheye included for 3DGUT) leaves the pixel's MgsMeshHit.  The handle's own depth plane gets
+ *    clip.z / clip.w of clip = (meshHitWorldPos * view) * proj in fp32 on a hit, and 1.0 on a miss or outside the fisheye circle.
+ * 2. Raster frame: mgs_render's unlit frame with surface_outputs = 1, as in a hybrid frame without meshes, with that plane bound as
+ *    the occluder depth and no occluder colour.
+ * 3. Hand-over, as documented for mgs_render_hybrid, and besides: T = 1 - stored alpha in fp32, from the pixel as stored in its target
+ *    format (:357-358); a discarded pixel has radiance 0 and T = 1 (:468-478); a surface with a valid pick whose ray parameter is not
+ *    < t_mesh is not discarded: splatIsClosest fails (:1047), it keeps its raster colour unlit and its own T.
+ * 4. Light pass: the splat surface in front of the mesh is shaded as in mgs_render_traced_lit with mesh hits: every shadow ray asks
+ *    the meshes first, from the un-offset origin, then the particles.
+ * 5. Mesh shading, where a mesh is hit and T > min_mesh_composite_transmittance (compared in double): exactly the lit frame's of
+ *    "mesh hits in the traced frames" (emission unweighted, needShading, the lights in range at meshHitWorldPos with the un-flipped
+ *    normal, the mesh occlusion ray then the particle shadow ray, the headlight without lights), on the base colour and T of step 3.
+ * 6. Temporal accumulation runs after step 5.  MgsTraceLightOut::light_ms brackets steps 3 and 4.
+ * Deliberate differences from the reference: alpha is 1 where a mesh was composited, elsewhere the stored alpha, and 0 where the pixel
+ * is discarded (the reference writes 1.0 everywhere); the splat surface is shaded and its shadow rays start at ONE position, ray
+ * origin + ray parameter * ray direction, as in every hybrid frame.
+ * Afterwards mgs_trace_download_mesh_hits and mgs_trace_mesh_stats work as after a lit traced frame with mesh hits (`primary`: the
+ * pre-pass, both kernels; `shadow`: the occlusion rays, trace_ms around the mesh shading); mgs_frame_download_surface returns the
+ * raster pass's outputs untouched; mgs_trace_download_shadow_hits includes the mesh points' particle shadow hits; strip rows and frame
+ * contexts work.  The two downloads and the statistics answer for the handle's last HYBRID frame: a frame that fails clears them, a
+ * later mgs_render does not (as the traced frames' downloads outlive one).  The depth plane (4 B / pixel) belongs to the handle and counts into working_bytes with the per-pixel mesh buffers.
+ * Out of scope: bounces and soft shadows in hybrid frames with meshes. */
+#define MGS_HAS_HYBRID_MESHES 1
+int mgs_frame_set_hybrid_meshes(MgsScene scene_or_context, const MgsTraceMeshParams* params /* NULL = off */);
+/* test/debug hook: the depth plane of the handle's last hybrid frame's pre-pass, [height][width] floats (rows outside a strip frame's
+ * rows are stale); MGS_ERR_STATE unless that frame ran the pre-pass (setting on, a visible mesh instance with a leaf); waits */
+int mgs_debug_download_hybrid_depth(MgsScene scene_or_context, float* host_dst, size_t count);
 
 /* ---- reflection and refraction bounces (MGS_HAS_TRACE_BOUNCES): the indirect traced frame, the reference's LIGHTING_INDIRECT
  * (shaderio.h:133) for trace strategy 0: the bounce loop of shaders/threedgrt_raytrace.rgen.slang:230-337 off mesh materials that

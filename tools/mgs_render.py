@@ -30,6 +30,8 @@ primary surface, lit and shadowed by the traced light pass; --lights / --materia
 shadow rays.  Not combinable with --occluder-depth or --mesh.  --raster-pipeline: 3DGS (default) or 3DGUT, of --pipeline raster and hybrid.
 --pipeline trace: the ray-traced pipeline (mgs_render_traced: 3DGRT primary rays over the scene's device-built hierarchy) instead of
 the raster one; prints MgsTraceOut.  Not combinable with --occluder-depth.
+--pipeline hybrid --lighting 1 --mesh FILE.obj --hybrid-meshes 1 [--mesh-composite-threshold T]: the meshes take part in the hybrid frame
+(mgs_frame_set_hybrid_meshes): a traced mesh depth pre-pass in front of the raster frame, splats and meshes shadowing each other.
 --pipeline trace --mesh FILE.obj [--lighting 1 --shadows 1]: the meshes take part in the traced frame (mgs_frame_set_trace_meshes): mesh
 hits cut the particle walk, meshes are shaded and throw and receive shadows; prints both MgsMeshRayOut blocks.  --trace-meshes 0 leaves
 the setting off (the frame of the splats alone); --mesh-composite-threshold X is min_mesh_composite_transmittance.
@@ -127,6 +129,7 @@ def main():
     ap.add_argument("--mesh-pick-image", default=None, metavar="OUT.npy")  # --mesh: closest-hit global primitive ids of the primary rays (mgs_trace_mesh_rays_device)
     ap.add_argument("--mesh-shadows", type=int, choices=[0, 1], default=0)  # --mesh --lighting 1: the splats' shadows on the meshes
     ap.add_argument("--trace-meshes", type=int, choices=[0, 1], default=1)  # --pipeline trace --mesh: mgs_frame_set_trace_meshes
+    ap.add_argument("--hybrid-meshes", type=int, choices=[0, 1], default=0)  # --pipeline hybrid --mesh: mgs_frame_set_hybrid_meshes
     ap.add_argument("--mesh-composite-threshold", type=float, default=0.0)
     ap.add_argument("--lighting", type=int, choices=[0, 1, 2], default=0)  # 2: --pipeline trace --mesh, mgs_render_traced_indirect
     ap.add_argument("--max-bounces", type=int, default=3)  # --lighting 2
@@ -181,8 +184,12 @@ def main():
         import json
         with open(a.sensor) as f:
             scene.set_sensor(capi.sensor_model_from_frame(p).update(**json.load(f)))
-    if a.pipeline == "hybrid" and (a.occluder_depth or a.mesh):
-        ap.error("--pipeline hybrid lights and shadows splats alone (meshes in the traced scene are out of scope): no --occluder-depth or --mesh")
+    if a.pipeline == "hybrid" and (a.occluder_depth or (a.mesh and not a.hybrid_meshes)):
+        ap.error("--pipeline hybrid takes no --occluder-depth, and --mesh only with --hybrid-meshes 1 (the traced mesh depth pre-pass)")
+    if a.hybrid_meshes and not (a.pipeline == "hybrid" and a.mesh):
+        ap.error("--hybrid-meshes 1 needs --pipeline hybrid and --mesh")
+    if a.hybrid_meshes and a.shadows == 2:
+        ap.error("--hybrid-meshes 1 has hard shadows only (--shadows 1)")
     if a.pipeline == "hybrid" and not a.lighting:
         ap.error("--pipeline hybrid needs --lighting 1 (without lighting it is --pipeline raster)")
     if a.mesh_shadows and not (a.mesh and a.lighting and a.pipeline == "raster"):
@@ -236,6 +243,11 @@ def main():
         if a.mesh_pick_image:
             ap.error("--mesh-pick-image is for the raster pipelines (a traced frame's hits are mgs_trace_download_mesh_hits)")
         scene.set_trace_meshes(bool(a.trace_meshes), a.mesh_composite_threshold)
+    elif a.mesh and a.pipeline == "hybrid":
+        # the frame traces its own mesh depth pre-pass: no mesh pass, no caller's occluder (a hybrid frame refuses a bound one)
+        if a.mesh_pick_image:
+            ap.error("--mesh-pick-image is for the raster pipelines (a hybrid frame's hits are mgs_trace_download_mesh_hits)")
+        scene.set_hybrid_meshes(True, a.mesh_composite_threshold)
     elif a.mesh:
         mo = scene.render_meshes(p, want_stats=True)
         print(f"{mo.triangles_in} triangles, {mo.triangles_rasterised} rasterised, {mo.fragments} fragments, {mo.elapsed_ms:.3f} ms on the GPU")
@@ -314,6 +326,11 @@ def main():
         print(f"{scene.splat_count} splats, {o.sorted_count} sorted, raster frame {o.stage_ms[5]:.3f} ms and light pass {lo.light_ms:.3f} ms on the GPU, "
               f"{lo.shadow_rays} shadow rays, {lo.shadow_node_visits / sr:.1f} node visits, {lo.shadow_candidate_tests / sr:.1f} candidate tests and "
               f"{lo.shadow_accepted_hits / sr:.2f} hits per shadow ray")
+        if a.hybrid_meshes:
+            pm, sm = scene.trace_mesh_stats()
+            print(f"meshes: {pm.triangles} triangles, {pm.leaves} leaves (build {pm.build_ms:.3f} ms); depth pre-pass: {pm.hits} hits, "
+                  f"{pm.triangle_tests} triangle tests, {pm.trace_ms:.3f} ms; occlusion rays: {sm.hits} occluded, {sm.triangle_tests} triangle tests, "
+                  f"mesh composite {sm.trace_ms:.3f} ms")
     else:
         o = scene.render(p)
         img = scene.download_frame(p).astype(np.float32)

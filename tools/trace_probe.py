@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """trace_probe — MgsTraceOut and the stage times of the traced pipeline for synthetic scenes.
 
-  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--trace-meshes [--indirect]] [--json OUT.json]
+  python tools/trace_probe.py syn:<n> [syn:<n> ...] [--size W H] [--warmup 3] [--repeats 10] [--samples-per-pass 18] [--trace-strategy full|pass|anyhit] [--lit] [--hybrid] [--rays N [N ...]] [--shadow-rays N [N ...]] [--mesh-rays N [N ...] [--mesh file.obj]] [--trace-meshes [--indirect]] [--hybrid-meshes] [--json OUT.json]
 
 Per scene: one traced frame that builds the hierarchy (build_ms), then --warmup frames, then --repeats timed frames of the benchmark
 orbit's pose 5; prints the median, minimum and maximum traced frame time (HIP events around the traversal), node visits and candidate
@@ -28,6 +28,8 @@ points; the occlusion rays of the splat surface run inside light_ms, while shado
 --indirect (with --trace-meshes) adds mgs_render_traced_indirect: on that scene with every bounce material illum 0 (max_bounces 3 and
 16: what the rounds without a live pixel cost next to the lit frame), then with a mirror floor under the grid (max_bounces 1 and 3):
 MgsTraceBounceOut with the median bounce_ms, the live pixels per bounce and their share of the frame.
+--hybrid-meshes (with a syn: scene) adds the same grid and measures hybrid frames (3DGS surface, one point light, hard shadows) with
+mgs_frame_set_hybrid_meshes off and on: the medians of the mesh depth pre-pass, the raster frame, light_ms and the mesh composite.
 Needs an MI355X.
 """
 import argparse
@@ -103,14 +105,52 @@ def probe_mesh_rays(path, n, W, H, warmup, repeats):
     return out
 
 
+def add_mesh_grid(scene, path):
+    """the mesh on a 3 x 3 grid, once per scene (--trace-meshes and --hybrid-meshes share it): the grid's spacing"""
+    if getattr(scene, "_probe_grid", None) is None:
+        mesh = capi.Mesh.load_obj(path)
+        ext = float(np.abs(mesh.view()["positions"]).max()) * 2.5
+        for i in range(9):
+            M = np.eye(4, dtype=np.float32)
+            M[0, 3], M[2, 3] = (i % 3 - 1) * ext, (i // 3 - 1) * ext
+            scene.add_mesh_instance(mesh, M)
+        scene._probe_grid = (mesh, ext)
+    return scene._probe_grid[1]
+
+
+def probe_hybrid_meshes(scene, p, t, path, warmup, repeats):
+    """--hybrid-meshes: hybrid frames (3DGS surface, one point light, hard shadows) of the scene plus the mesh on the 3 x 3 grid, with
+    mgs_frame_set_hybrid_meshes off and on: the medians of the mesh depth pre-pass (primary.trace_ms: both kernels), the raster frame,
+    light_ms (hand-over and light pass) and the mesh composite (shadow.trace_ms)"""
+    add_mesh_grid(scene, path)
+    scene.set_material(0, capi.make_material(ambient=(0.1, 0.1, 0.1), diffuse=(0.8, 0.8, 0.8), emission=(0.0, 0.0, 0.0)))
+    scene.set_lights([capi.make_light(position=(4.0, 6.0, 3.0), range=1000.0, attenuation_mode=0)])
+    lp = capi.default_trace_light_params(shadows_mode=1)
+    out = dict(mesh=os.path.basename(path), instances=9, runs=[])
+    p.lighting_mode, p.collect_timings = 1, 1
+    for on in (0, 1):
+        scene.set_hybrid_meshes(bool(on))
+        pre, ras, lms, cms = [], [], [], []
+        for k in range(warmup + repeats):
+            fo, lo = scene.render_hybrid(p, t, lp, want_stats=True)
+            primary, shadow = scene.trace_mesh_stats() if on else (None, None)
+            if k >= warmup:
+                ras.append(fo.stage_ms[5]), lms.append(lo.light_ms)
+                pre.append(primary.trace_ms if on else 0.0), cms.append(shadow.trace_ms if on else 0.0)
+        d = dict(hybrid_meshes=on, prepass_ms_median=float(np.median(pre)), raster_ms_median=float(np.median(ras)), light_ms_median=float(np.median(lms)),
+                 light_ms_min=float(min(lms)), light_ms_max=float(max(lms)), composite_ms_median=float(np.median(cms)), shadow_rays=int(lo.shadow_rays))
+        if on:
+            d["primary"], d["shadow"] = primary.as_dict(), shadow.as_dict()
+            d["note"] = "prepass: k_trace_mesh_primary and the depth plane; composite: the mesh shading kernel; the splat surface's mesh occlusion rays are inside light_ms"
+        out["runs"].append(d)
+    p.lighting_mode, p.collect_timings = 0, 0
+    scene.set_hybrid_meshes(False)
+    return out
+
+
 def probe_trace_meshes(scene, p, t, path, eye, warmup, repeats, indirect=False):
     """--trace-meshes: unlit and lit frames of the scene plus the mesh on a 3 x 3 grid, the setting off and on"""
-    mesh = capi.Mesh.load_obj(path)
-    ext = float(np.abs(mesh.view()["positions"]).max()) * 2.5
-    for i in range(9):
-        M = np.eye(4, dtype=np.float32)
-        M[0, 3], M[2, 3] = (i % 3 - 1) * ext, (i // 3 - 1) * ext
-        scene.add_mesh_instance(mesh, M)
+    ext = add_mesh_grid(scene, path)
     scene.set_material(0, capi.make_material(ambient=(0.1, 0.1, 0.1), diffuse=(0.8, 0.8, 0.8), emission=(0.0, 0.0, 0.0)))
     scene.set_lights([capi.make_light(position=(4.0, 6.0, 3.0), range=1000.0, attenuation_mode=0)])
     lp = capi.default_trace_light_params(shadows_mode=1)
@@ -270,6 +310,7 @@ def main():
     ap.add_argument("--mesh-rays", type=int, nargs="+", default=[])
     ap.add_argument("--mesh", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "meshes", "fixture.obj"))
     ap.add_argument("--trace-meshes", action="store_true")
+    ap.add_argument("--hybrid-meshes", action="store_true")  # hybrid frames with mgs_frame_set_hybrid_meshes off and on, on the mesh grid
     ap.add_argument("--indirect", action="store_true")  # with --trace-meshes: MgsTraceBounceOut of mgs_render_traced_indirect
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -376,6 +417,9 @@ def main():
         if a.trace_meshes:
             tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
             r["trace_meshes"] = probe_trace_meshes(scene, p, tq, a.mesh, eye, a.warmup, a.repeats, a.indirect)
+        if a.hybrid_meshes:
+            tq = capi.default_trace_params(samples_per_pass=a.samples_per_pass)
+            r["hybrid_meshes"] = probe_hybrid_meshes(scene, p, tq, a.mesh, a.warmup, a.repeats)
         print(json.dumps(r))
         results.append(r)
         scene.close()

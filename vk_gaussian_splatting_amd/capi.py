@@ -473,6 +473,8 @@ def load_library():
         "mgs_trace_mesh_rays_device": (C.c_int, [vp, vp, C.c_uint64, P(MeshRayParams), vp, P(MeshRayOut)]),
         "mgs_trace_mesh_params_default": (None, [P(TraceMeshParams)]),
         "mgs_frame_set_trace_meshes": (C.c_int, [vp, P(TraceMeshParams)]),
+        "mgs_frame_set_hybrid_meshes": (C.c_int, [vp, P(TraceMeshParams)]),
+        "mgs_debug_download_hybrid_depth": (C.c_int, [vp, C.POINTER(C.c_float), C.c_size_t]),
         "mgs_trace_download_mesh_hits": (C.c_int, [vp, vp, C.c_size_t]),
         "mgs_trace_mesh_stats": (C.c_int, [vp, P(MeshRayOut), P(MeshRayOut)]),
         "mgs_bounce_material_default": (None, [P(BounceMaterial)]),
@@ -547,6 +549,7 @@ EXPORTED_SYMBOLS = [
     "mgs_trace_shadow_rays", "mgs_trace_shadow_rays_device", "mgs_shade_points", "mgs_shade_points_device",
     "mgs_mesh_ray_params_default", "mgs_trace_mesh_rays", "mgs_trace_mesh_rays_device",
     "mgs_trace_mesh_params_default", "mgs_frame_set_trace_meshes", "mgs_trace_download_mesh_hits", "mgs_trace_mesh_stats",
+    "mgs_frame_set_hybrid_meshes", "mgs_debug_download_hybrid_depth",
     "mgs_bounce_material_default", "mgs_bounce_material_from_mtl", "mgs_mesh_bounce_materials", "mgs_mesh_instance_set_bounce_materials",
     "mgs_trace_bounce_params_default", "mgs_render_traced_indirect",
     "mgs_frame_params_default", "mgs_render", "mgs_frame_stats", "mgs_timings_query", "mgs_frame_download", "mgs_frame_download_surface", "mgs_frame_copy_strip",
@@ -1140,6 +1143,22 @@ class Scene:
             self._lib.mgs_trace_mesh_params_default(C.byref(params))
             params.enabled, params.min_mesh_composite_transmittance = int(bool(enabled)), float(min_transmittance)
         _check(self._lib.mgs_frame_set_trace_meshes(self._h, C.byref(params)))
+
+    def set_hybrid_meshes(self, enabled=True, min_mesh_composite_transmittance=0.0, params=None):
+        """mgs_frame_set_hybrid_meshes: the scene's triangle meshes take part in this handle's render_hybrid frames through a traced
+        mesh depth pre-pass (a setting of its own: render_hybrid does not read set_trace_meshes while it is on).  params = a
+        TraceMeshParams replaces both; enabled=False turns the setting off."""
+        if params is None:
+            params = TraceMeshParams()
+            self._lib.mgs_trace_mesh_params_default(C.byref(params))
+            params.enabled, params.min_mesh_composite_transmittance = int(bool(enabled)), float(min_mesh_composite_transmittance)
+        _check(self._lib.mgs_frame_set_hybrid_meshes(self._h, C.byref(params)))
+
+    def hybrid_mesh_depth(self, params):
+        """mgs_debug_download_hybrid_depth: the depth plane of the last hybrid frame's mesh pre-pass, float32[H,W]"""
+        out = np.zeros((params.height, params.width), np.float32)
+        _check(self._lib.mgs_debug_download_hybrid_depth(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
 
     def trace_mesh_hits(self, params):
         """the per-pixel closest mesh hits of the last traced frame (setting on), a MESH_HIT_DTYPE array [H,W]"""

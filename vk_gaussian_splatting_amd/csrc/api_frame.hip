@@ -626,6 +626,11 @@ int renderFrame(MgsScene s, const MgsFrameParams* p, MgsFrameOut* out, FrameTail
     fp.occ.color       = s->occ.color;
     fp.occ.sortedByKey = p->sort_mode == MGS_SORT_GPU_RADIX;  // the CPU sorter orders by plane distance, not by the key's depth
   }
+  else if(tail && tail->occDepth)
+  {  // (mgs_render_hybrid refuses a caller's binding: the two never meet)
+    fp.occ.depth       = tail->occDepth;
+    fp.occ.sortedByKey = p->sort_mode == MGS_SORT_GPU_RADIX;
+  }
   if((rc = ensureFrameBuffers(fp))) return rc;
   const bool timed = p->collect_timings != 0;
   // this frame's constants, and its counters and plans zeroed: one 18 KB upload

@@ -644,9 +644,10 @@ static int mgs_render_traced_impl(MgsScene s, const MgsFrameParams* p, const Mgs
   HIPCHK(hipGetLastError());
   if(meshHierarchy.owns_lock())
     meshHierarchy.unlock();
-  tm.have       = meshOn;
-  tm.composited = meshActive;
-  tm.lit        = lit;
+  tm.have        = meshOn;
+  tm.composited  = meshActive;
+  tm.lit         = lit;
+  tm.hybridFrame = false;
   // the frame is the handle's last frame, as after mgs_render (downloads, strips, image compare); no bin lists belong to it
   // (mgs_frame_row_costs: MGS_ERR_STATE)
   recordLastFrameHead(s->last, *p, F, false, true);
@@ -745,6 +746,11 @@ struct HybridTail : FrameTail
   float                      buildMs = 0.0f;
   uint32_t                   rebuilt = 0;
 
+  // a frame with the handle's hybrid-mesh setting on (mgs_frame_set_hybrid_meshes): what the mesh step's set-up left.  meshActive: a
+  // visible instance has a leaf, the raster pass runs against the pre-pass's depth plane and the mesh kernels replace the plain ones
+  bool          meshOn = false, meshActive = false;
+  TraceMeshArgs M{};
+
   TraceProxy proxy() const { return traceProxy(*p, t); }
   int        afterUpload(const FrameArgs& A) override
   {
@@ -754,7 +760,50 @@ struct HybridTail : FrameTail
     const size_t pixels = (size_t)A.f.width * A.f.height;
     if((rc = ts.hybridNormal.ensure(pixels))) return rc;
     if((rc = ensureLightScratch(s, pixels))) return rc;
-    return ensureHierarchy(s, A, proxy(), &buildMs, &rebuilt);
+    if((rc = ensureHierarchy(s, A, proxy(), &buildMs, &rebuilt))) return rc;
+    if(meshOn)
+    {  // the mesh depth pre-pass (rgen.slang:252-281): the closest walk on the pixel's ray, then the plane the raster pass is tested against
+      TraceMeshState& tm = s->traceMesh;
+      hipStream_t     st = s->stream;
+      HIPCHK(hipMemsetAsync(tm.ctr.p, 0, 2 * sizeof(MeshRayCounters), st));
+      HIPCHK(hipEventRecord(tm.ev[kTmevPrimaryBegin], st));
+      launchTraceMeshPrimary(st, M, s->fb.dArgs.p, A.f);
+      if(meshActive)
+        launchHybridMeshDepth(st, s->fb.dArgs.p, tm.hits.p, tm.hybridDepth.p, A.f);
+      HIPCHK(hipEventRecord(tm.ev[kTmevPrimaryEnd], st));
+      HIPCHK(hipGetLastError());
+    }
+    return MGS_OK;
+  }
+  // the hand-over that leaves T, the light pass whose shadow rays ask the meshes first, and the mesh shading over the hand-over's pixels
+  int afterFrameWithMeshes(const FrameConst& F, int fmt)
+  {
+    TracePassState& ts = s->trace;
+    TraceMeshState& tm = s->traceMesh;
+    hipStream_t     st = s->stream;
+    HybridSurfaceMeshArgs H{};
+    H.a.frame       = s->fb.dArgs.p;
+    H.a.image       = s->fb.image.p;
+    H.a.depth       = s->surf.depth.p;
+    H.a.id          = s->surf.id.p;
+    H.a.normal      = s->surf.normal.p;
+    H.a.outIsoDist  = ts.isoDist.p;
+    H.a.outNormal   = ts.hybridNormal.p;
+    H.a.outRadiance = ts.radiance.p;
+    H.meshT         = tm.meshT.p;
+    H.outT          = tm.walkT.p;
+    H.minT          = tm.hybridMinT;
+    launchHybridSurfaceWithMeshes(st, H, F, fmt);
+    TraceLightMeshArgs G{};
+    G.l      = traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p);
+    G.m      = M;
+    G.litOut = ts.radiance.p;
+    launchTraceLightWithMeshes(st, G, F);
+    HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
+    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeBegin], st));
+    launchHybridMeshComposite(st, G, F);
+    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeEnd], st));
+    return MGS_OK;
   }
   int afterFrame(const FrameArgs& A, int fmt) override
   {
@@ -763,6 +812,15 @@ struct HybridTail : FrameTail
     hipStream_t       st = s->stream;
     HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
     HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
+    if(meshActive)
+    {
+      if(int rc = afterFrameWithMeshes(F, fmt))
+        return rc;
+      if(F.temporalSampling)
+        launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, fmt);
+      HIPCHK(hipGetLastError());
+      return MGS_OK;
+    }
     HybridSurfaceArgs H{};
     H.frame       = s->fb.dArgs.p;
     H.image       = s->fb.image.p;
@@ -800,23 +858,59 @@ static int mgs_render_hybrid_impl(MgsScene s, const MgsFrameParams* p, const Mgs
                                           "scope); unbind it with mgs_frame_set_occluder(handle, NULL, NULL, 0, 0)");
   if(int rc = refuseBoundSensor(s, "mgs_render_hybrid", "the shadow rays start from a surface unprojected through the perfect cameras"))
     return rc;
-  if(s->traceMesh.enabled)
-    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: mesh hits are mgs_render_traced's and mgs_render_traced_lit's (the hybrid frame's mesh depth "
-                                          "pre-pass is later work); turn the setting off with mgs_frame_set_trace_meshes(handle, NULL)");
+  TraceMeshState& tm     = s->traceMesh;
+  const bool      meshOn = tm.hybridEnabled;
+  if(!meshOn && tm.enabled)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: mesh hits are mgs_render_traced's and mgs_render_traced_lit's; a hybrid frame's meshes are "
+                                          "mgs_frame_set_hybrid_meshes'.  Turn the setting off with mgs_frame_set_trace_meshes(handle, NULL)");
+  if(meshOn && tail.lt.shadows_mode == MGS_SHADOWS_SOFT)
+    return failTrace(MGS_ERR_UNSUPPORTED, "mgs_render_hybrid: soft shadows with mgs_frame_set_hybrid_meshes on are not built (the mesh composite continues the "
+                                          "light pass's random state, whose conditions differ in a hybrid frame); MGS_SHADOWS_HARD or off");
   tail.s = s;
   tail.p = p;
+  // a frame that fails below must not leave the previous frame's flags over buffers its pre-pass may already have rewritten
+  tm.hybridFrame = false;
+  if(meshOn)
+    tm.have = false;
+  std::unique_lock<std::mutex> meshHierarchy;  // held from the mesh step's signature check to the frame's last launch
+  if(meshOn && s->d->committed)
+  {  // (an uncommitted scene: renderFrame says so)
+    HIPCHK(hipSetDevice(s->device));
+    const size_t pixels = (size_t)p->width * (size_t)p->height;
+    if(int rc = traceMeshSetUp(s, pixels, true, meshHierarchy, tail.M, tail.meshActive))
+      return rc;
+    tail.M.minT = tm.hybridMinT;
+    tail.meshOn = true;
+    if(tail.meshActive)
+    {
+      if(pixels > tm.hybridDepth.n && tm.hybridDepth.p && s->surf.lastOccDepth == tm.hybridDepth.p)
+        s->surf.lastOccGone = true;  // the plane the last frame was tested against is about to be freed (mgs_frame_download_surface, which = 3)
+      if(int rc = tm.hybridDepth.ensure(pixels))
+        return rc;
+      tail.occDepth = tm.hybridDepth.p;
+    }
+  }
   // step 1: exactly mgs_render's unlit frame with the surface outputs on (the deferred pass is off in hybrid mode, NEED_SURFACE_INFO on)
   MgsFrameParams q  = *p;
   q.lighting_mode   = MGS_LIGHTING_DISABLED;
   q.surface_outputs = 1;
   if(int rc = renderFrame(s, &q, out, &tail))
     return rc;
+  if(meshHierarchy.owns_lock())
+    meshHierarchy.unlock();
   s->last.params.lighting_mode = p->lighting_mode;  // (surface_outputs stays 1: the raster pass's outputs are there to download)
   TracePassState& ts = s->trace;
   ts.w       = p->width;
   ts.h       = p->height;
   ts.have    = false;  // no primary walk: there are no hit counts
   ts.haveLit = true;
+  tm.hybridFrame = tail.meshOn;  // the pre-pass's hit records and the mesh rays' sums are this frame's
+  if(tail.meshOn)
+  {
+    tm.have       = true;
+    tm.composited = tail.meshActive;
+    tm.lit        = true;
+  }
   if(lout)
     return readLightOut(s, lout);
   return MGS_OK;
@@ -880,14 +974,53 @@ int mgs_frame_set_trace_meshes(MgsScene s, const MgsTraceMeshParams* p)
   });
 }
 
+int mgs_frame_set_hybrid_meshes(MgsScene s, const MgsTraceMeshParams* p)
+{
+  return guarded("mgs_frame_set_hybrid_meshes", [&]() -> int {
+    if(p)
+    {  // (before the handle is looked at: mgs_frame_set_trace_meshes' ranges)
+      if(p->enabled != 0 && p->enabled != 1)
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: enabled must be 0 or 1");
+      if(!(p->min_mesh_composite_transmittance >= 0.0f && p->min_mesh_composite_transmittance <= 1.0f))
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: min_mesh_composite_transmittance must be in [0, 1]");
+      if(p->reserved[0] != 0 || p->reserved[1] != 0)
+        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: the reserved words of MgsTraceMeshParams must be 0");
+    }
+    if(!s)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: null scene");
+    s->traceMesh.hybridEnabled = p != nullptr && p->enabled == 1;
+    s->traceMesh.hybridMinT    = p ? p->min_mesh_composite_transmittance : 0.0f;
+    return (int)MGS_OK;
+  });
+}
+
+int mgs_debug_download_hybrid_depth(MgsScene s, float* dst, size_t count)
+{
+  return guarded("mgs_debug_download_hybrid_depth", [&]() -> int {
+    if(!s || !dst)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_debug_download_hybrid_depth: null argument");
+    const TraceMeshState& tm = s->traceMesh;
+    if(!tm.hybridFrame || !tm.composited)
+      return failTrace(MGS_ERR_STATE, "mgs_debug_download_hybrid_depth: the handle's last frame was not a hybrid frame that ran its mesh depth pre-pass "
+                                      "(mgs_frame_set_hybrid_meshes on, a visible mesh instance with a leaf)");
+    const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
+    if(count < n || tm.hybridDepth.n < n)
+      return failTrace(MGS_ERR_INVALID_ARG, "mgs_debug_download_hybrid_depth: destination too small");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpyAsync(dst, tm.hybridDepth.p, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return (int)MGS_OK;
+  });
+}
+
 int mgs_trace_download_mesh_hits(MgsScene s, MgsMeshHit* dst, size_t count)
 {
   return guarded("mgs_trace_download_mesh_hits", [&]() -> int {
     if(!s || !dst)
       return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_mesh_hits: null argument");
     const TraceMeshState& tm = s->traceMesh;
-    if(!tm.have || !s->trace.have)
-      return failTrace(MGS_ERR_STATE, "mgs_trace_download_mesh_hits: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on");
+    if(!tm.have || !(s->trace.have || tm.hybridFrame))
+      return failTrace(MGS_ERR_STATE, "mgs_trace_download_mesh_hits: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on (nor its last hybrid frame with mgs_frame_set_hybrid_meshes)");
     const size_t n = (size_t)s->trace.w * (size_t)s->trace.h;
     if(count < n || tm.hits.n < 4 * n)
       return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_download_mesh_hits: destination too small");
@@ -904,8 +1037,8 @@ int mgs_trace_mesh_stats(MgsScene s, MgsMeshRayOut* primary, MgsMeshRayOut* shad
     if(!s)
       return failTrace(MGS_ERR_INVALID_ARG, "mgs_trace_mesh_stats: null scene");
     const TraceMeshState& tm = s->traceMesh;
-    if(!tm.have || !s->trace.have)
-      return failTrace(MGS_ERR_STATE, "mgs_trace_mesh_stats: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on");
+    if(!tm.have || !(s->trace.have || tm.hybridFrame))
+      return failTrace(MGS_ERR_STATE, "mgs_trace_mesh_stats: the handle's last traced frame did not run with mgs_frame_set_trace_meshes on (nor its last hybrid frame with mgs_frame_set_hybrid_meshes)");
     HIPCHK(hipSetDevice(s->device));
     MeshRayCounters c[2] = {};
     HIPCHK(hipMemcpyAsync(c, tm.ctr.p, sizeof(c), hipMemcpyDeviceToHost, s->stream));

@@ -484,6 +484,15 @@ struct HybridSurfaceArgs
   float4*          outNormal;    // the normalised normal (the handle's own scratch)
   float4*          outRadiance;  // the stored pixel in fp32: rgb and alpha
 };
+// the hand-over of a hybrid frame with meshes (mgs_frame_set_hybrid_meshes): besides the above, the pixel's transmittance for the mesh
+// composite, and a surface that is not in front of the pixel's mesh hit is handed on settled
+struct HybridSurfaceMeshArgs
+{
+  HybridSurfaceArgs a;
+  const float*      meshT;  // [height][width] t of the pixel's closest mesh hit (the depth pre-pass), +inf = none
+  float*            outT;   // [height][width] 1 - stored alpha; 1 for a discarded pixel; -1 when T > minT fails in double
+  float             minT;   // min_mesh_composite_transmittance
+};
 
 // ---- mesh ray queries (k_mesh_bvh.hip, k_mesh_rays.hip, api_mesh_rays.hip) ----
 // The triangle hierarchy has the splat hierarchy's layout (above): level 0 holds one leaf per valid triangle of every mesh instance,

@@ -10,6 +10,9 @@
 // first is used, and writes the light pass's inputs (4 + 16 + 16 B; the picked ids are read as they are).  It never writes the frame or the raster side outputs:
 // a pixel the light pass must leave alone (valid depth, no picked id: rgen.slang:1047-1049) is handed on with a negative ray
 // parameter.  No loop, no LDS, nothing waits on another lane.
+// With the scene's meshes (mgs_frame_set_hybrid_meshes; rgen.slang:252-281, :1037-1062): k_hybrid_mesh_depth turns the hit records of
+// the mesh depth pre-pass into the plane the raster pass is tested against, and the hand-over's MESH instantiations also leave the
+// pixel's transmittance for the mesh composite (k_trace_mesh.hip).
 #include "kernels_common.h"
 #include "launchers.h"
 #include "shade_direct.h"
@@ -20,10 +23,19 @@
 
 namespace mgs {
 
-// FMT: the target format (kTargetF32, kTargetF16, kTargetU8)
-template <int FMT>
-__global__ __launch_bounds__(256) void k_hybrid_surface(const HybridSurfaceArgs a)
+// FMT: the target format (kTargetF32, kTargetF16, kTargetU8); MESH: a frame with the scene's meshes (mgs_frame_set_hybrid_meshes),
+// whose raster pass ran against the mesh depth pre-pass: the pixel's transmittance goes to the mesh composite (:357-358, T = 1 for a
+// discarded pixel, :468-478), and a surface with a pick that is not in front of the pixel's mesh hit fails splatIsClosest (:1047):
+// it is handed on settled, with its raster colour and its own T
+template <int FMT, bool MESH>
+__global__ __launch_bounds__(256) void k_hybrid_surface(const std::conditional_t<MESH, HybridSurfaceMeshArgs, HybridSurfaceArgs> args)
 {
+  const HybridSurfaceArgs& a = [&]() -> const HybridSurfaceArgs& {
+    if constexpr(MESH)
+      return args.a;
+    else
+      return args;
+  }();
   const FrameConst& F = a.frame->f;
   int px, py;
   tilePixel(F, (int)threadIdx.x, px, py);
@@ -81,9 +93,53 @@ __global__ __launch_bounds__(256) void k_hybrid_surface(const HybridSurfaceArgs 
     else if(t > 0.0f)
       outT = t;  // (a ray parameter that is not positive is no surface for the light pass: k_trace_light's own rule)
   }
-  a.outIsoDist[pix]  = outT;
-  a.outNormal[pix]   = make_float4(normal.x, normal.y, normal.z, nrm.w);
-  a.outRadiance[pix] = stored;
+  if constexpr(MESH)
+  {
+    float4 radiance = stored;
+    float  T        = 1.0f - stored.w;
+    if(outT > 0.0f && !(outT < args.meshT[pix]))
+      outT = -1.0f;  // behind (or at) the mesh: never the light pass's "store 0" branch
+    if(rayOk && outT == 0.0f)
+    {  // discardSplatContribution: the mesh or the background shows through
+      radiance = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      T        = 1.0f;
+    }
+    args.outT[pix]     = (double)T > (double)args.minT ? T : -1.0f;
+    a.outIsoDist[pix]  = outT;
+    a.outNormal[pix]   = make_float4(normal.x, normal.y, normal.z, nrm.w);
+    a.outRadiance[pix] = radiance;
+  }
+  else
+  {
+    a.outIsoDist[pix]  = outT;
+    a.outNormal[pix]   = make_float4(normal.x, normal.y, normal.z, nrm.w);
+    a.outRadiance[pix] = stored;
+  }
+}
+
+// The mesh depth pre-pass's second half (rgen.slang:259-270, meshDepthOnly): the hit records k_trace_mesh_primary left become the
+// depth plane the raster pass is tested against.  clip = (meshHitWorldPos * view) * proj, the plane gets clip.z / clip.w; 1.0 on a
+// miss (a fisheye pixel outside the circle is one).  A lane per pixel in k_trace's tiling, no loop, no LDS.
+__global__ __launch_bounds__(256) void k_hybrid_mesh_depth(const FrameArgs* __restrict__ Ap, const float4* __restrict__ hits, float* __restrict__ plane)
+{
+  const FrameConst& F = Ap->f;
+  int px, py;
+  tilePixel(F, (int)threadIdx.x, px, py);
+  if(px >= F.width || py >= F.height)
+    return;
+  const size_t pix = (size_t)py * F.width + px;
+  const float4 h0 = hits[4 * pix], h1 = hits[4 * pix + 1];
+  float        z  = 1.0f;
+  if(h0.x < __builtin_huge_valf())
+  {
+    const float  hx = h1.x, hy = h1.y, hz = h1.z;
+    const float *V = F.view, *P = F.proj;
+    const float  v0 = V[0] * hx + V[4] * hy + V[8] * hz + V[12], v1 = V[1] * hx + V[5] * hy + V[9] * hz + V[13],
+                v2 = V[2] * hx + V[6] * hy + V[10] * hz + V[14], v3 = V[3] * hx + V[7] * hy + V[11] * hz + V[15];
+    const float cz = P[2] * v0 + P[6] * v1 + P[10] * v2 + P[14] * v3, cw = P[3] * v0 + P[7] * v1 + P[11] * v2 + P[15] * v3;
+    z = cz / cw;
+  }
+  plane[pix] = z;
 }
 
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt)
@@ -92,11 +148,32 @@ void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const F
   if(tiles <= 0)
     return;
   if(fmt == kTargetF16)
-    hipLaunchKernelGGL(k_hybrid_surface<kTargetF16>, dim3(tiles), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetF16, false>), dim3(tiles), dim3(256), 0, stream, a);
   else if(fmt == kTargetU8)
-    hipLaunchKernelGGL(k_hybrid_surface<kTargetU8>, dim3(tiles), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetU8, false>), dim3(tiles), dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL(k_hybrid_surface<kTargetF32>, dim3(tiles), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetF32, false>), dim3(tiles), dim3(256), 0, stream, a);
+}
+
+void launchHybridSurfaceWithMeshes(hipStream_t stream, const HybridSurfaceMeshArgs& a, const FrameConst& F, int fmt)
+{
+  const int tiles = stripTiles(F);
+  if(tiles <= 0)
+    return;
+  if(fmt == kTargetF16)
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetF16, true>), dim3(tiles), dim3(256), 0, stream, a);
+  else if(fmt == kTargetU8)
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetU8, true>), dim3(tiles), dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL((k_hybrid_surface<kTargetF32, true>), dim3(tiles), dim3(256), 0, stream, a);
+}
+
+void launchHybridMeshDepth(hipStream_t stream, const FrameArgs* frame, const float4* hits, float* plane, const FrameConst& F)
+{
+  const int tiles = stripTiles(F);
+  if(tiles <= 0)
+    return;
+  hipLaunchKernelGGL(k_hybrid_mesh_depth, dim3(tiles), dim3(256), 0, stream, frame, hits, plane);
 }
 
 }  // namespace mgs

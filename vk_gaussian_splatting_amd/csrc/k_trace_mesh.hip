@@ -79,8 +79,11 @@ __global__ __launch_bounds__(256) void k_trace_mesh_primary(TraceMeshArgs m, con
 // MGS_SHADOWS_SOFT, the lights with a radius are sampled on their disk (lightToSurfaceSoft).  The pixel's random state is ONE for
 // both light loops of a pixel (rgen.slang:1054, :1061, the same inout seed): the mesh loop continues where the splat surface's loop
 // in k_trace_light ended.  That loop draws two numbers per point or spot light with a radius, culled or not, so its end state is
-// recomputed here from the light table and the light pass's own conditions for running its loop; no per-pixel word is carried
-template <int KB, bool LIT, bool SOFT>
+// recomputed here from the light table and the light pass's own conditions for running its loop; no per-pixel word is carried.
+// HYBRID (LIT, not SOFT): the composite of a hybrid frame with meshes (mgs_frame_set_hybrid_meshes).  The base colour and T are the
+// hand-over's (k_hybrid.hip), which has already applied discardSplatContribution and splatIsClosest to the raster surface: the traced
+// frame's rule below would be wrong for its settled pixels, whose ray parameter is negative and whose colour and T are their own
+template <int KB, bool LIT, bool SOFT, bool HYBRID = false>
 __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs args)
 {
   const TraceLightArgs& L = args.l;
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
 
   V3   color = {base.x, base.y, base.z};
   bool splatShaded = false;  // SOFT: the light pass reached its loop over the lights on this pixel
-  if constexpr(LIT)
+  if constexpr(LIT && !HYBRID)
   {  // surfaceFinalFiltering and splatIsClosest as the light pass decided them: a discarded splat surface is radiance 0, T = 1
     const float isoDist = L.isoDist[pix];
     if(pickId == kTraceInvalid || !(isoDist > 0.0f) || !(isoDist < tMesh))
@@ -270,6 +273,15 @@ void launchTraceMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, c
     else
       hipLaunchKernelGGL((k_trace_mesh_composite<decltype(kb)::value, true, false>), dim3(tiles), dim3(256), 0, stream, L);
   });
+}
+
+void launchHybridMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, const FrameConst& F)
+{
+  const int tiles = stripTiles(F);
+  if(tiles <= 0)
+    return;
+  withKBuffer("launchHybridMeshComposite", L.l.t.samplesPerPass,
+              [&](auto kb) { hipLaunchKernelGGL((k_trace_mesh_composite<decltype(kb)::value, true, false, true>), dim3(tiles), dim3(256), 0, stream, L); });
 }
 
 }  // namespace mgs

@@ -155,6 +155,11 @@ void launchMeshBvhRecords(hipStream_t stream, const MeshBvhRecordArgs& a);
 void launchMeshRays(hipStream_t stream, const MeshRayArgs& a, int mode);
 // the hand-over of a hybrid frame (k_hybrid.hip): the raster surface becomes the light pass's per-pixel inputs, in k_trace's tiling
 void launchHybridSurface(hipStream_t stream, const HybridSurfaceArgs& a, const FrameConst& F, int fmt);
+// a hybrid frame with meshes (mgs_frame_set_hybrid_meshes): the depth plane of the mesh pre-pass from its hit records, the hand-over
+// that also leaves the pixel's transmittance, and the mesh shading behind the light pass (k_trace_mesh.hip) over that hand-over
+void launchHybridMeshDepth(hipStream_t stream, const FrameArgs* frame, const float4* hits, float* plane, const FrameConst& F);
+void launchHybridSurfaceWithMeshes(hipStream_t stream, const HybridSurfaceMeshArgs& a, const FrameConst& F, int fmt);
+void launchHybridMeshComposite(hipStream_t stream, const TraceLightMeshArgs& L, const FrameConst& F);
 void launchDepthConsolidate(hipStream_t stream, const float* picked, const float* occDepth, float* out, uint32_t n);
 
 }  // namespace mgs

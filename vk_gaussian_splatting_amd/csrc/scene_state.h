@@ -590,8 +590,15 @@ struct TraceMeshState
   float                   buildMs = 0.0f;
   uint64_t                triangles = 0, leaves = 0, nodes = 0;
   hipEvent_t              ev[kTmevCount] = {};
+  // meshes in the hybrid frames (mgs_frame_set_hybrid_meshes): a setting of its own, the depth plane of the mesh pre-pass (the raster
+  // pass's occluder depth: never a caller's pointer), and whether the handle's last hybrid frame ran with the setting on (it then
+  // left hits, ctr and the events as a lit traced frame with meshes does, though it has no primary walk)
+  bool                    hybridEnabled = false;
+  float                   hybridMinT    = 0.0f;
+  DevBuf<float>           hybridDepth;
+  bool                    hybridFrame = false;
   template <class F>
-  void eachBuffer(F&& f) { f(hits); f(meshT); f(walkT); f(ctr); f(bounceLive); f(bounceRay); f(bounceT); f(bounceCtr); }
+  void eachBuffer(F&& f) { f(hits); f(meshT); f(walkT); f(ctr); f(bounceLive); f(bounceRay); f(bounceT); f(bounceCtr); f(hybridDepth); }
   void release()
   {
     eachBuffer([](auto& b) { b.release(); });
@@ -775,6 +782,7 @@ int  uploadFrameState(MgsScene s, const FrameArgs& A, hipStream_t st);        //
 // and the rays' inverses, temporal accumulation is left to afterFrame, and the captured graph ends at the compositor.
 struct FrameTail
 {
+  const float* occDepth = nullptr;  // the frame's own occluder depth (a hybrid frame's mesh depth plane), without colour; set before renderFrame
   virtual int afterUpload(const FrameArgs& A) = 0;          // the constants are on the device, nothing of the frame is launched yet
   virtual int afterFrame(const FrameArgs& A, int fmt) = 0;  // behind the frame's launches on the handle's stream
   virtual ~FrameTail() = default;
