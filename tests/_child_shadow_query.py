@@ -98,10 +98,11 @@ elif mode == "points":
     for name, cfg in sq.POINT_CONFIGS.items():
         scene = build(sq.MAIN, lights=cfg["lights"])
         lp = capi.default_trace_light_params(shadows_mode=cfg["shadows"])
+        tp = capi.default_trace_params(samples_per_pass=cfg["spp"]) if "spp" in cfg else None
         for reorder in (0, 1):
             r = torch.full((n * 4 + 8,), -7.25, dtype=torch.float32, device="cuda")
             torch.cuda.synchronize()
-            lo, bad = scene.shade_points_device(dev.data_ptr(), n, mats, params(), r.data_ptr(), None, lp, reorder=bool(reorder), want_stats=True)
+            lo, bad = scene.shade_points_device(dev.data_ptr(), n, mats, params(), r.data_ptr(), tp, lp, reorder=bool(reorder), want_stats=True)
             got = r.cpu().numpy()
             assert (got[n * 4:] == np.float32(-7.25)).all(), "the kernel wrote behind the results"
             res[f"{name}_{reorder}"] = got[:n * 4].view(capi.SHADE_RESULT_DTYPE)
@@ -113,11 +114,11 @@ elif mode == "points":
         good = pts.copy()
         good["material"][sq.INVALID_AT[4]] = 0  # the host variant refuses an index out of range as a whole
         try:
-            scene.shade_points(pts, mats, params(), None, lp)
+            scene.shade_points(pts, mats, params(), tp, lp)
             res[f"{name}_host_refused"] = False
         except capi.MgsError as e:
             res[f"{name}_host_refused"] = e.code == -1  # MGS_ERR_INVALID_ARG
-        host, lo, bad = scene.shade_points(good, mats, params(), None, lp, want_stats=True)
+        host, lo, bad = scene.shade_points(good, mats, params(), tp, lp, want_stats=True)
         res[f"{name}_host"], res[f"{name}_host_invalid"] = host, bad
         scene.close()
 else:

@@ -95,17 +95,18 @@ if mode == "cases":
         record(scene, case, name)
         scene.close()
 elif mode == "storage":
-    case = C["b1"]
-    for tag, fmt in (("f16", capi.FORMAT_FLOAT16), ("u8", capi.FORMAT_UINT8)):
-        scene, _ = build(case, storage=fmt)
-        for k, (arrays, _) in enumerate(case["sets"]):
-            n, cpc = arrays["positions"].shape[0], arrays["f_rest"].shape[1] // 3
-            res[f"b1_{tag}_rgba_{k}"] = scene.download_set(k, 2, 4 * n).reshape(n, 4)
-            sh = np.zeros((n, 15, 3), np.float32)  # the set's own stride is 3 * cpc floats per splat, [coef][rgb]
-            sh[:, :cpc] = scene.download_set(k, 3, 45 * n)[:3 * cpc * n].reshape(n, cpc, 3)
-            res[f"b1_{tag}_sh_{k}"] = sh
-        record(scene, case, f"b1_{tag}")
-        scene.close()
+    for cname in tbc.STORAGE_CASES:
+        case = C[cname]
+        for tag, fmt in (("f16", capi.FORMAT_FLOAT16), ("u8", capi.FORMAT_UINT8)):
+            scene, _ = build(case, storage=fmt)
+            for k, (arrays, _) in enumerate(case["sets"]):
+                n, cpc = arrays["positions"].shape[0], arrays["f_rest"].shape[1] // 3
+                res[f"{cname}_{tag}_rgba_{k}"] = scene.download_set(k, 2, 4 * n).reshape(n, 4)
+                sh = np.zeros((n, 15, 3), np.float32)  # the set's own stride is 3 * cpc floats per splat, [coef][rgb]
+                sh[:, :cpc] = scene.download_set(k, 3, 45 * n)[:3 * cpc * n].reshape(n, cpc, 3)
+                res[f"{cname}_{tag}_sh_{k}"] = sh
+            record(scene, case, f"{cname}_{tag}")
+            scene.close()
 elif mode == "bare":
     import torch
     case = C["bare"]

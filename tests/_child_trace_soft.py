@@ -84,9 +84,10 @@ for name, case in sc.cases().items():
     _, ids = scene.download_surface(p)
     res.update({f"{name}_image": img, f"{name}_hits": hits, f"{name}_shadow_hits": sh, f"{name}_id": ids, f"{name}_shadow_rays": lo.shadow_rays,
                 f"{name}_shadow_accepted": lo.shadow_accepted_hits, f"{name}_light_ms": lo.light_ms})
-    if name == "s06_mesh":  # a second sample, twice; radii 0 against the hard frame; the working set with the setting on
+    if "meshes" in case:  # a second sample
         s1 = lit(scene, case, params(case, frame_sample_id=1))
-        res["s06_sample1_image"], res["s06_sample1_shadow_hits"] = s1[0], s1[2]
+        res[f"{name}_sample1_image"], res[f"{name}_sample1_shadow_hits"] = s1[0], s1[2]
+    if name == "s06_mesh":  # the same frame twice; every strip row; radii 0 against the hard frame
         res["s06_same_twice"] = lit(scene, case, p)[0].tobytes() == img.tobytes()
         full_sh = sh
         for r in range(3):

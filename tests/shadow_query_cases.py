@@ -40,7 +40,9 @@ LIGHTS = [nl.default_light(position=tuple(POINT), range=2.3, intensity=4.0),  # 
           nl.default_light(type=nl.LIGHT_DIRECTIONAL, direction=tuple(SUN), intensity=0.5)]
 MATERIALS = [nl.default_material(), dict(lc.SHADED, specular=(0.5, 0.5, 0.5), shininess=64.0),
              dict(lc.SHADED, diffuse=(0.0, 0.0, 0.0), ambient=(0.6, 0.6, 0.6))]
-POINT_CONFIGS = {"three_lights": dict(lights=LIGHTS, shadows=1), "headlight": dict(lights=[], shadows=1), "no_shadows": dict(lights=LIGHTS, shadows=0)}
+POINT_CONFIGS = {"three_lights": dict(lights=LIGHTS, shadows=1), "headlight": dict(lights=[], shadows=1), "no_shadows": dict(lights=LIGHTS, shadows=0),
+                 # the K-buffer's ends (samples_per_pass; the others take the default 18): k_shade_points has an instantiation per size
+                 "three_lights_spp_4": dict(lights=LIGHTS, shadows=1, spp=4), "three_lights_spp_32": dict(lights=LIGHTS, shadows=1, spp=32)}
 CAMERA = (0.0, 1.3, 2.6)
 
 
@@ -136,4 +138,5 @@ def point_batch():
 @functools.lru_cache(maxsize=None)
 def restate_points(name):
     cfg = POINT_CONFIGS[name]
-    return nsq.shade_points(prepared(MAIN), point_batch(), MATERIALS, cfg["lights"], CAMERA, shadows=cfg["shadows"], offset=0.2, threshold=0.8, strength=0.0)
+    return nsq.shade_points(prepared(MAIN), point_batch(), MATERIALS, cfg["lights"], CAMERA, shadows=cfg["shadows"], offset=0.2, threshold=0.8, strength=0.0,
+                            K=cfg.get("spp", 18))

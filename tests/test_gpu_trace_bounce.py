@@ -53,6 +53,15 @@ def test_quantised_splat_storage_stays_within_the_bars(child, fmt):
     against_restatement(r, f"b1_{fmt}", tbc.restate_with(case, inst), case)
 
 
+@pytest.mark.parametrize("fmt", ["f16", "u8"])
+@pytest.mark.parametrize("name", [n for n in tbc.STORAGE_CASES if n != "b1"])
+def test_quantised_splat_storage_at_the_k_buffer_ends(child, name, fmt):
+    """the same with samples_per_pass 4 and 32 (k_trace_bounce<1 | 2, 4> and <1 | 2, 32>)"""
+    r, case = child("storage"), tbc.cases()[name]
+    inst = [(ntb.ntl.prepare_set(a, rgba=r[f"{name}_{fmt}_rgba_{k}"], sh=r[f"{name}_{fmt}_sh_{k}"]), M) for k, (a, M) in enumerate(case["sets"])]
+    against_restatement(r, f"{name}_{fmt}", tbc.restate_with(case, inst), case)
+
+
 def test_bare_mirror_adds_specular_times_the_ray_query_of_the_reflected_ray(child):
     """Ties the bounce walk to mgs_trace_rays.  On a mirror pixel with no particle hit in front (T = 1), whose bounce ray meets no
     mesh and whose splat material is emission (1, 1, 1) alone, one bounce adds specular x the radiance the ray query integrates on

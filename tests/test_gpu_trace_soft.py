@@ -49,7 +49,7 @@ def test_case_against_restatement(child, name):
 @pytest.mark.parametrize("name", sc.meshed())
 def test_mesh_case_against_restatement(child, name):
     """a lit frame with trace meshes: both loops over the lights of a pixel draw from one state.  test_gpu_trace_mesh.py's bars"""
-    for sid, img_key, sh_key in ((0, f"{name}_image", f"{name}_shadow_hits"), (1, "s06_sample1_image", "s06_sample1_shadow_hits")):
+    for sid, img_key, sh_key in ((0, f"{name}_image", f"{name}_shadow_hits"), (1, f"{name}_sample1_image", f"{name}_sample1_shadow_hits")):
         r = sc.restate_mesh(name, sid)
         ok = ~r["fragile"]
         img = child[img_key].astype(np.float64)

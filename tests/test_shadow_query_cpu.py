@@ -168,6 +168,9 @@ def test_fragile_share_of_the_point_batches(name):
         emissive = ref["valid"] & (pts["material"] == 0)
         assert not ref["rays"][emissive].any() and ref["rays"][ref["valid"] & (pts["material"] != 0)].min() >= 2  # the point light is out of range for some
         assert (ref["rays"] == 2).sum() > 50 and (ref["rays"] == 3).sum() > 50 and ref["shadow_hits"].sum() > 1000
+    if name == "three_lights_spp_4":  # the K-buffer's size decides some of the batch: the case pins k_shade_points<4> apart from <18>
+        wide = sq.restate_points("three_lights")
+        assert not np.array_equal(ref["shadow_hits"], wide["shadow_hits"]) and not np.array_equal(ref["color"], wide["color"])
 
 
 @pytest.mark.parametrize("name", sorted(sq.RAY_CONFIGS))

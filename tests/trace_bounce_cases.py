@@ -94,6 +94,10 @@ def cases():
     return out
 
 
+# the cases the child also renders with fp16 / uint8 colour and SH storage: k_trace_bounce<1, KB> and <2, KB> at KB 18, 4 and 32
+STORAGE_CASES = ("b1", "b5_4", "b5_32")
+
+
 def restate_with(c, inst, **over):
     L = c.get("light", {})
     kw = dict(tlc._trace_kw(c), **over)

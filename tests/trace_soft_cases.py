@@ -55,6 +55,9 @@ def cases():
     glow = lc.blob(centre=(0.55, 0.1, 0.2), opacity=0.0, seed=6, n=30)
     c["s06_mesh"] = _case([(veil, tc.I4), (glow, tc.I4)], [point, dict(spot, range=10.0)], [0.6, 0.4], materials=[lc.SHADED, nl.default_material()])
     c["s06_mesh"].update(meshes=[tmc.placed(tmc.FLOOR, materials=[tmc.MAT_SHADED, tmc.MAT_SPEC]), tmc.fixture(tc.trs((0.3, 0.3, 0.3), (0, 1, 0), 25.0, (-0.8, -0.32, 0.3)))], mesh_min_T=0.0)
+    # (the K-buffer's ends of the two lit mesh kernels' soft instantiations: the same frame at samples_per_pass 4 and 32)
+    for k in (4, 32):
+        c[f"s06_mesh_spp_{k}"] = dict(c["s06_mesh"], trace=dict(c["s06_mesh"]["trace"], samples_per_pass=k))
     # 7. hybrid frames, both raster pipelines
     c["s07_hybrid_3dgs"] = _case([(scene, tc.I4)], [point], [0.6], hybrid=hc.GS)
     c["s07_hybrid_3dgut"] = _case([(scene, tc.I4)], [point], [0.6], hybrid=hc.GUT)

@@ -775,12 +775,16 @@ struct HybridTail : FrameTail
     }
     return MGS_OK;
   }
-  // the hand-over that leaves T, the light pass whose shadow rays ask the meshes first, and the mesh shading over the hand-over's pixels
-  int afterFrameWithMeshes(const FrameConst& F, int fmt)
+  // the hand-over, the light pass and, in a frame whose meshes are active, the mesh shading over the hand-over's pixels: there the
+  // hand-over also leaves T and the light pass's shadow rays ask the meshes first
+  int afterFrame(const FrameArgs& A, int fmt) override
   {
-    TracePassState& ts = s->trace;
-    TraceMeshState& tm = s->traceMesh;
-    hipStream_t     st = s->stream;
+    TracePassState&   ts = s->trace;
+    TraceMeshState&   tm = s->traceMesh;
+    const FrameConst& F  = A.f;
+    hipStream_t       st = s->stream;
+    HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
+    HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
     HybridSurfaceMeshArgs H{};
     H.a.frame       = s->fb.dArgs.p;
     H.a.image       = s->fb.image.p;
@@ -790,49 +794,28 @@ struct HybridTail : FrameTail
     H.a.outIsoDist  = ts.isoDist.p;
     H.a.outNormal   = ts.hybridNormal.p;
     H.a.outRadiance = ts.radiance.p;
-    H.meshT         = tm.meshT.p;
-    H.outT          = tm.walkT.p;
-    H.minT          = tm.hybridMinT;
-    launchHybridSurfaceWithMeshes(st, H, F, fmt);
     TraceLightMeshArgs G{};
-    G.l      = traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p);
-    G.m      = M;
-    G.litOut = ts.radiance.p;
-    launchTraceLightWithMeshes(st, G, F);
-    HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
-    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeBegin], st));
-    launchHybridMeshComposite(st, G, F);
-    HIPCHK(hipEventRecord(tm.ev[kTmevCompositeEnd], st));
-    return MGS_OK;
-  }
-  int afterFrame(const FrameArgs& A, int fmt) override
-  {
-    TracePassState&   ts = s->trace;
-    const FrameConst& F  = A.f;
-    hipStream_t       st = s->stream;
-    HIPCHK(hipMemsetAsync(ts.lctr.p, 0, sizeof(TraceLightCounters), st));
-    HIPCHK(hipEventRecord(ts.ev[kEvLightBegin], st));
+    G.l = traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p);
     if(meshActive)
     {
-      if(int rc = afterFrameWithMeshes(F, fmt))
-        return rc;
-      if(F.temporalSampling)
-        launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, fmt);
-      HIPCHK(hipGetLastError());
-      return MGS_OK;
+      H.meshT = tm.meshT.p;
+      H.outT  = tm.walkT.p;
+      H.minT  = tm.hybridMinT;
+      launchHybridSurfaceWithMeshes(st, H, F, fmt);
+      G.m      = M;
+      G.litOut = ts.radiance.p;
+      launchTraceLightWithMeshes(st, G, F);
+      HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
+      HIPCHK(hipEventRecord(tm.ev[kTmevCompositeBegin], st));
+      launchHybridMeshComposite(st, G, F);
+      HIPCHK(hipEventRecord(tm.ev[kTmevCompositeEnd], st));
     }
-    HybridSurfaceArgs H{};
-    H.frame       = s->fb.dArgs.p;
-    H.image       = s->fb.image.p;
-    H.depth       = s->surf.depth.p;
-    H.id          = s->surf.id.p;
-    H.normal      = s->surf.normal.p;
-    H.outIsoDist  = ts.isoDist.p;
-    H.outNormal   = ts.hybridNormal.p;
-    H.outRadiance = ts.radiance.p;
-    launchHybridSurface(st, H, F, fmt);
-    launchTraceLight(st, traceLightArgs(s, traceArgs(s, proxy(), t, fmt), lt, s->surf.id.p, ts.hybridNormal.p), F);
-    HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
+    else
+    {
+      launchHybridSurface(st, H.a, F, fmt);
+      launchTraceLight(st, G.l, F);
+      HIPCHK(hipEventRecord(ts.ev[kEvLightEnd], st));
+    }
     if(F.temporalSampling)  // the lit sample is what the running mean folds in
       launchPostAccumulate(st, s->fb.dArgs.p, s->fb.accum.p, s->fb.image.p, fmt);
     HIPCHK(hipGetLastError());
@@ -954,18 +937,25 @@ int mgs_trace_download_hit_counts(MgsScene s, uint32_t* dst, size_t count)
 }
 
 // ---- mesh hits in the traced frames: the handle's setting, the last frame's hit records and its mesh rays' statistics ----
+// the ranges of MgsTraceMeshParams, which can be checked without a device; `fn`: the entry point's name for the message
+static int checkTraceMeshParams(const char* fn, const MgsTraceMeshParams* p)
+{
+  if(!p)
+    return MGS_OK;
+  if(p->enabled != 0 && p->enabled != 1)
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(fn) + ": enabled must be 0 or 1");
+  if(!(p->min_mesh_composite_transmittance >= 0.0f && p->min_mesh_composite_transmittance <= 1.0f))
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(fn) + ": min_mesh_composite_transmittance must be in [0, 1]");
+  if(p->reserved[0] != 0 || p->reserved[1] != 0)
+    return failTrace(MGS_ERR_INVALID_ARG, std::string(fn) + ": the reserved words of MgsTraceMeshParams must be 0");
+  return MGS_OK;
+}
+
 int mgs_frame_set_trace_meshes(MgsScene s, const MgsTraceMeshParams* p)
 {
   return guarded("mgs_frame_set_trace_meshes", [&]() -> int {
-    if(p)
-    {  // (before the handle is looked at: the ranges can be checked without a device)
-      if(p->enabled != 0 && p->enabled != 1)
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: enabled must be 0 or 1");
-      if(!(p->min_mesh_composite_transmittance >= 0.0f && p->min_mesh_composite_transmittance <= 1.0f))
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: min_mesh_composite_transmittance must be in [0, 1]");
-      if(p->reserved[0] != 0 || p->reserved[1] != 0)
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: the reserved words of MgsTraceMeshParams must be 0");
-    }
+    if(int rc = checkTraceMeshParams("mgs_frame_set_trace_meshes", p))  // (before the handle is looked at)
+      return rc;
     if(!s)
       return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_trace_meshes: null scene");
     s->traceMesh.enabled = p != nullptr && p->enabled == 1;
@@ -977,15 +967,8 @@ int mgs_frame_set_trace_meshes(MgsScene s, const MgsTraceMeshParams* p)
 int mgs_frame_set_hybrid_meshes(MgsScene s, const MgsTraceMeshParams* p)
 {
   return guarded("mgs_frame_set_hybrid_meshes", [&]() -> int {
-    if(p)
-    {  // (before the handle is looked at: mgs_frame_set_trace_meshes' ranges)
-      if(p->enabled != 0 && p->enabled != 1)
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: enabled must be 0 or 1");
-      if(!(p->min_mesh_composite_transmittance >= 0.0f && p->min_mesh_composite_transmittance <= 1.0f))
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: min_mesh_composite_transmittance must be in [0, 1]");
-      if(p->reserved[0] != 0 || p->reserved[1] != 0)
-        return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: the reserved words of MgsTraceMeshParams must be 0");
-    }
+    if(int rc = checkTraceMeshParams("mgs_frame_set_hybrid_meshes", p))  // (before the handle is looked at)
+      return rc;
     if(!s)
       return failTrace(MGS_ERR_INVALID_ARG, "mgs_frame_set_hybrid_meshes: null scene");
     s->traceMesh.hybridEnabled = p != nullptr && p->enabled == 1;

@@ -77,14 +77,7 @@ __global__ void __launch_bounds__(256) k_light(const LightArgs a)
       else
         hi = mid;
     }
-    const float4* mp = reinterpret_cast<const float4*>(&a.table->mats[lo]);
-    const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-    mat.ambient      = baseRadiance * V3{m0.x, m0.y, m0.z};
-    mat.diffuse      = baseRadiance * V3{m0.w, m1.x, m1.y};
-    mat.specular     = baseRadiance * V3{m1.z, m1.w, m2.x};
-    mat.emission     = baseRadiance * V3{m2.y, m2.z, m2.w};
-    mat.shininess    = m3.x;
-    mat.needShading  = __float_as_int(m3.y);
+    mat = splatMaterial(a.table->mats[lo], baseRadiance);
   }
   else
   {  // the shader's default material with the base colour as diffuse
@@ -103,21 +96,7 @@ __global__ void __launch_bounds__(256) k_light(const LightArgs a)
     for(int l = 0; l < count; ++l)
       shadeDirect(a.table->lights[l], worldPos, normal, mat, viewDir, color);
     if(count == 0)
-    {  // createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation
-      LightDev h;
-      h.type      = MGS_LIGHT_POINT;
-      h.attMode   = 0;
-      h.color[0] = h.color[1] = h.color[2] = 1.0f;
-      h.intensity = 1.0f;
-      h.pos[0]    = cameraPos.x;
-      h.pos[1]    = cameraPos.y;
-      h.pos[2]    = cameraPos.z;
-      h.range     = 1e10f;
-      h.dirN[0] = h.dirN[1] = 0.0f;
-      h.dirN[2]  = -1.0f;
-      h.innerCos = h.outerCos = 1.0f;
-      shadeDirect(h, worldPos, normal, mat, viewDir, color);
-    }
+      shadeDirect(headlight(F.cameraPos), worldPos, normal, mat, viewDir, color);
   }
   storePixel(a.image, FMT, o, color.x, color.y, color.z, 1.0f);
 }

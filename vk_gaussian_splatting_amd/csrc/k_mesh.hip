@@ -529,15 +529,7 @@ __global__ void __launch_bounds__(256) k_mesh_resolve(const MeshPassArgs a)
   const V3    worldNrm = combine3(pw0, pw1, pw2, N[0], N[1], N[2]) * inv;  // not renormalised, as written
   const V3    viewDir  = combine3(pw0, pw1, pw2, D[0], D[1], D[2]) * inv;
 
-  const float4* mp = reinterpret_cast<const float4*>(&I.mats[I.matId[t]]);
-  const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-  Mat           mat;
-  mat.ambient     = {m0.x, m0.y, m0.z};
-  mat.diffuse     = {m0.w, m1.x, m1.y};
-  mat.specular    = {m1.z, m1.w, m2.x};
-  mat.emission    = {m2.y, m2.z, m2.w};
-  mat.shininess   = m3.x;
-  mat.needShading = __float_as_int(m3.y);
+  const Mat mat = material(I.mats[I.matId[t]]);
   V3 color;
   if(a.lightingMode == MGS_LIGHTING_DISABLED)
     color = (mat.emission + mat.ambient) + mat.diffuse;  // threedmesh_raster.frag.slang:100
@@ -550,21 +542,7 @@ __global__ void __launch_bounds__(256) k_mesh_resolve(const MeshPassArgs a)
       for(int l = 0; l < count; ++l)
         shadeDirect(a.lights->lights[l], worldPos, worldNrm, mat, viewDir, color);
       if(count == 0)
-      {  // createHeadlight (wavefront.h.slang:104-119)
-        LightDev h;
-        h.type      = MGS_LIGHT_POINT;
-        h.attMode   = 0;
-        h.color[0] = h.color[1] = h.color[2] = 1.0f;
-        h.intensity = 1.0f;
-        h.pos[0]    = a.cameraPos[0];
-        h.pos[1]    = a.cameraPos[1];
-        h.pos[2]    = a.cameraPos[2];
-        h.range     = 1e10f;
-        h.dirN[0] = h.dirN[1] = 0.0f;
-        h.dirN[2]  = -1.0f;
-        h.innerCos = h.outerCos = 1.0f;
-        shadeDirect(h, worldPos, worldNrm, mat, viewDir, color);
-      }
+        shadeDirect(headlight(a.cameraPos), worldPos, worldNrm, mat, viewDir, color);
     }
   }
   a.outDepth[o] = __uint_as_float((uint32_t)(word >> 32));

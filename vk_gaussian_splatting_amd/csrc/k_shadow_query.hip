@@ -8,7 +8,8 @@
 //   shaders/wavefront.h.slang:33-70,233-280,388-403   computeLightToSurfaceVector, wavefrontComputeShadingDirectOnly (shade_direct.h)
 // Structure: one ray or point per lane, 256 lanes per workgroup; lane i of workgroup b takes the item at perm[b * 256 + i], or
 // b * 256 + i in the caller's order (the scheme of k_trace_rays.hip).  The K-buffer lives in registers (three instantiations: 4, 18,
-// 32 slots), the traversal's stack in TraceLds; the lights and the call's knobs are read through wave-uniform loads, a point's
+// 32 slots), the traversal's stack in TraceLds; a point is lit by the loop of trace_lights.h (no meshes, hard shadows, the headlight at
+// the call's camera position); the lights and the call's knobs are read through wave-uniform loads, a point's
 // material through one lane-indexed 64-byte record.  Every loop is bounded: lights by kMaxLights, the traversal by 2 * nodes + 2
 // steps, the walk by samples_per_pass, children by 8.  No flags, nothing waits on another lane, wave or workgroup, and no lane
 // returns: a tail workgroup's spare lanes and the invalid items skip the work.  The counters are integer atomics at the end.
@@ -18,6 +19,7 @@
 #include "shade_direct.h"
 #include "trace_common.h"
 #include "trace_dispatch.h"
+#include "trace_lights.h"
 #include "trace_shadow.h"
 #include "trace_traverse.h"
 
@@ -102,9 +104,8 @@ __global__ __launch_bounds__(256) void k_shade_points(ShadowQueryArgs q)
   const uint32_t matId = __float_as_uint(p0.w);
   const bool     ok    = mine && finite3(p0) && finite3(p1) && finite3(p2) && finite3(p3) && matId < q.matCount;
 
-  V3                 color = {0.0f, 0.0f, 0.0f};
-  uint32_t           shadowHits = 0;
-  unsigned long long shadowRays = 0, nodeVisits = 0, candTests = 0;
+  V3         color = {0.0f, 0.0f, 0.0f};
+  ShadowSums sums;
   if(ok)
   {
     const V3 worldPos = {p0.x, p0.y, p0.z};
@@ -113,73 +114,24 @@ __global__ __launch_bounds__(256) void k_shade_points(ShadowQueryArgs q)
     if(sqrtf(dot3(normal, normal)) <= 0.2f)  // surfaceFinalFiltering's fallback (rgen.slang:991-1009)
       normal = -rayDir;
     normal = normalize3(normal);
-    const V3      baseRadiance = {p3.x, p3.y, p3.z};
-    const float4* mp = reinterpret_cast<const float4*>(&q.mats[matId]);
-    const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-    Mat           mat;
-    mat.ambient     = baseRadiance * V3{m0.x, m0.y, m0.z};
-    mat.diffuse     = baseRadiance * V3{m0.w, m1.x, m1.y};
-    mat.specular    = baseRadiance * V3{m1.z, m1.w, m2.x};
-    mat.emission    = baseRadiance * V3{m2.y, m2.z, m2.w};
-    mat.shininess   = m3.x;
-    mat.needShading = __float_as_int(m3.y);
-    color           = mat.emission;
+    const Mat mat = splatMaterial(q.mats[matId], V3{p3.x, p3.y, p3.z});
+    color         = mat.emission;
     if(mat.needShading != 0)
-    {
-      const int         count = q.table->count;
-      const ShadowKnobs knobs = {q.shFormat, q.shadowThreshold, q.shadowColorStrength};
-      for(int l = 0; l < count && l < kMaxLights; ++l)  // bound: kMaxLights
-      {
-        const LightDev& light = q.table->lights[l];
-        V3    lightDir;
-        float lightDist;
-        if(!lightToSurface(light, worldPos, lightDir, lightDist))
-          continue;  // culled: no ambient term either (rgen.slang:1120-1121)
-        V3   shadowT  = {1.0f, 1.0f, 1.0f};
-        bool inShadow = false;
-        if(q.shadowsMode != 0 && a.nLevels > 0)
-        {
-          ++shadowRays;
-          TraceRay sr;
-          sr.o[0] = worldPos.x + lightDir.x * q.shadowOffset;
-          sr.o[1] = worldPos.y + lightDir.y * q.shadowOffset;
-          sr.o[2] = worldPos.z + lightDir.z * q.shadowOffset;
-          sr.d[0] = lightDir.x; sr.d[1] = lightDir.y; sr.d[2] = lightDir.z;
-#pragma unroll
-          for(int c = 0; c < 3; ++c)
-            sr.inv[c] = 1.0f / sr.d[c];
-          shadowT  = traceShadowRayParticle<KB>(a, S, tid, sr, 0.0f, lightDist, knobs, shadowHits, nodeVisits, candTests);
-          inShadow = fmaxf(fmaxf(shadowT.x, shadowT.y), shadowT.z) < 0.001f;  // rgen.slang:1127
-        }
-        shadeDirectT<true>(light, worldPos, normal, mat, rayDir, shadowT, inShadow, color);
-      }
-      if(count == 0)
-      {  // createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation, never shadowed (:1137-1143)
-        LightDev h;
-        h.type      = MGS_LIGHT_POINT;
-        h.attMode   = 0;
-        h.color[0] = h.color[1] = h.color[2] = 1.0f;
-        h.intensity = 1.0f;
-        h.pos[0]    = q.cameraPos[0];
-        h.pos[1]    = q.cameraPos[1];
-        h.pos[2]    = q.cameraPos[2];
-        h.range     = 1e10f;
-        h.dirN[0] = h.dirN[1] = 0.0f;
-        h.dirN[2]  = -1.0f;
-        h.innerCos = h.outerCos = 1.0f;
-        shadeDirect(h, worldPos, normal, mat, rayDir, color);
-      }
+    {  // no meshes; hard shadows
+      const LightLoopArgs g = {q.table, q.shadowsMode, q.shadowOffset, {q.shFormat, q.shadowThreshold, q.shadowColorStrength}, q.cameraPos};
+      uint32_t            noSeed = 0u;
+      (void)shadeLights<KB, false, false>(g, a, S, nullptr, nullptr, tid, mat, worldPos, normal, rayDir, noSeed, color, sums);
     }
   }
   if(mine)
   {
-    q.results[idx] = make_float4(color.x, color.y, color.z, __uint_as_float(shadowHits));
+    q.results[idx] = make_float4(color.x, color.y, color.z, __uint_as_float(sums.shadowHits));
     if(ok)
     {
-      atomicAdd(&q.lctr->shadowRays, shadowRays);
-      atomicAdd(&q.lctr->nodeVisits, nodeVisits);
-      atomicAdd(&q.lctr->candidateTests, candTests);
-      atomicAdd(&q.lctr->acceptedHits, (unsigned long long)shadowHits);
+      atomicAdd(&q.lctr->shadowRays, sums.shadowRays);
+      atomicAdd(&q.lctr->nodeVisits, sums.nodeVisits);
+      atomicAdd(&q.lctr->candidateTests, sums.candTests);
+      atomicAdd(&q.lctr->acceptedHits, (unsigned long long)sums.shadowHits);
     }
     else
       atomicAdd(q.invalid, 1u);

@@ -12,7 +12,8 @@
 // Structure: a lane per pixel in k_trace's tiling.  Bounce 0 is the lit mesh frame's launches as they are (k_trace_mesh_primary,
 // k_trace<., ., true>, k_trace_light<., true>) followed by k_trace_bounce_primary, the lit mesh composite in the indirect mode, which
 // also writes the pixel's bounce state.  Every bounce b >= 1 is ONE launch of k_trace_bounce: the closest mesh walk on the stored
-// ray, the particle pass walk below that hit, the light pass of the splat surface, the mesh's indirect shading, the next ray.  The
+// ray, the particle pass walk below that hit, the light pass of the splat surface, the mesh's indirect shading, the next ray (both
+// shading sites light their point with the loop of trace_lights.h; the bounce alone reads whether a light shaded it).  The
 // three stages share no register state beyond the ray, the radiance and T, so the compiler reuses the K-buffer's registers for the
 // shadow walks; a split into three kernels would carry the hit record, the pick and the normal through memory as well.  A lane
 // whose pixel is not live returns after the flag read.  The host enqueues max_bounces launches; nothing is read back in between.
@@ -28,9 +29,9 @@
 #include "target_pixel.h"
 #include "trace_common.h"
 #include "trace_dispatch.h"
+#include "trace_lights.h"
 #include "trace_primary_ray.h"
 #include "trace_shade.h"
-#include "trace_shadow.h"
 #include "trace_traverse.h"
 
 namespace mgs {
@@ -42,13 +43,6 @@ struct D3
   double x, y, z;
 };
 __device__ __forceinline__ double maxComponent(D3 t) { return fmax(fmax(t.x, t.y), t.z); }
-
-// the integer sums of a lane's shadow rays
-struct ShadowSums
-{
-  uint32_t           shadowHits = 0;
-  unsigned long long shadowRays = 0, nodeVisits = 0, candTests = 0, meshNodeVisits = 0, meshTriTests = 0, meshOccluded = 0;
-};
 
 __device__ __forceinline__ BounceMatDev bounceMaterial(const TraceBounceArgs& B, uint32_t inst, uint32_t mat)
 {
@@ -65,74 +59,6 @@ __device__ __forceinline__ BounceMatDev bounceMaterial(const TraceBounceArgs& B,
   return m;
 }
 
-// The loop over the lights of evaluateLightingAndShading{Particles,Meshes} (rgen.slang:1113-1143, :1179-1219) at a surface point,
-// with traceShadowRayForLight (:1262-1292): the meshes first, from the un-offset origin, then the particles from the offset one.
-// Returns whether a light shaded the point (one in range, or the headlight).
-template <int KB>
-__device__ __forceinline__ bool shadeLights(const TraceLightMeshArgs& args, TraceLds& S, TraceLds& SM, int tid, const FrameConst& F, const Mat& mat,
-                                            V3 worldPos, V3 normal, V3 rayDir, V3& color, ShadowSums& sums)
-{
-  const TraceLightArgs& L = args.l;
-  const TraceArgs&      a = L.t;
-  const int         count = L.table->count;
-  const ShadowKnobs knobs = {L.shFormat, L.shadowThreshold, L.shadowColorStrength};
-  bool              any   = count == 0;
-  for(int l = 0; l < count; ++l)  // bound: kMaxLights
-  {
-    const LightDev& light = L.table->lights[l];
-    V3    lightDir;
-    float lightDist;
-    if(!lightToSurface(light, worldPos, lightDir, lightDist))
-      continue;  // culled before anything happens (:1120-1121, :1186-1187)
-    any = true;
-    V3   shadowT  = {1.0f, 1.0f, 1.0f};
-    bool inShadow = false;
-    if(L.shadowsMode != 0)
-    {
-      TraceRay sr;
-      sr.o[0] = worldPos.x; sr.o[1] = worldPos.y; sr.o[2] = worldPos.z;
-      sr.d[0] = lightDir.x; sr.d[1] = lightDir.y; sr.d[2] = lightDir.z;
-#pragma unroll
-      for(int c = 0; c < 3; ++c)
-        sr.inv[c] = 1.0f / sr.d[c];
-      const MeshBest mb = meshWalk<1>(args.m.h, SM, tid, args.m.tris, args.m.table, sr, 0.001f, lightDist - 0.001f, sums.meshNodeVisits, sums.meshTriTests);
-      if(mb.t < __builtin_huge_valf())
-      {  // opaque: the particles are not asked (:1285)
-        ++sums.meshOccluded;
-        shadowT  = {0.0f, 0.0f, 0.0f};
-        inShadow = true;
-      }
-      else if(a.nLevels > 0)
-      {
-        ++sums.shadowRays;
-        sr.o[0] = worldPos.x + lightDir.x * L.shadowOffset;
-        sr.o[1] = worldPos.y + lightDir.y * L.shadowOffset;
-        sr.o[2] = worldPos.z + lightDir.z * L.shadowOffset;
-        shadowT  = traceShadowRayParticle<KB>(a, S, tid, sr, 0.0f, lightDist, knobs, sums.shadowHits, sums.nodeVisits, sums.candTests);
-        inShadow = fmaxf(fmaxf(shadowT.x, shadowT.y), shadowT.z) < 0.001f;
-      }
-    }
-    shadeDirectT<true>(light, worldPos, normal, mat, rayDir, shadowT, inShadow, color);
-  }
-  if(count == 0)
-  {  // createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation, never shadowed
-    LightDev h;
-    h.type      = MGS_LIGHT_POINT;
-    h.attMode   = 0;
-    h.color[0] = h.color[1] = h.color[2] = 1.0f;
-    h.intensity = 1.0f;
-    h.pos[0]    = F.cameraPos[0];
-    h.pos[1]    = F.cameraPos[1];
-    h.pos[2]    = F.cameraPos[2];
-    h.range     = 1e10f;
-    h.dirN[0] = h.dirN[1] = 0.0f;
-    h.dirN[2]  = -1.0f;
-    h.innerCos = h.outerCos = 1.0f;
-    shadeDirect(h, worldPos, normal, mat, rayDir, color);
-  }
-  return any;
-}
-
 // evaluateLightingAndShadingMeshes in the indirect mode (rgen.slang:1148-1219) at the closest hit (h0, h1, h2: its record) of the
 // ray along rayDir.  weight = float3(T).  Every light in range is shaded with the T the function was entered with (:1191-1197),
 // and what wavefrontComputeShading leaves of T and the ray does not depend on the light: it is applied once, when a light shaded.
@@ -144,22 +70,15 @@ __device__ __forceinline__ bool shadeMeshIndirect(const TraceBounceArgs& B, Trac
 {
   const TraceMeshArgs& M    = B.g.m;
   const uint32_t       inst = __float_as_uint(h0.y), matId = __float_as_uint(h0.w);
-  const MeshInstDev&   I    = M.table->inst[inst];
-  const float4*        mp   = reinterpret_cast<const float4*>(&I.mats[matId]);
-  const float4         m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-  const V3 ambient = {m0.x, m0.y, m0.z}, diffuse = {m0.w, m1.x, m1.y}, specular = {m1.z, m1.w, m2.x}, emission = {m2.y, m2.z, m2.w};
-  color = color + emission;  // unweighted, as written (:1159)
-  if(__float_as_int(m3.y) == 0)
+  const Mat            mm   = meshMaterial(M.table, h0);
+  color = color + mm.emission;  // unweighted, as written (:1159)
+  if(mm.needShading == 0)
     return false;  // needShading != 1: no lighting interaction, no bounce (:1162-1165)
-  Mat mat;  // the light term weights ambient and (diffuse + specular) with float3(T) (wavefront.h.slang:303, :332): the material goes in weighted
-  mat.ambient     = ambient * weight;
-  mat.diffuse     = diffuse * weight;
-  mat.specular    = specular * weight;
-  mat.emission    = emission;
-  mat.shininess   = m3.x;
-  mat.needShading = 1;
-  const V3 worldPos = {h1.x, h1.y, h1.z}, normal = {h2.x, h2.y, h2.z};
-  if(!shadeLights<KB>(B.g, S, SM, tid, F, mat, worldPos, normal, rayDir, color, sums))
+  // the light term weights ambient and (diffuse + specular) with float3(T) (wavefront.h.slang:303, :332): the material goes in weighted
+  const Mat mat      = weightedMaterial(mm, weight);
+  const V3  worldPos = {h1.x, h1.y, h1.z}, normal = {h2.x, h2.y, h2.z};
+  uint32_t  noSeed   = 0u;  // (hard shadows only: the loop never reads the random state)
+  if(!shadeLights<KB, true, false>(lightLoopArgs(B.g.l, F), B.g.l.t, S, &M, &SM, tid, mat, worldPos, normal, rayDir, noSeed, color, sums))
     return false;  // every light out of range: nothing is called, done stays 1 (:1186-1187)
   const BounceMatDev bm = bounceMaterial(B, inst, matId);
   if(bm.illum <= 0)
@@ -171,9 +90,9 @@ __device__ __forceinline__ bool shadeMeshIndirect(const TraceBounceArgs& B, Trac
   const float dn = dot3(rayDir, normal);
   if(bm.illum == 1)
   {  // reflection (wavefront.h.slang:340-346)
-    T.x *= (double)specular.x;
-    T.y *= (double)specular.y;
-    T.z *= (double)specular.z;
+    T.x *= (double)mm.specular.x;
+    T.y *= (double)mm.specular.y;
+    T.z *= (double)mm.specular.z;
     newD = rayDir - normal * (2.0f * dn);
     return true;
   }
@@ -405,25 +324,13 @@ __global__ __launch_bounds__(256) void k_trace_bounce(TraceBounceArgs B)
   ShadowSums sums;
   if(pickId != kTraceInvalid && isoDist > 0.0f && isoDist < best.t)
   {  // the splat surface, on radiance - radianceBeforeParticles (:1053-1055); no surfaceFinalFiltering: the raw integrated normal
-    const V3 baseRadiance = {cr - br, cg - bg, cb - bb};
-    int      inst = 0;
-    for(int i = 1; i < F.nInstances; ++i)  // bound: kMaxInstances
-      if(pickId >= Ap->inst[i].globalOffset)
-        inst = i;
-    const float4* mp = reinterpret_cast<const float4*>(&L.table->mats[inst]);
-    const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-    Mat           mat;
-    mat.ambient     = baseRadiance * V3{m0.x, m0.y, m0.z};
-    mat.diffuse     = baseRadiance * V3{m0.w, m1.x, m1.y};
-    mat.specular    = baseRadiance * V3{m1.z, m1.w, m2.x};
-    mat.emission    = baseRadiance * V3{m2.y, m2.z, m2.w};
-    mat.shininess   = m3.x;
-    mat.needShading = __float_as_int(m3.y);
+    const Mat mat = splatMaterial(L.table->mats[splatInstance(Ap, pickId)], V3{cr - br, cg - bg, cb - bb});
     V3 color = mat.emission;
     if(mat.needShading != 0)
     {
       const V3 worldPos = {ray.o[0] + isoDist * ray.d[0], ray.o[1] + isoDist * ray.d[1], ray.o[2] + isoDist * ray.d[2]};
-      (void)shadeLights<KB>(args, S, SM, tid, F, mat, worldPos, V3{nx, ny, nz}, rayDir, color, sums);
+      uint32_t noSeed = 0u;
+      (void)shadeLights<KB, true, false>(lightLoopArgs(L, F), a, S, &args.m, &SM, tid, mat, worldPos, V3{nx, ny, nz}, rayDir, noSeed, color, sums);
     }
     cr = color.x + br;
     cg = color.y + bg;

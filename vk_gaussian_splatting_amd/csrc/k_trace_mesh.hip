@@ -11,8 +11,8 @@
 // honoured).  k_trace_mesh_primary runs the closest walk of mesh_traverse.h on the ray k_trace traces (trace_primary_ray.h) and
 // leaves the pixel's 64-byte hit record and its t; k_trace cuts its walk there and leaves float(T); k_trace_mesh_composite adds the
 // mesh's radiance to the fp32 pixel k_trace (unlit) or the light pass (lit) left and stores the pixel again.  In a lit frame it
-// traces, per light, the mesh occlusion ray and then the shadow ray through the particles (trace_shadow.h) from the mesh's surface
-// point.  Every loop is bounded: lights by kMaxLights, the traversals by 2 * nodes + 2 steps, the walk by samples_per_pass, children
+// lights the mesh's surface point with the loop of trace_lights.h: per light the mesh occlusion ray, then the shadow ray through the
+// particles.  Every loop is bounded: lights by kMaxLights, the traversals by 2 * nodes + 2 steps, the walk by samples_per_pass, children
 // by 8.  No flags, nothing waits on another lane, wave or workgroup; the counters are integer atomics at the end.
 #include "gut_common.h"
 #include "kernels_common.h"
@@ -22,8 +22,8 @@
 #include "target_pixel.h"
 #include "trace_common.h"
 #include "trace_dispatch.h"
+#include "trace_lights.h"
 #include "trace_primary_ray.h"
-#include "trace_shadow.h"
 #include "trace_traverse.h"
 
 namespace mgs {
@@ -135,44 +135,26 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
       walkT = (double)1.0f > (double)args.m.minT ? 1.0f : -1.0f;
     }
     else if constexpr(SOFT)
-    {  // the picked instance's needShading, as k_trace_light reads it (rgen.slang:1091-1095 returns before the loop)
-      int inst = 0;
-      for(int i = 1; i < F.nInstances; ++i)  // bound: kMaxInstances
-        if(pickId >= Ap->inst[i].globalOffset)
-          inst = i;
-      splatShaded = L.table->mats[inst].needShading != 0;
-    }
+      splatShaded = L.table->mats[splatInstance(Ap, pickId)].needShading != 0;  // as k_trace_light reads it (rgen.slang:1091-1095 returns before the loop)
   }
   if(walkT < 0.0f)
     return;  // T > min_mesh_composite_transmittance failed (:1058-1059, :1065-1066): the mesh is not composited
 
-  const MeshInstDev& I  = args.m.table->inst[__float_as_uint(h0.y)];
-  const float4*      mp = reinterpret_cast<const float4*>(&I.mats[__float_as_uint(h0.w)]);
-  const float4       m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-  const V3 ambient = {m0.x, m0.y, m0.z}, diffuse = {m0.w, m1.x, m1.y}, specular = {m1.z, m1.w, m2.x}, emission = {m2.y, m2.z, m2.w};
-
-  uint32_t           shadowHits = 0;
-  unsigned long long shadowRays = 0, nodeVisits = 0, candTests = 0, meshNodeVisits = 0, meshTriTests = 0, meshOccluded = 0;
+  const Mat  mm = meshMaterial(args.m.table, h0);
+  ShadowSums sums;
   if constexpr(!LIT)
-    color = color + (emission + ambient + diffuse) * walkT;  // :1073-1074
+    color = color + (mm.emission + mm.ambient + mm.diffuse) * walkT;  // :1073-1074
   else
   {
-    color = color + emission;  // unweighted, as written (:1159)
-    if(__float_as_int(m3.y) != 0)
+    color = color + mm.emission;  // unweighted, as written (:1159)
+    if(mm.needShading != 0)
     {
       // wavefrontComputeShadingDirectOnly weights the ambient and the (diffuse + specular) terms with float(T) (wavefront.h.slang:249,
       // :279): the material goes in weighted
-      Mat mat;
-      mat.ambient     = ambient * walkT;
-      mat.diffuse     = diffuse * walkT;
-      mat.specular    = specular * walkT;
-      mat.emission    = emission;
-      mat.shininess   = m3.x;
-      mat.needShading = 1;
-      const V3 worldPos = {h1.x, h1.y, h1.z}, normal = {h2.x, h2.y, h2.z};  // meshHitWorldPos, meshHitWorldNrm: the closest hit's
-      const int         count = L.table->count;
-      const ShadowKnobs knobs = {L.shFormat, L.shadowThreshold, L.shadowColorStrength};
-      uint32_t          seedRayPass = SOFT ? rngXxhash32((uint32_t)px, (uint32_t)py, (uint32_t)F.frameSampleId) : 0u;  // :228
+      const Mat mat      = weightedMaterial(mm, V3{walkT, walkT, walkT});
+      const V3  worldPos = {h1.x, h1.y, h1.z}, normal = {h2.x, h2.y, h2.z};  // meshHitWorldPos, meshHitWorldNrm: the closest hit's
+      const int count    = L.table->count;
+      uint32_t  seedRayPass = SOFT ? rngXxhash32((uint32_t)px, (uint32_t)py, (uint32_t)F.frameSampleId) : 0u;  // :228
       if constexpr(SOFT)
         if(splatShaded)
           for(int l = 0; l < count; ++l)  // bound: kMaxLights.  The splat surface's loop: two draws per light with a disk
@@ -181,71 +163,20 @@ __global__ __launch_bounds__(256) void k_trace_mesh_composite(TraceLightMeshArgs
               (void)rngPcg(seedRayPass);
               (void)rngPcg(seedRayPass);
             }
-      for(int l = 0; l < count; ++l)  // bound: kMaxLights
-      {
-        const LightDev& light = L.table->lights[l];
-        V3    lightDir;
-        float lightDist;
-        if(!(SOFT ? lightToSurfaceSoft(light, worldPos, seedRayPass, lightDir, lightDist) : lightToSurface(light, worldPos, lightDir, lightDist)))
-          continue;  // culled (:1230-1231)
-        V3   shadowT  = {1.0f, 1.0f, 1.0f};
-        bool inShadow = false;
-        if(L.shadowsMode != 0)
-        {  // traceShadowRayForLight (:1262-1292): the meshes first, from the un-offset origin (:1295-1341) ...
-          TraceRay sr;
-          sr.o[0] = worldPos.x; sr.o[1] = worldPos.y; sr.o[2] = worldPos.z;
-          sr.d[0] = lightDir.x; sr.d[1] = lightDir.y; sr.d[2] = lightDir.z;
-#pragma unroll
-          for(int c = 0; c < 3; ++c)
-            sr.inv[c] = 1.0f / sr.d[c];
-          const MeshBest mb = meshWalk<1>(args.m.h, SM, tid, args.m.tris, args.m.table, sr, 0.001f, lightDist - 0.001f, meshNodeVisits, meshTriTests);
-          if(mb.t < __builtin_huge_valf())
-          {  // opaque: the particles are not asked (:1285)
-            ++meshOccluded;
-            shadowT  = {0.0f, 0.0f, 0.0f};
-            inShadow = true;
-          }
-          else if(a.nLevels > 0)
-          {  // ... then the particles, from the offset origin (:1344-1464; trace_shadow.h)
-            ++shadowRays;
-            sr.o[0] = worldPos.x + lightDir.x * L.shadowOffset;
-            sr.o[1] = worldPos.y + lightDir.y * L.shadowOffset;
-            sr.o[2] = worldPos.z + lightDir.z * L.shadowOffset;
-            shadowT  = traceShadowRayParticle<KB>(a, S, tid, sr, 0.0f, lightDist, knobs, shadowHits, nodeVisits, candTests);
-            inShadow = fmaxf(fmaxf(shadowT.x, shadowT.y), shadowT.z) < 0.001f;  // :1236
-          }
-        }
-        shadeDirectT<true>(light, worldPos, normal, mat, rayDir, shadowT, inShadow, color);
-      }
-      if(count == 0)
-      {  // createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation, never shadowed (:1246-1252)
-        LightDev h;
-        h.type      = MGS_LIGHT_POINT;
-        h.attMode   = 0;
-        h.color[0] = h.color[1] = h.color[2] = 1.0f;
-        h.intensity = 1.0f;
-        h.pos[0]    = F.cameraPos[0];
-        h.pos[1]    = F.cameraPos[1];
-        h.pos[2]    = F.cameraPos[2];
-        h.range     = 1e10f;
-        h.dirN[0] = h.dirN[1] = 0.0f;
-        h.dirN[2]  = -1.0f;
-        h.innerCos = h.outerCos = 1.0f;
-        shadeDirect(h, worldPos, normal, mat, rayDir, color);
-      }
+      (void)shadeLights<KB, true, SOFT>(lightLoopArgs(L, F), a, S, &args.m, &SM, tid, mat, worldPos, normal, rayDir, seedRayPass, color, sums);
     }
-    L.shadowHits[pix] += shadowHits;  // (this lane's own word: the light pass wrote it)
+    L.shadowHits[pix] += sums.shadowHits;  // (this lane's own word: the light pass wrote it)
   }
   storePixel(a.image, a.fmt, pix, color.x, color.y, color.z, 1.0f);  // the mesh is opaque
   if constexpr(LIT)
   {  // statistics: integer sums, so the totals do not depend on the order of arrival
-    atomicAdd(&L.lctr->shadowRays, shadowRays);
-    atomicAdd(&L.lctr->nodeVisits, nodeVisits);
-    atomicAdd(&L.lctr->candidateTests, candTests);
-    atomicAdd(&L.lctr->acceptedHits, (unsigned long long)shadowHits);
-    atomicAdd(&args.m.ctr[1].nodeVisits, meshNodeVisits);
-    atomicAdd(&args.m.ctr[1].triangleTests, meshTriTests);
-    atomicAdd(&args.m.ctr[1].hits, meshOccluded);
+    atomicAdd(&L.lctr->shadowRays, sums.shadowRays);
+    atomicAdd(&L.lctr->nodeVisits, sums.nodeVisits);
+    atomicAdd(&L.lctr->candidateTests, sums.candTests);
+    atomicAdd(&L.lctr->acceptedHits, (unsigned long long)sums.shadowHits);
+    atomicAdd(&args.m.ctr[1].nodeVisits, sums.meshNodeVisits);
+    atomicAdd(&args.m.ctr[1].triangleTests, sums.meshTriTests);
+    atomicAdd(&args.m.ctr[1].hits, sums.meshOccluded);
   }
 }
 

@@ -1,7 +1,8 @@
 // shade_direct.h — the direct shading the deferred lighting pass (k_light.hip), the mesh pass (k_mesh.hip) and the light pass of a
 // traced frame (k_trace_light.hip) evaluate: wavefrontComputeShadingDirectOnly with wavefrontComputeSpecular
-// (shaders/wavefront.h.slang:233-280,388-403) in their own order of operations, the material and light types it reads, the small
-// vector helpers, and for the traced pass computeLightToSurfaceVector (:33-70) with the shadow's factor on the light's colour.
+// (shaders/wavefront.h.slang:233-280,388-403) in their own order of operations, the material and light types it reads with the
+// materials' unpacking and createHeadlight (:104-119), each once for the raster and the traced passes, the small vector helpers, and
+// for the traced pass computeLightToSurfaceVector (:33-70) with the shadow's factor on the light's colour.
 // Device code only; every kernel file that includes it gets its own inlined copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,58 @@ struct Mat
   float shininess;
   int   needShading;
 };
+
+// a material record as the shading reads it: four 16-byte loads
+__device__ __forceinline__ Mat material(const MaterialDev& m)
+{
+  const float4* mp = reinterpret_cast<const float4*>(&m);
+  const float4  m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
+  Mat           mat;
+  mat.ambient     = {m0.x, m0.y, m0.z};
+  mat.diffuse     = {m0.w, m1.x, m1.y};
+  mat.specular    = {m1.z, m1.w, m2.x};
+  mat.emission    = {m2.y, m2.z, m2.w};
+  mat.shininess   = m3.x;
+  mat.needShading = __float_as_int(m3.y);
+  return mat;
+}
+// the splat surface's material: an instance's record times the base radiance (splatSetDesc.material, rgen.slang:1084-1105)
+__device__ __forceinline__ Mat splatMaterial(const MaterialDev& m, V3 baseRadiance)
+{
+  Mat mat      = material(m);
+  mat.ambient  = baseRadiance * mat.ambient;
+  mat.diffuse  = baseRadiance * mat.diffuse;
+  mat.specular = baseRadiance * mat.specular;
+  mat.emission = baseRadiance * mat.emission;
+  return mat;
+}
+// a mesh's material with the transmittance in front of it: wavefrontComputeShading{,DirectOnly} weight the ambient and the
+// (diffuse + specular) terms (wavefront.h.slang:249, :279, :303, :332); the emission is added unweighted, as written (rgen.slang:1159)
+__device__ __forceinline__ Mat weightedMaterial(Mat mat, V3 weight)
+{
+  mat.ambient  = mat.ambient * weight;
+  mat.diffuse  = mat.diffuse * weight;
+  mat.specular = mat.specular * weight;
+  return mat;
+}
+
+// createHeadlight (wavefront.h.slang:104-119): a point light at the camera, no attenuation; what shades a scene without lights
+__device__ __forceinline__ LightDev headlight(const float cameraPos[3])
+{
+  LightDev h;
+  h.type      = MGS_LIGHT_POINT;
+  h.attMode   = 0;
+  h.color[0] = h.color[1] = h.color[2] = 1.0f;
+  h.intensity = 1.0f;
+  h.pos[0]    = cameraPos[0];
+  h.pos[1]    = cameraPos[1];
+  h.pos[2]    = cameraPos[2];
+  h.range     = 1e10f;
+  h.dirN[0] = h.dirN[1] = 0.0f;
+  h.dirN[2]  = -1.0f;
+  h.innerCos = h.outerCos = 1.0f;
+  return h;
+}
 
 // distance attenuation of computePointLight / computeSpotLight (wavefront.h.slang:160-174, 193-206)
 __device__ __forceinline__ float attenuate(int mode, float distance, float range)

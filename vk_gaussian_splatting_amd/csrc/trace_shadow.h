@@ -1,5 +1,5 @@
-// trace_shadow.h — the shadow ray through the particles, once: the light pass of the lit and hybrid frames (k_trace_light.hip) and
-// the shadow and light queries (k_shadow_query.hip) call it.
+// trace_shadow.h — the shadow ray through the particles, once: the loop over the lights of every traced shading site
+// (trace_lights.h) and the shadow queries (k_shadow_rays, k_shadow_query.hip) call it.
 //
 // Replaces (hard shadows, no mesh in the traced scene)
 //   shaders/threedgrt_raytrace.rgen.slang:1344-1464   traceShadowRayParticle: one collection, the walk, the ramp and the tint
